@@ -2,7 +2,14 @@
 """Headline benchmark: training images/s (+ peak GPU bytes) of the clm_offload hot path on a
 seeded synthetic Rubble-4K-shaped scene (BASELINE.json: 28 M Gaussians, 4608x3456, bsz 4).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line: `value`, `ms_per_step`, peak bytes and what the
+timed steps counted.  --full adds everything that costs runs of its own: the streamed-GT pass, the per-kernel
+instrumented pass and roofline, the solo batch, the CPU baseline with its parity check, the host-resident, trainer,
+heavy-scene and all-reduce legs, the allocation / gather-rate probes, clock telemetry and the block-skip and replica
+checks.  --dump-outputs DIR writes what the last timed step handed its caller (losses, visible fractions, a fixed
+seeded sample of the trained model's rows) as float .npy files.
 
 A "step" is one pass of the hot path over one batch of `bsz` cameras
 (clm_offload_train_one_batch: visibility filters -> per camera projection / SH / tile binning
@@ -39,15 +46,16 @@ def _requested_gpus(argv):
 
 def _self_launch():
     """`python bench.py --gpus N` with N > 1 and no RANK / WORLD_SIZE in the environment (the driver's plain
-    command form): this process becomes the launcher -- it re-executes itself as N ranks, one per GPU, under
-    torch.distributed.run (127.0.0.1 rendezvous on a free port), exactly the command the contract gives for
-    N > 1; rank 0 prints the ONE JSON line on the inherited stdout.  Fewer than N visible devices is an error
-    (CLMGS_SHARE_GPU=1, the test hook for several ranks on one device, lifts it)."""
+    command form): this process becomes the launcher -- it starts this script as N ranks, one per GPU, under
+    torch.distributed.run (127.0.0.1 rendezvous on a free port) in a child process, exactly the command the contract
+    gives for N > 1, and exits with its status; rank 0 prints the ONE JSON line on the inherited stdout.  Fewer than N
+    visible devices is an error (CLMGS_SHARE_GPU=1, the test hook for several ranks on one device, lifts it)."""
     n = _requested_gpus(sys.argv[1:])
     if n <= 1 or "RANK" in os.environ or "WORLD_SIZE" in os.environ:
         return
     import socket
-    import torch  # device count only: no context is created, and this process is replaced below
+    import subprocess
+    import torch  # device count only: no tensor is created here; the ranks are fresh child processes
     have = torch.cuda.device_count()
     if have < n and os.environ.get("CLMGS_SHARE_GPU") != "1":
         sys.stderr.write(f"bench: --gpus {n} but only {have} GPU(s) are visible to this process "
@@ -62,7 +70,7 @@ def _self_launch():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n),
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
-    os.execvpe(cmd[0], cmd, env)
+    sys.exit(subprocess.call(cmd, env=env))
 
 
 _self_launch()
@@ -162,7 +170,7 @@ def parse():
                     help="where the ground-truth images are when the timed region starts.  resident: in HBM (the bench "
                          "contract: inputs resident before the timed region; `value`); host: in pinned host memory, every "
                          "batch's images uploaded on a side stream one batch ahead (the reference: train.py:310-312); both "
-                         "(default): `value` with resident images, then the same K steps again with streamed images as "
+                         "(default): `value` with resident images, then (--full) the same K steps again with streamed images as "
                          "`value_gt_streamed`")
     ap.add_argument("--gt-layout", default="chw", choices=["chw", "hwc"],
                     help="memory layout of the synthetic ground-truth images: chw = planar contiguous [3,H,W] as the "
@@ -200,7 +208,39 @@ def parse():
                          "BigCity at bsz 64, release_scripts/bigcity.sh:73-92: `--config bigcity102m --bsz 64` is the "
                          "single-GPU form of that row); the optimizer hyper-parameters scale with it (lr_scale_mode sqrt)")
     ap.add_argument("--opt", action="append", default=[], help="engine option override, key=value")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: every extra pass, leg, probe and check (see the module docstring); a plain "
+                         "run does only what `value` / `ms_per_step` need")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps: write the last timed step's outputs as DIR/<name>.npy (float32 / float64)")
+    a = ap.parse_args()
+    if not a.full:  # the legs that the existing switches already turn off
+        a.no_cpu_baseline = a.no_kernel_timing = a.no_allreduce_leg = True
+        a.no_host_leg = a.no_trainer_leg = a.no_heavy_leg = True
+    return a
+
+
+DUMP_ROWS = 1 << 17  # sampled model rows in --dump-outputs: 59 floats each, 31 MB in all
+
+
+def dump_outputs(out_dir, gaussians, losses, sparsity):
+    """--dump-outputs: what clm_offload_train_one_batch (or the strategy's step) handed its caller in the last timed step
+    -- the batch's losses and visible fractions -- and the model it trained, read the way save_tensors reads it: the
+    five parameter tensors at a fixed seeded sample of DUMP_ROWS rows (ascending row order), every column."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "losses.npy"), np.array([float(l) for l in losses], dtype=np.float32))
+    if sparsity:
+        np.save(os.path.join(out_dir, "sparsity.npy"), np.array([float(s) for s in sparsity], dtype=np.float64))
+    gaussians._flush_before_read()
+    n = int(gaussians._xyz.shape[0])
+    idx = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:min(n, DUMP_ROWS)].sort().values
+    for name in ("xyz", "opacity", "scaling", "rotation"):
+        t = getattr(gaussians, "_" + name).detach()
+        np.save(os.path.join(out_dir, name + ".npy"), t[idx.to(t.device)].float().cpu().numpy())
+    mask = torch.zeros(n, dtype=torch.bool, device="cuda")
+    mask[idx.cuda()] = True
+    np.save(os.path.join(out_dir, "shs.npy"), gaussians._shs48_rows(mask).float().cpu().numpy())
 
 
 def make_gt_images(cams, scene, args_ns, width, height):
@@ -712,7 +752,7 @@ def heavy_leg(a):
     from the other legs).  The headline `value` / `config.scene` stay the slab scene of SURVEY 8d."""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), "--scene", "heavy", "--config", a.config, "--steps", str(a.heavy_steps),
-           "--warmup", "2", "--no-cpu-baseline", "--no-host-leg", "--no-trainer-leg", "--no-heavy-leg", "--gt", "resident",
+           "--warmup", "2", "--full", "--no-cpu-baseline", "--no-host-leg", "--no-trainer-leg", "--no-heavy-leg", "--gt", "resident",
            "--prime-seconds", "3", "--camera-order", a.camera_order, "--row-order", a.row_order]
     for kv in a.opt:
         cmd += ["--opt", kv]
@@ -859,7 +899,7 @@ def main():
     alloc_info = None
     try:
         _tabs = {}
-        if a.strategy == "clm_offload" and getattr(gaussians, "_parameters", None) is not None and gaussians._parameters.is_cuda:
+        if a.full and a.strategy == "clm_offload" and getattr(gaussians, "_parameters", None) is not None and gaussians._parameters.is_cuda:
             _st = gaussians.optimizer.cpu_adam.state[gaussians._parameters]
             _tabs = {"sh_rows": gaussians._parameters.data, "sh_exp_avg": _st["exp_avg"], "sh_exp_avg_sq": _st["exp_avg_sq"],
                      "sh_grad_rows": gaussians.parameters_grad_buffer, "xyz": gaussians._xyz.data}
@@ -890,7 +930,7 @@ def main():
                 alloc_info[_nm]["gather_GBps"] = round(_pl.gather_rate(_t, _idx, _scr), 1)
                 alloc_info[_nm]["gather_in_place_GBps"] = round(_pl.gather_rate(_t, _idx, _scr, in_place=True), 1)
             _idx = _scr = None
-        if _pl.probe_log():
+        if alloc_info is not None and _pl.probe_log():
             alloc_info["placement_probe"] = _pl.probe_log()
         _rows48 = None
         _tabs = _flat = _t = _st = None  # (no reference to the tables may outlive this block: the later legs free the model)
@@ -988,8 +1028,9 @@ def main():
     # device telemetry of the timed region (clm_gs_amd/telemetry.py): full snapshots before / after, sclk + socket power
     # sampled at 10 Hz by a host thread that only reads sysfs files -- nothing is enqueued on the device for it
     from clm_gs_amd import telemetry as _tel
-    _tel_main = _tel.Sampler()
-    _tel_main.__enter__()
+    _tel_main = _tel.Sampler() if a.full else None
+    if _tel_main:
+        _tel_main.__enter__()
     # ---- the timed region: exactly K steps, NO per-kernel event instrumentation inside it
     t0 = time.perf_counter()
     step_marks = []
@@ -1009,7 +1050,8 @@ def main():
     t_enq = time.perf_counter() - t0  # host: enqueue work + size readbacks, before the final fence
     fence()
     dt = time.perf_counter() - t0
-    _tel_main.__exit__(None, None, None)
+    if _tel_main:
+        _tel_main.__exit__(None, None, None)
     _lib.check_device_errors()  # a look-back scan / sort pass of the binning chain that gave up raises here
     host_wait = _lib.STATS["host_wait_s"]
     n_redo = int(_lib.STATS.get("isect_capacity_redo", 0))
@@ -1029,6 +1071,8 @@ def main():
         gaussians.flush_lazy_rows()  # replicas complete again (collective), outside the timed region
         torch.cuda.synchronize()
         completing_flush_ms = (time.perf_counter() - tf0) * 1e3
+    if a.dump_outputs and rank == 0:  # before any further pass moves the model on
+        dump_outputs(a.dump_outputs, gaussians, losses, sp)
 
     def replicas_equal():
         """Checksums (float64 sums of every parameter tensor) of the completed replicas, compared over the ranks."""
@@ -1039,13 +1083,13 @@ def main():
         allsums = [torch.empty_like(sums) for _ in range(world)]
         torch.distributed.all_gather(allsums, sums)
         return bool(all(torch.equal(x, allsums[0]) for x in allsums))
-    rep_equal = replicas_equal() if (world > 1 and a.strategy == "clm_offload") else None
+    rep_equal = replicas_equal() if (a.full and world > 1 and a.strategy == "clm_offload") else None
     n_loss_timed = len(all_losses)
     # ---- the same K steps once more with the ground-truth images where the reference keeps them (pinned host
     # memory, train.py:310-312), every batch's images uploaded on a side stream one batch ahead: reported beside
     # `value` as value_gt_streamed; the passes below (instrumented, solo) keep that mode
     dt_res = peak_res = None
-    if a.gt == "both" and gt_mode["v"] == "resident":
+    if a.full and a.gt == "both" and gt_mode["v"] == "resident":
         gt_to_pinned_host(cams)  # (no empty_cache: the allocator keeps the blocks the steps have been using)
         gt_mode["v"] = "host"
         feeder.start(a.warmup, cams[a.warmup * bsz:(a.warmup + 1) * bsz])  # ring buffers + first batch: before the clock
@@ -1113,7 +1157,7 @@ def main():
     # filters from that route are compared, index for index, with the exact pass over ALL rows after every waiting step
     # has been applied (flush_small -> clmgs_visibility_select_count without block flags).
     block_skip = None
-    if (a.strategy == "clm_offload" and a.residency == "hbm" and world == 1 and not grouped
+    if (a.full and a.strategy == "clm_offload" and a.residency == "hbm" and world == 1 and not grouped
             and getattr(gaussians, "small_deferred", False) and (gaussians._small_def or {}).get("hist")):
         from clm_gs_amd.strategies.base_engine import select_filters
         nxt = cams[a.warmup * bsz:(a.warmup + 1) * bsz]
@@ -1283,7 +1327,7 @@ def main():
             "value_instrumented": round(n_images * world / dt_instr, 4) if dt_instr else None,
             "gt_images": ("pinned host memory, every batch uploaded on a side stream one batch ahead (train.py:310-312)"
                           if (a.gt == "host" or a.residency == "host") else
-                          "all resident in HBM before the timed region (bench contract); value_gt_streamed = the same K steps with "
+                          "all resident in HBM before the timed region (bench contract); value_gt_streamed (--full) = the same K steps with "
                           "the images in pinned host memory, uploaded per batch as the reference does (train.py:310-312)"),
             "value_gt_streamed": round(n_images * world / dt_res, 4) if dt_res else None,
             "peak_gpu_bytes": int(peak),
@@ -1298,7 +1342,7 @@ def main():
                          "I_emitted_avg": round(I_emitted, 1), "I_emitted_first_last": [emitted[0], emitted[-1]] if emitted else None,
                          "touched_rows_per_batch": round(touched_avg, 1),
                          "small_blocks_flagged_fraction": small_flagged,
-                         "clocks": _tel_main.summary(), "alloc": alloc_info,
+                         "clocks": _tel_main.summary() if _tel_main else None, "alloc": alloc_info,
                          "block_skip_filters_equal": block_skip["filters_equal"] if block_skip else None,
                          "block_skip": block_skip,
                          "pixels": P, "tiles": T, "loss_first": round(loss_first, 6), "loss_last": round(loss_last, 6),

@@ -4,7 +4,7 @@
 mkdir -p gpurun_out/r06
 OUT=gpurun_out/r06/host_budget_curve.jsonl; : > $OUT
 for B in 0 1.8 5.4 10.75 16.1 21.6; do
-  timeout 600 python bench.py --steps 14 --warmup 2 --no-cpu-baseline --no-trainer-leg --no-heavy-leg --no-kernel-timing \
+  timeout 600 python bench.py --full --steps 14 --warmup 2 --no-cpu-baseline --no-trainer-leg --no-heavy-leg --no-kernel-timing \
     --no-host-staging-pair --host-budget-leg-gb 0 --host-budget-gb $B --host-steps 12 > /tmp/hb.log 2>/tmp/hb.err
   python - "$B" >> $OUT <<'PY'
 import json, sys

@@ -198,7 +198,7 @@ def test_bench_plain_python_starts_its_own_ranks(dev):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(CLMGS_DIST_BACKEND="gloo", CLMGS_SHARE_GPU="1")
     out = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                "--config", "small", "--prime-seconds", "0"], env=env)
+                "--config", "small", "--prime-seconds", "0", "--full"], env=env)
     lines = [l for l in out.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out[-2000:]
     j = json.loads(lines[0])
@@ -240,7 +240,7 @@ def test_bench_prints_its_line_when_the_allreduce_leg_does_not_finish(dev):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(CLMGS_DIST_BACKEND="gloo", CLMGS_SHARE_GPU="1")
     out = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                "--config", "small", "--prime-seconds", "0", "--allreduce-timeout", "0.05"], env=env)
+                "--config", "small", "--prime-seconds", "0", "--allreduce-timeout", "0.05", "--full"], env=env)
     lines = [l for l in out.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out[-2000:]
     j = json.loads(lines[0])
