@@ -359,8 +359,11 @@ def rasterize_to_pixels(
                 dy = m2[g, 1][None, :] - py[:, None]
                 a_, b_, c_ = cn[g, 0][None], cn[g, 1][None], cn[g, 2][None]
                 sigma = 0.5 * (a_ * dx * dx + c_ * dy * dy) + b_ * dx * dy
-                alpha = torch.clamp(op[g][None] * torch.exp(-sigma), max=0.999)
-                valid = (sigma.detach() >= 0) & (alpha.detach() >= 1.0 / 255.0)
+                # pairs with sigma < 0 are skipped: exp() sees 0 there, so a very negative sigma (non-positive-definite
+                # conic) cannot overflow to inf and turn the zero cotangent of a skipped pair into 0 * inf = NaN
+                neg = sigma.detach() < 0
+                alpha = torch.clamp(op[g][None] * torch.exp(-torch.where(neg, torch.zeros_like(sigma), sigma)), max=0.999)
+                valid = ~neg & (alpha.detach() >= 1.0 / 255.0)
                 a_eff = torch.where(valid, alpha, torch.zeros_like(alpha))
                 one_m = 1.0 - a_eff
                 incl = torch.cumprod(one_m, dim=1)  # next_T after k
