@@ -20,6 +20,11 @@
 //     lane) and one DPP chain (the ninth), and ONE 64 B partial line per (Gaussian, tile) leaves the wave
 //     (engine path: plain stores at the intersection's slot; gsplat-compatible op: float atomics), 64
 //     Gaussians at a time by 64 lanes;
+//   * both tile kernels are templates on the number of blended channels: 3, or 4 for gsplat's depth modes
+//     (rasterize_to_pixels with colors[..., 4]: clmgs_rasterize4_fwd / _bwd).  The fourth channel rides in the record's
+//     spare word, takes one more accumulator per pixel in the forward and a tenth wave-wide sum (a second DPP chain) and
+//     a tenth atomic in the backward's atomic route; the 3-channel instantiations are, instruction for instruction, the
+//     kernels they were without the parameter ("Depth");
 //   * blockIdx -> tile mapping is XCD-aware: each XCD's L2 sees a contiguous stripe of tiles,
 //     so neighbouring tiles' shared Gaussians hit in L2.
 #include <stdlib.h>
@@ -51,10 +56,16 @@ __device__ __forceinline__ float scaled_sigma(float as, float bs, float cs, floa
 }
 
 // Per-Gaussian raster record, one 64 B line: {x, y, opacity, conic.a | conic.b, conic.c, r, g |
-// b, -, -, - | -}.  The tile kernels gather ONE line per (Gaussian, tile) instead of touching
+// b, d, -, - | -}.  The tile kernels gather ONE line per (Gaussian, tile) instead of touching
 // four arrays (measured: 4.6 GB fetched per backward launch vs 1.3 GB algorithmic before).
+// d: the fourth blended channel of the NCH = 4 kernels (gsplat's render_mode="RGB+D": the camera-space depth rides as a
+// fourth colour); 0 in a 3-channel record.  It sits in the word next to blue, so the staging lane's gather of rec[2]
+// brings it along: no second gather per (Gaussian, tile).
 constexpr int REC_F4 = 4;
 
+// NCH (3 or 4) = blended channels.  Everything the fourth channel adds is under `if constexpr (NCH == 4)`; the
+// 3-channel instantiations compile to the code they were before the parameter existed.
+template <int NCH>
 __global__ void __launch_bounds__(256)
 raster_pack_kernel(int64_t n, const float* __restrict__ means2d, const float* __restrict__ conics,
                    const float* __restrict__ colors, const float* __restrict__ opacities,
@@ -63,15 +74,16 @@ raster_pack_kernel(int64_t n, const float* __restrict__ means2d, const float* __
        i += (int64_t)gridDim.x * blockDim.x) {
     const float2 m = *reinterpret_cast<const float2*>(means2d + 2 * i);
     const float* cn = conics + 3 * i;
-    const float* cl = colors + 3 * i;
+    const float* cl = colors + NCH * i;
     float4* rec = packed + REC_F4 * i;
     rec[0] = make_float4(m.x, m.y, opacities[i], cn[0]);
     rec[1] = make_float4(cn[1], cn[2], cl[0], cl[1]);
-    rec[2] = make_float4(cl[2], 0.f, 0.f, 0.f);
+    rec[2] = make_float4(cl[2], NCH == 4 ? cl[NCH - 1] : 0.f, 0.f, 0.f);
   }
 }
 
-// packed_grad line: x y ca cb | cc r g b | o - - - | -
+// packed_grad line: x y ca cb | cc r g b | o d - - | -   (d: NCH = 4 only)
+template <int NCH>
 __global__ void __launch_bounds__(256)
 raster_unpack_grad_kernel(int64_t n, const float4* __restrict__ packed_grad,
                           float* __restrict__ v_means2d, float* __restrict__ v_conics,
@@ -79,18 +91,20 @@ raster_unpack_grad_kernel(int64_t n, const float4* __restrict__ packed_grad,
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x) {
     const float4 a = packed_grad[REC_F4 * i], b = packed_grad[REC_F4 * i + 1];
-    const float o = packed_grad[REC_F4 * i + 2].x;
+    const float4 c = packed_grad[REC_F4 * i + 2];
     *reinterpret_cast<float2*>(v_means2d + 2 * i) = make_float2(a.x, a.y);
     v_conics[3 * i] = a.z; v_conics[3 * i + 1] = a.w; v_conics[3 * i + 2] = b.x;
-    v_colors[3 * i] = b.y; v_colors[3 * i + 1] = b.z; v_colors[3 * i + 2] = b.w;
-    v_opacities[i] = o;
+    v_colors[NCH * i] = b.y; v_colors[NCH * i + 1] = b.z; v_colors[NCH * i + 2] = b.w;
+    if constexpr (NCH == 4) v_colors[NCH * i + 3] = c.y;
+    v_opacities[i] = c.x;
   }
 }
 
+template <int NCH>
 struct TileLds {
   float4 a[64];   // x, y, opacity, conic.a
   float4 b[64];   // conic.b, conic.c, r, g
-  float c[64];    // b
+  float c[NCH - 2][64];  // b (, d)
   int meta[64];   // (offset in staging round << 4) | quadrant mask
 };
 
@@ -154,17 +168,23 @@ __device__ __forceinline__ int special_entry(float opac, float ca, float cb, flo
 #ifndef CLMGS_FWD_WAVES
 #define CLMGS_FWD_WAVES 6
 #endif
+// ... and the 4-channel forward: its four extra accumulators do not fit the 80 VGPRs of 6 waves without spills
+#ifndef CLMGS_FWD4_WAVES
+#define CLMGS_FWD4_WAVES 5
+#endif
 #ifndef CLMGS_FWD_ASM
 #define CLMGS_FWD_ASM 1
 #endif
-__global__ void __launch_bounds__(64, CLMGS_FWD_WAVES)
+template <int NCH>
+__global__ void __launch_bounds__(64, NCH == 4 ? CLMGS_FWD4_WAVES : CLMGS_FWD_WAVES)
 rasterize_fwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ packed,
                      const float* __restrict__ backgrounds,
                      int W, int H, int tile_w, int tile_h, const int32_t* __restrict__ offsets,
                      const int32_t* __restrict__ flatten_ids, float* __restrict__ render_colors,
                      float* __restrict__ render_alphas, int32_t* __restrict__ last_ids,
                      const int64_t* __restrict__ n_dev) {
-  __shared__ TileLds sm;
+  static_assert(NCH == 3 || NCH == 4, "3 or 4 blended channels");
+  __shared__ TileLds<NCH> sm;
   if (n_dev) n_isects = min(n_isects, *n_dev);  // device-side count (the launch was prepared for a capacity)
   const int n_tiles = tile_w * tile_h;
   const int n_tiles_total = C * n_tiles;
@@ -179,14 +199,14 @@ rasterize_fwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
   // Per-pixel state kept lean (the VGPR budget decides the waves per SIMD, and the issue rate of one-wave
   // workgroups grows with them): pixel centres are recomputed from the lane, and "this pixel still
   // accumulates" is the SIGN of T (T > 1e-4 while alive; a terminated or out-of-image pixel holds -T).
-  float T[PPL], cr[PPL], cg[PPL], cb[PPL];
+  float T[PPL], cr[PPL], cg[PPL], cb[PPL], cd[PPL];
   int last[PPL];
   const float px0 = tile_x0 + (float)qx + 0.5f, py0 = tile_y0 + (float)qy + 0.5f;
 #pragma unroll
   for (int k = 0; k < PPL; ++k) {
     const int j = tx * TILE + 8 * (k & 1) + qx;
     const int i = ty * TILE + 8 * (k >> 1) + qy;
-    cr[k] = cg[k] = cb[k] = 0.f; last[k] = 0;
+    cr[k] = cg[k] = cb[k] = cd[k] = 0.f; last[k] = 0;
     T[k] = ((i < H) && (j < W)) ? 1.f : -1.f;
   }
 
@@ -198,12 +218,13 @@ rasterize_fwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
   // Two-deep: ids run two rounds ahead of the blend loop, records one round ahead, so neither of
   // the two dependent gathers (id -> record) is ever waited for right after it is issued.
   float4 nA = make_float4(0.f, 0.f, 0.f, 0.f), nB = nA;
-  float nblue = 0.f;
+  float nblue = 0.f, ndep = 0.f;
   int cur_g = (rs + lane < re) ? flatten_ids[rs + lane] : -1;        // ids of round 0
   int nxt_g = (rs + 64 + lane < re) ? flatten_ids[rs + 64 + lane] : -1;  // ids of round 1
   if (cur_g >= 0) {
     const float4* rec = packed + REC_F4 * (size_t)cur_g;
     nA = rec[0]; nB = rec[1]; nblue = rec[2].x;
+    if constexpr (NCH == 4) ndep = rec[2].y;
   }
   // Per-quadrant termination (gsplat's per-pixel `done`, at the granularity this kernel branches on): bit k of
   // `alive` = some pixel of quadrant k still accumulates.  A quadrant whose 64 pixels have all terminated (or lie
@@ -215,12 +236,13 @@ rasterize_fwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
   for (int bs = rs; bs < re; bs += 64) {
     if (!alive) break;
     const float4 A = nA, B = nB;
-    const float blue = nblue;
+    const float blue = nblue, dep = ndep;
     const int mask = (cur_g >= 0) ? (quadrant_mask(A.x, A.y, A.z, A.w, B.x, B.y, tile_x0, tile_y0) & alive) : 0;
     cur_g = nxt_g;
     if (cur_g >= 0) {  // records of the next round (their ids arrived a round ago)
       const float4* rec = packed + REC_F4 * (size_t)cur_g;
       nA = rec[0]; nB = rec[1]; nblue = rec[2].x;
+      if constexpr (NCH == 4) ndep = rec[2].y;
     }
     {
       const int nidx = bs + 128 + lane;  // ids of the round after next
@@ -233,14 +255,17 @@ rasterize_fwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
     if (mask) {
       sm.a[pos] = make_float4(A.x, A.y, A.z, A.w * CONIC_DIAG);
       sm.b[pos] = make_float4(B.x * LOG2E, B.y * CONIC_DIAG, B.z, B.w);
-      sm.c[pos] = blue; sm.meta[pos] = (lane << 4) | mask;
+      sm.c[0][pos] = blue; sm.meta[pos] = (lane << 4) | mask;
+      if constexpr (NCH == 4) sm.c[1][pos] = dep;
     }
     __syncthreads();
     for (int t = 0; t < bn; ++t) {
       const float4 RA = sm.a[t];
       const float4 RB = sm.b[t];
       const int meta = __builtin_amdgcn_readfirstlane(sm.meta[t]);
-      const float rblue = sm.c[t];
+      const float rblue = sm.c[0][t];
+      float rdep = 0.f;
+      if constexpr (NCH == 4) rdep = sm.c[1][t];
       const int gi = bs + (meta >> 4);
       int gi_v;  // the wave-uniform index in a VGPR, once per entry (v_cndmask cannot take it as a scalar
       asm("v_mov_b32 %0, %1" : "=v"(gi_v) : "s"(gi));  // next to its mask; the compiler re-moved it per pass)
@@ -265,6 +290,7 @@ rasterize_fwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
           float vis = alpha * T[k];
           asm("v_cndmask_b32_e64 %0, 0, %0, %1" : "+v"(vis) : "s"(acc_m));
           cr[k] += RB.z * vis; cg[k] += RB.w * vis; cb[k] += rblue * vis;
+          if constexpr (NCH == 4) cd[k] += rdep * vis;
           asm("v_cndmask_b32_e64 %0, %0, %1, %2" : "+v"(last[k]) : "v"(gi_v), "s"(acc_m));
           asm("v_cndmask_b32_e64 %0, %0, %1, %2" : "+v"(T[k]) : "v"(next_T), "s"(acc_m));
           if (stop_m != 0ull) {
@@ -284,6 +310,7 @@ rasterize_fwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
           const bool term = valid && !goes_on;
           const float vis = acc ? alpha * T[k] : 0.f;
           cr[k] += RB.z * vis; cg[k] += RB.w * vis; cb[k] += rblue * vis;
+          if constexpr (NCH == 4) cd[k] += rdep * vis;
           last[k] = acc ? gi_v : last[k];
           T[k] = acc ? next_T : (term ? -T[k] : T[k]);
           // only a pass in which some pixel terminated can empty its quadrant: one ballot of `term` per pass
@@ -296,8 +323,11 @@ rasterize_fwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
     }
   }
 
-  float bgr = 0.f, bgg = 0.f, bgb = 0.f;
-  if (backgrounds) { bgr = backgrounds[3 * cam]; bgg = backgrounds[3 * cam + 1]; bgb = backgrounds[3 * cam + 2]; }
+  float bgr = 0.f, bgg = 0.f, bgb = 0.f, bgd = 0.f;
+  if (backgrounds) {
+    bgr = backgrounds[NCH * cam]; bgg = backgrounds[NCH * cam + 1]; bgb = backgrounds[NCH * cam + 2];
+    if constexpr (NCH == 4) bgd = backgrounds[NCH * cam + 3];
+  }
 #pragma unroll
   for (int k = 0; k < PPL; ++k) {
     const int j = tx * TILE + 8 * (k & 1) + qx;
@@ -305,9 +335,10 @@ rasterize_fwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
     if (i < H && j < W) {
       const size_t pix = ((size_t)cam * H + i) * W + j;
       const float Tf = fabsf(T[k]);
-      render_colors[3 * pix] = cr[k] + Tf * bgr;
-      render_colors[3 * pix + 1] = cg[k] + Tf * bgg;
-      render_colors[3 * pix + 2] = cb[k] + Tf * bgb;
+      render_colors[NCH * pix] = cr[k] + Tf * bgr;
+      render_colors[NCH * pix + 1] = cg[k] + Tf * bgg;
+      render_colors[NCH * pix + 2] = cb[k] + Tf * bgb;
+      if constexpr (NCH == 4) render_colors[NCH * pix + 3] = cd[k] + Tf * bgd;
       render_alphas[pix] = 1.f - Tf;
       last_ids[pix] = last[k];
     }
@@ -318,13 +349,14 @@ rasterize_fwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
 #ifndef CLMGS_BWD_LDS_REDUCE
 #define CLMGS_BWD_LDS_REDUCE 1
 #endif
+template <int NCH>
 struct TileLdsBwd {
   float4 a[64];
   float4 b[64];
-  float c[64];
+  float c[NCH - 2][64];
   int meta[64];
   int id[64];        // Gaussian id (cam*N + g) of the compacted slot, or its emit slot (PART)
-  __attribute__((aligned(16))) float acc[64][12];  // reduced per-Gaussian sums of this tile (9 used)
+  __attribute__((aligned(16))) float acc[64][12];  // reduced per-Gaussian sums of this tile (6 + NCH used)
 #if CLMGS_BWD_LDS_REDUCE
   __attribute__((aligned(16))) float red[8][64];   // transposed scratch of the wave-wide sums: [value][lane]
 #endif
@@ -342,7 +374,8 @@ __device__ unsigned long long g_dbg[16];
 // (slot = its emit index, see isect2_emit_kernel); the tile's wave STORES the reduced sums there
 // (zeros for culled / unreached entries, so every line is written exactly once per launch) and
 // raster_partials_sum_kernel adds each row's contiguous range.
-template <int DBG, bool PART>
+// NCH = 4: the atomic route only (a tenth sum g_d = sum fac * vd, a tenth atomic at word 9 of the gradient line).
+template <int DBG, bool PART, int NCH>
 __global__ void __launch_bounds__(64, CLMGS_BWD_WAVES)
 rasterize_bwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ packed,
                      const float* __restrict__ backgrounds,
@@ -353,7 +386,8 @@ rasterize_bwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
                      const float* __restrict__ v_render_alphas, float* __restrict__ packed_grad,
                      const int32_t* __restrict__ emit_slot, float4* __restrict__ partials,
                      const int64_t* __restrict__ n_dev) {
-  __shared__ TileLdsBwd sm;
+  static_assert(NCH == 3 || (NCH == 4 && !PART), "4 channels: atomic route only");
+  __shared__ TileLdsBwd<NCH> sm;
   if (n_dev) n_isects = min(n_isects, *n_dev);
   const int n_tiles = tile_w * tile_h;
   const int n_tiles_total = C * n_tiles;
@@ -379,7 +413,9 @@ rasterize_bwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
   int max_bin = -1;
   int qmax[PPL];  // per quadrant: the deepest contributor of its 64 pixels (wave-uniform)
   float bgr = 0.f, bgg = 0.f, bgb = 0.f;
-  if (backgrounds) { bgr = backgrounds[3 * cam]; bgg = backgrounds[3 * cam + 1]; bgb = backgrounds[3 * cam + 2]; }
+  if (backgrounds) { bgr = backgrounds[NCH * cam]; bgg = backgrounds[NCH * cam + 1]; bgb = backgrounds[NCH * cam + 2]; }
+  float vd[PPL], bgd = 0.f;  // the fourth channel's cotangents and background (NCH = 4)
+  if constexpr (NCH == 4) { if (backgrounds) bgd = backgrounds[NCH * cam + 3]; }
   const float px0 = tile_x0 + (float)qx + 0.5f, py0 = tile_y0 + (float)qy + 0.5f;
 #pragma unroll
   for (int k = 0; k < PPL; ++k) {
@@ -389,15 +425,18 @@ rasterize_bwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
       const size_t pix = ((size_t)cam * H + i) * W + j;
       const float Tf = 1.f - render_alphas[pix];
       bin[k] = last_ids[pix];
-      vr[k] = v_render_colors[3 * pix]; vg[k] = v_render_colors[3 * pix + 1]; vb[k] = v_render_colors[3 * pix + 2];
+      vr[k] = v_render_colors[NCH * pix]; vg[k] = v_render_colors[NCH * pix + 1]; vb[k] = v_render_colors[NCH * pix + 2];
+      vd[k] = 0.f;
+      if constexpr (NCH == 4) vd[k] = v_render_colors[NCH * pix + 3];
       float va = v_render_alphas ? v_render_alphas[pix] : 0.f;
       // d(out)/d(T_final) through the background term folds into the alpha cotangent
       va -= (bgr * vr[k] + bgg * vg[k] + bgb * vb[k]);
+      if constexpr (NCH == 4) va -= bgd * vd[k];
       Bk[k] = -Tf * va;
       T[k] = Tf;
       max_bin = max(max_bin, bin[k]);
     } else {
-      T[k] = 1.f; bin[k] = -1; vr[k] = vg[k] = vb[k] = Bk[k] = 0.f;
+      T[k] = 1.f; bin[k] = -1; vr[k] = vg[k] = vb[k] = vd[k] = Bk[k] = 0.f;
     }
   }
 #pragma unroll
@@ -411,7 +450,7 @@ rasterize_bwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
   // records one round ahead; nothing is waited for right after issue, and the waits never
   // include the previous round's atomics
   float4 nA = make_float4(0.f, 0.f, 0.f, 0.f), nB = nA;
-  float nblue = 0.f;
+  float nblue = 0.f, ndep = 0.f;
   int cur_g = (hi - lane >= rs) ? flatten_ids[hi - lane] : -1;
   int nxt_g = (hi - 64 - lane >= rs) ? flatten_ids[hi - 64 - lane] : -1;
   int cur_p = 0, nxt_p = 0;
@@ -428,11 +467,12 @@ rasterize_bwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
   if (cur_g >= 0) {
     const float4* rec = packed + REC_F4 * (size_t)cur_g;
     nA = rec[0]; nB = rec[1]; nblue = rec[2].x;
+    if constexpr (NCH == 4) ndep = rec[2].y;
   }
   for (int bh = hi; bh >= rs; bh -= 64) {
     const unsigned long long tA = DBG_CLK();
     const float4 A = nA, B = nB;
-    const float blue = nblue;
+    const float blue = nblue, dep = ndep;
     const int gid = cur_g;
     const int pid = cur_p;
     // Per-quadrant termination: entry gi matters to quadrant k only while gi <= qmax[k] (`valid` needs
@@ -447,6 +487,7 @@ rasterize_bwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
     if (cur_g >= 0) {
       const float4* rec = packed + REC_F4 * (size_t)cur_g;
       nA = rec[0]; nB = rec[1]; nblue = rec[2].x;
+      if constexpr (NCH == 4) ndep = rec[2].y;
     }
     {
       const int nidx = bh - 128 - lane;
@@ -466,8 +507,9 @@ rasterize_bwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
     if (mask) {
       sm.a[pos] = make_float4(A.x, A.y, A.z, A.w * CONIC_DIAG);
       sm.b[pos] = make_float4(B.x * LOG2E, B.y * CONIC_DIAG, B.z, B.w);
-      sm.c[pos] = blue; sm.meta[pos] = (lane << META_SHIFT) | special_entry(A.z, A.w, B.x, B.y) | mask;
+      sm.c[0][pos] = blue; sm.meta[pos] = (lane << META_SHIFT) | special_entry(A.z, A.w, B.x, B.y) | mask;
       sm.id[pos] = PART ? pid : gid;
+      if constexpr (NCH == 4) sm.c[1][pos] = dep;
     }
     __syncthreads();
     const unsigned long long tB = DBG_CLK();
@@ -476,12 +518,15 @@ rasterize_bwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
       const float4 RA = sm.a[t];
       const float4 RB = sm.b[t];
       const int meta = __builtin_amdgcn_readfirstlane(sm.meta[t]);
-      const float rblue = sm.c[t];
+      const float rblue = sm.c[0][t];
+      float rdep = 0.f;
+      if constexpr (NCH == 4) rdep = sm.c[1][t];
       const int gi = bh - (meta >> META_SHIFT);
       const bool special = (meta & META_SPECIAL) != 0;  // wave-uniform
       if (DBG == 3) { n_ent++; n_quad += __popc(meta & 15); }
       // moments of w = v_sigma over the tile: the five screen-space gradients are linear in them
       // (g_x = a Sx + b Sy, g_y = b Sx + c Sy, g_conic = Sxx/2, Sxy, Syy/2), applied at the flush
+      float g_d = 0.f;  // NCH = 4: sum fac * vd
       float g_r = 0.f, g_g = 0.f, g_b = 0.f, Sx = 0.f, Sy = 0.f, Sxx = 0.f, Sxy = 0.f, Syy = 0.f,
             g_o = 0.f;
       // OR of the passes' valid masks, kept as scalar mask arithmetic on the compares' results (a per-lane flag costs a
@@ -510,7 +555,8 @@ rasterize_bwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
               T[k] *= ra;
               const float fac = alpha * T[k];
               g_r += fac * vr[k]; g_g += fac * vg[k]; g_b += fac * vb[k];
-              const float cv = RB.z * vr[k] + RB.w * vg[k] + rblue * vb[k];
+              float cv = RB.z * vr[k] + RB.w * vg[k] + rblue * vb[k];
+              if constexpr (NCH == 4) { g_d += fac * vd[k]; cv += rdep * vd[k]; }
               // a saturated alpha (o * G > 0.999, clamped; special entries only) passes no gradient to sigma / opacity
               float v_alpha = T[k] * cv - ra * Bk[k];
               if (__builtin_expect(special, 0)) { asm volatile(""); v_alpha = (oa <= 0.999f) ? v_alpha : 0.f; }
@@ -544,6 +590,7 @@ rasterize_bwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
         const float4* rp = reinterpret_cast<const float4*>(&sm.red[lane >> 3][4 * (lane & 7)]);
         const float4 r0 = rp[0], r1 = rp[8];
         g_o = wave_sum_to_lane63(g_o);
+        if constexpr (NCH == 4) g_d = wave_sum_to_lane63(g_d);  // the transpose carries eight values: a second chain
         float u = ((r0.x + r0.y) + (r0.z + r0.w)) + ((r1.x + r1.y) + (r1.z + r1.w));
         u = dpp_add<0x111>(u);
         u = dpp_add<0x112>(u);
@@ -552,11 +599,13 @@ rasterize_bwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
         __builtin_amdgcn_wave_barrier();  // (the next entry's stores stay below this entry's loads)
         if ((lane & 7) == 7) sm.acc[t][lane >> 3] = u;   // Sx Sy Sxx Sxy | Syy r g b | o
         if (lane == 63) sm.acc[t][8] = g_o;
+        if constexpr (NCH == 4) { if (lane == 63) sm.acc[t][9] = g_d; }
 #else
         // 9 wave-wide sums: two 4-packs on the permlane-swap butterfly + one plain DPP chain
         const float u1 = wave_sum4_rows(Sx, Sy, Sxx, Sxy);       // lanes 15/31/47/63: Sx, Sxx, Sy, Sxy
         const float u2 = wave_sum4_rows(Syy, g_r, g_g, g_b);     //                    Syy, g, r, b
         g_o = wave_sum_to_lane63(g_o);
+        if constexpr (NCH == 4) g_d = wave_sum_to_lane63(g_d);
         if ((lane & 15) == 15) {
           const int r = lane >> 4;
           const int m = ((r & 1) << 1) | (r >> 1);               // row -> slot {0,2,1,3}
@@ -564,6 +613,7 @@ rasterize_bwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
           a[m] = u1;
           a[4 + m] = u2;
           if (lane == 63) a[8] = g_o;
+          if constexpr (NCH == 4) { if (lane == 63) a[9] = g_d; }
         }
 #endif
       }
@@ -592,7 +642,7 @@ rasterize_bwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
         if (PART_F4 > 3) dst[3] = z4;
       }
     } else if ((touched >> lane) & 1ull) {
-      // all nine atomics of a Gaussian land in its one 64 B gradient line
+      // all nine (ten: NCH = 4) atomics of a Gaussian land in its one 64 B gradient line
       float* dst = packed_grad + 4 * REC_F4 * (size_t)sm.id[lane];
       const float* a = sm.acc[lane];
       const float ca = sm.a[lane].w * CONIC_DIAG_INV, cb = sm.b[lane].x * CONIC_OFF_INV,
@@ -603,7 +653,7 @@ rasterize_bwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
       atomicAdd(dst + 3, a[3]);                   // conic b
       atomicAdd(dst + 4, 0.5f * a[4]);            // conic c
 #pragma unroll
-      for (int c = 5; c < 9; ++c) atomicAdd(dst + c, a[c]);
+      for (int c = 5; c < 6 + NCH; ++c) atomicAdd(dst + c, a[c]);
     }
     if (DBG == 3) {
       const unsigned long long tD = DBG_CLK();
@@ -678,7 +728,8 @@ extern "C" size_t clmgs_rasterize_pack_bytes(int C, int N) {
   return (size_t)C * (size_t)N * REC_F4 * sizeof(float4);
 }
 
-static int rasterize_fwd_impl(void* stream, int C, int N, int64_t n_isects,
+// nch: blended channels (3, or 4 = clmgs_rasterize4_*): colors / backgrounds / render_colors rows of nch floats
+static int rasterize_fwd_impl(int nch, void* stream, int C, int N, int64_t n_isects,
                               const float* means2d, const float* conics, const float* colors,
                               const float* opacities, const float* backgrounds, int width,
                               int height, int tile_size, int tile_width, int tile_height,
@@ -695,8 +746,13 @@ static int rasterize_fwd_impl(void* stream, int C, int N, int64_t n_isects,
   hipStream_t s = (hipStream_t)stream;
   const int64_t CN = (int64_t)C * N;
   if (means2d && n_isects > 0 && CN > 0) {  // means2d == NULL: `packed` was filled by the caller
-    hipLaunchKernelGGL(raster_pack_kernel, dim3(min(ceil_div(CN, 256), 256 * 8)), dim3(256), 0, s, CN,
-                       means2d, conics, colors, opacities, (float4*)packed);
+    const dim3 grid(min(ceil_div(CN, 256), 256 * 8));
+    if (nch == 4)
+      hipLaunchKernelGGL(raster_pack_kernel<4>, grid, dim3(256), 0, s, CN, means2d, conics, colors, opacities,
+                         (float4*)packed);
+    else
+      hipLaunchKernelGGL(raster_pack_kernel<3>, grid, dim3(256), 0, s, CN, means2d, conics, colors, opacities,
+                         (float4*)packed);
     CLMGS_LAUNCH_CHECK();
   }
   const int n_blocks = C * tile_width * tile_height;
@@ -705,9 +761,12 @@ static int rasterize_fwd_impl(void* stream, int C, int N, int64_t n_isects,
 #else
   const int fwd_pad = 0;
 #endif
-  hipLaunchKernelGGL(rasterize_fwd_kernel, dim3(n_blocks), dim3(64), fwd_pad, s, C, N, n_isects,
-                     (const float4*)packed, backgrounds, width, height, tile_width, tile_height,
-                     offsets, flatten_ids, render_colors, render_alphas, last_ids, n_dev);
+#define CLMGS_LAUNCH_FWD(NCH)                                                                          \
+  hipLaunchKernelGGL(rasterize_fwd_kernel<NCH>, dim3(n_blocks), dim3(64), fwd_pad, s, C, N, n_isects, \
+                     (const float4*)packed, backgrounds, width, height, tile_width, tile_height,       \
+                     offsets, flatten_ids, render_colors, render_alphas, last_ids, n_dev)
+  if (nch == 4) CLMGS_LAUNCH_FWD(4); else CLMGS_LAUNCH_FWD(3);
+#undef CLMGS_LAUNCH_FWD
   CLMGS_LAUNCH_CHECK();
   return 0;
 }
@@ -718,7 +777,19 @@ extern "C" int clmgs_rasterize_fwd(void* stream, int C, int N, int64_t n_isects,
                                    int height, int tile_size, int tile_width, int tile_height,
                                    const int32_t* offsets, const int32_t* flatten_ids, void* packed,
                                    float* render_colors, float* render_alphas, int32_t* last_ids) {
-  return rasterize_fwd_impl(stream, C, N, n_isects, means2d, conics, colors, opacities, backgrounds, width, height,
+  return rasterize_fwd_impl(3, stream, C, N, n_isects, means2d, conics, colors, opacities, backgrounds, width, height,
+                            tile_size, tile_width, tile_height, offsets, flatten_ids, packed, render_colors,
+                            render_alphas, last_ids, nullptr);
+}
+
+// Four blended channels (gsplat's rasterize_to_pixels with colors[..., 4], render_mode="RGB+D"): same contract, rows of 4.
+extern "C" int clmgs_rasterize4_fwd(void* stream, int C, int N, int64_t n_isects,
+                                    const float* means2d, const float* conics, const float* colors,
+                                    const float* opacities, const float* backgrounds, int width,
+                                    int height, int tile_size, int tile_width, int tile_height,
+                                    const int32_t* offsets, const int32_t* flatten_ids, void* packed,
+                                    float* render_colors, float* render_alphas, int32_t* last_ids) {
+  return rasterize_fwd_impl(4, stream, C, N, n_isects, means2d, conics, colors, opacities, backgrounds, width, height,
                             tile_size, tile_width, tile_height, offsets, flatten_ids, packed, render_colors,
                             render_alphas, last_ids, nullptr);
 }
@@ -731,12 +802,12 @@ extern "C" int clmgs_rasterize_fwd_dev(void* stream, int C, int N, int64_t capac
                                        const int32_t* flatten_ids, void* packed, float* render_colors,
                                        float* render_alphas, int32_t* last_ids) {
   CLMGS_CHECK_ARG(n_isects_dev && capacity > 0);
-  return rasterize_fwd_impl(stream, C, N, capacity, nullptr, nullptr, nullptr, nullptr, backgrounds, width, height,
+  return rasterize_fwd_impl(3, stream, C, N, capacity, nullptr, nullptr, nullptr, nullptr, backgrounds, width, height,
                             tile_size, tile_width, tile_height, offsets, flatten_ids, packed, render_colors,
                             render_alphas, last_ids, n_isects_dev);
 }
 
-static int rasterize_bwd_impl(void* stream, int C, int N, int64_t n_isects, const void* packed,
+static int rasterize_bwd_impl(int nch, void* stream, int C, int N, int64_t n_isects, const void* packed,
                               const float* backgrounds, int width, int height, int tile_size,
                               int tile_width, int tile_height, const int32_t* offsets,
                               const int32_t* flatten_ids, const float* render_alphas,
@@ -745,6 +816,11 @@ static int rasterize_bwd_impl(void* stream, int C, int N, int64_t n_isects, cons
                               float* v_means2d, float* v_conics, float* v_colors,
                               float* v_opacities, const int32_t* emit_slot,
                               const int64_t* row_cum, void* partials, const int64_t* n_dev) {
+  if (nch == 4 && (partials || emit_slot)) {  // before anything is written
+    clmgs::set_error("clmgs_rasterize4_bwd: the slot route (emit_slot / partials) blends three channels only; "
+                     "pass emit_slot = partials = NULL for the atomic route");
+    return CLMGS_EINVAL;
+  }
   CLMGS_CHECK_ARG(tile_size == TILE);
   CLMGS_CHECK_ARG(C >= 1 && width > 0 && height > 0 && tile_width * TILE >= width &&
                   tile_height * TILE >= height);
@@ -772,21 +848,26 @@ static int rasterize_bwd_impl(void* stream, int C, int N, int64_t n_isects, cons
 #else
     const int bwd_pad = 0;
 #endif
-#define CLMGS_LAUNCH_BWD(D, P)                                                                     \
-  hipLaunchKernelGGL((rasterize_bwd_kernel<D, P>), dim3(n_blocks), dim3(64), bwd_pad, s, C, N,     \
+#define CLMGS_LAUNCH_BWD(D, P, NCH)                                                                \
+  hipLaunchKernelGGL((rasterize_bwd_kernel<D, P, NCH>), dim3(n_blocks), dim3(64), bwd_pad, s, C, N, \
                      n_isects, (const float4*)packed, backgrounds, width, height, tile_width,      \
                      tile_height, offsets, flatten_ids, render_alphas, last_ids, v_render_colors,  \
                      v_render_alphas, (float*)packed_grad, emit_slot, (float4*)partials, n_dev)
 #ifdef CLMGS_PROFILE_BUILD
     if (part) {
-      if (dbg == 1) CLMGS_LAUNCH_BWD(1, true); else if (dbg == 3) CLMGS_LAUNCH_BWD(3, true);
-      else CLMGS_LAUNCH_BWD(0, true);
+      if (dbg == 1) CLMGS_LAUNCH_BWD(1, true, 3); else if (dbg == 3) CLMGS_LAUNCH_BWD(3, true, 3);
+      else CLMGS_LAUNCH_BWD(0, true, 3);
+    } else if (nch == 4) {
+      if (dbg == 1) CLMGS_LAUNCH_BWD(1, false, 4); else if (dbg == 2) CLMGS_LAUNCH_BWD(2, false, 4);
+      else if (dbg == 3) CLMGS_LAUNCH_BWD(3, false, 4); else CLMGS_LAUNCH_BWD(0, false, 4);
     } else {
-      if (dbg == 1) CLMGS_LAUNCH_BWD(1, false); else if (dbg == 2) CLMGS_LAUNCH_BWD(2, false);
-      else if (dbg == 3) CLMGS_LAUNCH_BWD(3, false); else CLMGS_LAUNCH_BWD(0, false);
+      if (dbg == 1) CLMGS_LAUNCH_BWD(1, false, 3); else if (dbg == 2) CLMGS_LAUNCH_BWD(2, false, 3);
+      else if (dbg == 3) CLMGS_LAUNCH_BWD(3, false, 3); else CLMGS_LAUNCH_BWD(0, false, 3);
     }
 #else
-    if (part) CLMGS_LAUNCH_BWD(0, true); else CLMGS_LAUNCH_BWD(0, false);
+    if (part) CLMGS_LAUNCH_BWD(0, true, 3);
+    else if (nch == 4) CLMGS_LAUNCH_BWD(0, false, 4);
+    else CLMGS_LAUNCH_BWD(0, false, 3);
 #endif
 #undef CLMGS_LAUNCH_BWD
     CLMGS_LAUNCH_CHECK();
@@ -797,8 +878,13 @@ static int rasterize_bwd_impl(void* stream, int C, int N, int64_t n_isects, cons
     }
   }
   if (v_means2d) {  // NULL: the caller consumes the packed gradient lines directly
-    hipLaunchKernelGGL(raster_unpack_grad_kernel, dim3(min(ceil_div(CN, 256), 256 * 8)), dim3(256), 0,
-                       s, CN, (const float4*)packed_grad, v_means2d, v_conics, v_colors, v_opacities);
+    const dim3 grid(min(ceil_div(CN, 256), 256 * 8));
+    if (nch == 4)
+      hipLaunchKernelGGL(raster_unpack_grad_kernel<4>, grid, dim3(256), 0, s, CN, (const float4*)packed_grad,
+                         v_means2d, v_conics, v_colors, v_opacities);
+    else
+      hipLaunchKernelGGL(raster_unpack_grad_kernel<3>, grid, dim3(256), 0, s, CN, (const float4*)packed_grad,
+                         v_means2d, v_conics, v_colors, v_opacities);
     CLMGS_LAUNCH_CHECK();
   }
   return 0;
@@ -813,7 +899,23 @@ extern "C" int clmgs_rasterize_bwd(void* stream, int C, int N, int64_t n_isects,
                                    float* v_means2d, float* v_conics, float* v_colors,
                                    float* v_opacities, const int32_t* emit_slot,
                                    const int64_t* row_cum, void* partials) {
-  return rasterize_bwd_impl(stream, C, N, n_isects, packed, backgrounds, width, height, tile_size, tile_width,
+  return rasterize_bwd_impl(3, stream, C, N, n_isects, packed, backgrounds, width, height, tile_size, tile_width,
+                            tile_height, offsets, flatten_ids, render_alphas, last_ids, v_render_colors,
+                            v_render_alphas, packed_grad, v_means2d, v_conics, v_colors, v_opacities, emit_slot,
+                            row_cum, partials, nullptr);
+}
+
+// Four blended channels, atomic route only: emit_slot / partials != NULL is refused before anything is written.
+extern "C" int clmgs_rasterize4_bwd(void* stream, int C, int N, int64_t n_isects, const void* packed,
+                                    const float* backgrounds, int width, int height, int tile_size,
+                                    int tile_width, int tile_height, const int32_t* offsets,
+                                    const int32_t* flatten_ids, const float* render_alphas,
+                                    const int32_t* last_ids, const float* v_render_colors,
+                                    const float* v_render_alphas, void* packed_grad,
+                                    float* v_means2d, float* v_conics, float* v_colors,
+                                    float* v_opacities, const int32_t* emit_slot,
+                                    const int64_t* row_cum, void* partials) {
+  return rasterize_bwd_impl(4, stream, C, N, n_isects, packed, backgrounds, width, height, tile_size, tile_width,
                             tile_height, offsets, flatten_ids, render_alphas, last_ids, v_render_colors,
                             v_render_alphas, packed_grad, v_means2d, v_conics, v_colors, v_opacities, emit_slot,
                             row_cum, partials, nullptr);
@@ -829,7 +931,7 @@ extern "C" int clmgs_rasterize_bwd_dev(void* stream, int C, int N, int64_t capac
                                        const float* v_render_alphas, const int32_t* emit_slot,
                                        const int64_t* row_cum, void* partials) {
   CLMGS_CHECK_ARG(n_isects_dev && capacity > 0 && emit_slot && partials);
-  return rasterize_bwd_impl(stream, C, N, capacity, packed, backgrounds, width, height, tile_size, tile_width,
+  return rasterize_bwd_impl(3, stream, C, N, capacity, packed, backgrounds, width, height, tile_size, tile_width,
                             tile_height, offsets, flatten_ids, render_alphas, last_ids, v_render_colors,
                             v_render_alphas, nullptr, nullptr, nullptr, nullptr, nullptr, emit_slot, row_cum,
                             partials, n_isects_dev);

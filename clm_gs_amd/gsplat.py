@@ -475,12 +475,14 @@ class _Rasterize(torch.autograd.Function):
         offsets = isect_offsets.contiguous()
         fids = flatten_ids.contiguous()
         th, tw = offsets.shape[1:]
-        out = torch.empty((C, height, width, 3), dtype=F32, device=dev)
+        nch = colors.shape[-1]  # 3, or 4 (the fourth channel rides in the record's spare word: clmgs_rasterize4_*)
+        fwd = L.clmgs_rasterize4_fwd if nch == 4 else L.clmgs_rasterize_fwd
+        out = torch.empty((C, height, width, nch), dtype=F32, device=dev)
         alphas = torch.empty((C, height, width, 1), dtype=F32, device=dev)
         last_ids = torch.empty((C, height, width), dtype=I32, device=dev)
         n_isects = fids.numel()
         packed = torch.empty((C * N, 16), dtype=F32, device=dev)  # one 64 B record per Gaussian
-        check(L.clmgs_rasterize_fwd(
+        check(fwd(
             stream(), C, N, n_isects, dptr(means2d, F32), dptr(conics, F32), dptr(colors, F32),
             dptr(opacities, F32), dptr(bg, F32, True), int(width), int(height), int(tile_size), tw,
             th, dptr(offsets, I32), dptr(fids, I32), dptr(packed), dptr(out), dptr(alphas),
@@ -506,7 +508,8 @@ class _Rasterize(torch.autograd.Function):
         v_colors = torch.empty(s_col, dtype=F32, device=dev)
         v_opacities = torch.empty(s_op, dtype=F32, device=dev)
         packed_grad = torch.empty_like(packed)
-        check(L.clmgs_rasterize_bwd(
+        bwd = L.clmgs_rasterize4_bwd if s_col[-1] == 4 else L.clmgs_rasterize_bwd
+        check(bwd(
             stream(), C, N, fids.numel(), dptr(packed), dptr(bg, F32, True), width, height,
             tile_size, tw, th, dptr(offsets), dptr(fids), dptr(alphas), dptr(last_ids),
             dptr(v_out, F32), dptr(v_alphas, F32, True), dptr(packed_grad), dptr(v_means2d),
@@ -518,15 +521,20 @@ def rasterize_to_pixels(means2d, conics, colors, opacities, image_width, image_h
                         isect_offsets, flatten_ids, backgrounds=None, masks=None, packed=False,
                         absgrad=False):
     """-> (render_colors[C,H,W,3], render_alphas[C,H,W,1]).  backgrounds: None, [3] or [C,3]
-    (the reference passes both shapes: no_offload/engine.py:96 vs base_engine.py:189-191)."""
+    (the reference passes both shapes: no_offload/engine.py:96 vs base_engine.py:189-191).
+    colors[..., 4] (gsplat's render_mode="RGB+D": the camera-space depth as a fourth colour) -> render_colors[C,H,W,4],
+    backgrounds None, [4] or [C,4]; channels 0..2 and the alphas are bit-identical to the 3-channel call."""
     if packed or absgrad or masks is not None:
         raise NotImplementedError("packed/absgrad/masks are not used by the CLM-GS engines")
-    if colors.shape[-1] != 3:
-        raise NotImplementedError("3 colour channels only")
+    nch = colors.shape[-1]
+    if nch not in (3, 4):
+        raise NotImplementedError("3 or 4 colour channels only")
     C = opacities.shape[0]
     if backgrounds is not None:
-        backgrounds = backgrounds.reshape(-1, 3).to(F32)
+        if backgrounds.shape[-1] != nch:
+            raise ValueError(f"backgrounds must hold {nch} values per camera, like colors")
+        backgrounds = backgrounds.reshape(-1, nch).to(F32)
         if backgrounds.shape[0] != C:
-            backgrounds = backgrounds.expand(C, 3)
+            backgrounds = backgrounds.expand(C, nch)
     return _Rasterize.apply(means2d, conics, colors, opacities, backgrounds, int(image_width),
                             int(image_height), int(tile_size), isect_offsets, flatten_ids)

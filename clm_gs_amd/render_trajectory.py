@@ -6,7 +6,10 @@ goes through the strategy's own single-camera eval entry (`*_eval_one_cam`, the 
 training) and is written as an 8-bit PNG.
 
     python -m clm_gs_amd.render_trajectory -m <model dir | .ply> --clm_offload --n_frames 120 \
-        --manual_height 30 --width 1920 --height 1080 [--output_dir DIR] [--hull x,y x,y ...]
+        --manual_height 30 --width 1920 --height 1080 [--output_dir DIR] [--hull x,y x,y ...] [--render_depth]
+
+--render_depth: next to each frame_%05d.png, depth_%05d.npy (float32 [H,W], expected depth D / alpha) and
+depth_%05d.png (the same map in grey, normalised to its min / max over the pixels with alpha > 0.5).
 
 `render_single_image` keeps the reference's signature and return value ([H,W,3] in [0,1] on the GPU).
 No imageio / PIL in this image: PNGs are written with zlib (8-bit RGB, no interlace).
@@ -92,39 +95,66 @@ def read_png(path):
     return raw[:, 1:].reshape(h, w, 3).copy()
 
 
-def render_single_image(camera, gaussians, background, save_path, args, scene=None):
-    """One frame through the strategy's eval entry, clamped to [0,1], saved to `save_path` unless
-    args.save_video (render_bigcity_images.py:638-722).  -> colors [H,W,3] on the GPU."""
+def eval_one_cam(camera, gaussians, background, args, scene=None, render_mode="RGB"):
+    """The strategy's single-camera eval entry -> image[3,H,W], or (image, depth[1,H,W], alpha[1,H,W]) with a depth
+    mode."""
+    kw = {} if render_mode == "RGB" else dict(render_mode=render_mode, return_alpha=True)
     if getattr(args, "naive_offload", False):
         from .strategies.naive_offload import naive_offload_eval_one_cam
-        img = naive_offload_eval_one_cam(gaussians=gaussians, scene=scene, camera=camera, background=background)
-    elif getattr(args, "clm_offload", False):
+        return naive_offload_eval_one_cam(gaussians=gaussians, scene=scene, camera=camera, background=background, **kw)
+    if getattr(args, "clm_offload", False):
         from .strategies.clm_offload import clm_offload_eval_one_cam
-        img = clm_offload_eval_one_cam(camera=camera, gaussians=gaussians, background=background, scene=scene)
-    elif getattr(args, "no_offload", False):
+        return clm_offload_eval_one_cam(camera=camera, gaussians=gaussians, background=background, scene=scene, **kw)
+    if getattr(args, "no_offload", False):
         from .strategies.no_offload import baseline_accumGrads_micro_step
         with torch.no_grad():
-            img, _, _, _ = baseline_accumGrads_micro_step(
+            res = baseline_accumGrads_micro_step(
                 means3D=gaussians.get_xyz, opacities=gaussians.get_opacity, scales=gaussians.get_scaling,
                 rotations=gaussians.get_rotation, shs=gaussians.get_features, sh_degree=gaussians.active_sh_degree,
-                camera=camera, background=background, mode="eval")
+                camera=camera, background=background, mode="eval", **kw)
+        return res[0] if render_mode == "RGB" else (res[0], res[4], res[5])
+    raise ValueError("Invalid offload configuration")
+
+
+def depth_to_grey(depth, mask):
+    """[H,W] float depth -> [H,W,3] uint8 grey, normalised to the min / max over the pixels of `mask` (over all
+    pixels if it is empty); a constant map comes out black."""
+    sel = depth[mask] if mask.any() else depth
+    lo, hi = float(sel.min()), float(sel.max())
+    g = np.clip((depth - lo) / (hi - lo), 0.0, 1.0) if hi > lo else np.zeros_like(depth)
+    return np.repeat((g * 255).astype(np.uint8)[..., None], 3, axis=2)
+
+
+def render_single_image(camera, gaussians, background, save_path, args, scene=None, depth_path=None):
+    """One frame through the strategy's eval entry, clamped to [0,1], saved to `save_path` unless
+    args.save_video (render_bigcity_images.py:638-722).  -> colors [H,W,3] on the GPU.
+    depth_path: the same render also blends the depth channel ("RGB+ED"); the expected depth goes to
+    depth_path + ".npy" (float32 [H,W]) and, in grey over the range of the pixels with alpha > 0.5, depth_path + ".png"."""
+    if depth_path:
+        img, depth, alpha = eval_one_cam(camera, gaussians, background, args, scene, render_mode="RGB+ED")
     else:
-        raise ValueError("Invalid offload configuration")
+        img = eval_one_cam(camera, gaussians, background, args, scene)
     colors = torch.clamp(img, 0.0, 1.0)
     if colors.shape[0] == 3:
         colors = colors.permute(1, 2, 0)
     if save_path and not getattr(args, "save_video", False):
         write_png(save_path, (colors * 255).to(torch.uint8).cpu().numpy())
+    if depth_path:
+        d = depth[0].float().cpu().numpy()
+        np.save(depth_path + ".npy", d)
+        write_png(depth_path + ".png", depth_to_grey(d, alpha[0].cpu().numpy() > 0.5))
     return colors
 
 
 def render_trajectory(gaussians, cameras, args, output_dir, background=None, log=None):
-    """All frames of a path -> output_dir/frame_%05d.png; returns the list of paths."""
+    """All frames of a path -> output_dir/frame_%05d.png (with args.render_depth also depth_%05d.npy / .png);
+    returns the list of frame paths."""
     os.makedirs(output_dir, exist_ok=True)
     paths = []
     for i, cam in enumerate(cameras):
         p = os.path.join(output_dir, f"frame_{i:05d}.png")
-        render_single_image(cam, gaussians, background, p, args, scene=None)
+        dp = os.path.join(output_dir, f"depth_{i:05d}") if getattr(args, "render_depth", False) else None
+        render_single_image(cam, gaussians, background, p, args, scene=None, depth_path=dp)
         paths.append(p)
     if log is not None:
         log.write(f"Rendering completed. Images saved to: {output_dir}\n")
@@ -155,6 +185,8 @@ def main(argv=None):
     ap.add_argument("--hull", nargs="*", default=None, help="closed polyline as x,y pairs (default: the BigCity hull)")
     ap.add_argument("--white_background", action="store_true")
     ap.add_argument("--save_video", action="store_true", help="skip the per-frame PNGs (no video writer in this image)")
+    ap.add_argument("--render_depth", action="store_true",
+                    help="also write depth_%%05d.npy (float32 expected depth) and depth_%%05d.png (grey) per frame")
     g = ap.add_mutually_exclusive_group()
     g.add_argument("--clm_offload", action="store_true")
     g.add_argument("--naive_offload", action="store_true")
@@ -163,7 +195,7 @@ def main(argv=None):
     if not (a.clm_offload or a.naive_offload or a.no_offload):
         a.clm_offload = True
     args = utils.default_args(bsz=4)
-    for k in ("clm_offload", "naive_offload", "no_offload", "save_video"):
+    for k in ("clm_offload", "naive_offload", "no_offload", "save_video", "render_depth"):
         setattr(args, k, getattr(a, k))
     utils.set_args(args)
     utils.set_img_size(a.height, a.width)

@@ -80,14 +80,41 @@ def torch_compiled_loss(image, image_gt_original):
     return loss_combined(image, image_gt, ssim_loss)
 
 
+RENDER_MODES = ("RGB", "RGB+D", "RGB+ED")
+
+
+def colors_with_depth(colors, depths, backgrounds, render_mode):
+    """The rasterizer's inputs for a render mode (gsplat's rasterization(render_mode=...)): with a depth mode the
+    camera-space depths[C,N] ride as a fourth colour channel whose background is 0."""
+    if render_mode not in RENDER_MODES:
+        raise ValueError(f"render_mode must be one of {RENDER_MODES}, got {render_mode!r}")
+    if render_mode == "RGB":
+        return colors, backgrounds
+    colors = torch.cat([colors, depths.unsqueeze(-1)], dim=-1)
+    if backgrounds is not None:
+        backgrounds = torch.cat([backgrounds, backgrounds.new_zeros(backgrounds.shape[:-1] + (1,))], dim=-1)
+    return colors, backgrounds
+
+
+def split_depth(rendered, alphas, render_mode):
+    """rendered[1,H,W,4], alphas[1,H,W,1] -> (image[3,H,W] view, depth[1,H,W], alpha[1,H,W]): the accumulated depth
+    sum w_i z_i ("RGB+D") or the expected depth D / clamp(alpha, 1e-10) ("RGB+ED", gsplat's definition)."""
+    depth, alpha = rendered[..., 3], alphas[..., 0]
+    if render_mode == "RGB+ED":
+        depth = depth / alpha.clamp(min=1e-10)
+    return rendered[..., :3].squeeze(0).permute(2, 0, 1), depth, alpha
+
+
 def _tile_counts(w, h):
     return math.ceil(w / float(TILE_SIZE)), math.ceil(h / float(TILE_SIZE))
 
 
 def pipeline_forward_one_step(filtered_opacity_gpu, filtered_scaling_gpu, filtered_rotation_gpu,
                               filtered_xyz_gpu, filtered_shs, camera, scene, gaussians, background,
-                              pipe_args, eval=False):
-    """One camera over the gathered rows, SH through autograd (base_engine.py:106-207)."""
+                              pipe_args, eval=False, render_mode="RGB", return_alpha=False):
+    """One camera over the gathered rows, SH through autograd (base_engine.py:106-207).
+    render_mode "RGB+D" / "RGB+ED": a fourth result depth[1,H,W] (see split_depth), and with return_alpha a fifth,
+    alpha[1,H,W]."""
     image_width, image_height = int(utils.get_img_width()), int(utils.get_img_height())
     fx = image_width / (2 * math.tan(camera.FoVx * 0.5))
     fy = image_height / (2 * math.tan(camera.FoVy * 0.5))
@@ -113,9 +140,13 @@ def pipeline_forward_one_step(filtered_opacity_gpu, filtered_scaling_gpu, filter
                                             tile_height=tile_height, packed=False)
     isect_offsets = isect_offset_encode(isect_ids, 1, tile_width, tile_height)
     backgrounds = background.reshape(1, 3) if background is not None else None
-    rendered_image, _ = rasterize_to_pixels(
+    colors, backgrounds = colors_with_depth(colors, depths, backgrounds, render_mode)
+    rendered_image, alphas = rasterize_to_pixels(
         means2d=means2D, conics=conics, colors=colors, opacities=opacities,
         image_width=image_width, image_height=image_height, tile_size=TILE_SIZE,
         isect_offsets=isect_offsets, flatten_ids=flatten_ids, backgrounds=backgrounds)
+    if render_mode != "RGB":
+        rendered_image, depth, alpha = split_depth(rendered_image, alphas, render_mode)
+        return (rendered_image, means2D, radiis, depth) + ((alpha,) if return_alpha else ())
     rendered_image = rendered_image.squeeze(0).permute(2, 0, 1)  # [3,H,W] view, no copy
     return rendered_image, means2D, radiis

@@ -881,8 +881,9 @@ def clm_offload_train_one_batch(gaussians, scene, batched_cameras, parameters_gr
                                  background, pipe_args, comm_stream, perm_generator, args)
 
 
-def clm_offload_eval_one_cam(camera, gaussians, background, scene):
-    """Single-camera render of the visible rows (engine.py:928-979) -> image[3,H,W]."""
+def clm_offload_eval_one_cam(camera, gaussians, background, scene, render_mode="RGB", return_alpha=False):
+    """Single-camera render of the visible rows (engine.py:928-979) -> image[3,H,W]; with render_mode "RGB+D" /
+    "RGB+ED" -> (image, depth[1,H,W]) or, with return_alpha, (image, depth, alpha[1,H,W])."""
     with torch.no_grad():
         a_ = utils.get_args()
         dp_partial = bool(getattr(gaussians, "lazy_rows", False) and dp.active()
@@ -905,6 +906,7 @@ def clm_offload_eval_one_cam(camera, gaussians, background, scene):
         rot = gaussians.rotation_activation(gaussians._rotation.detach()[f])
         shs = torch.empty((f.shape[0], 48), device=xyz.device)
         send_shs2gpu_stream(shs, gaussians._parameters.data, f)
-        image, _, _ = pipeline_forward_one_step(opa, sca, rot, xyz, shs, camera, scene, gaussians,
-                                                background, None, eval=True)
-    return image
+        res = pipeline_forward_one_step(opa, sca, rot, xyz, shs, camera, scene, gaussians,
+                                        background, None, eval=True, render_mode=render_mode,
+                                        return_alpha=return_alpha)
+    return res[0] if render_mode == "RGB" else (res[0],) + tuple(res[3:])

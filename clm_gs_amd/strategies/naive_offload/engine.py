@@ -72,15 +72,16 @@ def naive_offload_train_one_batch(gaussians, scene, batched_cameras, background,
     return losses, visibility
 
 
-def naive_offload_eval_one_cam(gaussians, scene, camera, background):
-    """Whole model to the GPU, one render (engine.py:20-46) -> image[3,H,W]."""
+def naive_offload_eval_one_cam(gaussians, scene, camera, background, render_mode="RGB", return_alpha=False):
+    """Whole model to the GPU, one render (engine.py:20-46) -> image[3,H,W]; with render_mode "RGB+D" / "RGB+ED"
+    -> (image, depth[1,H,W]) or, with return_alpha, (image, depth, alpha[1,H,W])."""
     with torch.no_grad():
         rep = _DeviceReplica(gaussians)
-        image, _, _ = pipeline_forward_one_step(
+        res = pipeline_forward_one_step(
             gaussians.opacity_activation(rep._opacity), gaussians.scaling_activation(rep._scaling),
             gaussians.rotation_activation(rep._rotation), rep._xyz, rep.shs, camera, scene, gaussians,
-            background, None, eval=True)
-    return image
+            background, None, eval=True, render_mode=render_mode, return_alpha=return_alpha)
+    return res[0] if render_mode == "RGB" else (res[0],) + tuple(res[3:])
 
 
 def render_single_image(gaussians, scene, camera, background=None):

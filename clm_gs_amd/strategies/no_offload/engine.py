@@ -9,13 +9,16 @@ from ... import utils
 from ...densification import update_densification_stats_baseline_accum_grads
 from ...gsplat import (fully_fused_projection, isect_offset_encode, isect_tiles,
                        rasterize_to_pixels, spherical_harmonics)
-from ..base_engine import torch_compiled_loss
+from ..base_engine import colors_with_depth, split_depth, torch_compiled_loss
 
 
 def baseline_accumGrads_micro_step(means3D, opacities, scales, rotations, shs, sh_degree, camera,
-                                   background, mode="train", tile_size=16):
+                                   background, mode="train", tile_size=16, render_mode="RGB",
+                                   return_alpha=False):
     """One camera: K from FoV, projection(N) -> SH(masked) -> +0.5 clamp -> tile binning ->
-    rasterize -> [3,H,W].  Returns (image, means2D (grad retained), radii, None)."""
+    rasterize -> [3,H,W].  Returns (image, means2D (grad retained), radii, None); with render_mode "RGB+D" /
+    "RGB+ED" a fifth result depth[1,H,W] (accumulated / expected depth, base_engine.split_depth), and with
+    return_alpha a sixth, alpha[1,H,W]."""
     args = utils.get_args()
     image_width, image_height = int(utils.get_img_width()), int(utils.get_img_height())
     fx = image_width / (2 * math.tan(camera.FoVx * 0.5))
@@ -40,10 +43,14 @@ def baseline_accumGrads_micro_step(means3D, opacities, scales, rotations, shs, s
                                             tile_size=tile_size, tile_width=tile_width,
                                             tile_height=tile_height, packed=False)
     isect_offsets = isect_offset_encode(isect_ids, 1, tile_width, tile_height)
-    rendered_image, _ = rasterize_to_pixels(
+    colors, background = colors_with_depth(colors, depths, background, render_mode)
+    rendered_image, alphas = rasterize_to_pixels(
         means2d=means2D, conics=conics, colors=colors, opacities=opacities.squeeze(1).unsqueeze(0),
         image_width=image_width, image_height=image_height, tile_size=tile_size,
         isect_offsets=isect_offsets, flatten_ids=flatten_ids, backgrounds=background)
+    if render_mode != "RGB":
+        rendered_image, depth, alpha = split_depth(rendered_image, alphas, render_mode)
+        return (rendered_image, means2D, radiis, None, depth) + ((alpha,) if return_alpha else ())
     rendered_image = rendered_image.squeeze(0).permute(2, 0, 1)  # [3,H,W] view, no copy
     return rendered_image, means2D, radiis, None
 

@@ -168,6 +168,30 @@ int clmgs_rasterize_bwd(void* stream, int C, int N, int64_t n_isects, const void
                         float* v_conics, float* v_colors, float* v_opacities,
                         const int32_t* emit_slot, const int64_t* row_cum, void* partials);
 
+/* ---- gsplat.rasterize_to_pixels with colors[..., 4]  (what gsplat's rasterization(render_mode="RGB+D" / "RGB+ED")
+ * calls: the camera-space depth rides as a fourth colour channel and is blended with the same weights)
+ * Same contract as clmgs_rasterize_fwd / _bwd with rows of four: colors[C*N,4], backgrounds[C,4] or NULL ->
+ * render_colors[C,H,W,4]; v_render_colors[C,H,W,4] -> v_colors[C*N,4].  `packed` / `packed_grad` have the same
+ * sizes (clmgs_rasterize_pack_bytes): the fourth channel travels in the record's spare word next to blue, its
+ * gradient in word 9 of the gradient line (x y ca cb | cc r g b | o d).  Channels 0..2, render_alphas and last_ids
+ * are bit-identical to clmgs_rasterize_fwd on the same inputs.  means2d == NULL: `packed` already holds 4-channel
+ * records (an earlier clmgs_rasterize4_fwd; clmgs_preprocess_fwd writes 3-channel ones, fourth word 0).
+ * Backward: the atomic route only -- emit_slot or partials != NULL returns CLMGS_EINVAL before anything is written. */
+int clmgs_rasterize4_fwd(void* stream, int C, int N, int64_t n_isects, const float* means2d,
+                         const float* conics, const float* colors, const float* opacities,
+                         const float* backgrounds, int width, int height, int tile_size,
+                         int tile_width, int tile_height, const int32_t* offsets,
+                         const int32_t* flatten_ids, void* packed, float* render_colors,
+                         float* render_alphas, int32_t* last_ids);
+int clmgs_rasterize4_bwd(void* stream, int C, int N, int64_t n_isects, const void* packed,
+                         const float* backgrounds, int width, int height, int tile_size,
+                         int tile_width, int tile_height, const int32_t* offsets,
+                         const int32_t* flatten_ids, const float* render_alphas,
+                         const int32_t* last_ids, const float* v_render_colors,
+                         const float* v_render_alphas, void* packed_grad, float* v_means2d,
+                         float* v_conics, float* v_colors, float* v_opacities,
+                         const int32_t* emit_slot, const int64_t* row_cum, void* partials);
+
 /* ---- device-count forms (engine fast path): the data-dependent size I of a camera need not reach the host
  * before the consumers of the list are enqueued.  The reference reads it back synchronously
  * (strategies/base_engine.py:64-69 `counts.cpu()`, gsplat.isect_tiles' cum[-1].item()); here `capacity` (a
