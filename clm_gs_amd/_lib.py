@@ -171,16 +171,17 @@ def check(rc):
 
 
 def check_device_errors():
-    """Raises if a look-back scan / sort pass of the binning chain timed out since the last check
-    (clmgs_device_errors; synchronises the device).  Called where the host synchronises anyway."""
+    """Raises if a kernel has raised the library's device error word since the last check (clmgs_device_errors;
+    synchronises the device).  Called where the host synchronises anyway.  The one value in use is 4 (the deferred
+    small-attribute Adam); 1 and 2 are retired."""
     bits = ctypes.c_uint32(0)
     check(lib().clmgs_device_errors(ctypes.byref(bits), 1))
     if bits.value & 4:
         raise ClmgsError("deferred small-attribute Adam: a block of rows was further behind than the recorded step history "
                          "(clmgs_adam_small_deferred, device error bit 4): its parameters are wrong")
     if bits.value:
-        raise ClmgsError(f"binning chain: look-back timed out on the device (bits {bits.value}: 1 = scan, 2 = sort pass); "
-                         "the intersection lists built since the last check are invalid")
+        raise ClmgsError(f"device error word {bits.value}: no kernel of this library raises that value (4 is the only one "
+                         "in use); the results since the last check cannot be trusted")
 
 
 HOST_REGIONS = None  # set to {} to accumulate host wall time per engine region (diagnostics)

@@ -12,7 +12,19 @@
 #include "radix.h"
 
 namespace clmgs {
-uint32_t* device_error_word();  // isect.hip: the library's zero-initialised device error word
+// Device error word: value 4 = adam_small_deferred_kernel met a block further behind than its step history (values 1
+// and 2 are retired: no kernel raises them).  Read (and cleared) by clmgs_device_errors().
+__device__ uint32_t g_dev_err;
+static uint32_t* device_error_word() {
+  static thread_local uint32_t* p[16] = {nullptr};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = 0;
+  if (!p[dev]) {
+    void* a = nullptr;
+    if (hipGetSymbolAddress(&a, HIP_SYMBOL(g_dev_err)) == hipSuccess) p[dev] = (uint32_t*)a;
+  }
+  return p[dev];
+}
 
 
 template <typename IdxT>
@@ -626,7 +638,7 @@ adam_small_deferred_kernel(int64_t n, SmallAdam t, float4* __restrict__ packed_p
     if (k > n_hist) {
       // further behind than the recorded history reaches (the caller keeps kmax steps and this kernel forces a block at
       // k == kmax, so this cannot happen while that invariant holds): replaying with another step's constants would be
-      // silently wrong -- raise bit 2 of the device error word (clmgs_device_errors) and replay what IS recorded
+      // silently wrong -- raise value 4 of the device error word (clmgs_device_errors) and replay what IS recorded
       if (tid == 0 && dev_err) atomicOr(dev_err, 4u);
       k = n_hist;
     }
@@ -1118,7 +1130,7 @@ extern "C" int clmgs_small_deferred_kmax(void) { return SD_KMAX; }
 // block is brought to to_step (no camera needed).  Blocks more than n_hist steps behind are an error of the caller
 // (it must flush at least every n_hist steps): checked on the host side by construction (a block is never left
 // behind for more than kmax steps: the kernel forces it at k == kmax, and the caller trims its history to kmax entries);
-// the kernel itself raises bit 2 of the device error word (clmgs_device_errors) if it ever meets one.
+// the kernel itself raises value 4 of the device error word (clmgs_device_errors) if it ever meets one.
 extern "C" int clmgs_adam_small_deferred(void* stream, int64_t n, float* const* params, float* const* exp_avg,
                                          float* const* exp_avg_sq, void* packed_p, const void* packed_g,
                                          const int32_t* g_stamp, int32_t* blk_last, int to_step, int n_hist,
@@ -1162,6 +1174,19 @@ extern "C" int clmgs_adam_small_deferred(void* stream, int64_t n, float* const* 
                      (float)beta1, (float)beta2, ob1, ob2, (float)eps, grad_scale, C, viewmats, Ks, (float)width,
                      (float)height, eps2d, near_plane, far_plane, flush_all, blk_flag, n_hist, device_error_word());
   CLMGS_LAUNCH_CHECK();
+  return 0;
+}
+
+// *out = the device error word (4 = clmgs_adam_small_deferred met a block further behind than the step history it was
+// given: those rows' parameters are wrong; 1 and 2 are retired); cleared when `reset`.  Synchronises the device.
+extern "C" int clmgs_device_errors(uint32_t* out, int reset) {
+  CLMGS_CHECK_ARG(out);
+  CLMGS_HIP(hipDeviceSynchronize());
+  CLMGS_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(clmgs::g_dev_err), sizeof(uint32_t)));
+  if (reset && *out) {
+    const uint32_t z = 0;
+    CLMGS_HIP(hipMemcpyToSymbol(HIP_SYMBOL(clmgs::g_dev_err), &z, sizeof(z)));
+  }
   return 0;
 }
 

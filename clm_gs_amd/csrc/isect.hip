@@ -10,58 +10,8 @@
 #include "radix.h"
 #include "vis_math.h"
 #include "isect_math.h"
-#ifdef CLMGS_PROFILE_BUILD
-#include "onesweep.h"  // round 4's one-launch-per-digit passes by decoupled look-back: measured slower, profiling builds only
-#endif
 
 namespace clmgs {
-// Device error word of the look-back primitives (onesweep.h): bit 0 = scan look-back timed out, bit 1 = sort
-// look-back timed out.  Read (and cleared) by clmgs_device_errors().
-__device__ uint32_t g_dev_err;
-uint32_t* device_error_word() {
-  static thread_local uint32_t* p[16] = {nullptr};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = 0;
-  if (!p[dev]) {
-    void* a = nullptr;
-    if (hipGetSymbolAddress(&a, HIP_SYMBOL(g_dev_err)) == hipSuccess) p[dev] = (uint32_t*)a;
-  }
-  return p[dev];
-}
-
-// CLMGS_LEGACY_BINNING=1: the round-3 chain (three launches per radix digit, three per scan) -- kept for A/B
-// measurements and as the second, independent route of the equality tests.
-static int env_int(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return (e && e[0]) ? atoi(e) : dflt;
-}
-static int os_rounds(const char* name, int dflt) {
-  const int r = env_int(name, dflt);
-  return (r == 1 || r == 2 || r == 4 || r == 8) ? r : dflt;
-}
-// Routes through the binning chain.  The PRODUCT library has ONE (BIN_FUSED):
-//   fused    three kernels per radix digit (multi-chunk histogram, segment-per-thread row scan, scatter); the two scans
-//            folded into their producers + ONE finishing launch each; the tile ids are produced chunk by chunk with
-//            coalesced stores by the kernel that also counts the first digit of the tile sort (isect2_emit_hist_kernel,
-//            round 5); the last tile-sort pass writes flatten_ids / emit_slot directly.
-// A profiling build (make PROFILE=1) can select the older ones per call with CLMGS_BINNING (the equality test of
-// tests/test_gpu_ops.py runs in that build); all produce the same lists element for element:
-//   r4       round 4's default: a thread-per-rank emit kernel (uncoalesced 4 + 8 B stores) + a separate histogram
-//   lookback round 4's single-launch passes by decoupled look-back (onesweep.h) -- measured SLOWER on MI355X (a sort
-//            pass of 3.3 M keys 60-79 us against 30 + 11 + 11 us, of 9.3 M keys 155-205 against 106 + 34 + 34;
-//            DESIGN.md section 3)
-//   legacy   the round-3 chain
-enum { BIN_FUSED = 0, BIN_LOOKBACK = 1, BIN_LEGACY = 2, BIN_R4 = 3 };
-static int binning_route() {
-#ifdef CLMGS_PROFILE_BUILD
-  const char* e = getenv("CLMGS_BINNING");
-  if (e && e[0] == 'l' && e[1] == 'o') return BIN_LOOKBACK;
-  if (e && e[0] == 'l' && e[1] == 'e') return BIN_LEGACY;
-  if (e && e[0] == 'r' && e[1] == '4') return BIN_R4;
-#endif
-  return BIN_FUSED;
-}
-static bool legacy_binning() { return binning_route() == BIN_LEGACY; }
 
 __global__ void __launch_bounds__(256)
 isect_count_kernel(int64_t CN, const float* __restrict__ means2d, const int32_t* __restrict__ radii,
@@ -189,8 +139,7 @@ extern "C" int clmgs_isect_emit_sort(void* stream, int C, int N, int64_t n_isect
   CLMGS_LAUNCH_CHECK();
   uint64_t* sorted = nullptr;  // the caller's isect_ids doubles as the second key buffer
   int rc = radix_sort_pairs<uint64_t>(s, n_isects, keys_a, (uint64_t*)isect_ids, vals_a, vals_b,
-                                      flatten_ids, 0, 32 + tile_bits + cam_bits, table, &sorted, nullptr,
-                                      !legacy_binning());
+                                      flatten_ids, 0, 32 + tile_bits + cam_bits, table, &sorted);
   if (rc) return rc;
   if (sorted != (uint64_t*)isect_ids)
     CLMGS_HIP(hipMemcpyAsync(isect_ids, sorted, (size_t)n_isects * 8, hipMemcpyDeviceToDevice, s));
@@ -216,122 +165,151 @@ extern "C" int clmgs_isect_offsets(void* stream, int64_t n_isects, const int64_t
 }
 
 // ======================================================================================
-// Two-level binning (engine fast path).  Bit-identical order to the 64-bit (tile | depth)
-// sort above at ~1/4 of its traffic:
+// Two-level binning.  Bit-identical order to the 64-bit (tile | depth) sort above at ~1/4 of
+// its traffic:
 //   A. stable sort of the V rows by depth bits (32-bit keys, culled rows last), then the tile
 //      count of every row in that order + inclusive scan (-> I);
 //   B. emit (tile id, row) in depth order, ONE stable sort on the tile-id bits only
 //      (16 bits at 4K: 2 radix passes instead of 6 over 64-bit keys), offsets from the sorted ids.
 // Ties: equal depths keep row order in A (stable), B is stable -> within a tile (depth, row)
 // order, exactly what the single stable 64-bit sort of (row-major emit) produces.
+//
+// The launches:
+//   A. isect2_keys (keys, boxes, masks, per-row counts scanned inside each chunk) -> scan_i64_finish (row_cum) ->
+//      4 radix passes (radix.h: histogram, row scan, scatter) -> isect2_count (boxes in depth order, counts scanned
+//      inside each chunk, un-culled total) -> scan_i64_finish (cum, emitted total);
+//   B. isect2_emit_hist (tile ids + payload chunk by chunk, with the first digit's histogram) -> the radix passes over
+//      the tile-id bits (the last one writes flatten_ids / emit_slot directly) -> isect2_offsets.
+// Both scans are folded into their producers: a producer block leaves the inclusive values inside its chunk of
+// ROW_CHUNK rows and the chunk's total, ONE finishing launch adds the totals of the chunks before.
 // ======================================================================================
 namespace clmgs {
+
+constexpr int ROW_ROUNDS = 4;
+constexpr int ROW_CHUNK = 256 * ROW_ROUNDS;  // rows (ranks) per block of the keys / count kernels
+
+__host__ __device__ static inline int row_chunks(int V) { return (V + ROW_CHUNK - 1) / ROW_CHUNK; }
 
 // Row order (coalesced): depth key, identity payload, the row's tile box and tile mask -- the only
 // place the means / radii / raster records are read; count and emit then work from 16 B per row
 // (one gather in depth order, afterwards sequential) instead of re-gathering the arrays.
 // packed == NULL: no exact culling (mask all ones, the gsplat.isect_tiles list).
+// row_cum (optional) gets the inclusive scan of the emitted counts INSIDE the block's chunk, block_tot[chunk] the
+// chunk's total (scan_i64_finish_kernel adds the offsets); block 0 zeroes the totals the count kernel accumulates into.
 __global__ void __launch_bounds__(256)
 isect2_keys_kernel(int V, const int32_t* __restrict__ radii, const float* __restrict__ depths,
-                   const float* __restrict__ means2d, const float4* __restrict__ packed,
-                   float tile_size, int tile_w, int tile_h, uint32_t* __restrict__ keys,
-                   int32_t* __restrict__ vals, unsigned long long* __restrict__ box_by_row,
-                   int64_t* __restrict__ row_cnt) {
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < V; i += gridDim.x * blockDim.x) {
-    const int r = radii[i];
-    keys[i] = r > 0 ? (uint32_t)__float_as_int(depths[i]) : 0xFFFFFFFFu;
-    vals[i] = i;
-    unsigned long long b = 0ull, m = ~0ull;
-    int cnt = 0;
-    if (r > 0) {
-      const float2 mm = *reinterpret_cast<const float2*>(means2d + 2 * (size_t)i);
-      const TileBox tb = tile_box(mm.x, mm.y, (float)r, tile_size, tile_w, tile_h);
-      b = pack_box(tb);
-      if (packed) m = exact_tile_mask(packed + 4 * (size_t)i, tb.x0, tb.y0, tb.x1, tb.y1);
-      const int nt = (tb.x1 - tb.x0) * (tb.y1 - tb.y0);
-      cnt = nt <= 64 ? __popcll(m & (nt == 64 ? ~0ull : ((1ull << nt) - 1ull))) : nt;
+                   const float* __restrict__ means2d, const float4* __restrict__ packed, float tile_size,
+                   int tile_w, int tile_h, uint32_t* __restrict__ keys, int32_t* __restrict__ vals,
+                   unsigned long long* __restrict__ box_by_row, int64_t* __restrict__ row_cum,
+                   int64_t* __restrict__ totals, int64_t* __restrict__ block_tot) {
+  __shared__ long long wsum[4];
+  const int tid = threadIdx.x, chunk = blockIdx.x;
+  if (chunk == 0 && tid == 0) { totals[0] = 0; totals[1] = 0; }
+  long long c[ROW_ROUNDS];
+#pragma unroll
+  for (int r = 0; r < ROW_ROUNDS; ++r) {
+    const int i = chunk * ROW_CHUNK + r * 256 + tid;
+    c[r] = 0;
+    if (i < V) {
+      const int rad = radii[i];
+      keys[i] = rad > 0 ? (uint32_t)__float_as_int(depths[i]) : 0xFFFFFFFFu;
+      vals[i] = i;
+      unsigned long long b = 0ull, m = ~0ull;
+      int cnt = 0;
+      if (rad > 0) {
+        const float2 mm = *reinterpret_cast<const float2*>(means2d + 2 * (size_t)i);
+        const TileBox tb = tile_box(mm.x, mm.y, (float)rad, tile_size, tile_w, tile_h);
+        b = pack_box(tb);
+        if (packed) m = exact_tile_mask(packed + 4 * (size_t)i, tb.x0, tb.y0, tb.x1, tb.y1);
+        const int nt = (tb.x1 - tb.x0) * (tb.y1 - tb.y0);
+        cnt = nt <= 64 ? __popcll(m & (nt == 64 ? ~0ull : ((1ull << nt) - 1ull))) : nt;
+      }
+      box_by_row[2 * (size_t)i] = b;
+      box_by_row[2 * (size_t)i + 1] = m;
+      c[r] = cnt;  // emitted intersections of row i (same rule as isect2_count_kernel)
     }
-    box_by_row[2 * (size_t)i] = b;
-    box_by_row[2 * (size_t)i + 1] = m;
-    if (row_cnt) row_cnt[i] = cnt;  // emitted intersections of row i (same rule as isect2_count_kernel)
+  }
+  if (row_cum) {  // inclusive scan of the emitted counts in ROW order (the slot ranges of the backward)
+    long long inc[ROW_ROUNDS];
+    long long carry = 0;
+#pragma unroll
+    for (int r = 0; r < ROW_ROUNDS; ++r) {
+      const long long incl = block_incl_scan_i64(c[r], wsum);
+      inc[r] = carry + incl;
+      carry += wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    }
+    if (tid == 0) block_tot[chunk] = carry;
+#pragma unroll
+    for (int r = 0; r < ROW_ROUNDS; ++r) {
+      const int i = chunk * ROW_CHUNK + r * 256 + tid;
+      if (i < V) row_cum[i] = inc[r];
+    }
   }
 }
 
-// boxes[2*j] = packed box of rank j (0 = nothing to emit), boxes[2*j+1] = its tile mask;
-// ref_total accumulates the UN-culled intersection count.
+// boxes[2*j] = packed box of rank j (0 = nothing to emit), boxes[2*j+1] = its tile mask; cum = inclusive scan of the
+// emitted counts inside the block's chunk, block_tot[chunk] = the chunk's total (scan_i64_finish_kernel adds the
+// offsets and writes totals[0]); totals[1] += the UN-culled count (zeroed by the keys kernel).
 __global__ void __launch_bounds__(256)
 isect2_count_kernel(int V, const int32_t* __restrict__ order,
                     const unsigned long long* __restrict__ box_by_row,
                     unsigned long long* __restrict__ boxes, int64_t* __restrict__ cum,
-                    unsigned long long* __restrict__ ref_total) {
+                    int64_t* __restrict__ totals, int64_t* __restrict__ block_tot) {
+  __shared__ long long wsum[4];
+  __shared__ unsigned long long rsum[4];
+  const int tid = threadIdx.x, chunk = blockIdx.x;
   unsigned long long ref = 0ull;
-  for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < V; j += gridDim.x * blockDim.x) {
-    const int i = order[j];
-    const unsigned long long b = box_by_row[2 * (size_t)i], m = box_by_row[2 * (size_t)i + 1];
-    const int x0 = (int)(b & 0xFFFF), y0 = (int)((b >> 16) & 0xFFFF);
-    const int x1 = (int)((b >> 32) & 0xFFFF), y1 = (int)(b >> 48);
-    const int nt = (x1 - x0) * (y1 - y0);
-    const int cnt = nt <= 64 ? __popcll(m & (nt == 64 ? ~0ull : ((1ull << nt) - 1ull))) : nt;
-    boxes[2 * (size_t)j] = cnt > 0 ? b : 0ull;
-    boxes[2 * (size_t)j + 1] = m;
-    cum[j] = cnt;
-    ref += (unsigned long long)nt;
-  }
-  if (ref_total) {  // one atomic per BLOCK: same-address atomics serialise at the memory side
-    __shared__ unsigned long long wsum[4];
-    ref = (unsigned long long)wave_sum_i64((long long)ref);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = ref;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const unsigned long long tot = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-      if (tot) atomicAdd(ref_total, tot);
+  long long inc[ROW_ROUNDS];
+  long long carry = 0;
+#pragma unroll
+  for (int r = 0; r < ROW_ROUNDS; ++r) {
+    const int j = chunk * ROW_CHUNK + r * 256 + tid;
+    long long cnt = 0;
+    if (j < V) {
+      const int i = order[j];
+      const unsigned long long b = box_by_row[2 * (size_t)i], m = box_by_row[2 * (size_t)i + 1];
+      const int x0 = (int)(b & 0xFFFF), y0 = (int)((b >> 16) & 0xFFFF);
+      const int x1 = (int)((b >> 32) & 0xFFFF), y1 = (int)(b >> 48);
+      const int nt = (x1 - x0) * (y1 - y0);
+      cnt = nt <= 64 ? __popcll(m & (nt == 64 ? ~0ull : ((1ull << nt) - 1ull))) : nt;
+      boxes[2 * (size_t)j] = cnt > 0 ? b : 0ull;
+      boxes[2 * (size_t)j + 1] = m;
+      ref += (unsigned long long)nt;
     }
+    const long long incl = block_incl_scan_i64(cnt, wsum);
+    inc[r] = carry + incl;
+    carry += wsum[0] + wsum[1] + wsum[2] + wsum[3];
+  }
+  if (tid == 0) block_tot[chunk] = carry;
+#pragma unroll
+  for (int r = 0; r < ROW_ROUNDS; ++r) {
+    const int j = chunk * ROW_CHUNK + r * 256 + tid;
+    if (j < V) cum[j] = inc[r];
+  }
+  // one atomic per BLOCK: same-address atomics serialise at the memory side
+  ref = (unsigned long long)wave_sum_i64((long long)ref);
+  __syncthreads();
+  if ((tid & 63) == 0) rsum[tid >> 6] = ref;
+  __syncthreads();
+  if (tid == 0) {
+    const unsigned long long tot = rsum[0] + rsum[1] + rsum[2] + rsum[3];
+    if (tot) atomicAdd((unsigned long long*)(totals + 1), tot);
   }
 }
 
-// vals2 != NULL ("slot mode"): the sort payload is the pair (row id, SLOT).  Slots are numbered in ROW
-// order: row i owns the contiguous range [row_cum[i-1], row_cum[i]) (its tiles in row-major tile
-// order).  The backward tile kernel stores its per-(row, tile) partial gradients at the slot with
-// plain stores; whoever consumes the row's gradient (clmgs_preprocess_bwd, or the row-sum kernel of
-// clmgs_rasterize_bwd) adds the row's range in ascending order: no float atomics, deterministic, and
-// both the partial lines and the consumer's rows are walked sequentially.
-__global__ void __launch_bounds__(256)
-isect2_emit_kernel(int V, const int32_t* __restrict__ order,
-                   const unsigned long long* __restrict__ boxes,
-                   const int64_t* __restrict__ cum, int tile_w, uint32_t* __restrict__ tkeys,
-                   int32_t* __restrict__ vals, int2* __restrict__ vals2,
-                   const int64_t* __restrict__ row_cum, int64_t cap) {
-  for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < V; j += gridDim.x * blockDim.x) {
-    const unsigned long long b = boxes[2 * (size_t)j];
-    if (b == 0ull) continue;
-    const unsigned long long m = boxes[2 * (size_t)j + 1];
-    const int x0 = (int)(b & 0xFFFF), y0 = (int)((b >> 16) & 0xFFFF);
-    const int x1 = (int)((b >> 32) & 0xFFFF), y1 = (int)(b >> 48);
-    const bool masked = (x1 - x0) * (y1 - y0) <= 64;
-    const int i = order[j];
-    int64_t cur = (j == 0) ? 0 : cum[j - 1];
-    int slot = (vals2 && i > 0) ? (int)row_cum[i - 1] : 0;
-    int t = 0;
-    for (int ty = y0; ty < y1; ++ty)
-      for (int tx = x0; tx < x1; ++tx, ++t) {
-        if (masked && !((m >> t) & 1ull)) continue;
-        if (cur >= cap) return;  // device-count mode, capacity exceeded: dropped (the caller compares the totals)
-        tkeys[cur] = (uint32_t)(ty * tile_w + tx);
-        if (vals2) vals2[cur] = make_int2(i, slot++);
-        else vals[cur] = i;
-        ++cur;
-      }
-  }
-}
-
-// Round 5: the same list, produced CHUNK BY CHUNK.  Block b owns the entries [1024 b, 1024 (b+1)) of the unsorted
-// list (the chunking of the first tile-sort pass).  It finds the first rank reaching into its chunk with a 256-ary
-// search over `cum` (three dependent steps at 3 M ranks instead of 22), lets one thread per rank expand that rank's
-// tiles into LDS, and then (i) stores tile ids and payload with coalesced 4 / 8 B-per-lane stores -- the
-// thread-per-rank kernel above writes each rank's 2.8 entries at a different address, 112 MB at ~1 TB/s -- and (ii)
-// counts the chunk's first digit into the radix table, which is the whole first histogram launch of the tile sort.
-// Entry for entry the list of isect2_emit_kernel (same index = cum of the ranks before + the tile's place inside
-// the rank's box, same payload).  Capacity form: entries at or beyond min(capacity, *n_dev) do not exist.
+// The (tile id, payload) list in depth order, produced CHUNK BY CHUNK.  Entry e of the list belongs to the rank j with
+// cum[j-1] <= e < cum[j] and is the (e - cum[j-1])-th kept tile, in row-major order, of that rank's box.
+// SLOTS: the sort payload is the pair (row id, SLOT).  Slots are numbered in ROW order: row i owns the contiguous
+// range [row_cum[i-1], row_cum[i]) (its tiles in row-major tile order).  The backward tile kernel stores its
+// per-(row, tile) partial gradients at the slot with plain stores; whoever consumes the row's gradient
+// (clmgs_preprocess_bwd, or the row-sum kernel of clmgs_rasterize_bwd) adds the row's range in ascending order: no
+// float atomics, deterministic, and both the partial lines and the consumer's rows are walked sequentially.
+// Block b owns the entries [1024 b, 1024 (b+1)) of the unsorted list (the chunking of the first tile-sort pass).  It
+// finds the first rank reaching into its chunk with a 256-ary search over `cum` (three dependent steps at 3 M ranks
+// instead of 22), lets one thread per rank expand that rank's tiles into LDS, and then (i) stores tile ids and payload
+// with coalesced 4 / 8 B-per-lane stores -- a thread per rank would write each rank's 2.8 entries at a different
+// address, 112 MB at ~1 TB/s -- and (ii) counts the chunk's first digit into the radix table, which is the whole first
+// histogram launch of the tile sort.  Capacity form: entries at or beyond min(n, *n_dev) do not exist.
 template <bool SLOTS>
 __global__ void __launch_bounds__(256, 8)
 isect2_emit_hist_kernel(int V, int64_t n, const int64_t* __restrict__ n_dev, const int32_t* __restrict__ order,
@@ -438,267 +416,13 @@ isect2_emit_hist_kernel(int V, int64_t n, const int64_t* __restrict__ n_dev, con
   table[(size_t)tid * n_blocks + blockIdx.x] = h[tid];
 }
 
-// slot mode: the sorted (row id, emit index) pairs are split into flatten_ids / emit_slot here.
-__global__ void __launch_bounds__(256)
-isect2_offsets_kernel(int64_t n_isects, const uint32_t* __restrict__ tkeys, int n_tiles,
-                      int32_t* __restrict__ offsets, int32_t* __restrict__ flatten_ids,
-                      int32_t* __restrict__ emit_slot, const int2* __restrict__ sorted2,
-                      const float* __restrict__ depths, int64_t* __restrict__ isect_ids,
-                      const int64_t* __restrict__ n_dev) {
-  if (n_dev) n_isects = min(n_isects, *n_dev);
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n_isects;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    const int cur = (int)tkeys[i];
-    if (i == 0) {
-      for (int t = 0; t <= cur; ++t) offsets[t] = 0;
-    } else {
-      const int prev = (int)tkeys[i - 1];
-      for (int t = prev + 1; t <= cur; ++t) offsets[t] = (int32_t)i;
-    }
-    if (i == n_isects - 1)
-      for (int t = cur + 1; t < n_tiles; ++t) offsets[t] = (int32_t)n_isects;
-    int gid;
-    if (sorted2) { const int2 v = sorted2[i]; gid = v.x; flatten_ids[i] = gid; emit_slot[i] = v.y; }
-    else gid = flatten_ids[i];
-    if (isect_ids)
-      isect_ids[i] = ((int64_t)cur << 32) | (int64_t)(uint32_t)__float_as_int(depths[gid]);
-  }
-}
-
-
-// ======================================================================================
-// Round 4: the same chain in 11 launches instead of ~30 (onesweep.h).
-//   memset(control block) -> keys_lb (keys, boxes, masks, per-row counts + their scan = row_cum, digit counts of all
-//   four depth-sort passes) -> 4 x onesweep pass -> count_lb (boxes in depth order, counts + their scan = cum, totals)
-//   | memset(control block) -> emit_lb (tile ids + payload, digit counts of the tile sort) -> 2 x onesweep pass (the last
-//   one writes flatten_ids / emit_slot directly) -> offsets.
-// Every list is element for element the legacy chain's (stable LSD passes in the same digit order).
-// ======================================================================================
-constexpr int LBK_ROUNDS = 4;
-constexpr int LBK_CHUNK = 256 * LBK_ROUNDS;  // rows (ranks) per ticket of the keys / count kernels
-
-__host__ __device__ static inline int lbk_chunks(int V) { return (V + LBK_CHUNK - 1) / LBK_CHUNK; }
-
-// LOOKBACK = false (default route): chunk = blockIdx.x, the scan stays block-relative (row_cum gets the inclusive
-// scan inside the chunk, block_tot[chunk] its total; scan_i64_finish_kernel adds the offsets), no digit counts.
-template <bool LOOKBACK>
-__global__ void __launch_bounds__(256)
-isect2_keys_lb_kernel(int V, const int32_t* __restrict__ radii, const float* __restrict__ depths,
-                      const float* __restrict__ means2d, const float4* __restrict__ packed, float tile_size,
-                      int tile_w, int tile_h, uint32_t* __restrict__ keys, int32_t* __restrict__ vals,
-                      unsigned long long* __restrict__ box_by_row, int64_t* __restrict__ row_cum,
-                      uint32_t* __restrict__ ghist /*[4][256]*/, unsigned long long* __restrict__ status,
-                      uint32_t* __restrict__ ticket_ctr, int64_t* __restrict__ totals, uint32_t* err,
-                      int64_t* __restrict__ block_tot) {
-  __shared__ uint32_t hist[LOOKBACK ? 4 : 1][256];
-  __shared__ long long wsum[4];
-  __shared__ long long sh[2];
-  __shared__ int ticket_s;
-  const int tid = threadIdx.x;
-  if constexpr (LOOKBACK) {
-#pragma unroll
-    for (int p = 0; p < 4; ++p) hist[p][tid] = 0;
-  }
-  const int n_chunks = lbk_chunks(V);
-  for (int iter = 0;; ++iter) {
-    int chunk;
-    if constexpr (LOOKBACK) {
-      __syncthreads();
-      if (tid == 0) ticket_s = (int)atomicAdd(ticket_ctr, 1u);
-      __syncthreads();
-      chunk = ticket_s;
-    } else {
-      chunk = blockIdx.x + iter * gridDim.x;
-    }
-    if (chunk >= n_chunks) break;
-    if (chunk == 0 && tid == 0) { totals[0] = 0; totals[1] = 0; }  // the count kernel accumulates into them (later launch)
-    long long c[LBK_ROUNDS];
-#pragma unroll
-    for (int r = 0; r < LBK_ROUNDS; ++r) {
-      const int i = chunk * LBK_CHUNK + r * 256 + tid;
-      c[r] = 0;
-      if (i < V) {
-        const int rad = radii[i];
-        const uint32_t key = rad > 0 ? (uint32_t)__float_as_int(depths[i]) : 0xFFFFFFFFu;
-        keys[i] = key;
-        vals[i] = i;
-        unsigned long long b = 0ull, m = ~0ull;
-        int cnt = 0;
-        if (rad > 0) {
-          const float2 mm = *reinterpret_cast<const float2*>(means2d + 2 * (size_t)i);
-          const TileBox tb = tile_box(mm.x, mm.y, (float)rad, tile_size, tile_w, tile_h);
-          b = pack_box(tb);
-          if (packed) m = exact_tile_mask(packed + 4 * (size_t)i, tb.x0, tb.y0, tb.x1, tb.y1);
-          const int nt = (tb.x1 - tb.x0) * (tb.y1 - tb.y0);
-          cnt = nt <= 64 ? __popcll(m & (nt == 64 ? ~0ull : ((1ull << nt) - 1ull))) : nt;
-        }
-        box_by_row[2 * (size_t)i] = b;
-        box_by_row[2 * (size_t)i + 1] = m;
-        c[r] = cnt;
-        if constexpr (LOOKBACK) {
-          atomicAdd(&hist[0][key & 0xFFu], 1u);
-          atomicAdd(&hist[1][(key >> 8) & 0xFFu], 1u);
-          atomicAdd(&hist[2][(key >> 16) & 0xFFu], 1u);
-          atomicAdd(&hist[3][key >> 24], 1u);
-        }
-      }
-    }
-    if (row_cum) {  // inclusive scan of the emitted counts in ROW order (the slot ranges of the backward)
-      long long inc[LBK_ROUNDS];
-      long long carry = 0;
-#pragma unroll
-      for (int r = 0; r < LBK_ROUNDS; ++r) {
-        const long long incl = block_incl_scan_i64(c[r], wsum);
-        inc[r] = carry + incl;
-        carry += wsum[0] + wsum[1] + wsum[2] + wsum[3];
-      }
-      long long excl = 0;
-#ifdef CLMGS_PROFILE_BUILD
-      if constexpr (LOOKBACK) excl = lb_chunk_prefix(status, chunk, carry, sh, err);
-      else
-#endif
-      if (tid == 0) block_tot[chunk] = carry;
-#pragma unroll
-      for (int r = 0; r < LBK_ROUNDS; ++r) {
-        const int i = chunk * LBK_CHUNK + r * 256 + tid;
-        if (i < V) row_cum[i] = excl + inc[r];
-      }
-    }
-  }
-  if constexpr (LOOKBACK) {
-    __syncthreads();
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      const uint32_t v = hist[p][tid];
-      if (v) atomicAdd(&ghist[p * 256 + tid], v);
-    }
-  }
-}
-
-// boxes / masks in depth order, cum = inclusive scan of the emitted counts in that order, totals[0] = the grand
-// total, totals[1] += the un-culled count (both zeroed by keys_lb).
-template <bool LOOKBACK>
-__global__ void __launch_bounds__(256)
-isect2_count_lb_kernel(int V, const int32_t* __restrict__ order,
-                       const unsigned long long* __restrict__ box_by_row,
-                       unsigned long long* __restrict__ boxes, int64_t* __restrict__ cum,
-                       int64_t* __restrict__ totals, unsigned long long* __restrict__ status,
-                       uint32_t* __restrict__ ticket_ctr, uint32_t* err, int64_t* __restrict__ block_tot) {
-  __shared__ long long wsum[4];
-  __shared__ long long sh[2];
-  __shared__ unsigned long long rsum[4];
-  __shared__ int ticket_s;
-  const int tid = threadIdx.x;
-  const int n_chunks = lbk_chunks(V);
-  unsigned long long ref = 0ull;
-  for (int iter = 0;; ++iter) {
-    int chunk;
-    if constexpr (LOOKBACK) {
-      __syncthreads();
-      if (tid == 0) ticket_s = (int)atomicAdd(ticket_ctr, 1u);
-      __syncthreads();
-      chunk = ticket_s;
-    } else {
-      chunk = blockIdx.x + iter * gridDim.x;
-    }
-    if (chunk >= n_chunks) break;
-    long long inc[LBK_ROUNDS];
-    long long carry = 0;
-#pragma unroll
-    for (int r = 0; r < LBK_ROUNDS; ++r) {
-      const int j = chunk * LBK_CHUNK + r * 256 + tid;
-      long long cnt = 0;
-      if (j < V) {
-        const int i = order[j];
-        const unsigned long long b = box_by_row[2 * (size_t)i], m = box_by_row[2 * (size_t)i + 1];
-        const int x0 = (int)(b & 0xFFFF), y0 = (int)((b >> 16) & 0xFFFF);
-        const int x1 = (int)((b >> 32) & 0xFFFF), y1 = (int)(b >> 48);
-        const int nt = (x1 - x0) * (y1 - y0);
-        cnt = nt <= 64 ? __popcll(m & (nt == 64 ? ~0ull : ((1ull << nt) - 1ull))) : nt;
-        boxes[2 * (size_t)j] = cnt > 0 ? b : 0ull;
-        boxes[2 * (size_t)j + 1] = m;
-        ref += (unsigned long long)nt;
-      }
-      const long long incl = block_incl_scan_i64(cnt, wsum);
-      inc[r] = carry + incl;
-      carry += wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    }
-    long long excl = 0;
-#ifdef CLMGS_PROFILE_BUILD
-    if constexpr (LOOKBACK) excl = lb_chunk_prefix(status, chunk, carry, sh, err);
-    else
-#endif
-    if (tid == 0) block_tot[chunk] = carry;
-#pragma unroll
-    for (int r = 0; r < LBK_ROUNDS; ++r) {
-      const int j = chunk * LBK_CHUNK + r * 256 + tid;
-      if (j < V) cum[j] = excl + inc[r];
-    }
-    if (LOOKBACK && chunk == n_chunks - 1 && tid == 0) totals[0] = excl + carry;
-  }
-  ref = (unsigned long long)wave_sum_i64((long long)ref);
-  __syncthreads();
-  if ((tid & 63) == 0) rsum[tid >> 6] = ref;
-  __syncthreads();
-  if (tid == 0) {
-    const unsigned long long tot = rsum[0] + rsum[1] + rsum[2] + rsum[3];
-    if (tot) atomicAdd((unsigned long long*)(totals + 1), tot);
-  }
-}
-
-// emit + the digit counts of every pass of the tile sort (entries beyond the capacity are neither written nor
-// counted, so the counts always describe the min(capacity, total) keys the passes sort)
-__global__ void __launch_bounds__(256)
-isect2_emit_lb_kernel(int V, const int32_t* __restrict__ order,
-                      const unsigned long long* __restrict__ boxes,
-                      const int64_t* __restrict__ cum, int tile_w, uint32_t* __restrict__ tkeys,
-                      int32_t* __restrict__ vals, int2* __restrict__ vals2,
-                      const int64_t* __restrict__ row_cum, int64_t cap, int n_pass,
-                      uint32_t* __restrict__ ghist /*[4][256]*/) {
-  __shared__ uint32_t hist[4][256];
-#pragma unroll
-  for (int p = 0; p < 4; ++p) hist[p][threadIdx.x] = 0;
-  __syncthreads();
-  for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < V; j += gridDim.x * blockDim.x) {
-    const unsigned long long b = boxes[2 * (size_t)j];
-    if (b == 0ull) continue;
-    const unsigned long long m = boxes[2 * (size_t)j + 1];
-    const int x0 = (int)(b & 0xFFFF), y0 = (int)((b >> 16) & 0xFFFF);
-    const int x1 = (int)((b >> 32) & 0xFFFF), y1 = (int)(b >> 48);
-    const bool masked = (x1 - x0) * (y1 - y0) <= 64;
-    const int i = order[j];
-    int64_t cur = (j == 0) ? 0 : cum[j - 1];
-    int slot = (vals2 && i > 0) ? (int)row_cum[i - 1] : 0;
-    int t = 0;
-    for (int ty = y0; ty < y1 && cur < cap; ++ty)
-      for (int tx = x0; tx < x1; ++tx, ++t) {
-        if (masked && !((m >> t) & 1ull)) continue;
-        if (cur >= cap) break;  // device-count mode, capacity exceeded: dropped (the caller compares the totals)
-        const uint32_t key = (uint32_t)(ty * tile_w + tx);
-        tkeys[cur] = key;
-        if (vals2) vals2[cur] = make_int2(i, slot++);
-        else vals[cur] = i;
-        ++cur;
-        atomicAdd(&hist[0][key & 0xFFu], 1u);
-        if (n_pass > 1) atomicAdd(&hist[1][(key >> 8) & 0xFFu], 1u);
-        if (n_pass > 2) atomicAdd(&hist[2][(key >> 16) & 0xFFu], 1u);
-        if (n_pass > 3) atomicAdd(&hist[3][key >> 24], 1u);
-      }
-  }
-  __syncthreads();
-  for (int p = 0; p < n_pass; ++p) {
-    const uint32_t v = hist[p][threadIdx.x];
-    if (v) atomicAdd(&ghist[p * 256 + threadIdx.x], v);
-  }
-}
-
 // offsets from the sorted tile ids (+ optional isect_ids); a true count of 0 leaves no entry to derive them from:
 // the grid fills them with zeros itself (no memset launch).
 __global__ void __launch_bounds__(256)
-isect2_offsets_lb_kernel(int64_t n_isects, const uint32_t* __restrict__ tkeys, int n_tiles,
-                         int32_t* __restrict__ offsets, const int32_t* __restrict__ flatten_ids,
-                         const float* __restrict__ depths, int64_t* __restrict__ isect_ids,
-                         const int64_t* __restrict__ n_dev) {
+isect2_offsets_kernel(int64_t n_isects, const uint32_t* __restrict__ tkeys, int n_tiles,
+                      int32_t* __restrict__ offsets, const int32_t* __restrict__ flatten_ids,
+                      const float* __restrict__ depths, int64_t* __restrict__ isect_ids,
+                      const int64_t* __restrict__ n_dev) {
   if (n_dev) n_isects = min(n_isects, *n_dev);
   if (n_isects <= 0) {
     for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < n_tiles; t += gridDim.x * blockDim.x) offsets[t] = 0;
@@ -720,7 +444,7 @@ isect2_offsets_lb_kernel(int64_t n_isects, const uint32_t* __restrict__ tkeys, i
   }
 }
 
-// Second half of a scan whose producer left block-relative inclusive values (chunks of LBK_CHUNK) and the chunk totals:
+// Second half of a scan whose producer left block-relative inclusive values (chunks of ROW_CHUNK) and the chunk totals:
 // every block sums the totals of the chunks before its own (a block-wide reduction over <= a few thousand L2-resident
 // words) and adds that offset -- one launch instead of scan-the-totals + add.  last_out: the grand total.
 __global__ void __launch_bounds__(256)
@@ -736,32 +460,20 @@ scan_i64_finish_kernel(int n, int64_t* __restrict__ data, const int64_t* __restr
   const long long off = wsum[0] + wsum[1] + wsum[2] + wsum[3];
   if (chunk > 0) {
 #pragma unroll
-    for (int r = 0; r < LBK_ROUNDS; ++r) {
-      const int i = chunk * LBK_CHUNK + r * 256 + tid;
+    for (int r = 0; r < ROW_ROUNDS; ++r) {
+      const int i = chunk * ROW_CHUNK + r * 256 + tid;
       if (i < n) data[i] += off;
     }
   }
   if (last_out && chunk == (int)gridDim.x - 1 && tid == 0) *last_out = off + block_tot[chunk];
 }
 
-// control block of clmgs_isect2_order_count: [4][256] digit counts | 16 ticket words | scan status of keys_lb | scan
-// status of count_lb | 4 x sort status
-#ifdef CLMGS_PROFILE_BUILD
-static inline size_t order_ctrl_bytes(int V) {
-  return 4096 + 256 + 2 * align_up((size_t)lbk_chunks(V) * 8, 256) + 4 * os_status_bytes(V);
-}
-static inline size_t sort_ctrl_bytes(int64_t n) { return 4096 + 256 + 4 * os_status_bytes(n); }
-#else
-static inline size_t order_ctrl_bytes(int) { return 0; }
-static inline size_t sort_ctrl_bytes(int64_t) { return 0; }
-#endif
-
 }  // namespace clmgs
 
 extern "C" size_t clmgs_isect2_order_temp_bytes(int V) {
   if (V <= 0) return 256;
-  const size_t legacy = radix_table_bytes(V) + max(scan_scratch_bytes(V), (size_t)2 * lbk_chunks(V) * sizeof(int64_t) + 256);
-  return 4 * align_up((size_t)V * 4, 256) + align_up((size_t)V * 16, 256) + max(legacy, order_ctrl_bytes(V)) + 256;
+  return 4 * align_up((size_t)V * 4, 256) + align_up((size_t)V * 16, 256) + radix_table_bytes(V) +
+         align_up((size_t)2 * row_chunks(V) * sizeof(int64_t), 256) + 256;
 }
 
 // order[V] i32 (rows by depth, culled last), cum[V] i64 (inclusive tile counts in that order),
@@ -789,90 +501,33 @@ extern "C" int clmgs_isect2_order_count(void* stream, int V, const float* means2
   int32_t* v_b = (int32_t*)base; base += align_up((size_t)V * 4, 256);
   unsigned long long* box_by_row = (unsigned long long*)base; base += align_up((size_t)V * 16, 256);
   uint32_t* table = (uint32_t*)base; base += radix_table_bytes(V);
-  int64_t* scan_tmp = (int64_t*)base;
-  if (binning_route() == BIN_FUSED || binning_route() == BIN_R4) {
-    int64_t* tot_a = scan_tmp;                      // chunk totals of the two scans
-    int64_t* tot_b = scan_tmp + lbk_chunks(V);
-    const int nck = lbk_chunks(V);
-    hipLaunchKernelGGL((isect2_keys_lb_kernel<false>), dim3(nck), dim3(256), 0, s, V, radii, depths, means2d,
-                       (const float4*)packed, (float)tile_size, tile_width, tile_height, k_a, v_a, box_by_row,
-                       row_cum, (uint32_t*)nullptr, (unsigned long long*)nullptr, (uint32_t*)nullptr, totals,
-                       (uint32_t*)nullptr, tot_a);
-    if (row_cum)
-      hipLaunchKernelGGL(scan_i64_finish_kernel, dim3(nck), dim3(256), 0, s, V, row_cum, tot_a, (int64_t*)nullptr);
-    CLMGS_LAUNCH_CHECK();
-    uint32_t* sorted = nullptr;
-    int rc = radix_sort_pairs<uint32_t>(s, V, k_a, k_b, v_a, v_b, order, 0, 32, table, &sorted);
-    if (rc) return rc;
-    hipLaunchKernelGGL((isect2_count_lb_kernel<false>), dim3(nck), dim3(256), 0, s, V, order, box_by_row,
-                       (unsigned long long*)boxes, cum, totals, (unsigned long long*)nullptr, (uint32_t*)nullptr,
-                       (uint32_t*)nullptr, tot_b);
-    hipLaunchKernelGGL(scan_i64_finish_kernel, dim3(nck), dim3(256), 0, s, V, cum, tot_b, totals);
-    CLMGS_LAUNCH_CHECK();
-    return 0;
-  }
-#ifdef CLMGS_PROFILE_BUILD
-  if (binning_route() == BIN_LOOKBACK) {
-    // control block (zeroed by ONE memset): digit counts | tickets | scan status x 2 | sort status x 4
-    char* ctrl = (char*)table;  // (the legacy routes' radix table + scan scratch: the temp size is the max of both)
-    uint32_t* ghist = (uint32_t*)ctrl;
-    uint32_t* tickets = (uint32_t*)(ctrl + 4096);
-    const size_t sb = align_up((size_t)lbk_chunks(V) * 8, 256);
-    unsigned long long* st_keys = (unsigned long long*)(ctrl + 4096 + 256);
-    unsigned long long* st_count = (unsigned long long*)(ctrl + 4096 + 256 + sb);
-    char* st_sort = ctrl + 4096 + 256 + 2 * sb;
-    const size_t ssb = os_status_bytes(V);
-    uint32_t* err = device_error_word();
-    CLMGS_CHECK_ARG(err != nullptr);
-    CLMGS_HIP(hipMemsetAsync(ctrl, 0, order_ctrl_bytes(V), s));
-    const int nck = lbk_chunks(V);
-    hipLaunchKernelGGL((isect2_keys_lb_kernel<true>), dim3(min(nck, 1024)), dim3(256), 0, s, V, radii, depths, means2d,
-                       (const float4*)packed, (float)tile_size, tile_width, tile_height, k_a, v_a, box_by_row,
-                       row_cum, ghist, st_keys, tickets + 0, totals, err, (int64_t*)nullptr);
-    uint32_t* ksrc = k_a;
-    uint32_t* kdst = k_b;
-    int32_t* vsrc = v_a;
-    for (int p = 0; p < 4; ++p) {
-      int32_t* vdst = (p == 3) ? order : (vsrc == v_a ? v_b : v_a);
-      launch_onesweep_pass<int32_t, false>(s, os_rounds("CLMGS_OS_ROUNDS_V", 8), (int64_t)V, (const int64_t*)nullptr, ksrc,
-                                           vsrc, kdst, vdst, (int32_t*)nullptr, (int32_t*)nullptr, 8 * p,
-                                           ghist + 256 * p, (uint32_t*)(st_sort + ssb * p), tickets + 2 + p, err);
-      uint32_t* t_ = ksrc; ksrc = kdst; kdst = t_;
-      vsrc = vdst;
-    }
-    hipLaunchKernelGGL((isect2_count_lb_kernel<true>), dim3(min(nck, 1024)), dim3(256), 0, s, V, order, box_by_row,
-                       (unsigned long long*)boxes, cum, totals, st_count, tickets + 1, err, (int64_t*)nullptr);
-    CLMGS_LAUNCH_CHECK();
-    return 0;
-  }
-#endif
-  const int grid = min(ceil_div(V, 256), 256 * 16);
-  hipLaunchKernelGGL(isect2_keys_kernel, dim3(grid), dim3(256), 0, s, V, radii, depths, means2d,
-                     (const float4*)packed, (float)tile_size, tile_width, tile_height, k_a, v_a,
-                     box_by_row, row_cum);
+  const int nck = row_chunks(V);
+  int64_t* tot_a = (int64_t*)base;  // chunk totals of the two scans
+  int64_t* tot_b = tot_a + nck;
+  hipLaunchKernelGGL(isect2_keys_kernel, dim3(nck), dim3(256), 0, s, V, radii, depths, means2d, (const float4*)packed,
+                     (float)tile_size, tile_width, tile_height, k_a, v_a, box_by_row, row_cum, totals, tot_a);
+  if (row_cum)
+    hipLaunchKernelGGL(scan_i64_finish_kernel, dim3(nck), dim3(256), 0, s, V, row_cum, tot_a, (int64_t*)nullptr);
   CLMGS_LAUNCH_CHECK();
   uint32_t* sorted = nullptr;
-  int rc = radix_sort_pairs<uint32_t>(s, V, k_a, k_b, v_a, v_b, order, 0, 32, table, &sorted, nullptr, false);
+  int rc = radix_sort_pairs<uint32_t>(s, V, k_a, k_b, v_a, v_b, order, 0, 32, table, &sorted);
   if (rc) return rc;
-  if (row_cum) {
-    rc = inclusive_scan_i64(s, V, row_cum, scan_tmp);
-    if (rc) return rc;
-  }
-  CLMGS_HIP(hipMemsetAsync(totals, 0, 2 * sizeof(int64_t), s));
-  hipLaunchKernelGGL(isect2_count_kernel, dim3(min(grid, 1024)), dim3(256), 0, s, V, order, box_by_row,
-                     (unsigned long long*)boxes, cum, (unsigned long long*)(totals + 1));
+  hipLaunchKernelGGL(isect2_count_kernel, dim3(nck), dim3(256), 0, s, V, order, box_by_row,
+                     (unsigned long long*)boxes, cum, totals, tot_b);
+  hipLaunchKernelGGL(scan_i64_finish_kernel, dim3(nck), dim3(256), 0, s, V, cum, tot_b, totals);
   CLMGS_LAUNCH_CHECK();
-  return inclusive_scan_i64(s, V, cum, scan_tmp, totals);  // totals[0] = cum[V-1], no extra copy
+  return 0;
 }
 
 extern "C" size_t clmgs_isect2_sort_temp_bytes(int64_t n_isects) {
   if (n_isects <= 0) return 256;
-  return 8 * align_up((size_t)n_isects * 4, 256) + max(radix_table_bytes(n_isects), sort_ctrl_bytes(n_isects)) + 256;
+  return 6 * align_up((size_t)n_isects * 4, 256) + radix_table_bytes(n_isects) + 256;
 }
 
 // flatten_ids[I] i32 (row ids, sorted by tile then depth), offsets[tile_w*tile_h] i32,
 // isect_ids[I] i64 optional (NULL to skip).  emit_slot[I] optional: the emit index of every sorted
 // intersection, consumed (with order / cum) by clmgs_rasterize_bwd's atomic-free accumulation.
+// n_dev != NULL: n_isects is a capacity, the true count is read on the device.
 static int isect2_emit_sort_impl(void* stream, int V, int64_t n_isects, const float* depths,
                                  const int32_t* order, const int64_t* cum,
                                  const uint64_t* boxes, int tile_width, int tile_height,
@@ -882,12 +537,9 @@ static int isect2_emit_sort_impl(void* stream, int V, int64_t n_isects, const fl
   CLMGS_CHECK_ARG(V >= 0 && n_isects >= 0 && offsets);
   hipStream_t s = (hipStream_t)stream;
   const int n_tiles = tile_width * tile_height;
-  const int route = binning_route();
-  const bool lb = route == BIN_LOOKBACK && n_isects < ((int64_t)1 << 30);  // 30-bit counts in the look-back words
-  const bool fused = route == BIN_FUSED || route == BIN_R4;
-  if (n_isects == 0 || (n_dev && !lb && !fused)) {  // device-count mode: a true count of 0 leaves no thread to write the offsets
+  if (n_isects == 0) {
     CLMGS_HIP(hipMemsetAsync(offsets, 0, sizeof(int32_t) * (size_t)n_tiles, s));
-    if (n_isects == 0) return 0;
+    return 0;
   }
   CLMGS_CHECK_ARG(n_isects < ((int64_t)1 << 31));
   CLMGS_CHECK_ARG(depths && order && cum && boxes && flatten_ids && temp);
@@ -898,103 +550,37 @@ static int isect2_emit_sort_impl(void* stream, int V, int64_t n_isects, const fl
   uint32_t* k_b = (uint32_t*)base; base += a4;
   char* v_a = base; base += 2 * a4;   // int32 payload (plain) or int2 payload (slot mode)
   char* v_b = base; base += 2 * a4;
-  char* v_f = base; base += 2 * a4;
   uint32_t* table = (uint32_t*)base;
   const bool slots = emit_slot != nullptr;
   CLMGS_CHECK_ARG(!slots || row_cum);
   const int tile_bits = ilog2_floor((unsigned)n_tiles) + 1;
-#ifdef CLMGS_PROFILE_BUILD
-  if (lb) {
-    const int n_pass = (tile_bits + 7) / 8;
-    char* ctrl = (char*)table;
-    uint32_t* ghist = (uint32_t*)ctrl;
-    uint32_t* tickets = (uint32_t*)(ctrl + 4096);
-    char* st_sort = ctrl + 4096 + 256;
-    const size_t ssb = os_status_bytes(n_isects);
-    uint32_t* err = device_error_word();
-    CLMGS_CHECK_ARG(err != nullptr);
-    CLMGS_HIP(hipMemsetAsync(ctrl, 0, 4096 + 256 + (size_t)n_pass * ssb, s));
-    hipLaunchKernelGGL(isect2_emit_lb_kernel, dim3(min(ceil_div(V, 256), 1024)), dim3(256), 0, s, V, order,
-                       (const unsigned long long*)boxes, cum, tile_width, k_a, (int32_t*)v_a,
-                       slots ? (int2*)v_a : nullptr, row_cum, n_isects, n_pass, ghist);
-    uint32_t* ksrc = k_a;
-    uint32_t* kdst = k_b;
-    char* vsrc = v_a;
-    const int rounds = os_rounds("CLMGS_OS_ROUNDS_I", 8);
-    for (int p = 0; p < n_pass; ++p) {
-      const bool last = p == n_pass - 1;
-      char* vdst = (vsrc == v_a) ? v_b : v_a;
-      uint32_t* st = (uint32_t*)(st_sort + ssb * p);
-      if (slots) {
-        if (last)
-          launch_onesweep_pass<int2, true>(s, rounds, n_isects, n_dev, ksrc, (const int2*)vsrc, kdst, (int2*)nullptr,
-                                           flatten_ids, emit_slot, 8 * p, ghist + 256 * p, st, tickets + p, err);
-        else
-          launch_onesweep_pass<int2, false>(s, rounds, n_isects, n_dev, ksrc, (const int2*)vsrc, kdst, (int2*)vdst,
-                                            (int32_t*)nullptr, (int32_t*)nullptr, 8 * p, ghist + 256 * p, st,
-                                            tickets + p, err);
-      } else {
-        launch_onesweep_pass<int32_t, false>(s, rounds, n_isects, n_dev, ksrc, (const int32_t*)vsrc, kdst,
-                                             last ? flatten_ids : (int32_t*)vdst, (int32_t*)nullptr,
-                                             (int32_t*)nullptr, 8 * p, ghist + 256 * p, st, tickets + p, err);
-      }
-      uint32_t* t_ = ksrc; ksrc = kdst; kdst = t_;
-      vsrc = vdst;
-    }
-    hipLaunchKernelGGL(isect2_offsets_lb_kernel, dim3(min(ceil_div(n_isects, 256), 256 * 16)), dim3(256), 0, s,
-                       n_isects, ksrc, n_tiles, offsets, flatten_ids, depths, isect_ids, n_dev);
-    CLMGS_LAUNCH_CHECK();
-    return 0;
-  }
-#endif
+  // one block per 1024-entry chunk of the (unsorted) list expands the ranks that fall into it through LDS, stores
+  // tile ids + payload coalesced and leaves the chunk's first-digit counts in the radix table
+  const int n_blocks = (int)((n_isects + RS_MIN_CHUNK - 1) / RS_MIN_CHUNK);
+  if (slots)
+    hipLaunchKernelGGL((isect2_emit_hist_kernel<true>), dim3(n_blocks), dim3(256), 0, s, V, n_isects, n_dev, order,
+                       (const unsigned long long*)boxes, cum, tile_width, row_cum, k_a, (int32_t*)nullptr, (int2*)v_a,
+                       n_blocks, table);
+  else
+    hipLaunchKernelGGL((isect2_emit_hist_kernel<false>), dim3(n_blocks), dim3(256), 0, s, V, n_isects, n_dev, order,
+                       (const unsigned long long*)boxes, cum, tile_width, row_cum, k_a, (int32_t*)v_a, (int2*)nullptr,
+                       n_blocks, table);
+  CLMGS_LAUNCH_CHECK();
+  // the last pass writes flatten_ids / emit_slot itself (no int2 list to split afterwards); the offsets kernel then
+  // reads the sorted tile ids only and zero-fills the offsets itself when the true count is 0
   uint32_t* sorted = nullptr;
   int rc;
-  const bool emit_hist = route == BIN_FUSED && tile_bits > 0;
-  if (emit_hist) {
-    // round 5: one block per 1024-entry chunk of the (unsorted) list expands the ranks that fall into it through LDS,
-    // stores tile ids + payload coalesced and leaves the chunk's first-digit counts in the radix table
-    const int n_blocks = (int)((n_isects + RS_MIN_CHUNK - 1) / RS_MIN_CHUNK);
-    if (slots)
-      hipLaunchKernelGGL((isect2_emit_hist_kernel<true>), dim3(n_blocks), dim3(256), 0, s, V, n_isects, n_dev, order,
-                         (const unsigned long long*)boxes, cum, tile_width, row_cum, k_a, (int32_t*)nullptr, (int2*)v_a,
-                         n_blocks, table);
-    else
-      hipLaunchKernelGGL((isect2_emit_hist_kernel<false>), dim3(n_blocks), dim3(256), 0, s, V, n_isects, n_dev, order,
-                         (const unsigned long long*)boxes, cum, tile_width, row_cum, k_a, (int32_t*)v_a, (int2*)nullptr,
-                         n_blocks, table);
-  } else {
-    hipLaunchKernelGGL(isect2_emit_kernel, dim3(min(ceil_div(V, 256), 256 * 16)), dim3(256), 0, s, V,
-                       order, (const unsigned long long*)boxes, cum, tile_width, k_a, (int32_t*)v_a,
-                       slots ? (int2*)v_a : nullptr, row_cum, n_isects);
-  }
-  CLMGS_LAUNCH_CHECK();
-  if (fused) {
-    // the last pass writes flatten_ids / emit_slot itself (no int2 list to split afterwards); the offsets kernel then
-    // reads the sorted tile ids only and zero-fills the offsets itself when the true count is 0
-    if (slots)
-      rc = radix_sort_pairs_impl<uint32_t, int2, RS_DEFAULT_ITEMS>(s, n_isects, k_a, k_b, (int2*)v_a, (int2*)v_b, (int2*)nullptr,
-                                                                    0, tile_bits, table, &sorted, n_dev, flatten_ids, emit_slot,
-                                                                    true, emit_hist);
-    else
-      rc = radix_sort_pairs_impl<uint32_t, int32_t, RS_DEFAULT_ITEMS>(s, n_isects, k_a, k_b, (int32_t*)v_a, (int32_t*)v_b,
-                                                                       flatten_ids, 0, tile_bits, table, &sorted, n_dev,
-                                                                       nullptr, nullptr, true, emit_hist);
-    if (rc) return rc;
-    hipLaunchKernelGGL(isect2_offsets_lb_kernel, dim3(min(ceil_div(n_isects, 256), 256 * 16)), dim3(256), 0, s,
-                       n_isects, sorted, n_tiles, offsets, flatten_ids, depths, isect_ids, n_dev);
-    CLMGS_LAUNCH_CHECK();
-    return 0;
-  }
   if (slots)
-    rc = radix_sort_pairs<uint32_t, int2>(s, n_isects, k_a, k_b, (int2*)v_a, (int2*)v_b, (int2*)v_f, 0,
-                                          tile_bits, table, &sorted, n_dev, false);
+    rc = radix_sort_pairs_impl<uint32_t, int2, RS_DEFAULT_ITEMS>(s, n_isects, k_a, k_b, (int2*)v_a, (int2*)v_b, (int2*)nullptr,
+                                                                  0, tile_bits, table, &sorted, n_dev, flatten_ids, emit_slot,
+                                                                  true);
   else
-    rc = radix_sort_pairs<uint32_t, int32_t>(s, n_isects, k_a, k_b, (int32_t*)v_a, (int32_t*)v_b,
-                                             flatten_ids, 0, tile_bits, table, &sorted, n_dev, false);
+    rc = radix_sort_pairs_impl<uint32_t, int32_t, RS_DEFAULT_ITEMS>(s, n_isects, k_a, k_b, (int32_t*)v_a, (int32_t*)v_b,
+                                                                     flatten_ids, 0, tile_bits, table, &sorted, n_dev,
+                                                                     nullptr, nullptr, true);
   if (rc) return rc;
-  hipLaunchKernelGGL(isect2_offsets_kernel, dim3(min(ceil_div(n_isects, 256), 256 * 16)), dim3(256), 0,
-                     s, n_isects, sorted, n_tiles, offsets, flatten_ids, emit_slot,
-                     slots ? (const int2*)v_f : nullptr, depths, isect_ids, n_dev);
+  hipLaunchKernelGGL(isect2_offsets_kernel, dim3(min(ceil_div(n_isects, 256), 256 * 16)), dim3(256), 0, s,
+                     n_isects, sorted, n_tiles, offsets, flatten_ids, depths, isect_ids, n_dev);
   CLMGS_LAUNCH_CHECK();
   return 0;
 }
@@ -1252,12 +838,7 @@ visibility_emit_kernel(int C, int N, int W64, const unsigned long long* __restri
 
 extern "C" size_t clmgs_visibility_select_temp_bytes(int C, int N) {
   const size_t words = (size_t)(C + 1) * (size_t)((N + 63) / 64);
-#ifdef CLMGS_PROFILE_BUILD
-  const size_t ctrl = lb_scan_ctrl_bytes((int64_t)words);
-#else
-  const size_t ctrl = 0;
-#endif
-  return 2 * align_up(words * 8, 256) + max(scan_scratch_bytes((int64_t)words), ctrl) + 256;
+  return 2 * align_up(words * 8, 256) + scan_scratch_bytes((int64_t)words) + 256;
 }
 
 extern "C" int clmgs_visibility_select_count_blocks(void* stream, int C, int N, const float* means,
@@ -1299,14 +880,7 @@ extern "C" int clmgs_visibility_select_count_blocks(void* stream, int C, int N, 
                      dim3(256), 0, s, C, N, W64, means, quats_raw, log_scales, viewmats, Ks,
                      (float)width, (float)height, eps2d, near_plane, far_plane, radius_clip, bits, counts, block_flags);
   CLMGS_LAUNCH_CHECK();
-  int rc;
-#ifdef CLMGS_PROFILE_BUILD
-  if (binning_route() == BIN_LOOKBACK) {  // one launch (decoupled look-back) + the memset of its control words
-    CLMGS_HIP(hipMemsetAsync(scratch, 0, lb_scan_ctrl_bytes((int64_t)words), s));
-    rc = lb_inclusive_scan_i64(s, (int64_t)words, counts, scratch);
-  } else
-#endif
-  rc = inclusive_scan_i64(s, (int64_t)words, counts, scratch);
+  const int rc = inclusive_scan_i64(s, (int64_t)words, counts, scratch);
   if (rc) return rc;
   // cum_totals[r] = number of set bits in rows 0..r (device array of C+1, read back by the caller)
   for (int r = 0; r <= C; ++r)
@@ -1343,20 +917,5 @@ extern "C" int clmgs_visibility_candidates(void* stream, int C, int N, int own_l
                      (hipStream_t)stream, C, N, own_lo, own_hi, means, log_scales, viewmats, Ks, (float)width,
                      (float)height, eps2d, near_plane, far_plane, pos_margin, scale_gain, mask);
   CLMGS_LAUNCH_CHECK();
-  return 0;
-}
-
-
-// Device error word of the look-back primitives: *out = bits (1 = a scan look-back, 2 = a sort look-back gave up
-// after its spin bound: a workgroup of the launch never published -- results of that call are invalid); cleared when
-// `reset`.  Synchronises the device.
-extern "C" int clmgs_device_errors(uint32_t* out, int reset) {
-  CLMGS_CHECK_ARG(out);
-  CLMGS_HIP(hipDeviceSynchronize());
-  CLMGS_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(clmgs::g_dev_err), sizeof(uint32_t)));
-  if (reset && *out) {
-    const uint32_t z = 0;
-    CLMGS_HIP(hipMemcpyToSymbol(HIP_SYMBOL(clmgs::g_dev_err), &z, sizeof(z)));
-  }
   return 0;
 }

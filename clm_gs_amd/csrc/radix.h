@@ -2,15 +2,17 @@
 // gfx950 -- the sorting / scanning primitives of the tile-binning stage (isect.hip).
 //
 // One pass per 8-bit digit, three kernels per pass:
-//   histogram : every block counts the digits of its 4096-key chunk (LDS atomics) and writes a
-//               digit-major [256][n_blocks] table;
-//   scan      : exclusive scan of every digit's row (one block per digit) + the 256 row totals
-//               (their exclusive scan, the global base of every digit, is redone by every
-//               scatter block: cheaper than a fourth dependent launch per pass);
-//   scatter   : every block re-reads its chunk (16 keys per thread kept in registers); the stable
+//   histogram : every block counts the digits of four consecutive 1024-key chunks (LDS atomics, all
+//               loads in flight at once) and writes a digit-major [256][n_blocks] table, one column
+//               per chunk (radix_hist_multi_kernel);
+//   scan      : exclusive scan of every digit's row (one block per digit, one contiguous segment of
+//               the row per thread) + the 256 row totals (their exclusive scan, the global base of
+//               every digit, is redone by every scatter block: cheaper than a fourth dependent
+//               launch per pass) (radix_scan_rows_seg_kernel);
+//   scatter   : every block re-reads its chunk (4 keys per thread kept in registers); the stable
 //               rank of a key inside its wave comes from 8 ballots (lanes with the same digit) +
 //               a popcount of the lanes below; the (round, wave) groups are ordered by ONE
-//               per-digit prefix over a [16][4][256] LDS count table (2 barriers per 4096 keys).
+//               per-digit prefix over a [4][4][256] LDS count table (2 barriers per 1024 keys).
 // Stability (equal digits keep input order) is what makes multi-pass LSD sorting correct and
 // what the two-level binning relies on for depth ties.
 #pragma once
@@ -28,63 +30,8 @@ constexpr int RS_THREADS = 256;
 constexpr int RS_DEFAULT_ITEMS = CLMGS_RS_ITEMS;
 constexpr int RS_MIN_CHUNK = RS_THREADS * RS_DEFAULT_ITEMS;
 
-template <typename KeyT, int RS_ITEMS>
-__global__ void __launch_bounds__(RS_THREADS)
-radix_hist_kernel(int64_t n, const KeyT* __restrict__ keys, int shift, int n_blocks,
-                  uint32_t* __restrict__ table /*[256][n_blocks]*/, const int64_t* __restrict__ n_dev) {
-  constexpr int RS_CHUNK = RS_THREADS * RS_ITEMS;
-  if (n_dev) n = min(n, *n_dev);  // device-side count: the launch was sized for the capacity `n`
-  __shared__ uint32_t h[256];
-  h[threadIdx.x] = 0;
-  __syncthreads();
-  const int64_t base = (int64_t)blockIdx.x * RS_CHUNK;
-#pragma unroll 4
-  for (int it = 0; it < RS_ITEMS; ++it) {
-    const int64_t i = base + it * RS_THREADS + threadIdx.x;
-    if (i < n) atomicAdd(&h[(unsigned)((keys[i] >> shift) & 0xFF)], 1u);
-  }
-  __syncthreads();
-  table[(size_t)threadIdx.x * n_blocks + blockIdx.x] = h[threadIdx.x];
-}
-
-// exclusive scan of every digit's row of the [256][n_blocks] table (block d = digit d) + row totals.
-// 256-thread blocks on purpose (like every kernel of the binning chain): next to the alpha-blend
-// kernels, whose one-wave blocks refill every freed wave slot, a 1024-thread block (16 slots on ONE
-// CU at once) was not dispatched until the tile kernel had drained -- 1.5 ms instead of 5 us.
-constexpr int RS_SCAN_THREADS = 256;
-static __global__ void __launch_bounds__(RS_SCAN_THREADS)
-radix_scan_rows_kernel(int n_blocks, uint32_t* __restrict__ table, uint32_t* __restrict__ row_tot) {
-  __shared__ uint32_t wsum[RS_SCAN_THREADS / 64];
-  __shared__ uint32_t carry_s;
-  if (threadIdx.x == 0) carry_s = 0;
-  __syncthreads();
-  uint32_t* row = table + (size_t)blockIdx.x * n_blocks;
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  for (int base = 0; base < n_blocks; base += RS_SCAN_THREADS) {
-    const int i = base + threadIdx.x;
-    const uint32_t v = i < n_blocks ? row[i] : 0u;
-    uint32_t x = v;  // inclusive scan inside the wave
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t y = __shfl_up(x, o, 64);
-      if (lane >= o) x += y;
-    }
-    if (lane == 63) wsum[wid] = x;
-    __syncthreads();
-    uint32_t woff = 0;
-    for (int w = 0; w < wid; ++w) woff += wsum[w];
-    const uint32_t carry = carry_s;
-    if (i < n_blocks) row[i] = carry + woff + x - v;
-    __syncthreads();
-    if (threadIdx.x == RS_SCAN_THREADS - 1) carry_s = carry + woff + x;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) row_tot[blockIdx.x] = carry_s;
-}
-
-// Round 4 variants (the default route; the round-3 kernels above stay for CLMGS_BINNING=legacy):
-// histogram -- one block counts HB consecutive chunks: HB x RS_ITEMS independent loads in flight per thread instead
-// of RS_ITEMS, a quarter of the blocks (the kernel is a load -> LDS atomic -> store latency chain, not bandwidth).
+// histogram -- one block counts HB consecutive chunks: HB x RS_ITEMS independent loads in flight per thread instead of
+// RS_ITEMS, a quarter of the blocks (the kernel is a load -> LDS atomic -> store latency chain, not bandwidth).
 constexpr int RS_HIST_HB = 4;
 template <typename KeyT, int RS_ITEMS>
 __global__ void __launch_bounds__(RS_THREADS)
@@ -118,9 +65,14 @@ radix_hist_multi_kernel(int64_t n, const KeyT* __restrict__ keys, int shift, int
     if (c0 + c < n_blocks) table[(size_t)threadIdx.x * n_blocks + c0 + c] = h[c][threadIdx.x];
 }
 
-// row scan -- thread t of block d owns the contiguous segment [t K, (t+1) K) of digit d's row (K = ceil(n_blocks /
-// 256)): independent loads, ONE block-wide scan of the 256 segment sums, a second sweep writing the exclusive values;
-// the round-3 kernel walked the row in 256-wide steps with three barriers each (36 dependent steps at 9.3 M keys).
+// row scan -- exclusive scan of every digit's row of the [256][n_blocks] table (block d = digit d) + row totals.
+// Thread t of block d owns the contiguous segment [t K, (t+1) K) of the row (K = ceil(n_blocks / 256)): independent
+// loads, ONE block-wide scan of the 256 segment sums, a second sweep writing the exclusive values (walking the row in
+// 256-wide steps took three barriers per step: 36 dependent steps at 9.3 M keys).
+// 256-thread blocks on purpose (like every kernel of the binning chain): next to the alpha-blend
+// kernels, whose one-wave blocks refill every freed wave slot, a 1024-thread block (16 slots on ONE
+// CU at once) was not dispatched until the tile kernel had drained -- 1.5 ms instead of 5 us.
+constexpr int RS_SCAN_THREADS = 256;
 static __global__ void __launch_bounds__(RS_SCAN_THREADS)
 radix_scan_rows_seg_kernel(int n_blocks, uint32_t* __restrict__ table, uint32_t* __restrict__ row_tot) {
   __shared__ uint32_t wsum[RS_SCAN_THREADS / 64];
@@ -283,8 +235,7 @@ template <typename KeyT, typename ValT, int ITEMS>
 static int radix_sort_pairs_impl(hipStream_t s, int64_t n, KeyT* keysA, KeyT* keysB, ValT* valsA,
                                  ValT* valsB, ValT* vals_final, int begin_bit, int end_bit,
                                  uint32_t* table, KeyT** keys_sorted, const int64_t* n_dev = nullptr,
-                                 int32_t* split_a = nullptr, int32_t* split_b = nullptr, bool round4 = true,
-                                 bool hist0_done = false) {
+                                 int32_t* split_a = nullptr, int32_t* split_b = nullptr, bool hist0_done = false) {
   constexpr int RS_CHUNK = RS_THREADS * ITEMS;
   const int passes = (end_bit - begin_bit + 7) / 8;
   const int n_blocks = (int)((n + RS_CHUNK - 1) / RS_CHUNK);
@@ -300,17 +251,11 @@ static int radix_sort_pairs_impl(hipStream_t s, int64_t n, KeyT* keysA, KeyT* ke
     const int shift = begin_bit + 8 * p;
     KeyT* kdst = (ksrc == keysA) ? keysB : keysA;
     ValT* vdst = (p == passes - 1) ? vals_final : ((vsrc == valsA) ? valsB : valsA);
-    if (round4) {
-      // hist0_done: the producer of the keys (isect2_emit_hist_kernel) has already left the first digit's counts in `table`
-      if (!(hist0_done && p == 0))
-        hipLaunchKernelGGL((radix_hist_multi_kernel<KeyT, ITEMS>), dim3((n_blocks + RS_HIST_HB - 1) / RS_HIST_HB),
-                           dim3(RS_THREADS), 0, s, n, ksrc, shift, n_blocks, table, n_dev);
-      hipLaunchKernelGGL(radix_scan_rows_seg_kernel, dim3(256), dim3(RS_SCAN_THREADS), 0, s, n_blocks, table, row_tot);
-    } else {
-      hipLaunchKernelGGL((radix_hist_kernel<KeyT, ITEMS>), dim3(n_blocks), dim3(RS_THREADS), 0, s, n, ksrc, shift,
-                         n_blocks, table, n_dev);
-      hipLaunchKernelGGL(radix_scan_rows_kernel, dim3(256), dim3(RS_SCAN_THREADS), 0, s, n_blocks, table, row_tot);
-    }
+    // hist0_done: the producer of the keys (isect2_emit_hist_kernel) has already left the first digit's counts in `table`
+    if (!(hist0_done && p == 0))
+      hipLaunchKernelGGL((radix_hist_multi_kernel<KeyT, ITEMS>), dim3((n_blocks + RS_HIST_HB - 1) / RS_HIST_HB),
+                         dim3(RS_THREADS), 0, s, n, ksrc, shift, n_blocks, table, n_dev);
+    hipLaunchKernelGGL(radix_scan_rows_seg_kernel, dim3(256), dim3(RS_SCAN_THREADS), 0, s, n_blocks, table, row_tot);
     if constexpr (sizeof(ValT) == 8) {
       if (split_a && p == passes - 1) {
         hipLaunchKernelGGL((radix_scatter_kernel<KeyT, ValT, ITEMS, true>), dim3(n_blocks), dim3(RS_THREADS), 0, s, n, ksrc,
@@ -333,10 +278,9 @@ static int radix_sort_pairs_impl(hipStream_t s, int64_t n, KeyT* keysA, KeyT* ke
 template <typename KeyT, typename ValT = int32_t>
 static int radix_sort_pairs(hipStream_t s, int64_t n, KeyT* keysA, KeyT* keysB, ValT* valsA,
                             ValT* valsB, ValT* vals_final, int begin_bit, int end_bit,
-                            uint32_t* table, KeyT** keys_sorted, const int64_t* n_dev = nullptr, bool round4 = true) {
+                            uint32_t* table, KeyT** keys_sorted, const int64_t* n_dev = nullptr) {
   return radix_sort_pairs_impl<KeyT, ValT, RS_DEFAULT_ITEMS>(s, n, keysA, keysB, valsA, valsB, vals_final,
-                                                      begin_bit, end_bit, table, keys_sorted, n_dev, nullptr, nullptr,
-                                                      round4);
+                                                      begin_bit, end_bit, table, keys_sorted, n_dev);
 }
 
 // Inclusive scan of 256 values (one per thread, thread order) -> inclusive result; wsum[0..3] (LDS) get the four wave
@@ -396,7 +340,7 @@ scan_i64_blocks_kernel(int64_t n, int64_t* __restrict__ data, int64_t* __restric
   if (threadIdx.x == SC_THREADS - 1) block_tot[blockIdx.x] = off + run;
 }
 
-// pass 2: exclusive scan of the block totals, one block (256 threads, see radix_scan_rows_kernel)
+// pass 2: exclusive scan of the block totals, one block (256 threads, see radix_scan_rows_seg_kernel)
 static __global__ void __launch_bounds__(SC_THREADS)
 scan_i64_totals_kernel(int nb, int64_t* __restrict__ tot) {
   __shared__ int64_t wsum[SC_THREADS / 64];

@@ -269,8 +269,8 @@ def training(gaussians, scene, train_cameras, test_cameras, log_file, iterations
     from . import _lib
 
     def _check_device():
-        # the host has just synchronised: an asynchronous device fault / a timed-out pass of the profiling build's
-        # look-back binning route surfaces HERE, not at the end of the run with the model unsaved
+        # the host has just synchronised: an asynchronous device fault / a raised device error word (the deferred
+        # small-attribute Adam) surfaces HERE, not at the end of the run with the model unsaved
         _lib.check_device_errors()
     defer = bool(getattr(args, "defer_loss_log", True))
     loss_log = _LossLog(log_file, defer)

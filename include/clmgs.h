@@ -516,13 +516,11 @@ int clmgs_adam_small_deferred(void* stream, int64_t n, float* const* params, flo
 /* Profiling aid: counters of the CLMGS_BWD_DEBUG=3 variant of the backward tile kernel. */
 int clmgs_debug_counters(unsigned long long* out16, int reset);
 
-/* Device error word of the single-launch scan / sort-pass kernels of the binning chain (csrc/onesweep.h: workgroups
- * of one launch hand per-chunk aggregates to each other by decoupled look-back; every poll loop is bounded).
- * *bits: 1 = a scan look-back, 2 = a sort-pass look-back gave up after its bound -- the lists of that call are
- * invalid; 4 = clmgs_adam_small_deferred met a block further behind than the step history it was given (the caller's
- * invariant was broken: those rows' parameters are wrong).  Synchronises the device; `reset` clears the word.  No reference counterpart (gsplat.isect_tiles sorts
- * with cub, strategies/base_engine.py:175-186); callers check it where they synchronise anyway (evaluation, saving,
- * the end of a benchmark). */
+/* Device error word: kernels that meet a broken invariant of their caller raise a bit in one device word instead of
+ * failing silently.  *bits: 4 = clmgs_adam_small_deferred met a block further behind than the step history it was given
+ * (those rows' parameters are wrong).  1 and 2 are retired (they belonged to binning kernels that no longer exist) and
+ * are never raised; any nonzero value is an error.  Synchronises the device; `reset` clears the word.  No reference
+ * counterpart; callers check it where they synchronise anyway (evaluation, saving, the end of a benchmark). */
 int clmgs_device_errors(uint32_t* bits, int reset);
 
 /* ---- pinned host memory  (numba.cuda.pinned_array at clm_offload/gaussian_model.py:34-44) */

@@ -298,6 +298,65 @@ def isect_offset_encode(isect_ids, n_cameras, tile_width, tile_height):
     return off.to(torch.int32).reshape(n_cameras, tile_height, tile_width)
 
 
+def isect_two_level_lists(means2d, radii, depths, tile_width, tile_height, masks=None, capacity=None, tile_size=16):
+    """Every list of the library's two-level binning chain (one camera), restated with vectorised torch on whatever
+    device the inputs live on -> dict: order[V] i32, cum[V] i64, boxes[V,2] i64, totals[2] i64, row_cum[V] i64,
+    flatten_ids[I] i32, offsets[1,th,tw] i32, isect_ids[I] i64, emit_slot[I] i32.
+
+    Row i's tile box is isect_tiles' (float32; exact for a power-of-two tile size); rows with radii <= 0 have box 0 and
+    an all-ones mask.  masks[V] i64 (optional): bit t = tile t (row-major) of the row's box is kept; it applies to
+    boxes of at most 64 tiles only.  order = rows by depth bits, culled rows last, stable; cum / row_cum = inclusive
+    emitted counts in depth / row order; totals = {emitted, un-culled}; boxes[j] = (packed box or 0 when nothing is
+    emitted, mask) of row order[j].  An entry's slot is its place in the row-major (row, tile) list.  Entries are
+    emitted by rank of their row (`capacity` keeps the first `capacity` of them), then stably sorted by tile id."""
+    dev = means2d.device
+    mu = means2d.detach().reshape(-1, 2).to(torch.float32)
+    r = radii.reshape(-1)
+    V = r.numel()
+    alive = r > 0
+    tr = r.to(torch.float32) / tile_size
+    t = mu / tile_size
+    zero = torch.zeros(V, dtype=torch.int64, device=dev)
+    x0 = torch.where(alive, torch.clamp(torch.floor(t[:, 0] - tr), 0, tile_width).to(torch.int64), zero)
+    y0 = torch.where(alive, torch.clamp(torch.floor(t[:, 1] - tr), 0, tile_height).to(torch.int64), zero)
+    x1 = torch.where(alive, torch.clamp(torch.ceil(t[:, 0] + tr), 0, tile_width).to(torch.int64), zero)
+    y1 = torch.where(alive, torch.clamp(torch.ceil(t[:, 1] + tr), 0, tile_height).to(torch.int64), zero)
+    bw = x1 - x0
+    nt = bw * (y1 - y0)
+    ones = torch.full((V,), -1, dtype=torch.int64, device=dev)
+    m = ones if masks is None else torch.where(alive, masks.reshape(-1).to(torch.int64), ones)
+    # the kept (row, tile) entries in row-major order: their index is the slot
+    rows = torch.repeat_interleave(torch.arange(V, device=dev), nt)
+    tl = torch.arange(rows.numel(), device=dev) - (torch.cumsum(nt, 0) - nt)[rows]  # tile index inside the row's box
+    keep = (nt[rows] > 64) | (((m[rows] >> tl.clamp(max=63)) & 1) == 1)
+    rows, tl = rows[keep], tl[keep]
+    tile_id = (y0[rows] + tl // bw[rows]) * tile_width + x0[rows] + tl % bw[rows]
+    cnt = torch.bincount(rows, minlength=V)
+    depth_bits = depths.detach().reshape(-1).to(torch.float32).contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    key = torch.where(alive, depth_bits, torch.full_like(depth_bits, 0xFFFFFFFF))
+    order = torch.sort(key, stable=True).indices
+    rank = torch.empty_like(order)
+    rank[order] = torch.arange(V, device=dev)
+    box = x0 | (y0 << 16) | (x1 << 32) | (y1 << 48)
+    e = torch.sort(rank[rows], stable=True).indices  # emit order: by rank, row-major tiles inside a rank
+    if capacity is not None:
+        e = e[:capacity]
+    e = e[torch.sort(tile_id[e], stable=True).indices]
+    flatten_ids, tiles = rows[e], tile_id[e]
+    offsets = torch.searchsorted(tiles.contiguous(), torch.arange(tile_width * tile_height, device=dev))
+    return {
+        "order": order.to(torch.int32),
+        "cum": torch.cumsum(cnt[order], 0),
+        "boxes": torch.stack((torch.where(cnt > 0, box, zero)[order], m[order]), 1),
+        "totals": torch.stack((cnt.sum(), nt.sum())),
+        "row_cum": torch.cumsum(cnt, 0),
+        "flatten_ids": flatten_ids.to(torch.int32),
+        "offsets": offsets.to(torch.int32).reshape(1, tile_height, tile_width),
+        "isect_ids": (tiles << 32) | key[flatten_ids],
+        "emit_slot": e.to(torch.int32),
+    }
+
+
 # ----------------------------------------------------------------------------
 # A5/A6: rasterize   (call sites: base_engine.py:192-203)
 # ----------------------------------------------------------------------------

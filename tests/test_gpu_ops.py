@@ -710,71 +710,53 @@ def test_device_count_forms_equal_exact_forms(dev, slack):
     assert torch.equal(part2[:I], part[:I]) and bool((part2[I:] == 7.0).all())
 
 
-class _use_library:
-    """with _use_library(path): clm_gs_amd._lib serves the entry points of ANOTHER build of the library (the profiling
-    build, which can still walk the older routes of the binning chain: csrc/isect.hip binning_route)."""
-
-    def __init__(self, path):
-        self.path = path
-
-    def __enter__(self):
-        from clm_gs_amd import _lib
-        self.keep = (_lib._lib, _lib.LIB_PATH)
-        _lib._lib, _lib.LIB_PATH = None, self.path
-        return _lib.lib()
-
-    def __exit__(self, *exc):
-        from clm_gs_amd import _lib
-        _lib._lib, _lib.LIB_PATH = self.keep
-        return False
-
-
-def _profile_library():
-    import os
-    from clm_gs_amd import _lib
-    path = os.path.join(os.path.dirname(_lib.LIB_PATH), "libclmgs_hip_prof.so")
-    if not os.path.exists(path):
-        pytest.skip("profiling build absent (make -C clm_gs_amd/csrc PROFILE=1 BUILD=build_prof OUT=../libclmgs_hip_prof.so; "
-                    "__graft_entry__.build() makes it)")
-    return path
-
-
-def _binning_lists(G, m2, radii, d, tw, th, n, pk, cap_slack, route=None):
-    """Every list the two binning calls produce, through whatever library clm_gs_amd._lib currently serves."""
-    import os
-    if route:
-        os.environ["CLMGS_BINNING"] = route
-    try:
-        c = G.isect2_begin(m2, radii, d, 16, tw, th, want_isect_ids=True, want_slots=True, packed=pk)
-        torch.cuda.synchronize()
-        tot = c.totals.clone()
-        res = [c.order[:n].clone(), c.cum[:n].clone(), c.boxes[:n].clone(), tot, c.row_cum[:n].clone()]
-        cap = None if cap_slack is None else max(1, int(int(tot[0]) * cap_slack))
-        fids, off, ids, (slot, _) = G.isect2_finish(c, capacity=cap)
-        torch.cuda.synchronize()
-        I = int(tot[0]) if cap is None else min(int(tot[0]), cap)
-        return res + [fids[:I].clone(), off.clone(), ids[:I].clone(), slot[:I].clone()]
-    finally:
-        os.environ.pop("CLMGS_BINNING", None)
+def _binning_lists(G, m2, radii, d, tw, th, n, pk, cap_slack):
+    """Every list the two binning calls produce."""
+    c = G.isect2_begin(m2, radii, d, 16, tw, th, want_isect_ids=True, want_slots=True, packed=pk)
+    torch.cuda.synchronize()
+    tot = c.totals.clone()
+    res = [c.order[:n].clone(), c.cum[:n].clone(), c.boxes[:n].clone(), tot, c.row_cum[:n].clone()]
+    cap = None if cap_slack is None else max(1, int(int(tot[0]) * cap_slack))
+    fids, off, ids, (slot, _) = G.isect2_finish(c, capacity=cap)
+    torch.cuda.synchronize()
+    I = int(tot[0]) if cap is None else min(int(tot[0]), cap)
+    return res + [fids[:I].clone(), off.clone(), ids[:I].clone(), slot[:I].clone()]
 
 
 _LIST_NAMES = ("order", "cum", "boxes", "totals", "row_cum", "flatten_ids", "offsets", "isect_ids", "emit_slot")
 
 
+def _reference_lists(m2, radii, d, tw, th, masks, cap_slack):
+    """The same nine lists from oracle.gs_oracle.isect_two_level_lists (torch on the GPU, no library call); the capacity is
+    derived from the reference's own total, as _binning_lists derives it from the library's."""
+    from oracle import gs_oracle as O
+    full = O.isect_two_level_lists(m2, radii, d, tw, th, masks=masks)
+    if cap_slack is None:
+        return [full[nm] for nm in _LIST_NAMES]
+    cap = max(1, int(int(full["totals"][0]) * cap_slack))
+    return [O.isect_two_level_lists(m2, radii, d, tw, th, masks=masks, capacity=cap)[nm] for nm in _LIST_NAMES]
+
+
+def _same(a, b):
+    return a.dtype == b.dtype and a.shape == b.shape and torch.equal(a, b)
+
+
 @pytest.mark.parametrize("n,wh", [(3000, (150, 101)), (180_000, (640, 480))])
-def test_single_launch_binning_equals_legacy_chain(dev, n, wh):
-    """The PRODUCT library's binning chain (round 5: scans folded into their producers, multi-chunk histograms, segment
-    row scans, the chunk-driven emit that also counts the first tile-sort digit, the last tile-sort pass writing
-    flatten_ids / emit_slot itself) == the round-3 chain (three launches per digit and per scan), element for element:
-    depth order, both cumulative counts, boxes / masks, totals, flatten_ids, emit_slot, offsets, isect_ids -- exact form,
-    device-count form (also with a capacity BELOW the count), with and without exact tile culling.  The older routes
-    live in the profiling build only (CLMGS_BINNING=legacy | lookback | r4, csrc/isect.hip): they are compared too --
-    r4 = round 4's thread-per-rank emit + separate histogram, lookback = one launch per radix digit (measured slower).
-    Also the visibility selection (look-back scan vs three-launch scan)."""
+def test_two_level_binning_equals_torch_reference(dev, n, wh):
+    """The library's two-level binning chain (scans folded into their producers, multi-chunk histograms, segment row
+    scans, the chunk-driven emit that also counts the first tile-sort digit, the last tile-sort pass writing flatten_ids
+    / emit_slot itself) == oracle.gs_oracle.isect_two_level_lists, the chain's contract restated in vectorised torch,
+    element for element: depth order, both cumulative counts, boxes / masks, totals, flatten_ids, emit_slot, offsets,
+    isect_ids -- exact form, device-count form (also with a capacity BELOW the count), with and without exact tile
+    culling.  The tile masks of the culled form are not restated (exact_tile_mask uses the fast log and reciprocal): the
+    reference takes the library's mask words, after `order` (which does not depend on them) has been checked and the
+    words have been checked for form, and the resulting lists are ALSO held to the tile-major route's, whose kernel
+    builds its masks itself.
+    Also the visibility selection == nonzero(radii > 0) at this size."""
     from clm_gs_amd import _lib, gsplat as G
     from clm_gs_amd._lib import check, dptr, stream
     from clm_gs_amd.synthetic import nadir_cameras, synth_gaussians
-    prof = _profile_library()
+    from oracle import gs_oracle as O
     L = _lib.lib()
     w, h = wh
     tw, th = math.ceil(w / 16), math.ceil(h / 16)
@@ -793,45 +775,54 @@ def test_single_launch_binning_equals_legacy_chain(dev, n, wh):
     out, al, last = torch.empty((h, w, 3), device=dev), torch.empty((h, w), device=dev), torch.empty((h, w), dtype=torch.int32, device=dev)
     check(L.clmgs_rasterize_fwd(stream(), 1, n, fids0.numel(), dptr(m2), dptr(cn), dptr(colors), dptr(opac), None, w, h, 16, tw,
                                 th, dptr(off0), dptr(fids0), dptr(packed), dptr(out), dptr(al), dptr(last)))  # fills `packed`
+    plain = O.isect_two_level_lists(m2, radii, d, tw, th)
     for pk in (None, packed):
-        with _use_library(prof):
-            ref = {sl: _binning_lists(G, m2, radii, d, tw, th, n, pk, sl, "legacy") for sl in (None, 0.6)}
+        masks = None
+        if pk is not None:
+            got = _binning_lists(G, m2, radii, d, tw, th, n, pk, None)
+            assert _same(got[0], plain["order"])  # the depth order does not depend on the masks
+            masks = torch.empty(n, dtype=torch.int64, device=dev)
+            masks[got[0].long()] = got[2][:, 1]   # the library's mask words, back in row order
+            x0, y0 = plain["boxes"][:, 0] & 0xFFFF, (plain["boxes"][:, 0] >> 16) & 0xFFFF
+            x1, y1 = (plain["boxes"][:, 0] >> 32) & 0xFFFF, (plain["boxes"][:, 0] >> 48) & 0xFFFF
+            nt = torch.empty(n, dtype=torch.int64, device=dev)
+            nt[got[0].long()] = (x1 - x0) * (y1 - y0)
+            # the two forms exact_tile_mask returns: no bit at or above the box's tile count, or all ones
+            assert bool(((masks == -1) | ((nt < 64) & ((masks >> nt.clamp(max=63)) == 0)) | (nt == 64)).all())
+        ref = {sl: _reference_lists(m2, radii, d, tw, th, masks, sl) for sl in (None, 0.6)}
         assert int(ref[None][3][0]) > (100_000 if n > 100_000 else 100)
+        if pk is not None:
+            assert int(ref[None][3][0]) < int(ref[None][3][1])  # culling happens
+            tm = _tile_major_lists(G, m2, radii, d, tw, th, n, pk, None)  # [totals, row_cum, fids, offsets, ids, slot]
+            assert _same(tm[2], ref[None][5]) and _same(tm[4], ref[None][7])
+        else:
+            assert int(ref[None][3][0]) == int(ref[None][3][1])
         for slack in (None, 1.0, 1.3, 0.6):
             want = ref[0.6] if slack == 0.6 else ref[None]
-            got = _binning_lists(G, m2, radii, d, tw, th, n, pk, slack)  # the product library
+            got = _binning_lists(G, m2, radii, d, tw, th, n, pk, slack)
             for nm, a, b in zip(_LIST_NAMES, got, want):
-                assert torch.equal(a, b), ("product", nm, pk is not None, slack)
-            with _use_library(prof):
-                for route in ("fused", "r4", "lookback"):
-                    got = _binning_lists(G, m2, radii, d, tw, th, n, pk, slack, route)
-                    for nm, a, b in zip(_LIST_NAMES, got, want):
-                        assert torch.equal(a, b), (route, nm, pk is not None, slack)
-    # visibility selection through the look-back scan == through the three-launch scan
+                assert _same(a, b), (nm, pk is not None, slack)
+    _lib.check_device_errors()
+    # visibility selection == nonzero(radii > 0) per camera, and its extra row == the union
     cams = nadir_cameras(3, n, w, h, 0.4, seed=5, device="cuda")
     Ks = torch.stack([c.K for c in cams])
     vms = torch.stack([c.world_view_transform.t() for c in cams])
-    import os
-    with _use_library(prof):
-        os.environ["CLMGS_BINNING"] = "lookback"
-        try:
-            f_ref, u_ref = G.visibility_select(sc["xyz"], sc["rotation"], sc["scaling"], vms, Ks, w, h)
-        finally:
-            os.environ.pop("CLMGS_BINNING", None)
-        _lib.check_device_errors()
-    f_new, u_new = G.visibility_select(sc["xyz"], sc["rotation"], sc["scaling"], vms, Ks, w, h)
-    assert torch.equal(u_new, u_ref) and all(torch.equal(a, b) for a, b in zip(f_new, f_ref))
+    vr = G.visibility_radii(sc["xyz"], sc["rotation"], sc["scaling"], vms, Ks, w, h, raw=True)
+    filters, union = G.visibility_select(sc["xyz"], sc["rotation"], sc["scaling"], vms, Ks, w, h)
+    assert len(filters) == 3
+    for c in range(3):
+        assert torch.equal(filters[c], torch.nonzero(vr[c] > 0).flatten())
+    assert torch.equal(union, torch.nonzero((vr > 0).any(dim=0)).flatten())
     _lib.check_device_errors()
 
 
 def test_chunked_emit_with_boxes_spanning_many_chunks(dev):
     """The chunk-driven emit (isect2_emit_hist_kernel: one block per 1024 entries of the list) on what a thread-per-rank
-    emit never had to think about: rows whose box covers the WHOLE image (1 200 tiles = more than a chunk, unmasked),
+    emit never has to think about: rows whose box covers the WHOLE image (1 200 tiles = more than a chunk, unmasked),
     long runs of culled rows and of rows outside the image (ranks that emit nothing, in the middle of the depth
     order), exact depth ties, a list that ends in the middle of a chunk, and capacities that cut a rank in two -- against
-    the round-3 chain of the profiling build, element for element."""
+    oracle.gs_oracle.isect_two_level_lists, element for element."""
     from clm_gs_amd import gsplat as G
-    prof = _profile_library()
     n, w, h = 60_000, 640, 480
     tw, th = math.ceil(w / 16), math.ceil(h / 16)
     g = torch.Generator().manual_seed(3)
@@ -845,13 +836,11 @@ def test_chunked_emit_with_boxes_spanning_many_chunks(dev):
     d[0, :2000] = 7.0
     m2[0, 20000:26000] = torch.tensor([-500.0, -500.0], device=dev)  # boxes clipped to nothing: ranks with zero entries
     for slack in (None, 1.0, 0.37, 0.9991):
-        with _use_library(prof):
-            want = _binning_lists(G, m2, radii, d, tw, th, n, None, slack, "legacy")
-            r4 = _binning_lists(G, m2, radii, d, tw, th, n, None, slack, "r4")
+        want = _reference_lists(m2, radii, d, tw, th, None, slack)
         got = _binning_lists(G, m2, radii, d, tw, th, n, None, slack)
         assert int(want[3][0]) > 40 * tw * th
-        for nm, a, b, c in zip(_LIST_NAMES, got, want, r4):
-            assert torch.equal(a, b) and torch.equal(c, b), (nm, slack)
+        for nm, a, b in zip(_LIST_NAMES, got, want):
+            assert _same(a, b), (nm, slack)
 
 
 @pytest.mark.parametrize("bsz", [4, 8, 32, 64])
