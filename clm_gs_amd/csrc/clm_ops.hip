@@ -214,12 +214,50 @@ __global__ void set_signal_kernel(int32_t* signal, int idx, int32_t value) {
 }
 
 // --------------------------------------------------------------------- Adam
-// update term  m / (sqrt(v) / sqrt(bc2) + eps)  with the hardware sqrt and reciprocal (1 ulp each):
-// the lazy replay is VALU-bound on the ~20-instruction IEEE sqrt + divide sequences (0.92 G VALU
-// instructions per launch), and a 2-ulp error of the update is far below one ulp of the parameter
-// it is subtracted from.  All three Adam kernels share it, so eager, lazy and packed agree.
-__device__ __forceinline__ float adam_ratio(float m, float v, float inv_sqrt_bc2, float eps) {
-  return m * __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(v) * inv_sqrt_bc2 + eps);
+// ONE element step for all five Adam kernels, every rounding written out: a product is fused into an add only where
+// __builtin_fmaf says so.  Everything else is written with the PLAIN operators inside functions that switch
+// contraction off: the pragma is lexical, so it holds for a * b and a - b written here and not for the bodies of
+// header functions (__fmul_rn, __fsub_rn are plain operators compiled under the file's default, and would fuse).
+// The bits of a result therefore do not depend on where the compiler finds an a * b + c: what the eager, lazy, packed
+// and deferred forms compute is stated here once, and the step can be moved or included elsewhere without changing
+// results.
+//
+// update term  m / (sqrt(v) / sqrt(bc2) + eps)  with the hardware sqrt and reciprocal (1 ulp each): the lazy replay is
+// VALU-bound on the ~20-instruction IEEE sqrt + divide sequences (0.92 G VALU instructions per launch), and a 2-ulp
+// error of the update is far below one ulp of the parameter it is subtracted from.  lr_bc = lr / bc1, rounded once.
+__device__ __forceinline__ float adam_update(float p, float m, float v, float lr_bc, float inv_sqrt_bc2, float eps) {
+#pragma clang fp contract(off)
+  const float ratio = m * __builtin_amdgcn_rcpf(__builtin_fmaf(__builtin_amdgcn_sqrtf(v), inv_sqrt_bc2, eps));
+  return __builtin_fmaf(-lr_bc, ratio, p);
+}
+
+// The gradient step.  The moment updates  beta m + (1 - beta) g  exist in two roundings, both inherited: the eager
+// kernels and the small-attribute kernels round the gradient term and fuse the decay (GRAD_FUSED = false); the
+// catch-up kernels' waiting gradient step rounds the decay and fuses the gradient term (GRAD_FUSED = true).  They
+// differ in the last bit of m and v; making them one is a one-word change here that changes training results.
+template <bool GRAD_FUSED = false>
+__device__ __forceinline__ float adam_elem(float& m, float& v, float p, float g, float lr_bc, float beta1,
+                                           float beta2, float ob1, float ob2, float eps,
+                                           float inv_sqrt_bc2) {
+#pragma clang fp contract(off)
+  if constexpr (GRAD_FUSED) {
+    m = __builtin_fmaf(ob1, g, beta1 * m);
+    v = __builtin_fmaf(ob2 * g, g, beta2 * v);
+  } else {
+    m = __builtin_fmaf(beta1, m, ob1 * g);
+    v = __builtin_fmaf(beta2, v, (ob2 * g) * g);
+  }
+  return adam_update(p, m, v, lr_bc, inv_sqrt_bc2, eps);
+}
+
+// The zero-gradient step of the replays.  Either form above gives the same m, v and p for g = 0, except that a moment
+// of -0 comes back as -0 here and as +0 there; this form saves the multiplies and adds of the zero gradient.
+__device__ __forceinline__ float adam_elem_nograd(float& m, float& v, float p, float lr_bc, float beta1, float beta2,
+                                                  float eps, float inv_sqrt_bc2) {
+#pragma clang fp contract(off)
+  m = beta1 * m;
+  v = beta2 * v;
+  return adam_update(p, m, v, lr_bc, inv_sqrt_bc2, eps);
 }
 
 // VEC = 4 when cols % 4 == 0 (the [N,48] SH rows): one 16 B access per array per thread, the
@@ -257,10 +295,8 @@ adam_rows_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict
     if (g) vload<VEC>(g + o, gg);  // g == NULL: rows known to have zero gradient
 #pragma unroll
     for (int c = 0; c < VEC; ++c) {
-      const float gs = g ? gg[c] * grad_scale : 0.f;
-      mm[c] = beta1 * mm[c] + ob1 * gs;
-      vv[c] = beta2 * vv[c] + ob2 * gs * gs;
-      pp[c] -= (lr[c] * inv_bc1) * adam_ratio(mm[c], vv[c], inv_sqrt_bc2, eps);
+      pp[c] = adam_elem(mm[c], vv[c], pp[c], g ? gg[c] * grad_scale : 0.f, lr[c] * inv_bc1, beta1, beta2, ob1, ob2,
+                        eps, inv_sqrt_bc2);
       gg[c] = 0.f;
     }
     vstore<VEC>(m + o, mm); vstore<VEC>(v + o, vv); vstore<VEC>(p + o, pp);
@@ -283,6 +319,78 @@ __device__ __forceinline__ float pow_beta(float beta, float x) {
   return __builtin_amdgcn_exp2f(x * __builtin_amdgcn_logf(beta));
 }
 
+// what a catch-up needs besides the row: the kernel's scalar arguments
+struct CatchUpK {
+  float beta1, beta2, ob1, ob2, eps, grad_scale;
+  int bias_correction, max_replay;
+};
+
+// 1 / bc1 and 1 / sqrt(bc2) of a deferred step from pw = beta^step: IEEE subtraction, square root and division.  The
+// subtraction is a plain operator under the pragma, so it stays a subtraction whatever product pw comes from (the
+// running product of adam_replay, were its loop unrolled, would otherwise fuse into 1 - pw * beta)
+__device__ __forceinline__ void adam_bias(const CatchUpK& K, float pw1, float pw2, float& inv_bc1, float& inv_sqrt_bc2) {
+#pragma clang fp contract(off)
+  inv_bc1 = inv_sqrt_bc2 = 1.f;
+  if (K.bias_correction) {
+    inv_bc1 = 1.f / (1.f - pw1);
+    inv_sqrt_bc2 = 1.f / sqrtf(1.f - pw2);
+  }
+}
+
+// zero-gradient steps from+1 .. to: the first max_replay are replayed exactly; by then the first moment
+// has decayed by beta1^max_replay (1e-12 at 0.9^256, far less with the batch-scaled betas), the remaining
+// parameter increments are below float resolution and only the moments' decay is applied
+template <int VEC>
+__device__ __forceinline__ void adam_replay(const CatchUpK& K, int from, int to, float (&pp)[VEC], float (&mm)[VEC],
+                                            float (&vv)[VEC], const float (&lr)[VEC]) {
+#pragma clang fp contract(off)
+  const int missed = to - from;
+  if (missed <= 0) return;
+  const int n = min(missed, K.max_replay);
+  float pw1 = pow_beta(K.beta1, (float)(from + 1)), pw2 = pow_beta(K.beta2, (float)(from + 1));
+  for (int j = 0; j < n; ++j) {
+    float inv_bc1, inv_sqrt_bc2;
+    adam_bias(K, pw1, pw2, inv_bc1, inv_sqrt_bc2);
+#pragma unroll
+    for (int c = 0; c < VEC; ++c)
+      pp[c] = adam_elem_nograd(mm[c], vv[c], pp[c], lr[c] * inv_bc1, K.beta1, K.beta2, K.eps, inv_sqrt_bc2);
+    pw1 = pw1 * K.beta1; pw2 = pw2 * K.beta2;
+  }
+  if (missed > n) {
+    const int d = missed - n;
+    const float f1 = pow_beta(K.beta1, (float)d), f2 = pow_beta(K.beta2, (float)d);
+#pragma unroll
+    for (int c = 0; c < VEC; ++c) { mm[c] = mm[c] * f1; vv[c] = vv[c] * f2; }
+  }
+}
+
+// DEFERRED gradient step: the row's gradient line holds the gradient of optimizer step gs (> last_step: not
+// applied yet).  It is applied at its own step, between the zero-gradient replays before and after it -- an eager
+// update at the end of that batch, but the row's p / m / v make ONE round trip per touch instead of two (catch-up +
+// end-of-batch Adam).  gg comes back zeroed: what a consumed line is cleared with.
+template <int VEC>
+__device__ __forceinline__ void adam_waiting_step(const CatchUpK& K, int gs, float (&pp)[VEC], float (&mm)[VEC],
+                                                  float (&vv)[VEC], float (&gg)[VEC], const float (&lr)[VEC]) {
+#pragma clang fp contract(off)
+  float inv_bc1, inv_sqrt_bc2;
+  adam_bias(K, pow_beta(K.beta1, (float)gs), pow_beta(K.beta2, (float)gs), inv_bc1, inv_sqrt_bc2);
+#pragma unroll
+  for (int c = 0; c < VEC; ++c) {
+    pp[c] = adam_elem<true>(mm[c], vv[c], pp[c], gg[c] * K.grad_scale, lr[c] * inv_bc1, K.beta1, K.beta2, K.ob1, K.ob2,
+                            K.eps, inv_sqrt_bc2);
+    gg[c] = 0.f;
+  }
+}
+
+// all-zero state (rows that never had a gradient): every replayed step is the identity (m, v stay 0 and
+// p -= lr * 0 / (0 + eps)), so neither the loop nor the stores are needed
+template <int VEC> __device__ __forceinline__ bool adam_any_state(const float (&mm)[VEC], const float (&vv)[VEC]) {
+  bool any_state = false;
+#pragma unroll
+  for (int c = 0; c < VEC; ++c) any_state |= (mm[c] != 0.f) | (vv[c] != 0.f);
+  return any_state;
+}
+
 template <typename IdxT, int VEC>
 __global__ void __launch_bounds__(256)
 adam_catch_up_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
@@ -292,6 +400,7 @@ adam_catch_up_kernel(float* __restrict__ p, float* __restrict__ m, float* __rest
                      float* __restrict__ g, const int32_t* __restrict__ g_step, float grad_scale,
                      float ob1, float ob2,  // 1 - beta, rounded from double like the eager kernel's
                      int keep_grad) {  // 1: the consumed gradient row is left as it is (first-touch producers)
+  const CatchUpK K = {beta1, beta2, ob1, ob2, eps, grad_scale, bias_correction, max_replay};
   const int cv = cols / VEC;
   const int64_t total = n_rows * cv;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total;
@@ -300,12 +409,8 @@ adam_catch_up_kernel(float* __restrict__ p, float* __restrict__ m, float* __rest
     const int k = (int)(i - r * cv) * VEC;
     const int64_t row = row_of<IdxT>(rows, r);
     int a = last_step[row];
-    // DEFERRED gradient step: g[row] holds the gradient of optimizer step g_step[row] (> last_step: not
-    // applied yet).  It is applied here, at its own step, between the zero-gradient replays before and
-    // after it -- the same operations in the same order as an eager update at the end of that batch, but
-    // the row's p / m / v make ONE round trip per touch instead of two (catch-up + end-of-batch Adam).
     const int gs = g_step ? g_step[row] : 0;
-    const bool pending = gs > a && gs <= to_step;
+    const bool pending = gs > a && gs <= to_step;  // (see adam_waiting_step)
     if (to_step - a <= 0) continue;
     const int64_t o = row * cols + k;
     float mm[VEC], vv[VEC], pp[VEC], lr[VEC], gg[VEC];
@@ -313,61 +418,14 @@ adam_catch_up_kernel(float* __restrict__ p, float* __restrict__ m, float* __rest
     // to this kernel are the ones a batch touches, and nearly all of them have work to do
     vload<VEC>(m + o, mm); vload<VEC>(v + o, vv); vload<VEC>(p + o, pp); vload<VEC>(col_lr + k, lr);
     if (pending) vload<VEC>(g + o, gg);
-    if (!pending) {  // all-zero state (rows that never had a gradient): every replayed step is the identity
-      // (m, v stay 0 and p -= lr * 0 / (0 + eps)), so neither the loop nor the stores are needed
-      bool any_state = false;
-#pragma unroll
-      for (int c = 0; c < VEC; ++c) any_state |= (mm[c] != 0.f) | (vv[c] != 0.f);
-      if (!any_state) continue;
-    }
-    // zero-gradient steps from+1 .. to: the first max_replay are replayed exactly; by then the first moment
-    // has decayed by beta1^max_replay (1e-12 at 0.9^256, far less with the batch-scaled betas), the remaining
-    // parameter increments are below float resolution and only the moments' decay is applied
-    auto replay = [&](int from, int to) {
-      const int missed = to - from;
-      if (missed <= 0) return;
-      const int n = min(missed, max_replay);
-      float pw1 = pow_beta(beta1, (float)(from + 1)), pw2 = pow_beta(beta2, (float)(from + 1));
-      for (int j = 0; j < n; ++j) {
-        float inv_bc1 = 1.f, inv_sqrt_bc2 = 1.f;
-        if (bias_correction) {
-          inv_bc1 = 1.f / (1.f - pw1);
-          inv_sqrt_bc2 = 1.f / sqrtf(1.f - pw2);
-        }
-#pragma unroll
-        for (int c = 0; c < VEC; ++c) {
-          mm[c] *= beta1;
-          vv[c] *= beta2;
-          pp[c] -= (lr[c] * inv_bc1) * adam_ratio(mm[c], vv[c], inv_sqrt_bc2, eps);
-        }
-        pw1 *= beta1; pw2 *= beta2;
-      }
-      if (missed > n) {
-        const int d = missed - n;
-        const float f1 = pow_beta(beta1, (float)d), f2 = pow_beta(beta2, (float)d);
-#pragma unroll
-        for (int c = 0; c < VEC; ++c) { mm[c] *= f1; vv[c] *= f2; }
-      }
-    };
+    if (!pending && !adam_any_state<VEC>(mm, vv)) continue;
     if (pending) {
-      replay(a, gs - 1);
-      float inv_bc1 = 1.f, inv_sqrt_bc2 = 1.f;
-      if (bias_correction) {
-        inv_bc1 = 1.f / (1.f - pow_beta(beta1, (float)gs));
-        inv_sqrt_bc2 = 1.f / sqrtf(1.f - pow_beta(beta2, (float)gs));
-      }
-#pragma unroll
-      for (int c = 0; c < VEC; ++c) {
-        const float gsc = gg[c] * grad_scale;
-        mm[c] = beta1 * mm[c] + ob1 * gsc;
-        vv[c] = beta2 * vv[c] + ob2 * gsc * gsc;
-        pp[c] -= (lr[c] * inv_bc1) * adam_ratio(mm[c], vv[c], inv_sqrt_bc2, eps);
-        gg[c] = 0.f;
-      }
+      adam_replay<VEC>(K, a, gs - 1, pp, mm, vv, lr);
+      adam_waiting_step<VEC>(K, gs, pp, mm, vv, gg, lr);
       if (!keep_grad) vstore<VEC>(g + o, gg);  // consumed: cleared for producers that accumulate
       a = gs;
     }
-    replay(a, to_step);
+    adam_replay<VEC>(K, a, to_step, pp, mm, vv, lr);
     vstore<VEC>(m + o, mm); vstore<VEC>(v + o, vv); vstore<VEC>(p + o, pp);
   }
 }
@@ -387,6 +445,7 @@ adam_catch_up48_kernel(float* __restrict__ p, float* __restrict__ m, float* __re
                        float* __restrict__ g, const int32_t* __restrict__ g_step, float grad_scale,
                        float ob1, float ob2, int keep_grad) {
   constexpr int VEC = 4;
+  const CatchUpK K = {beta1, beta2, ob1, ob2, eps, grad_scale, bias_correction, max_replay};
   const unsigned t0 = blockIdx.x * 256u + threadIdx.x;
   const unsigned r_stride = gridDim.x * 256u / 12u;  // (grid is a multiple of 3)
   unsigned r = t0 / 12u;
@@ -420,57 +479,14 @@ adam_catch_up48_kernel(float* __restrict__ p, float* __restrict__ m, float* __re
     if (to_step - a <= 0) continue;
     vload<VEC>(m + o, mm); vload<VEC>(v + o, vv); vload<VEC>(p + o, pp);
     if (pending) vload<VEC>(g + o, gg);
-    if (!pending) {
-      bool any_state = false;
-#pragma unroll
-      for (int c = 0; c < VEC; ++c) any_state |= (mm[c] != 0.f) | (vv[c] != 0.f);
-      if (!any_state) continue;
-    }
-    auto replay = [&](int from, int to) {
-      const int missed = to - from;
-      if (missed <= 0) return;
-      const int n = min(missed, max_replay);
-      float pw1 = pow_beta(beta1, (float)(from + 1)), pw2 = pow_beta(beta2, (float)(from + 1));
-      for (int j = 0; j < n; ++j) {
-        float inv_bc1 = 1.f, inv_sqrt_bc2 = 1.f;
-        if (bias_correction) {
-          inv_bc1 = 1.f / (1.f - pw1);
-          inv_sqrt_bc2 = 1.f / sqrtf(1.f - pw2);
-        }
-#pragma unroll
-        for (int c = 0; c < VEC; ++c) {
-          mm[c] *= beta1;
-          vv[c] *= beta2;
-          pp[c] -= (lr[c] * inv_bc1) * adam_ratio(mm[c], vv[c], inv_sqrt_bc2, eps);
-        }
-        pw1 *= beta1; pw2 *= beta2;
-      }
-      if (missed > n) {
-        const int d = missed - n;
-        const float f1 = pow_beta(beta1, (float)d), f2 = pow_beta(beta2, (float)d);
-#pragma unroll
-        for (int c = 0; c < VEC; ++c) { mm[c] *= f1; vv[c] *= f2; }
-      }
-    };
+    if (!pending && !adam_any_state<VEC>(mm, vv)) continue;
     if (pending) {
-      replay(a, gs - 1);
-      float inv_bc1 = 1.f, inv_sqrt_bc2 = 1.f;
-      if (bias_correction) {
-        inv_bc1 = 1.f / (1.f - pow_beta(beta1, (float)gs));
-        inv_sqrt_bc2 = 1.f / sqrtf(1.f - pow_beta(beta2, (float)gs));
-      }
-#pragma unroll
-      for (int c = 0; c < VEC; ++c) {
-        const float gsc = gg[c] * grad_scale;
-        mm[c] = beta1 * mm[c] + ob1 * gsc;
-        vv[c] = beta2 * vv[c] + ob2 * gsc * gsc;
-        pp[c] -= (lr[c] * inv_bc1) * adam_ratio(mm[c], vv[c], inv_sqrt_bc2, eps);
-        gg[c] = 0.f;
-      }
+      adam_replay<VEC>(K, a, gs - 1, pp, mm, vv, lr);
+      adam_waiting_step<VEC>(K, gs, pp, mm, vv, gg, lr);
       if (!keep_grad) vstore<VEC>(g + o, gg);
       a = gs;
     }
-    replay(a, to_step);
+    adam_replay<VEC>(K, a, to_step, pp, mm, vv, lr);
     vstore<VEC>(m + o, mm); vstore<VEC>(v + o, vv); vstore<VEC>(p + o, pp);
   }
 }
@@ -490,15 +506,68 @@ struct SmallAdam {
 // mirror rows leave with coalesced 16 B stores: every global access is a full-wave 16 B/lane run.
 constexpr int SA_ROWS = 256;
 
-__device__ __forceinline__ float adam_elem(float& m, float& v, float p, float g, float lr_bc, float beta1,
-                                           float beta2, float ob1, float ob2, float eps,
-                                           float inv_sqrt_bc2) {
-  // explicit roundings (no contraction left to the compiler): the <false> and <true> forms of the kernel below, and
-  // any future caller, produce the same bits from the same inputs
-  m = __builtin_fmaf(beta1, m, __fmul_rn(ob1, g));
-  v = __builtin_fmaf(beta2, v, __fmul_rn(__fmul_rn(ob2, g), g));
-  const float ratio = __fmul_rn(m, __builtin_amdgcn_rcpf(__builtin_fmaf(__builtin_amdgcn_sqrtf(v), inv_sqrt_bc2, eps)));
-  return __builtin_fmaf(-lr_bc, ratio, p);
+// column layout of a packed [N,12] line: tensor ti is small_w(ti) floats wide and starts at column small_co(ti)
+__device__ __forceinline__ constexpr int small_w(int ti) { return ti == 0 ? 3 : (ti == 1 ? 1 : (ti == 2 ? 3 : 4)); }
+__device__ __forceinline__ constexpr int small_co(int ti) { return ti == 0 ? 0 : (ti == 1 ? 3 : (ti == 2 ? 4 : 7)); }
+
+// the block's gradient lines into LDS; a line that admit(row) refuses is not read (zero).  (Kept a plain loop: unrolled
+// or interleaved, its loads in flight cost adam_small_packed_kernel a wave of occupancy.)
+template <typename Admit>
+__device__ __forceinline__ void small_stage(float (&sg)[SA_ROWS * 12], const float4* __restrict__ packed_g,
+                                            int64_t row0, int rows, Admit admit) {
+#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
+  for (int i = threadIdx.x; i < rows * 3; i += SA_ROWS)
+    reinterpret_cast<float4*>(sg)[i] = admit(i / 3) ? packed_g[row0 * 3 + i] : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+// The walk of one block over the four tensors, four elements per thread (one at a time in the ragged tail of the last
+// block): step(ti, row[N], p[N], m[N], v[N], g[N]) advances p / m / v of N elements of tensor ti, given the block-local
+// rows they belong to and their scaled gradients; the new parameters also go to the mirror lines in sp.
+template <typename Step>
+__device__ __forceinline__ void small_walk(const SmallAdam& t, int64_t row0, int rows, const float* sg, float* sp,
+                                           float grad_scale, Step step) {
+  const int tid = threadIdx.x;
+  if (tid < rows) sp[tid * 12 + 11] = 0.f;  // the mirror's pad column
+  __syncthreads();                          // sg staged
+#pragma unroll
+  for (int ti = 0; ti < 4; ++ti) {
+    const int w = small_w(ti), co = small_co(ti);
+    const int n_el = rows * w;
+    float* P = t.p[ti] + row0 * w;
+    float* M = t.m[ti] + row0 * w;
+    float* V = t.v[ti] + row0 * w;
+    for (int i = tid * 4; i < n_el; i += SA_ROWS * 4) {
+      if (i + 3 < n_el) {
+        float4 p4 = *reinterpret_cast<float4*>(P + i), m4 = *reinterpret_cast<float4*>(M + i),
+               v4 = *reinterpret_cast<float4*>(V + i);
+        float pp[4] = {p4.x, p4.y, p4.z, p4.w}, mm[4] = {m4.x, m4.y, m4.z, m4.w},
+              vv[4] = {v4.x, v4.y, v4.z, v4.w};
+        float gg[4];
+        int row[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          row[k] = (i + k) / w;
+          gg[k] = sg[row[k] * 12 + co + (i + k - row[k] * w)] * grad_scale;
+        }
+        step(ti, row, pp, mm, vv, gg);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) sp[row[k] * 12 + co + (i + k - row[k] * w)] = pp[k];
+        *reinterpret_cast<float4*>(P + i) = make_float4(pp[0], pp[1], pp[2], pp[3]);
+        *reinterpret_cast<float4*>(M + i) = make_float4(mm[0], mm[1], mm[2], mm[3]);
+        *reinterpret_cast<float4*>(V + i) = make_float4(vv[0], vv[1], vv[2], vv[3]);
+      } else {
+        for (int idx = i; idx < n_el; ++idx) {  // ragged tail of the last block
+          const int row[1] = {idx / w};
+          float pp[1] = {P[idx]}, mm[1] = {M[idx]}, vv[1] = {V[idx]};
+          const float gg[1] = {sg[row[0] * 12 + co + (idx - row[0] * w)] * grad_scale};
+          step(ti, row, pp, mm, vv, gg);
+          P[idx] = pp[0]; M[idx] = mm[0]; V[idx] = vv[0];
+          sp[row[0] * 12 + co + (idx - row[0] * w)] = pp[0];
+        }
+      }
+    }
+  }
+  __syncthreads();
 }
 
 // g_stamp != NULL (first-touch producers, clmgs_preprocess_bwd with sh_stamp): row r carries a gradient of
@@ -525,59 +594,28 @@ adam_small_packed_kernel(int64_t n, int64_t row_begin, int64_t row_end, SmallAda
       __shared__ uint8_t has_g[SA_ROWS];
       if (tid < rows) has_g[tid] = (uint8_t)(g_stamp[row0 + tid] == cur_step);
       __syncthreads();
-      for (int i = tid; i < rows * 3; i += SA_ROWS)
-        reinterpret_cast<float4*>(sg)[i] = has_g[i / 3] ? packed_g[row0 * 3 + i] : make_float4(0.f, 0.f, 0.f, 0.f);
+      small_stage(sg, packed_g, row0, rows, [&](int row) { return has_g[row] != 0; });
     } else {
-      for (int i = tid; i < rows * 3; i += SA_ROWS)
-        reinterpret_cast<float4*>(sg)[i] = packed_g[row0 * 3 + i];
+      small_stage(sg, packed_g, row0, rows, [](int) { return true; });
     }
-    if (tid < rows) sp[tid * 12 + 11] = 0.f;
-    __syncthreads();
-#pragma unroll
-    for (int ti = 0; ti < 4; ++ti) {
-      const int w = ti == 0 ? 3 : (ti == 1 ? 1 : (ti == 2 ? 3 : 4));
-      const int co = ti == 0 ? 0 : (ti == 1 ? 3 : (ti == 2 ? 4 : 7));
-      const int n_el = rows * w;
-      float* P = t.p[ti] + row0 * w;
-      float* M = t.m[ti] + row0 * w;
-      float* V = t.v[ti] + row0 * w;
+    small_walk(t, row0, rows, sg, sp, grad_scale,
+               [&](int ti, const auto& row, auto& pp, auto& mm, auto& vv, const auto& gg) {
       const float lr_bc = t.lr[ti] * inv_bc1;
-      for (int i = tid * 4; i < n_el; i += SA_ROWS * 4) {
-        if (i + 3 < n_el) {
-          float4 p4 = *reinterpret_cast<float4*>(P + i), m4 = *reinterpret_cast<float4*>(M + i),
-                 v4 = *reinterpret_cast<float4*>(V + i);
-          float pp[4] = {p4.x, p4.y, p4.z, p4.w}, mm[4] = {m4.x, m4.y, m4.z, m4.w},
-                vv[4] = {v4.x, v4.y, v4.z, v4.w};
+      constexpr int N = (int)(sizeof(pp) / sizeof(float));
+      // (RANGE: the same arithmetic for all N, then the selects -- the rows outside the range are written back as they
+      // were; with the select inside the first loop the compiler no longer packs the arithmetic in pairs)
+      float pn[N], m2[N], v2[N];
 #pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const int idx = i + k, row = idx / w, e = idx - row * w;
-            // (RANGE: the same arithmetic, then a select -- a branch around it changes how the compiler contracts the
-            // moment updates, and the two forms of the kernel must agree bit for bit)
-            float m2 = mm[k], v2 = vv[k];
-            const float pn = adam_elem(m2, v2, pp[k], sg[row * 12 + co + e] * grad_scale, lr_bc, beta1, beta2,
-                                       ob1, ob2, eps, inv_sqrt_bc2);
-            const bool act = !RANGE || (row0 + row >= row_begin && row0 + row < row_end);
-            pp[k] = act ? pn : pp[k]; mm[k] = act ? m2 : mm[k]; vv[k] = act ? v2 : vv[k];
-            sp[row * 12 + co + e] = pp[k];
-          }
-          *reinterpret_cast<float4*>(P + i) = make_float4(pp[0], pp[1], pp[2], pp[3]);
-          *reinterpret_cast<float4*>(M + i) = make_float4(mm[0], mm[1], mm[2], mm[3]);
-          *reinterpret_cast<float4*>(V + i) = make_float4(vv[0], vv[1], vv[2], vv[3]);
-        } else {
-          for (int idx = i; idx < n_el; ++idx) {  // ragged tail of the last block
-            const int row = idx / w, e = idx - row * w;
-            float mm = M[idx], vv = V[idx];
-            const float p0 = P[idx];
-            const float pn = adam_elem(mm, vv, p0, sg[row * 12 + co + e] * grad_scale, lr_bc, beta1, beta2, ob1, ob2,
-                                       eps, inv_sqrt_bc2);
-            const bool act = !RANGE || (row0 + row >= row_begin && row0 + row < row_end);
-            if (act) { P[idx] = pn; M[idx] = mm; V[idx] = vv; }
-            sp[row * 12 + co + e] = act ? pn : p0;
-          }
-        }
+      for (int k = 0; k < N; ++k) {
+        m2[k] = mm[k]; v2[k] = vv[k];
+        pn[k] = adam_elem(m2[k], v2[k], pp[k], gg[k], lr_bc, beta1, beta2, ob1, ob2, eps, inv_sqrt_bc2);
       }
-    }
-    __syncthreads();
+#pragma unroll
+      for (int k = 0; k < N; ++k) {
+        const bool act = !RANGE || (row0 + row[k] >= row_begin && row0 + row[k] < row_end);
+        pp[k] = act ? pn[k] : pp[k]; mm[k] = act ? m2[k] : mm[k]; vv[k] = act ? v2[k] : vv[k];
+      }
+    });
     const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int i = tid; i < rows * 3; i += SA_ROWS) {
       packed_p[row0 * 3 + i] = reinterpret_cast<const float4*>(sp)[i];
@@ -671,65 +709,22 @@ adam_small_deferred_kernel(int64_t n, SmallAdam t, float4* __restrict__ packed_p
       gstep_s[tid] = (gs > last && gs <= d.to_step) ? gs : -1;
     }
     __syncthreads();
-    for (int i = tid; i < rows * 3; i += SA_ROWS)
-      reinterpret_cast<float4*>(sg)[i] = gstep_s[i / 3] >= 0 ? packed_g[row0 * 3 + i] : make_float4(0.f, 0.f, 0.f, 0.f);
-    if (tid < rows) sp[tid * 12 + 11] = 0.f;
-    __syncthreads();
+    small_stage(sg, packed_g, row0, rows, [&](int row) { return gstep_s[row] >= 0; });
+    small_walk(t, row0, rows, sg, sp, grad_scale,
+               [&](int ti, const auto& row, auto& pp, auto& mm, auto& vv, const auto& gg) {
+      constexpr int N = (int)(sizeof(pp) / sizeof(float));
+      int gst[N];
 #pragma unroll
-    for (int ti = 0; ti < 4; ++ti) {
-      const int w = ti == 0 ? 3 : (ti == 1 ? 1 : (ti == 2 ? 3 : 4));
-      const int co = ti == 0 ? 0 : (ti == 1 ? 3 : (ti == 2 ? 4 : 7));
-      const int n_el = rows * w;
-      float* P = t.p[ti] + row0 * w;
-      float* M = t.m[ti] + row0 * w;
-      float* V = t.v[ti] + row0 * w;
-      for (int i = tid * 4; i < n_el; i += SA_ROWS * 4) {
-        if (i + 3 < n_el) {
-          float4 p4 = *reinterpret_cast<float4*>(P + i), m4 = *reinterpret_cast<float4*>(M + i),
-                 v4 = *reinterpret_cast<float4*>(V + i);
-          float pp[4] = {p4.x, p4.y, p4.z, p4.w}, mm[4] = {m4.x, m4.y, m4.z, m4.w},
-                vv[4] = {v4.x, v4.y, v4.z, v4.w};
-          float gg[4];
-          int gst[4];
+      for (int q = 0; q < N; ++q) gst[q] = gstep_s[row[q]];
+      for (int s_ = last + 1; s_ <= d.to_step; ++s_) {
+        const int j = d.to_step - s_;
+        const float lr_bc = d.lr[j][ti] * d.inv_bc1[j];
+        const float isb2 = d.inv_sqrt_bc2[j];
 #pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const int idx = i + q, row = idx / w, e = idx - row * w;
-            gg[q] = sg[row * 12 + co + e] * grad_scale;
-            gst[q] = gstep_s[row];
-          }
-          for (int s_ = last + 1; s_ <= d.to_step; ++s_) {
-            const int j = d.to_step - s_;
-            const float lr_bc = d.lr[j][ti] * d.inv_bc1[j];
-            const float isb2 = d.inv_sqrt_bc2[j];
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-              pp[q] = adam_elem(mm[q], vv[q], pp[q], gst[q] == s_ ? gg[q] : 0.f, lr_bc, beta1, beta2, ob1, ob2, eps, isb2);
-          }
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const int idx = i + q, row = idx / w, e = idx - row * w;
-            sp[row * 12 + co + e] = pp[q];
-          }
-          *reinterpret_cast<float4*>(P + i) = make_float4(pp[0], pp[1], pp[2], pp[3]);
-          *reinterpret_cast<float4*>(M + i) = make_float4(mm[0], mm[1], mm[2], mm[3]);
-          *reinterpret_cast<float4*>(V + i) = make_float4(vv[0], vv[1], vv[2], vv[3]);
-        } else {
-          for (int idx = i; idx < n_el; ++idx) {  // ragged tail of the last block
-            const int row = idx / w, e = idx - row * w;
-            float mm = M[idx], vv = V[idx], pq = P[idx];
-            const float g1 = sg[row * 12 + co + e] * grad_scale;
-            for (int s_ = last + 1; s_ <= d.to_step; ++s_) {
-              const int j = d.to_step - s_;
-              pq = adam_elem(mm, vv, pq, gstep_s[row] == s_ ? g1 : 0.f, d.lr[j][ti] * d.inv_bc1[j], beta1, beta2, ob1, ob2,
-                             eps, d.inv_sqrt_bc2[j]);
-            }
-            P[idx] = pq; M[idx] = mm; V[idx] = vv;
-            sp[row * 12 + co + e] = pq;
-          }
-        }
+        for (int q = 0; q < N; ++q)
+          pp[q] = adam_elem(mm[q], vv[q], pp[q], gst[q] == s_ ? gg[q] : 0.f, lr_bc, beta1, beta2, ob1, ob2, eps, isb2);
       }
-    }
-    __syncthreads();
+    });
     for (int i = tid; i < rows * 3; i += SA_ROWS) packed_p[row0 * 3 + i] = reinterpret_cast<const float4*>(sp)[i];
     if (tid == 0) blk_last[blk] = d.to_step;
   }
@@ -974,6 +969,27 @@ extern "C" int clmgs_set_signal(void* stream, int32_t* signal_pinned, int idx, i
   return 0;
 }
 
+// 1 / bc1 and 1 / sqrt(bc2) of optimizer step `step`, from double (1 when there is no bias correction)
+static void adam_bias_host(double beta1, double beta2, int step, int bias_correction, float* inv_bc1,
+                           float* inv_sqrt_bc2) {
+  *inv_bc1 = *inv_sqrt_bc2 = 1.f;
+  if (bias_correction) {
+    *inv_bc1 = (float)(1.0 / (1.0 - pow(beta1, (double)step)));
+    *inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow(beta2, (double)step)));
+  }
+}
+
+// the four small-attribute tensors with their moments; lr4 == NULL: the learning rates travel another way
+static bool small_adam_fill(SmallAdam* t, float* const* params, float* const* exp_avg, float* const* exp_avg_sq,
+                            const double* lr4) {
+  if (!params || !exp_avg || !exp_avg_sq) return false;
+  for (int i = 0; i < 4; ++i) {
+    if (!params[i] || !exp_avg[i] || !exp_avg_sq[i]) return false;
+    t->p[i] = params[i]; t->m[i] = exp_avg[i]; t->v[i] = exp_avg_sq[i]; t->lr[i] = lr4 ? (float)lr4[i] : 0.f;
+  }
+  return true;
+}
+
 extern "C" int clmgs_adam_rows(void* stream, float* p, float* g, float* m, float* v,
                                const void* rows, int idx_is_64, const uint8_t* mask,
                                int64_t n_rows, int cols, const float* col_lr, double beta1,
@@ -982,11 +998,8 @@ extern "C" int clmgs_adam_rows(void* stream, float* p, float* g, float* m, float
   CLMGS_CHECK_ARG(n_rows >= 0 && cols > 0 && step >= 1);
   if (n_rows == 0) return 0;
   CLMGS_CHECK_ARG(p && m && v && col_lr);  // g may be NULL (= all-zero gradient)
-  float inv_bc1 = 1.f, inv_sqrt_bc2 = 1.f;
-  if (bias_correction) {
-    inv_bc1 = (float)(1.0 / (1.0 - pow(beta1, (double)step)));
-    inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow(beta2, (double)step)));
-  }
+  float inv_bc1, inv_sqrt_bc2;
+  adam_bias_host(beta1, beta2, step, bias_correction, &inv_bc1, &inv_sqrt_bc2);
   // 1 - beta in double on the host: (1.f - 0.999f) alone is off by 1.3e-5 relative
   const float ob1 = (float)(1.0 - beta1), ob2 = (float)(1.0 - beta2);
   const bool v4 = (cols % 4 == 0) && (((uintptr_t)p | (uintptr_t)m | (uintptr_t)v | (uintptr_t)g |
@@ -1093,18 +1106,11 @@ extern "C" int clmgs_adam_small_packed_range(void* stream, int64_t n, int64_t ro
   const bool ranged = row_end >= 0;
   if (ranged) CLMGS_CHECK_ARG(row_begin >= 0 && row_begin <= row_end && row_end <= n);
   if (n == 0 || (ranged && row_end == row_begin)) return 0;
-  CLMGS_CHECK_ARG(params && exp_avg && exp_avg_sq && lr4 && packed_p && packed_g &&
-                  (((uintptr_t)packed_p | (uintptr_t)packed_g) & 15) == 0);
+  CLMGS_CHECK_ARG(lr4 && packed_p && packed_g && (((uintptr_t)packed_p | (uintptr_t)packed_g) & 15) == 0);
   SmallAdam t;
-  for (int i = 0; i < 4; ++i) {
-    CLMGS_CHECK_ARG(params[i] && exp_avg[i] && exp_avg_sq[i]);
-    t.p[i] = params[i]; t.m[i] = exp_avg[i]; t.v[i] = exp_avg_sq[i]; t.lr[i] = (float)lr4[i];
-  }
-  float inv_bc1 = 1.f, inv_sqrt_bc2 = 1.f;
-  if (bias_correction) {
-    inv_bc1 = (float)(1.0 / (1.0 - pow(beta1, (double)step)));
-    inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow(beta2, (double)step)));
-  }
+  CLMGS_CHECK_ARG(small_adam_fill(&t, params, exp_avg, exp_avg_sq, lr4));
+  float inv_bc1, inv_sqrt_bc2;
+  adam_bias_host(beta1, beta2, step, bias_correction, &inv_bc1, &inv_sqrt_bc2);
   const float ob1 = (float)(1.0 - beta1), ob2 = (float)(1.0 - beta2);
   if (ranged) {
     const int64_t blocks = (row_end + SA_ROWS - 1) / SA_ROWS - row_begin / SA_ROWS;
@@ -1146,21 +1152,17 @@ extern "C" int clmgs_adam_small_deferred(void* stream, int64_t n, float* const* 
     if (blk_flag) CLMGS_HIP(hipMemsetAsync(blk_flag, 1, (size_t)((n + SA_ROWS - 1) / SA_ROWS), (hipStream_t)stream));
     return 0;
   }
-  CLMGS_CHECK_ARG(params && exp_avg && exp_avg_sq && packed_p && packed_g && g_stamp && blk_last && lr4_hist &&
-                  step_index && pos_margin && scale_gain && (((uintptr_t)packed_p | (uintptr_t)packed_g) & 15) == 0);
+  CLMGS_CHECK_ARG(packed_p && packed_g && g_stamp && blk_last && lr4_hist && step_index && pos_margin && scale_gain &&
+                  (((uintptr_t)packed_p | (uintptr_t)packed_g) & 15) == 0);
   CLMGS_CHECK_ARG(flush_all || (C >= 1 && C <= VB_MAX_CAMS && viewmats && Ks && width > 0 && height > 0));
   SmallAdam t;
-  for (int i = 0; i < 4; ++i) {
-    CLMGS_CHECK_ARG(params[i] && exp_avg[i] && exp_avg_sq[i]);
-    t.p[i] = params[i]; t.m[i] = exp_avg[i]; t.v[i] = exp_avg_sq[i]; t.lr[i] = 0.f;
-  }
+  CLMGS_CHECK_ARG(small_adam_fill(&t, params, exp_avg, exp_avg_sq, nullptr));  // (the learning rates are per step: d.lr)
   SmallDeferred d;
   for (int j = 0; j < SD_KMAX; ++j) {
     const int jj = j < n_hist ? j : n_hist - 1;
     for (int i = 0; i < 4; ++i) d.lr[j][i] = (float)lr4_hist[4 * jj + i];
     CLMGS_CHECK_ARG(step_index[jj] >= 1);
-    d.inv_bc1[j] = (float)(1.0 / (1.0 - pow(beta1, (double)step_index[jj])));       // as clmgs_adam_small_packed_range
-    d.inv_sqrt_bc2[j] = (float)(1.0 / sqrt(1.0 - pow(beta2, (double)step_index[jj])));
+    adam_bias_host(beta1, beta2, step_index[jj], 1, &d.inv_bc1[j], &d.inv_sqrt_bc2[j]);
   }
   for (int k = 0; k <= SD_KMAX; ++k) {
     const int kk = k <= n_hist ? k : n_hist;

@@ -63,6 +63,55 @@ class UnifiedAdam(torch.optim.Optimizer):
         self.param_groups = self.gpu_adam.param_groups + self.cpu_adam.param_groups
         self.state = self.gpu_adam.state | self.cpu_adam.state
 
+    def _gpu_state(self, p):
+        """torch.optim.Adam's own state of a GPU-resident parameter, created if empty."""
+        st = self.gpu_adam.state[p]
+        if len(st) == 0:
+            st["step"] = torch.zeros((), dtype=torch.float32, device=p.device)
+            st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        return st
+
+    def small_groups(self):
+        """The four small-attribute groups in the kernels' order, their state created if empty."""
+        groups = {g["name"]: g for g in self.gpu_adam.param_groups}
+        order = [groups[n] for n in ("xyz", "opacity", "scaling", "rotation")]
+        for g in order:
+            self._gpu_state(g["params"][0])
+        return order
+
+    def small_pointers(self, order):
+        """The p / exp_avg / exp_avg_sq pointer arrays of small_groups(), as the clmgs_adam_small_* entries take them."""
+        import ctypes
+        cols = ([], [], [])
+        for g in order:
+            p = g["params"][0]
+            st = self.gpu_adam.state[p]
+            assert p.is_contiguous() and st["exp_avg"].is_contiguous() and st["exp_avg_sq"].is_contiguous()
+            for col, t in zip(cols, (p, st["exp_avg"], st["exp_avg_sq"])):
+                col.append(t.data_ptr())
+        return tuple((ctypes.c_void_p * 4)(*c) for c in cols)
+
+    def _count_steps(self, groups):
+        """Advances the step counter of every group of `groups` (one launch) and returns their new step indices."""
+        cache = self.__dict__.setdefault("_gpu_steps", {})
+        counters = [self._gpu_state(g["params"][0])["step"] for g in groups]
+        for t in counters:
+            if id(t) not in cache:  # one host read per (re)created state, then counted here
+                cache.clear() if len(cache) > 64 else None
+                cache[id(t)] = int(t.item())
+            cache[id(t)] += 1
+        if counters:
+            torch._foreach_add_(counters, 1)  # torch-Adam's own counters stay what a torch .step() leaves
+        self.state = self.gpu_adam.state | self.cpu_adam.state
+        return [cache[id(t)] for t in counters]
+
+    def advance_steps(self, groups):
+        """The step counters of `groups` advance together: returns the step index they are at now."""
+        steps = self._count_steps(groups)
+        assert all(s == steps[0] for s in steps), "the groups step together"
+        return steps[0]
+
     @torch.no_grad()
     def gpu_step_scaled(self, grad_scale=1.0):
         """Dense Adam of the GPU-resident groups through clmgs_adam_rows: gradient scale (the
@@ -73,22 +122,10 @@ class UnifiedAdam(torch.optim.Optimizer):
         bias-corrected formula as torch (step_size = lr / bc1, denom = sqrt(v) / sqrt(bc2) + eps)."""
         from .clm_kernels import adam_rows
         assert not isinstance(self.gpu_adam, SelectiveAdam)
-        for group in self.gpu_adam.param_groups:
+        stepped = [g for g in self.gpu_adam.param_groups if g["params"][0].grad is not None]
+        for group, step in zip(stepped, self._count_steps(stepped)):  # (each group at its own step index)
             p = group["params"][0]
-            if p.grad is None:
-                continue
             st = self.gpu_adam.state[p]
-            if len(st) == 0:
-                st["step"] = torch.zeros((), dtype=torch.float32, device=p.device)
-                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-            cache = self.__dict__.setdefault("_gpu_steps", {})
-            if id(st["step"]) not in cache:  # one host read per (re)created state, then counted here
-                cache.clear() if len(cache) > 64 else None
-                cache[id(st["step"])] = int(st["step"].item())
-            cache[id(st["step"])] += 1
-            step = cache[id(st["step"])]
-            st["step"] += 1
             # one learning rate per tensor -> the [N,d] layout is irrelevant: stream it as float4 rows
             cols = 4 if p.numel() % 4 == 0 else 1
             key = (cols, float(group["lr"]))
@@ -101,7 +138,6 @@ class UnifiedAdam(torch.optim.Optimizer):
             adam_rows(p.data.view(-1, cols), p.grad.view(-1, cols), st["exp_avg"].view(-1, cols),
                       st["exp_avg_sq"].view(-1, cols), None, lrs[key], b1, b2, group["eps"], step, True,
                       float(grad_scale), True)
-        self.state = self.gpu_adam.state | self.cpu_adam.state
 
     @torch.no_grad()
     def gpu_step_packed(self, packed_p, packed_g, grad_scale=1.0, g_stamp=None, cur_step=0, row_range=None):
@@ -115,39 +151,17 @@ class UnifiedAdam(torch.optim.Optimizer):
         import ctypes
         from . import _lib
         assert not isinstance(self.gpu_adam, SelectiveAdam)
-        groups = {g["name"]: g for g in self.gpu_adam.param_groups}
-        order = [groups[n] for n in ("xyz", "opacity", "scaling", "rotation")]
-        ps, ms, vs, lrs, steps = [], [], [], [], []
-        step = None
-        cache = self.__dict__.setdefault("_gpu_steps", {})
-        for group in order:
-            p = group["params"][0]
-            st = self.gpu_adam.state[p]
-            if len(st) == 0:
-                st["step"] = torch.zeros((), dtype=torch.float32, device=p.device)
-                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-            if id(st["step"]) not in cache:
-                cache.clear() if len(cache) > 64 else None
-                cache[id(st["step"])] = int(st["step"].item())
-            cache[id(st["step"])] += 1
-            steps.append(st["step"])
-            step = cache[id(st["step"])] if step is None else step
-            assert cache[id(st["step"])] == step, "the four groups step together"
-            assert p.is_contiguous() and st["exp_avg"].is_contiguous() and st["exp_avg_sq"].is_contiguous()
-            ps.append(p.data_ptr()); ms.append(st["exp_avg"].data_ptr()); vs.append(st["exp_avg_sq"].data_ptr())
-            lrs.append(float(group["lr"]))
-        torch._foreach_add_(steps, 1)  # the four torch-Adam step counters: one launch instead of four
+        order = self.small_groups()
+        step = self.advance_steps(order)
+        ps, ms, vs = self.small_pointers(order)
         g0 = order[0]
-        arr = lambda xs: (ctypes.c_void_p * 4)(*xs)
-        L = _lib.lib()
         lo, hi = (0, -1) if row_range is None else (int(row_range[0]), int(row_range[1]))
-        _lib.check(L.clmgs_adam_small_packed_range(
-            _lib.stream(), int(packed_p.shape[0]), lo, hi, arr(ps), arr(ms), arr(vs), (ctypes.c_double * 4)(*lrs),
+        _lib.check(_lib.lib().clmgs_adam_small_packed_range(
+            _lib.stream(), int(packed_p.shape[0]), lo, hi, ps, ms, vs,
+            (ctypes.c_double * 4)(*[float(g["lr"]) for g in order]),
             _lib.dptr(packed_p), _lib.dptr(packed_g), float(g0["betas"][0]), float(g0["betas"][1]),
             float(g0["eps"]), int(step), 1, float(grad_scale),
             None if g_stamp is None else _lib.dptr(g_stamp, torch.int32), int(cur_step)))
-        self.state = self.gpu_adam.state | self.cpu_adam.state
 
     def get_all_states(self):
         return [self.gpu_adam.state, self.cpu_adam.state]

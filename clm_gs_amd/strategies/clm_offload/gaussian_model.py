@@ -380,27 +380,8 @@ class GaussianModelCLMOffload(BaseGaussianModel):
         small attributes is RECORDED with the constants it must be replayed with."""
         import math
         sd = self._small_def
-        opt = self.optimizer
-        groups = {g["name"]: g for g in opt.gpu_adam.param_groups}
-        order = [groups[n_] for n_ in ("xyz", "opacity", "scaling", "rotation")]
-        cache = opt.__dict__.setdefault("_gpu_steps", {})
-        steps, idx = [], None
-        for g in order:
-            p = g["params"][0]
-            st = opt.gpu_adam.state[p]
-            if len(st) == 0:
-                st["step"] = torch.zeros((), dtype=torch.float32, device=p.device)
-                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-            if id(st["step"]) not in cache:
-                cache.clear() if len(cache) > 64 else None
-                cache[id(st["step"])] = int(st["step"].item())
-            cache[id(st["step"])] += 1
-            idx = cache[id(st["step"])] if idx is None else idx
-            assert cache[id(st["step"])] == idx, "the four groups step together"
-            steps.append(st["step"])
-        torch._foreach_add_(steps, 1)  # torch-Adam's own step counters stay what an eager run leaves (capture / restore)
-        opt.state = opt.gpu_adam.state | opt.cpu_adam.state
+        order = self.optimizer.small_groups()
+        idx = self.optimizer.advance_steps(order)  # torch-Adam's own counters stay what an eager run leaves (capture / restore)
         if sd["hist"] and sd["hist"][-1][0] != step - 1:
             self.flush_small()  # a gap in the step numbering (a batch ran in another mode): nothing may span it
             sd["hist"] = []
@@ -430,14 +411,8 @@ class GaussianModelCLMOffload(BaseGaussianModel):
         sd = self._small_def
         if not sd["hist"] or (cameras is None and self._small_def_clean()):
             return None
-        opt = self.optimizer
-        groups = {g["name"]: g for g in opt.gpu_adam.param_groups}
-        order = [groups[n_] for n_ in ("xyz", "opacity", "scaling", "rotation")]
-        ps, ms, vs = [], [], []
-        for g in order:
-            p = g["params"][0]
-            st = opt.gpu_adam.state[p]
-            ps.append(p.data_ptr()); ms.append(st["exp_avg"].data_ptr()); vs.append(st["exp_avg_sq"].data_ptr())
+        order = self.optimizer.small_groups()
+        ps, ms, vs = self.optimizer.small_pointers(order)
         hist = sd["hist"][::-1]  # newest first
         nh = len(hist)
         lr = (ctypes.c_double * (4 * nh))(*[x for h in hist for x in h[1]])
@@ -450,7 +425,6 @@ class GaussianModelCLMOffload(BaseGaussianModel):
             sg_.append(math.exp(dl) * 1.001)
         pos_margin = (ctypes.c_float * (nh + 1))(*pm)
         scale_gain = (ctypes.c_float * (nh + 1))(*sg_)
-        arr = lambda xs: (ctypes.c_void_p * 4)(*xs)
         pk, gk, blk = self.small_packed(), self.small_grad(), self._small_def_tables()
         b1, b2 = order[0]["betas"]
         C, vm, Ks, flags = 0, None, None, None
@@ -462,7 +436,7 @@ class GaussianModelCLMOffload(BaseGaussianModel):
             Ks = torch.stack([c.create_k_on_gpu() if getattr(c, "K", None) is None else c.K for c in cameras]).contiguous()
             vm = torch.stack([c.world_view_transform.transpose(0, 1) for c in cameras]).contiguous()
         _lib.check(_lib.lib().clmgs_adam_small_deferred(
-            _lib.stream(), int(self._xyz.shape[0]), arr(ps), arr(ms), arr(vs), _lib.dptr(pk), _lib.dptr(gk),
+            _lib.stream(), int(self._xyz.shape[0]), ps, ms, vs, _lib.dptr(pk), _lib.dptr(gk),
             _lib.dptr(self._row_g_step, torch.int32), _lib.dptr(blk, torch.int32), int(hist[0][0]), nh, lr, sidx,
             pos_margin, scale_gain, float(b1), float(b2), float(order[0]["eps"]), 1.0 / float(self.args.bsz), C,
             _lib.dptr(vm, None, True), _lib.dptr(Ks, None, True), int(utils.get_img_width()), int(utils.get_img_height()),

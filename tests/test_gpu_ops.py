@@ -558,6 +558,93 @@ def test_adam_catch_up_equals_replayed_zero_gradient_steps(dev):
         assert (p - pe).abs().max() < 5e-6   # bias corrections: running product vs pow()
 
 
+def test_adam_catch_up_with_waiting_gradients_all_forms(dev):
+    """clmgs_adam_catch_up with g / g_step == the eager kernels step by step: for every step s, clmgs_adam_rows with
+    g = NULL on the rows that have missed s and hold no gradient for it, and with the gradient (same grad_scale) on
+    the rows whose g_step == s.  Rows at different staleness; a third carry a waiting gradient; stamps <= last
+    (consumed leftovers) and > to_step (not yet due) are ignored; every seventh row has all-zero moments and no
+    gradient and comes back bit for bit; keep_grad 0 clears the consumed lines, 1 leaves them; every other gradient
+    line and every row outside the list is untouched.  Three forms at the smallest shapes whose loops iterate: the
+    48-column kernel above 262 081 listed rows (three iterations: both prefetch stages and both tail conditions;
+    int32 and int64 lists), the generic float4 kernel (8 columns, 1.2 M float4 over at most 4 096 x 256 threads) and
+    the generic scalar kernel (48 columns one float off 16-byte alignment, above 21 846 rows).
+    Tolerances of test_adam_catch_up_equals_replayed_zero_gradient_steps (running product vs pow()): rel-L2 1e-7 for
+    p, 1e-6 for m and v, max |dp| 5e-6.  Measured on these inputs, rel-L2 of p / m / v and max |dp| (int32 = int64
+    lists, keep_grad 0 = 1):
+      48 columns:  7.4e-9 / 2.31e-8 / 2.28e-8, 7.2e-7
+      8 columns:   1.46e-8 / 2.36e-8 / 2.31e-8, 7.2e-7
+      unaligned:   7.2e-9 / 2.35e-8 / 2.29e-8, 4.8e-7
+    (m and v: the waiting gradient step and the eager step round their moment updates differently, adam_elem in
+    clm_ops.hip: one ulp)"""
+    from clm_gs_amd import clm_kernels as K
+    b1, b2, eps, to_step, scale = 0.9, 0.999, 1e-15, 14, 0.25
+    lr48 = torch.cat([torch.full((3,), 2.5e-3), torch.full((45,), 1.25e-4)]).cuda()
+
+    def flat(n, cols, off):  # an [n, cols] table `off` floats past an allocation's (aligned) start
+        return torch.empty(n * cols + off, device="cuda")[off:].view(n, cols)
+
+    for name, n, n_list, cols, off, idx_types in (("48 columns", 300_000, 270_000, 48, 0, (torch.int32, torch.int64)),
+                                                  ("8 columns", 660_000, 600_000, 8, 0, (torch.int32,)),
+                                                  ("unaligned", 33_000, 30_000, 48, 1, (torch.int64,))):
+        gen = torch.Generator(device="cuda").manual_seed(5)
+        col_lr = lr48[:cols].contiguous()
+        p0, m0, v0, g0 = (flat(n, cols, off) for _ in range(4))
+        p0.copy_(torch.randn(n, cols, generator=gen, device="cuda"))
+        m0.copy_(torch.randn(n, cols, generator=gen, device="cuda") * 1e-3)
+        # (second moments bounded away from 0, so that m / sqrt(v) is O(1) as for moments Adam itself produced: of 14 M
+        # draws of rand() * 1e-6 alone a few are 0 or nearly, one step is then m / eps ~ 1e12 and |dp| measures nothing)
+        v0.copy_((torch.rand(n, cols, generator=gen, device="cuda") + 1.0) * 1e-6)
+        g0.copy_(torch.randn(n, cols, generator=gen, device="cuda") * 4e-3)
+        last = torch.randint(3, 12, (n,), generator=gen, device="cuda", dtype=torch.int32)
+        kind = torch.randint(0, 9, (n,), generator=gen, device="cuda")  # 0-2 waiting, 3 consumed, 4 not due, else none
+        u = torch.rand(n, generator=gen, device="cuda")
+        g_step = torch.zeros(n, dtype=torch.int32, device="cuda")
+        waiting = last + 1 + (u * (to_step - last)).int().clamp(max=to_step - 1 - last)
+        g_step = torch.where(kind < 3, waiting, g_step)
+        g_step = torch.where(kind == 3, (u * (last + 1)).int().clamp(max=last), g_step)
+        g_step = torch.where(kind == 4, to_step + 1 + (u * 3).int(), g_step).int()
+        zero_rows = torch.arange(0, n, 7, device="cuda")
+        m0[zero_rows] = 0.0
+        v0[zero_rows] = 0.0
+        g_step[zero_rows] = 0
+        listed = torch.zeros(n, dtype=torch.bool, device="cuda")
+        listed[torch.randperm(n, generator=gen, device="cuda")[:n_list]] = True
+        rows = torch.nonzero(listed).flatten()  # sorted
+        pending = (g_step > last) & (g_step <= to_step)
+        assert 0.25 < float(pending.float().mean()) < 0.4 and int(((g_step > 0) & (g_step <= last)).sum()) > 0
+
+        pe, me, ve = (flat(n, cols, off) for _ in range(3))  # eager, step by step (once per form)
+        pe.copy_(p0); me.copy_(m0); ve.copy_(v0)
+        for s in range(4, to_step + 1):
+            with_g = listed & pending & (g_step == s)
+            K.adam_rows(pe, None, me, ve, torch.nonzero(listed & (last < s) & ~with_g).flatten().int(), col_lr, b1, b2,
+                        eps, s, True, 1.0, False)
+            K.adam_rows(pe, g0, me, ve, torch.nonzero(with_g).flatten().int(), col_lr, b1, b2, eps, s, True, scale, False)
+        consumed = listed & pending
+        for idx_t in idx_types:
+            for keep_grad in (0, 1):
+                p, m, v, g = (flat(n, cols, off) for _ in range(4))
+                p.copy_(p0); m.copy_(m0); v.copy_(v0); g.copy_(g0)
+                K.adam_catch_up(p, m, v, last.clone(), rows.to(idx_t), col_lr, b1, b2, eps, to_step, True, max_replay=256,
+                                g=g, g_step=g_step, grad_scale=scale, keep_grad=bool(keep_grad))
+                figures = (rel_l2(p, pe), rel_l2(m, me), rel_l2(v, ve), float((p - pe).abs().max()))
+                print(f"{name} {idx_t} keep_grad={keep_grad}: rel-L2 p {figures[0]:.3e} m {figures[1]:.3e} "
+                      f"v {figures[2]:.3e} max|dp| {figures[3]:.3e}")
+                assert torch.equal(p[zero_rows], p0[zero_rows]) and float(m[zero_rows].abs().max()) == 0.0
+                assert float(v[zero_rows].abs().max()) == 0.0
+                for x, x0 in ((p, p0), (m, m0), (v, v0)):
+                    assert torch.equal(x[~listed], x0[~listed]), "rows outside the list"
+                assert torch.equal(g[~consumed], g0[~consumed]), "gradient lines that were not consumed"
+                if keep_grad:
+                    assert torch.equal(g[consumed], g0[consumed])
+                else:
+                    assert float(g[consumed].abs().max()) == 0.0
+                assert figures[0] < 1e-7 and figures[1] < 1e-6 and figures[2] < 1e-6
+                assert figures[3] < 5e-6   # bias corrections: running product vs pow()
+                del p, m, v, g
+        del p0, m0, v0, g0, pe, me, ve
+
+
 def test_visibility_select_equals_radii_nonzero(dev):
     """GPU-side filter selection == nonzero(radii > 0) per camera, and its extra row == the union."""
     from clm_gs_amd import gsplat as G
