@@ -27,8 +27,6 @@
 //     kernels they were without the parameter ("Depth");
 //   * blockIdx -> tile mapping is XCD-aware: each XCD's L2 sees a contiguous stripe of tiles,
 //     so neighbouring tiles' shared Gaussians hit in L2.
-#include <stdlib.h>
-
 #include "common.h"
 #include "gs_math.h"
 
@@ -100,13 +98,42 @@ raster_unpack_grad_kernel(int64_t n, const float4* __restrict__ packed_grad,
   }
 }
 
+// The words of one record that the tile kernels use, in registers: the prefetch slot of the staging pipeline.
+struct Rec {
+  float4 A, B;      // rec[0], rec[1]
+  float blue, dep;  // rec[2].x, rec[2].y (NCH = 4)
+};
+// Gather of record g (g < 0: no record, `r` keeps its value)
+template <int NCH>
+__device__ __forceinline__ void gather_record(Rec& r, const float4* __restrict__ packed, int g) {
+  if (g >= 0) {
+    const float4* rec = packed + REC_F4 * (size_t)g;
+    r.A = rec[0]; r.B = rec[1]; r.blue = rec[2].x;
+    if constexpr (NCH == 4) r.dep = rec[2].y;
+  }
+}
+
 template <int NCH>
 struct TileLds {
   float4 a[64];   // x, y, opacity, conic.a
   float4 b[64];   // conic.b, conic.c, r, g
   float c[NCH - 2][64];  // b (, d)
-  int meta[64];   // (offset in staging round << 4) | quadrant mask
+  int meta[64];   // (offset in staging round << 4) | quadrant mask  (backward: << META_SHIFT, | META_SPECIAL)
+  // The staging lane's store of its record at compacted slot `pos`; the conic is pre-scaled here (LOG2E above).
+  __device__ __forceinline__ void stage(int pos, const Rec& r, int meta_word) {
+    a[pos] = make_float4(r.A.x, r.A.y, r.A.z, r.A.w * CONIC_DIAG);
+    b[pos] = make_float4(r.B.x * LOG2E, r.B.y * CONIC_DIAG, r.B.z, r.B.w);
+    c[0][pos] = r.blue; meta[pos] = meta_word;
+    if constexpr (NCH == 4) c[1][pos] = r.dep;
+  }
 };
+
+// Depth-ordered compaction of the lanes that keep their record: this lane's slot; n = records kept by the wave.
+__device__ __forceinline__ int wave_compact(bool keep, int lane, int& n) {
+  const unsigned long long bal = __ballot(keep);
+  n = __popcll(bal);
+  return __popcll(bal & ((1ull << lane) - 1ull));
+}
 
 __device__ __forceinline__ void tile_range(const int32_t* __restrict__ offsets, int tile,
                                            int n_tiles_total, int64_t n_isects, int& s, int& e) {
@@ -114,14 +141,40 @@ __device__ __forceinline__ void tile_range(const int32_t* __restrict__ offsets, 
   e = (tile == n_tiles_total - 1) ? (int)n_isects : offsets[tile + 1];
 }
 
+// Block -> tile (XCD-aware) and lane -> 8x8 position, shared by both tile kernels.
+struct TileGeom {
+  int n_tiles_total, tile, cam, tx, ty, lane, qx, qy;
+  float x0, y0;    // the tile's corner
+  float px0, py0;  // this lane's pixel centre in quadrant 0; quadrant k lies 8 (k & 1), 8 (k >> 1) further
+  __device__ __forceinline__ TileGeom(int C, int tile_w, int tile_h) {
+    const int n_tiles = tile_w * tile_h;
+    n_tiles_total = C * n_tiles;
+    tile = (int)xcd_remap(blockIdx.x, (unsigned)n_tiles_total);
+    cam = tile / n_tiles;
+    const int t_in = tile - cam * n_tiles;
+    ty = t_in / tile_w; tx = t_in - ty * tile_w;
+    lane = threadIdx.x;
+    qx = lane & 7; qy = lane >> 3;
+    x0 = (float)(tx * TILE); y0 = (float)(ty * TILE);
+    px0 = x0 + (float)qx + 0.5f; py0 = y0 + (float)qy + 0.5f;
+  }
+  // this lane's pixel of quadrant k: inside the image?  pix = its index
+  __device__ __forceinline__ bool pixel_of(int k, int W, int H, size_t& pix) const {
+    const int j = tx * TILE + 8 * (k & 1) + qx;
+    const int i = ty * TILE + 8 * (k >> 1) + qy;
+    pix = ((size_t)cam * H + i) * W + j;
+    return (i < H) && (j < W);
+  }
+};
+
 // Quadrant mask of the pixels (centres) where alpha can reach 1/255, i.e. sigma <= L = ln(255 o).
 // Exact: the minimum of sigma over each quadrant's rectangle of pixel centres is compared with L
 // (a small margin absorbs rounding), so a quadrant is skipped only if EVERY pixel in it fails the
 // reference's own alpha >= 1/255 test -- results are unchanged.  The test costs ~150 VALU but
 // runs once per entry on the staging lane (64 entries per instruction): ~2.5 VALU per entry to
 // save whole 64-lane blend passes.
-__device__ __forceinline__ int quadrant_mask(float mx, float my, float opac, float ca, float cb,
-                                             float cc, float tile_x0, float tile_y0) {
+__device__ __forceinline__ int quadrant_mask(const Rec& r, float tile_x0, float tile_y0) {
+  const float mx = r.A.x, my = r.A.y, opac = r.A.z, ca = r.A.w, cb = r.B.x, cc = r.B.y;
   if (!(opac >= ALPHA_MIN)) return 0;
   const float L = __logf(255.f * opac);
   const float det = ca * cc - cb * cb;
@@ -172,9 +225,6 @@ __device__ __forceinline__ int special_entry(float opac, float ca, float cb, flo
 #ifndef CLMGS_FWD4_WAVES
 #define CLMGS_FWD4_WAVES 5
 #endif
-#ifndef CLMGS_FWD_ASM
-#define CLMGS_FWD_ASM 1
-#endif
 template <int NCH>
 __global__ void __launch_bounds__(64, NCH == 4 ? CLMGS_FWD4_WAVES : CLMGS_FWD_WAVES)
 rasterize_fwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ packed,
@@ -186,46 +236,33 @@ rasterize_fwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
   static_assert(NCH == 3 || NCH == 4, "3 or 4 blended channels");
   __shared__ TileLds<NCH> sm;
   if (n_dev) n_isects = min(n_isects, *n_dev);  // device-side count (the launch was prepared for a capacity)
-  const int n_tiles = tile_w * tile_h;
-  const int n_tiles_total = C * n_tiles;
-  const int tile = (int)xcd_remap(blockIdx.x, (unsigned)n_tiles_total);
-  const int cam = tile / n_tiles;
-  const int t_in = tile - cam * n_tiles;
-  const int ty = t_in / tile_w, tx = t_in - ty * tile_w;
-  const int lane = threadIdx.x;
-  const int qx = lane & 7, qy = lane >> 3;
-  const float tile_x0 = (float)(tx * TILE), tile_y0 = (float)(ty * TILE);
+  const TileGeom g(C, tile_w, tile_h);
+  const int lane = g.lane, cam = g.cam;
+  const float px0 = g.px0, py0 = g.py0;
 
   // Per-pixel state kept lean (the VGPR budget decides the waves per SIMD, and the issue rate of one-wave
   // workgroups grows with them): pixel centres are recomputed from the lane, and "this pixel still
   // accumulates" is the SIGN of T (T > 1e-4 while alive; a terminated or out-of-image pixel holds -T).
   float T[PPL], cr[PPL], cg[PPL], cb[PPL], cd[PPL];
   int last[PPL];
-  const float px0 = tile_x0 + (float)qx + 0.5f, py0 = tile_y0 + (float)qy + 0.5f;
 #pragma unroll
   for (int k = 0; k < PPL; ++k) {
-    const int j = tx * TILE + 8 * (k & 1) + qx;
-    const int i = ty * TILE + 8 * (k >> 1) + qy;
+    size_t pix;
     cr[k] = cg[k] = cb[k] = cd[k] = 0.f; last[k] = 0;
-    T[k] = ((i < H) && (j < W)) ? 1.f : -1.f;
+    T[k] = g.pixel_of(k, W, H, pix) ? 1.f : -1.f;
   }
 
   int rs, re;
-  tile_range(offsets, tile, n_tiles_total, n_isects, rs, re);
+  tile_range(offsets, g.tile, g.n_tiles_total, n_isects, rs, re);
 
   // Software-pipelined staging: the id -> record gather of round r+1 is issued before round r's
   // blend loop and consumed after it, so its two dependent HBM/L2 latencies hide under compute.
   // Two-deep: ids run two rounds ahead of the blend loop, records one round ahead, so neither of
   // the two dependent gathers (id -> record) is ever waited for right after it is issued.
-  float4 nA = make_float4(0.f, 0.f, 0.f, 0.f), nB = nA;
-  float nblue = 0.f, ndep = 0.f;
+  Rec nxt = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f), 0.f, 0.f};
   int cur_g = (rs + lane < re) ? flatten_ids[rs + lane] : -1;        // ids of round 0
   int nxt_g = (rs + 64 + lane < re) ? flatten_ids[rs + 64 + lane] : -1;  // ids of round 1
-  if (cur_g >= 0) {
-    const float4* rec = packed + REC_F4 * (size_t)cur_g;
-    nA = rec[0]; nB = rec[1]; nblue = rec[2].x;
-    if constexpr (NCH == 4) ndep = rec[2].y;
-  }
+  gather_record<NCH>(nxt, packed, cur_g);
   // Per-quadrant termination (gsplat's per-pixel `done`, at the granularity this kernel branches on): bit k of
   // `alive` = some pixel of quadrant k still accumulates.  A quadrant whose 64 pixels have all terminated (or lie
   // outside the image) takes no further pass -- a pass over it changes nothing (`valid` needs T > 0) -- and an entry
@@ -235,29 +272,18 @@ rasterize_fwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
   for (int k = 0; k < PPL; ++k) alive |= __any(T[k] > 0.f) ? (1 << k) : 0;
   for (int bs = rs; bs < re; bs += 64) {
     if (!alive) break;
-    const float4 A = nA, B = nB;
-    const float blue = nblue, dep = ndep;
-    const int mask = (cur_g >= 0) ? (quadrant_mask(A.x, A.y, A.z, A.w, B.x, B.y, tile_x0, tile_y0) & alive) : 0;
+    const Rec cur = nxt;
+    const int mask = (cur_g >= 0) ? (quadrant_mask(cur, g.x0, g.y0) & alive) : 0;
     cur_g = nxt_g;
-    if (cur_g >= 0) {  // records of the next round (their ids arrived a round ago)
-      const float4* rec = packed + REC_F4 * (size_t)cur_g;
-      nA = rec[0]; nB = rec[1]; nblue = rec[2].x;
-      if constexpr (NCH == 4) ndep = rec[2].y;
-    }
+    gather_record<NCH>(nxt, packed, cur_g);  // records of the next round (their ids arrived a round ago)
     {
       const int nidx = bs + 128 + lane;  // ids of the round after next
       nxt_g = (nidx < re) ? flatten_ids[nidx] : -1;
     }
-    const unsigned long long bal = __ballot(mask != 0);
-    const int pos = __popcll(bal & ((1ull << lane) - 1ull));
-    const int bn = __popcll(bal);
+    int bn;
+    const int pos = wave_compact(mask != 0, lane, bn);
     __syncthreads();
-    if (mask) {
-      sm.a[pos] = make_float4(A.x, A.y, A.z, A.w * CONIC_DIAG);
-      sm.b[pos] = make_float4(B.x * LOG2E, B.y * CONIC_DIAG, B.z, B.w);
-      sm.c[0][pos] = blue; sm.meta[pos] = (lane << 4) | mask;
-      if constexpr (NCH == 4) sm.c[1][pos] = dep;
-    }
+    if (mask) sm.stage(pos, cur, (lane << 4) | mask);
     __syncthreads();
     for (int t = 0; t < bn; ++t) {
       const float4 RA = sm.a[t];
@@ -276,13 +302,11 @@ rasterize_fwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
           const float dy = RA.y - (py0 + (float)(8 * (k >> 1)));
           const float sigma = scaled_sigma(RA.w, RB.x, RB.y, dx, dy);  // log2(e) * sigma
           const float alpha = fminf(0.999f, RA.z * __builtin_amdgcn_exp2f(-sigma));
-#if CLMGS_FWD_ASM
-          // Round 6: three compares and three selects per pass instead of five and four, and no new scalar work (compares,
-          // selects and v_min issue at half the FMA rate: profiles/r06_valu_calib.jsonl).  A finished / out-of-image pixel
-          // holds a NEGATIVE T, so its next_T < 0 fails `next_T > eps` by itself (no `T > 0` compare); the two outcomes of a
-          // hit are mask arithmetic on the compares' scalar results (s_and / s_andn2; the compiler issued v_cmp_nlt AND
-          // v_cmp_lt for `goes_on` / `!goes_on`); the selects are written as v_cndmask on those scalar masks.  Results are
-          // bit-identical to the select form below (CLMGS_FWD_ASM=0, the round-5 code).
+          // Three compares and three selects per pass, and no scalar work beyond the mask arithmetic (compares, selects and
+          // v_min issue at half the FMA rate: profiles/r06_valu_calib.jsonl).  A finished / out-of-image pixel holds a
+          // NEGATIVE T, so its next_T < 0 fails `next_T > eps` by itself (no `T > 0` compare); the two outcomes of a hit are
+          // mask arithmetic on the compares' scalar results (s_and / s_andn2; written with bools the compiler issued
+          // v_cmp_nlt AND v_cmp_lt for `goes_on` / `!goes_on`); the selects are v_cndmask on those scalar masks.
           const float next_T = T[k] * (1.f - alpha);
           const unsigned long long hit_m = __builtin_amdgcn_ballot_w64(sigma >= 0.f) & __builtin_amdgcn_ballot_w64(alpha >= ALPHA_MIN);
           const unsigned long long go_m = __builtin_amdgcn_ballot_w64(next_T > T_EPS);
@@ -295,30 +319,16 @@ rasterize_fwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
           asm("v_cndmask_b32_e64 %0, %0, %1, %2" : "+v"(T[k]) : "v"(next_T), "s"(acc_m));
           if (stop_m != 0ull) {
             // rare (a pixel stops once; finished pixels of a part-finished quadrant come by again): the sign of T is set
-            // under a narrowed exec mask -- one full-rate v_or here instead of a fourth select in every pass.  (exec is all
-            // ones around this point: 64 threads per workgroup, no divergent region open.)
-            asm volatile("s_mov_b64 exec, %1\n\tv_or_b32_e32 %0, 0x80000000, %0\n\ts_mov_b64 exec, -1" : "+v"(T[k]) : "s"(stop_m));
+            // under a narrowed exec mask -- one full-rate v_or here instead of a fourth select in every pass.  The live mask
+            // is saved, narrowed and restored, so the block holds wherever the compiler places it.
+            unsigned long long exec_keep;
+            asm volatile("s_mov_b64 %1, exec\n\ts_and_b64 exec, exec, %2\n\t"
+                         "v_or_b32_e32 %0, 0x80000000, %0\n\ts_mov_b64 exec, %1"
+                         : "+v"(T[k]), "=&s"(exec_keep) : "s"(stop_m) : "scc");
             if (__builtin_amdgcn_ballot_w64(T[k] > 0.f) == 0ull) alive &= ~(1 << k);
           }
         }
       }
-#else
-          const bool valid = (T[k] > 0.f) && (sigma >= 0.f) && (alpha >= ALPHA_MIN);
-          const float next_T = T[k] * (1.f - alpha);
-          const bool goes_on = next_T > T_EPS;  // valid => alpha, T finite: one compare serves both cases
-          const bool acc = valid && goes_on;
-          const bool term = valid && !goes_on;
-          const float vis = acc ? alpha * T[k] : 0.f;
-          cr[k] += RB.z * vis; cg[k] += RB.w * vis; cb[k] += rblue * vis;
-          if constexpr (NCH == 4) cd[k] += rdep * vis;
-          last[k] = acc ? gi_v : last[k];
-          T[k] = acc ? next_T : (term ? -T[k] : T[k]);
-          // only a pass in which some pixel terminated can empty its quadrant: one ballot of `term` per pass
-          // (it replaces the per-entry whole-tile test: three v_max + a compare over all four T)
-          if (__any(term) && !__any(T[k] > 0.f)) alive &= ~(1 << k);
-        }
-      }
-#endif
       if (!alive) break;
     }
   }
@@ -330,10 +340,8 @@ rasterize_fwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
   }
 #pragma unroll
   for (int k = 0; k < PPL; ++k) {
-    const int j = tx * TILE + 8 * (k & 1) + qx;
-    const int i = ty * TILE + 8 * (k >> 1) + qy;
-    if (i < H && j < W) {
-      const size_t pix = ((size_t)cam * H + i) * W + j;
+    size_t pix;
+    if (g.pixel_of(k, W, H, pix)) {
       const float Tf = fabsf(T[k]);
       render_colors[NCH * pix] = cr[k] + Tf * bgr;
       render_colors[NCH * pix + 1] = cg[k] + Tf * bgg;
@@ -345,28 +353,22 @@ rasterize_fwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
   }
 }
 
-// Wave-wide sums of the backward through LDS (1) or through the permlane-swap / DPP butterflies (0).  See the loop.
-#ifndef CLMGS_BWD_LDS_REDUCE
-#define CLMGS_BWD_LDS_REDUCE 1
-#endif
 template <int NCH>
-struct TileLdsBwd {
-  float4 a[64];
-  float4 b[64];
-  float c[NCH - 2][64];
-  int meta[64];
+struct TileLdsBwd : TileLds<NCH> {
   int id[64];        // Gaussian id (cam*N + g) of the compacted slot, or its emit slot (PART)
   __attribute__((aligned(16))) float acc[64][12];  // reduced per-Gaussian sums of this tile (6 + NCH used)
-#if CLMGS_BWD_LDS_REDUCE
   __attribute__((aligned(16))) float red[8][64];   // transposed scratch of the wave-wide sums: [value][lane]
-#endif
+  // Moments -> gradients, both flush routes: words 0..3 of entry e's gradient line (x y ca cb) and word 4 (cc) from
+  // acc[e] = {Sx Sy Sxx Sxy | Syy ..}, with the conic of the entry taken back from its pre-scaled form.
+  __device__ __forceinline__ float4 grad_xy_conic(int e, float& g_cc) const {
+    const float ca = this->a[e].w * CONIC_DIAG_INV, cb = this->b[e].x * CONIC_OFF_INV,
+                cc = this->b[e].y * CONIC_DIAG_INV;
+    const float* m = acc[e];
+    g_cc = 0.5f * m[4];
+    return make_float4(ca * m[0] + cb * m[1], cb * m[0] + cc * m[1], 0.5f * m[2], m[3]);
+  }
 };
 
-// DBG: profiling-only variants (1 = skip the atomics flush, 2 = skip the reduction too, 3 = phase
-// timers + work counters accumulated into g_dbg, read with clmgs_debug_counters); the product
-// launches DBG = 0.
-__device__ unsigned long long g_dbg[16];
-#define DBG_CLK() (DBG == 3 ? (unsigned long long)__builtin_readcyclecounter() : 0ull)
 #ifndef CLMGS_BWD_WAVES
 #define CLMGS_BWD_WAVES 4  // 5 spills (96 VGPRs): scratch reloads force vmcnt(0) and kill the prefetch
 #endif
@@ -375,7 +377,7 @@ __device__ unsigned long long g_dbg[16];
 // (zeros for culled / unreached entries, so every line is written exactly once per launch) and
 // raster_partials_sum_kernel adds each row's contiguous range.
 // NCH = 4: the atomic route only (a tenth sum g_d = sum fac * vd, a tenth atomic at word 9 of the gradient line).
-template <int DBG, bool PART, int NCH>
+template <bool PART, int NCH>
 __global__ void __launch_bounds__(64, CLMGS_BWD_WAVES)
 rasterize_bwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ packed,
                      const float* __restrict__ backgrounds,
@@ -389,18 +391,12 @@ rasterize_bwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
   static_assert(NCH == 3 || (NCH == 4 && !PART), "4 channels: atomic route only");
   __shared__ TileLdsBwd<NCH> sm;
   if (n_dev) n_isects = min(n_isects, *n_dev);
-  const int n_tiles = tile_w * tile_h;
-  const int n_tiles_total = C * n_tiles;
-  const int tile = (int)xcd_remap(blockIdx.x, (unsigned)n_tiles_total);
-  const int cam = tile / n_tiles;
-  const int t_in = tile - cam * n_tiles;
-  const int ty = t_in / tile_w, tx = t_in - ty * tile_w;
-  const int lane = threadIdx.x;
-  const int qx = lane & 7, qy = lane >> 3;
-  const float tile_x0 = (float)(tx * TILE), tile_y0 = (float)(ty * TILE);
+  const TileGeom g(C, tile_w, tile_h);
+  const int lane = g.lane, cam = g.cam;
+  const float px0 = g.px0, py0 = g.py0;
 
   int rs, re;
-  tile_range(offsets, tile, n_tiles_total, n_isects, rs, re);
+  tile_range(offsets, g.tile, g.n_tiles_total, n_isects, rs, re);
   if (re <= rs) return;
 
   // per-pixel state kept lean (VGPR budget decides waves/SIMD): pixel centres are recomputed from
@@ -416,13 +412,10 @@ rasterize_bwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
   if (backgrounds) { bgr = backgrounds[NCH * cam]; bgg = backgrounds[NCH * cam + 1]; bgb = backgrounds[NCH * cam + 2]; }
   float vd[PPL], bgd = 0.f;  // the fourth channel's cotangents and background (NCH = 4)
   if constexpr (NCH == 4) { if (backgrounds) bgd = backgrounds[NCH * cam + 3]; }
-  const float px0 = tile_x0 + (float)qx + 0.5f, py0 = tile_y0 + (float)qy + 0.5f;
 #pragma unroll
   for (int k = 0; k < PPL; ++k) {
-    const int j = tx * TILE + 8 * (k & 1) + qx;
-    const int i = ty * TILE + 8 * (k >> 1) + qy;
-    if ((i < H) && (j < W)) {
-      const size_t pix = ((size_t)cam * H + i) * W + j;
+    size_t pix;
+    if (g.pixel_of(k, W, H, pix)) {
       const float Tf = 1.f - render_alphas[pix];
       bin[k] = last_ids[pix];
       vr[k] = v_render_colors[NCH * pix]; vg[k] = v_render_colors[NCH * pix + 1]; vb[k] = v_render_colors[NCH * pix + 2];
@@ -443,14 +436,11 @@ rasterize_bwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
   for (int k = 0; k < PPL; ++k) qmax[k] = __builtin_amdgcn_readfirstlane(wave_max_i32(bin[k]));
   max_bin = max(max(qmax[0], qmax[1]), max(qmax[2], qmax[3]));
   const int hi = min(re - 1, max_bin);  // nothing behind the deepest contributor matters
-  unsigned long long c_stage = 0, c_loop = 0, c_flush = 0, n_ent = 0, n_valid = 0, n_quad = 0, n_round = 0;
-  const unsigned long long t_begin = DBG_CLK();
 
   // two-deep software-pipelined staging (see the forward kernel): ids two rounds ahead,
   // records one round ahead; nothing is waited for right after issue, and the waits never
   // include the previous round's atomics
-  float4 nA = make_float4(0.f, 0.f, 0.f, 0.f), nB = nA;
-  float nblue = 0.f, ndep = 0.f;
+  Rec nxt = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f), 0.f, 0.f};
   int cur_g = (hi - lane >= rs) ? flatten_ids[hi - lane] : -1;
   int nxt_g = (hi - 64 - lane >= rs) ? flatten_ids[hi - 64 - lane] : -1;
   int cur_p = 0, nxt_p = 0;
@@ -464,15 +454,9 @@ rasterize_bwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
     cur_p = (hi - lane >= rs) ? emit_slot[hi - lane] : 0;
     nxt_p = (hi - 64 - lane >= rs) ? emit_slot[hi - 64 - lane] : 0;
   }
-  if (cur_g >= 0) {
-    const float4* rec = packed + REC_F4 * (size_t)cur_g;
-    nA = rec[0]; nB = rec[1]; nblue = rec[2].x;
-    if constexpr (NCH == 4) ndep = rec[2].y;
-  }
+  gather_record<NCH>(nxt, packed, cur_g);
   for (int bh = hi; bh >= rs; bh -= 64) {
-    const unsigned long long tA = DBG_CLK();
-    const float4 A = nA, B = nB;
-    const float blue = nblue, dep = ndep;
+    const Rec cur = nxt;
     const int gid = cur_g;
     const int pid = cur_p;
     // Per-quadrant termination: entry gi matters to quadrant k only while gi <= qmax[k] (`valid` needs
@@ -481,14 +465,10 @@ rasterize_bwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
     const int gidx = bh - lane;
     const int reach = (gidx <= qmax[0] ? 1 : 0) | (gidx <= qmax[1] ? 2 : 0) | (gidx <= qmax[2] ? 4 : 0) |
                       (gidx <= qmax[3] ? 8 : 0);
-    const int mask = (gid >= 0) ? (quadrant_mask(A.x, A.y, A.z, A.w, B.x, B.y, tile_x0, tile_y0) & reach) : 0;
+    const int mask = (gid >= 0) ? (quadrant_mask(cur, g.x0, g.y0) & reach) : 0;
     cur_g = nxt_g;
     cur_p = nxt_p;
-    if (cur_g >= 0) {
-      const float4* rec = packed + REC_F4 * (size_t)cur_g;
-      nA = rec[0]; nB = rec[1]; nblue = rec[2].x;
-      if constexpr (NCH == 4) ndep = rec[2].y;
-    }
+    gather_record<NCH>(nxt, packed, cur_g);
     {
       const int nidx = bh - 128 - lane;
       nxt_g = (nidx >= rs) ? flatten_ids[nidx] : -1;
@@ -500,19 +480,14 @@ rasterize_bwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
 #pragma unroll
       for (int q = 0; q < PART_F4; ++q) dst[q] = z4;
     }
-    const unsigned long long bal = __ballot(mask != 0);
-    const int pos = __popcll(bal & ((1ull << lane) - 1ull));
-    const int bn = __popcll(bal);
+    int bn;
+    const int pos = wave_compact(mask != 0, lane, bn);
     __syncthreads();
     if (mask) {
-      sm.a[pos] = make_float4(A.x, A.y, A.z, A.w * CONIC_DIAG);
-      sm.b[pos] = make_float4(B.x * LOG2E, B.y * CONIC_DIAG, B.z, B.w);
-      sm.c[0][pos] = blue; sm.meta[pos] = (lane << META_SHIFT) | special_entry(A.z, A.w, B.x, B.y) | mask;
+      sm.stage(pos, cur, (lane << META_SHIFT) | special_entry(cur.A.z, cur.A.w, cur.B.x, cur.B.y) | mask);
       sm.id[pos] = PART ? pid : gid;
-      if constexpr (NCH == 4) sm.c[1][pos] = dep;
     }
     __syncthreads();
-    const unsigned long long tB = DBG_CLK();
     unsigned long long touched = 0ull;
     for (int t = 0; t < bn; ++t) {
       const float4 RA = sm.a[t];
@@ -523,7 +498,6 @@ rasterize_bwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
       if constexpr (NCH == 4) rdep = sm.c[1][t];
       const int gi = bh - (meta >> META_SHIFT);
       const bool special = (meta & META_SPECIAL) != 0;  // wave-uniform
-      if (DBG == 3) { n_ent++; n_quad += __popc(meta & 15); }
       // moments of w = v_sigma over the tile: the five screen-space gradients are linear in them
       // (g_x = a Sx + b Sy, g_y = b Sx + c Sy, g_conic = Sxx/2, Sxy, Syy/2), applied at the flush
       float g_d = 0.f;  // NCH = 4: sum fac * vd
@@ -570,71 +544,47 @@ rasterize_bwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
           }
         }
       if (any_valid == 0ull) continue;
-      if (DBG == 3) n_valid++;
-      if (DBG != 2) {
-#if CLMGS_BWD_LDS_REDUCE
-        // Eight of the nine wave-wide sums through LDS, transposed: lane L stores value q at red[q][L] (four
-        // ds_write2st64_b32: the two values of a pair lie 64 dwords apart); lane j = 8 q + c then loads eight
-        // floats of red[q][.] (two ds_read_b128, conflict-free: see below), adds them (7 VALU) and three
-        // row_shr DPP adds finish value q in lane 8 q + 7.  ~12 issue slots for eight sums against ~37 for the two
-        // permlane-swap butterflies; the LDS instructions issue beside other waves' VALU.  The ninth sum (opacity)
-        // keeps its DPP chain.  One wave per workgroup: LDS operations of a wave execute in order, the fences only
-        // keep the compiler from moving the loads above the stores.
-        sm.red[0][lane] = Sx; sm.red[1][lane] = Sy; sm.red[2][lane] = Sxx; sm.red[3][lane] = Sxy;
-        sm.red[4][lane] = Syy; sm.red[5][lane] = g_r; sm.red[6][lane] = g_g; sm.red[7][lane] = g_b;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
-        // (lane 8q + c takes floats [4c, 4c+4) and [32 + 4c, 32 + 4c + 4) of value q: consecutive lanes read consecutive
-        //  16 B pieces -- the [8c, 8c+8) assignment had a stride of 32 B between lanes and a 2-way bank conflict on both loads)
-        const float4* rp = reinterpret_cast<const float4*>(&sm.red[lane >> 3][4 * (lane & 7)]);
-        const float4 r0 = rp[0], r1 = rp[8];
-        g_o = wave_sum_to_lane63(g_o);
-        if constexpr (NCH == 4) g_d = wave_sum_to_lane63(g_d);  // the transpose carries eight values: a second chain
-        float u = ((r0.x + r0.y) + (r0.z + r0.w)) + ((r1.x + r1.y) + (r1.z + r1.w));
-        u = dpp_add<0x111>(u);
-        u = dpp_add<0x112>(u);
-        u = dpp_add<0x114>(u);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
-        __builtin_amdgcn_wave_barrier();  // (the next entry's stores stay below this entry's loads)
-        if ((lane & 7) == 7) sm.acc[t][lane >> 3] = u;   // Sx Sy Sxx Sxy | Syy r g b | o
-        if (lane == 63) sm.acc[t][8] = g_o;
-        if constexpr (NCH == 4) { if (lane == 63) sm.acc[t][9] = g_d; }
-#else
-        // 9 wave-wide sums: two 4-packs on the permlane-swap butterfly + one plain DPP chain
-        const float u1 = wave_sum4_rows(Sx, Sy, Sxx, Sxy);       // lanes 15/31/47/63: Sx, Sxx, Sy, Sxy
-        const float u2 = wave_sum4_rows(Syy, g_r, g_g, g_b);     //                    Syy, g, r, b
-        g_o = wave_sum_to_lane63(g_o);
-        if constexpr (NCH == 4) g_d = wave_sum_to_lane63(g_d);
-        if ((lane & 15) == 15) {
-          const int r = lane >> 4;
-          const int m = ((r & 1) << 1) | (r >> 1);               // row -> slot {0,2,1,3}
-          float* a = sm.acc[t];                                   // Sx Sy Sxx Sxy | Syy r g b | o
-          a[m] = u1;
-          a[4 + m] = u2;
-          if (lane == 63) a[8] = g_o;
-          if constexpr (NCH == 4) { if (lane == 63) a[9] = g_d; }
-        }
-#endif
-      }
+      // Eight of the nine wave-wide sums through LDS, transposed: lane L stores value q at red[q][L] (four
+      // ds_write2st64_b32: the two values of a pair lie 64 dwords apart); lane j = 8 q + c then loads eight
+      // floats of red[q][.] (two ds_read_b128, conflict-free: see below), adds them (7 VALU) and three
+      // row_shr DPP adds finish value q in lane 8 q + 7.  ~12 issue slots for eight sums (the cross-lane
+      // butterflies before it took ~37); the LDS instructions issue beside other waves' VALU.  The ninth sum (opacity)
+      // keeps its DPP chain.  One wave per workgroup: LDS operations of a wave execute in order, the fences only
+      // keep the compiler from moving the loads above the stores.
+      sm.red[0][lane] = Sx; sm.red[1][lane] = Sy; sm.red[2][lane] = Sxx; sm.red[3][lane] = Sxy;
+      sm.red[4][lane] = Syy; sm.red[5][lane] = g_r; sm.red[6][lane] = g_g; sm.red[7][lane] = g_b;
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
+      // (lane 8q + c takes floats [4c, 4c+4) and [32 + 4c, 32 + 4c + 4) of value q: consecutive lanes read consecutive
+      //  16 B pieces -- the [8c, 8c+8) assignment had a stride of 32 B between lanes and a 2-way bank conflict on both loads)
+      const float4* rp = reinterpret_cast<const float4*>(&sm.red[lane >> 3][4 * (lane & 7)]);
+      const float4 r0 = rp[0], r1 = rp[8];
+      g_o = wave_sum_to_lane63(g_o);
+      if constexpr (NCH == 4) g_d = wave_sum_to_lane63(g_d);  // the transpose carries eight values: a second chain
+      float u = ((r0.x + r0.y) + (r0.z + r0.w)) + ((r1.x + r1.y) + (r1.z + r1.w));
+      u = dpp_add<0x111>(u);
+      u = dpp_add<0x112>(u);
+      u = dpp_add<0x114>(u);
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
+      __builtin_amdgcn_wave_barrier();  // (the next entry's stores stay below this entry's loads)
+      if ((lane & 7) == 7) sm.acc[t][lane >> 3] = u;   // Sx Sy Sxx Sxy | Syy r g b | o
+      if (lane == 63) sm.acc[t][8] = g_o;
+      if constexpr (NCH == 4) { if (lane == 63) sm.acc[t][9] = g_d; }
       touched |= (1ull << t);
     }
     __syncthreads();
-    const unsigned long long tC = DBG_CLK();
-    if (DBG == 1 || DBG == 2) {
-      if (((touched >> lane) & 1ull) && sm.acc[lane][0] == 1.2345e30f) packed_grad[0] = 1.f;
-    } else if (PART) {
+    if (PART) {
       if (lane < bn) {  // one full line (PART_F4 float4) per entry of the round, zeros if no pixel was valid
         const bool hit = (touched >> lane) & 1ull;
         const float4* a = reinterpret_cast<const float4*>(sm.acc[lane]);
         const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
         float4 r0 = z4, r1 = z4, r2 = z4;
         if (hit) {  // moments -> gradients here (the conic is at hand): x y ca cb | cc r g b | o
-          const float4 m0 = a[0], m1 = a[1];
-          const float ca = sm.a[lane].w * CONIC_DIAG_INV, cb = sm.b[lane].x * CONIC_OFF_INV,
-                      cc = sm.b[lane].y * CONIC_DIAG_INV;  // back from the pre-scaled form
-          r0 = make_float4(ca * m0.x + cb * m0.y, cb * m0.x + cc * m0.y, 0.5f * m0.z, m0.w);
-          r1 = make_float4(0.5f * m1.x, m1.y, m1.z, m1.w);
+          const float4 m1 = a[1];
+          float g_cc;
+          r0 = sm.grad_xy_conic(lane, g_cc);
+          r1 = make_float4(g_cc, m1.y, m1.z, m1.w);
           r2 = make_float4(a[2].x, 0.f, 0.f, 0.f);
         }
         float4* dst = partials + PART_F4 * (size_t)sm.id[lane];
@@ -645,26 +595,16 @@ rasterize_bwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
       // all nine (ten: NCH = 4) atomics of a Gaussian land in its one 64 B gradient line
       float* dst = packed_grad + 4 * REC_F4 * (size_t)sm.id[lane];
       const float* a = sm.acc[lane];
-      const float ca = sm.a[lane].w * CONIC_DIAG_INV, cb = sm.b[lane].x * CONIC_OFF_INV,
-                      cc = sm.b[lane].y * CONIC_DIAG_INV;  // back from the pre-scaled form
-      atomicAdd(dst + 0, ca * a[0] + cb * a[1]);  // x
-      atomicAdd(dst + 1, cb * a[0] + cc * a[1]);  // y
-      atomicAdd(dst + 2, 0.5f * a[2]);            // conic a
-      atomicAdd(dst + 3, a[3]);                   // conic b
-      atomicAdd(dst + 4, 0.5f * a[4]);            // conic c
+      float g_cc;
+      const float4 g0 = sm.grad_xy_conic(lane, g_cc);
+      atomicAdd(dst + 0, g0.x);  // x
+      atomicAdd(dst + 1, g0.y);  // y
+      atomicAdd(dst + 2, g0.z);  // conic a
+      atomicAdd(dst + 3, g0.w);  // conic b
+      atomicAdd(dst + 4, g_cc);  // conic c
 #pragma unroll
       for (int c = 5; c < 6 + NCH; ++c) atomicAdd(dst + c, a[c]);
     }
-    if (DBG == 3) {
-      const unsigned long long tD = DBG_CLK();
-      c_stage += tB - tA; c_loop += tC - tB; c_flush += tD - tC; n_round++;
-    }
-  }
-  if (DBG == 3 && lane == 0) {
-    atomicAdd(&g_dbg[0], c_stage); atomicAdd(&g_dbg[1], c_loop); atomicAdd(&g_dbg[2], c_flush);
-    atomicAdd(&g_dbg[3], DBG_CLK() - t_begin); atomicAdd(&g_dbg[4], n_ent); atomicAdd(&g_dbg[5], n_valid);
-    atomicAdd(&g_dbg[6], n_quad); atomicAdd(&g_dbg[7], n_round); atomicAdd(&g_dbg[8], 1ull);
-    atomicAdd(&g_dbg[9], (unsigned long long)(re - rs));
   }
 }
 
@@ -712,18 +652,6 @@ extern "C" size_t clmgs_rasterize_partials_bytes(int64_t n_isects) {
   return (size_t)(n_isects > 0 ? n_isects : 1) * (PART_F4 * 16);
 }
 
-// Profiling aid (CLMGS_BWD_DEBUG=3): stage / loop / flush / total cycles, entries, entries with a
-// valid pixel, quadrant passes, staging rounds, tiles, list length.  out[16]; reset != 0 clears.
-extern "C" int clmgs_debug_counters(unsigned long long* out, int reset) {
-  CLMGS_HIP(hipDeviceSynchronize());
-  CLMGS_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_dbg), sizeof(unsigned long long) * 16));
-  if (reset) {
-    unsigned long long z[16] = {0};
-    CLMGS_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_dbg), z, sizeof(z)));
-  }
-  return 0;
-}
-
 extern "C" size_t clmgs_rasterize_pack_bytes(int C, int N) {
   return (size_t)C * (size_t)N * REC_F4 * sizeof(float4);
 }
@@ -747,26 +675,14 @@ static int rasterize_fwd_impl(int nch, void* stream, int C, int N, int64_t n_ise
   const int64_t CN = (int64_t)C * N;
   if (means2d && n_isects > 0 && CN > 0) {  // means2d == NULL: `packed` was filled by the caller
     const dim3 grid(min(ceil_div(CN, 256), 256 * 8));
-    if (nch == 4)
-      hipLaunchKernelGGL(raster_pack_kernel<4>, grid, dim3(256), 0, s, CN, means2d, conics, colors, opacities,
-                         (float4*)packed);
-    else
-      hipLaunchKernelGGL(raster_pack_kernel<3>, grid, dim3(256), 0, s, CN, means2d, conics, colors, opacities,
-                         (float4*)packed);
+    hipLaunchKernelGGL(nch == 4 ? raster_pack_kernel<4> : raster_pack_kernel<3>, grid, dim3(256), 0, s, CN, means2d,
+                       conics, colors, opacities, (float4*)packed);
     CLMGS_LAUNCH_CHECK();
   }
   const int n_blocks = C * tile_width * tile_height;
-#ifdef CLMGS_PROFILE_BUILD  // occupancy experiments: extra dynamic LDS per workgroup
-  static const int fwd_pad = getenv("CLMGS_FWD_LDS_PAD") ? atoi(getenv("CLMGS_FWD_LDS_PAD")) : 0;
-#else
-  const int fwd_pad = 0;
-#endif
-#define CLMGS_LAUNCH_FWD(NCH)                                                                          \
-  hipLaunchKernelGGL(rasterize_fwd_kernel<NCH>, dim3(n_blocks), dim3(64), fwd_pad, s, C, N, n_isects, \
-                     (const float4*)packed, backgrounds, width, height, tile_width, tile_height,       \
-                     offsets, flatten_ids, render_colors, render_alphas, last_ids, n_dev)
-  if (nch == 4) CLMGS_LAUNCH_FWD(4); else CLMGS_LAUNCH_FWD(3);
-#undef CLMGS_LAUNCH_FWD
+  hipLaunchKernelGGL(nch == 4 ? rasterize_fwd_kernel<4> : rasterize_fwd_kernel<3>, dim3(n_blocks), dim3(64), 0, s, C, N,
+                     n_isects, (const float4*)packed, backgrounds, width, height, tile_width, tile_height, offsets,
+                     flatten_ids, render_colors, render_alphas, last_ids, n_dev);
   CLMGS_LAUNCH_CHECK();
   return 0;
 }
@@ -839,37 +755,11 @@ static int rasterize_bwd_impl(int nch, void* stream, int C, int N, int64_t n_ise
   if (n_isects > 0) {
     CLMGS_CHECK_ARG(packed && offsets && flatten_ids && render_alphas && last_ids && v_render_colors);
     const int n_blocks = C * tile_width * tile_height;
-    // The product build launches <0, PART> only.  The profiling variants (skip the flush / skip the
-    // reduction / phase timers), which produce WRONG gradients by design, and the environment lookups
-    // that select them exist only in a -DCLMGS_PROFILE_BUILD library (make PROFILE=1).
-#ifdef CLMGS_PROFILE_BUILD
-    static const int dbg = getenv("CLMGS_BWD_DEBUG") ? atoi(getenv("CLMGS_BWD_DEBUG")) : 0;
-    static const int bwd_pad = getenv("CLMGS_BWD_LDS_PAD") ? atoi(getenv("CLMGS_BWD_LDS_PAD")) : 0;
-#else
-    const int bwd_pad = 0;
-#endif
-#define CLMGS_LAUNCH_BWD(D, P, NCH)                                                                \
-  hipLaunchKernelGGL((rasterize_bwd_kernel<D, P, NCH>), dim3(n_blocks), dim3(64), bwd_pad, s, C, N, \
-                     n_isects, (const float4*)packed, backgrounds, width, height, tile_width,      \
-                     tile_height, offsets, flatten_ids, render_alphas, last_ids, v_render_colors,  \
-                     v_render_alphas, (float*)packed_grad, emit_slot, (float4*)partials, n_dev)
-#ifdef CLMGS_PROFILE_BUILD
-    if (part) {
-      if (dbg == 1) CLMGS_LAUNCH_BWD(1, true, 3); else if (dbg == 3) CLMGS_LAUNCH_BWD(3, true, 3);
-      else CLMGS_LAUNCH_BWD(0, true, 3);
-    } else if (nch == 4) {
-      if (dbg == 1) CLMGS_LAUNCH_BWD(1, false, 4); else if (dbg == 2) CLMGS_LAUNCH_BWD(2, false, 4);
-      else if (dbg == 3) CLMGS_LAUNCH_BWD(3, false, 4); else CLMGS_LAUNCH_BWD(0, false, 4);
-    } else {
-      if (dbg == 1) CLMGS_LAUNCH_BWD(1, false, 3); else if (dbg == 2) CLMGS_LAUNCH_BWD(2, false, 3);
-      else if (dbg == 3) CLMGS_LAUNCH_BWD(3, false, 3); else CLMGS_LAUNCH_BWD(0, false, 3);
-    }
-#else
-    if (part) CLMGS_LAUNCH_BWD(0, true, 3);
-    else if (nch == 4) CLMGS_LAUNCH_BWD(0, false, 4);
-    else CLMGS_LAUNCH_BWD(0, false, 3);
-#endif
-#undef CLMGS_LAUNCH_BWD
+    const auto kernel = part ? rasterize_bwd_kernel<true, 3>
+                             : nch == 4 ? rasterize_bwd_kernel<false, 4> : rasterize_bwd_kernel<false, 3>;
+    hipLaunchKernelGGL(kernel, dim3(n_blocks), dim3(64), 0, s, C, N, n_isects, (const float4*)packed, backgrounds, width,
+                       height, tile_width, tile_height, offsets, flatten_ids, render_alphas, last_ids, v_render_colors,
+                       v_render_alphas, (float*)packed_grad, emit_slot, (float4*)partials, n_dev);
     CLMGS_LAUNCH_CHECK();
     if (part && packed_grad) {
       hipLaunchKernelGGL(raster_partials_sum_kernel, dim3(min(ceil_div(CN, 256), 256 * 16)), dim3(256),
@@ -879,12 +769,8 @@ static int rasterize_bwd_impl(int nch, void* stream, int C, int N, int64_t n_ise
   }
   if (v_means2d) {  // NULL: the caller consumes the packed gradient lines directly
     const dim3 grid(min(ceil_div(CN, 256), 256 * 8));
-    if (nch == 4)
-      hipLaunchKernelGGL(raster_unpack_grad_kernel<4>, grid, dim3(256), 0, s, CN, (const float4*)packed_grad,
-                         v_means2d, v_conics, v_colors, v_opacities);
-    else
-      hipLaunchKernelGGL(raster_unpack_grad_kernel<3>, grid, dim3(256), 0, s, CN, (const float4*)packed_grad,
-                         v_means2d, v_conics, v_colors, v_opacities);
+    hipLaunchKernelGGL(nch == 4 ? raster_unpack_grad_kernel<4> : raster_unpack_grad_kernel<3>, grid, dim3(256), 0, s, CN,
+                       (const float4*)packed_grad, v_means2d, v_conics, v_colors, v_opacities);
     CLMGS_LAUNCH_CHECK();
   }
   return 0;

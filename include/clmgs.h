@@ -513,9 +513,6 @@ int clmgs_adam_small_deferred(void* stream, int64_t n, float* const* params, flo
                               uint8_t* blk_flag /* optional [ceil(n/256)] out: 0 = no row of the block can be visible in
                               any of the C cameras; input of clmgs_visibility_select_count_blocks */);
 
-/* Profiling aid: counters of the CLMGS_BWD_DEBUG=3 variant of the backward tile kernel. */
-int clmgs_debug_counters(unsigned long long* out16, int reset);
-
 /* Device error word: kernels that meet a broken invariant of their caller raise a bit in one device word instead of
  * failing silently.  *bits: 4 = clmgs_adam_small_deferred met a block further behind than the step history it was given
  * (those rows' parameters are wrong).  1 and 2 are retired (they belonged to binning kernels that no longer exist) and

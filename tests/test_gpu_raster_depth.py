@@ -572,9 +572,9 @@ def product_depth_outputs(tmp_path_factory):
     return _depth_worker(PRODUCT_LIB, tmp_path_factory.mktemp("product4"))
 
 
-@pytest.mark.parametrize("variant", ["special0", "fwdasm0", "ldsreduce0"])
+@pytest.mark.parametrize("variant", ["special0"])
 def test_build_variants_honour_the_fourth_channel(dev, variant, product_depth_outputs, tmp_path):
-    """The 4-channel kernels under CLMGS_SPECIAL_ENTRIES=0, CLMGS_FWD_ASM=0 and CLMGS_BWD_LDS_REDUCE=0: the forward
+    """The 4-channel kernels under CLMGS_SPECIAL_ENTRIES=0: the forward
     (depth included) and last_ids bit for bit those of the product build; the gradients come from float atomics, whose
     order varies from launch to launch: REORDER_TOL, as for the 3-channel atomic route."""
     from tests.test_gpu_raster_edges import REORDER_TOL, ROOT
