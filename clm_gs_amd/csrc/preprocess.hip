@@ -251,10 +251,17 @@ struct PreGrads {
   int cur_step;
 };
 
-template <int DEG, bool PK>
+// ABS (clmgs_preprocess_abs_bwd, gsplat's absgrad): the row's third quarter-line is read whole, as  o - ax ay, the pair
+// is summed in the same ascending slot order and the statistic is taken from it instead of from the signed x y; every
+// gradient is the plain kernel's bit for bit.  o.v_means2d_abs_out [V,2] (optional) mirrors o.v_means2d_out; the pointer
+// is a member of the ABS kernels' argument alone, so the plain instantiations keep every argument offset.
+template <bool ABS> struct PreGradsOf : PreGrads {};
+template <> struct PreGradsOf<true> : PreGrads { float* v_means2d_abs_out; };
+
+template <int DEG, bool PK, bool ABS = false>
 __global__ void __launch_bounds__(PP_ROWS, 2)
 preprocess_bwd_kernel(int V, PreArgs a, const int32_t* __restrict__ radii,
-                      const float4* __restrict__ packed_grad, PreGrads o) {
+                      const float4* __restrict__ packed_grad, PreGradsOf<ABS> o) {
   constexpr int NB = (DEG + 1) * (DEG + 1);
   constexpr int NF4 = (NB * 3 + 3) / 4;
   __shared__ __attribute__((aligned(16))) float lds[PP_ROWS * PP_PITCH];
@@ -296,6 +303,7 @@ preprocess_bwd_kernel(int V, PreArgs a, const int32_t* __restrict__ radii,
     float go;
     float4 pa[4], pb[4];
     float po[4];
+    float2 gq = make_float2(0.f, 0.f), pq[4];  // ABS: ax ay of the line
     if (o.partials) {  // kernel-uniform.  The row's first four partial lines are requested here, with
       // everything else the lane needs; longer ranges (rare: 2.6 lines per row on average) follow below
       ga = make_float4(0.f, 0.f, 0.f, 0.f); gb = ga; go = 0.f;
@@ -303,12 +311,18 @@ preprocess_bwd_kernel(int V, PreArgs a, const int32_t* __restrict__ radii,
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         pa[u] = ga; pb[u] = ga; po[u] = 0.f;
-        if (mine && u < cnt) { pa[u] = src[PART_F4 * u]; pb[u] = src[PART_F4 * u + 1]; po[u] = src[PART_F4 * u + 2].x; }
+        if constexpr (ABS) pq[u] = gq;
+        if (mine && u < cnt) {
+          pa[u] = src[PART_F4 * u]; pb[u] = src[PART_F4 * u + 1];
+          if constexpr (ABS) { const float4 c = src[PART_F4 * u + 2]; po[u] = c.x; pq[u] = make_float2(c.z, c.w); }
+          else po[u] = src[PART_F4 * u + 2].x;
+        }
       }
     } else {
       ga = packed_grad[4 * (size_t)i];
       gb = packed_grad[4 * (size_t)i + 1];
-      go = packed_grad[4 * (size_t)i + 2].x;
+      if constexpr (ABS) { const float4 c = packed_grad[4 * (size_t)i + 2]; go = c.x; gq = make_float2(c.z, c.w); }
+      else go = packed_grad[4 * (size_t)i + 2].x;
     }
     const SmallRow sr = load_small<PK>(a, gl);
     const float m[3] = {sr.m[0], sr.m[1], sr.m[2]};
@@ -365,6 +379,7 @@ preprocess_bwd_kernel(int V, PreArgs a, const int32_t* __restrict__ radii,
         ga.x += pa[u].x; ga.y += pa[u].y; ga.z += pa[u].z; ga.w += pa[u].w;
         gb.x += pb[u].x; gb.y += pb[u].y; gb.z += pb[u].z; gb.w += pb[u].w;
         go += po[u];
+        if constexpr (ABS) { gq.x += pq[u].x; gq.y += pq[u].y; }
       }
       if (mine) {
         const float4* src = o.partials + PART_F4 * (size_t)s0;
@@ -372,7 +387,9 @@ preprocess_bwd_kernel(int V, PreArgs a, const int32_t* __restrict__ radii,
 #pragma unroll
           for (int u = 0; u < 4; ++u) {
             const int l = min(tt + u, cnt - 1);
-            pa[u] = src[PART_F4 * l]; pb[u] = src[PART_F4 * l + 1]; po[u] = src[PART_F4 * l + 2].x;
+            pa[u] = src[PART_F4 * l]; pb[u] = src[PART_F4 * l + 1];
+            if constexpr (ABS) { const float4 c = src[PART_F4 * l + 2]; po[u] = c.x; pq[u] = make_float2(c.z, c.w); }
+            else po[u] = src[PART_F4 * l + 2].x;
           }
 #pragma unroll
           for (int u = 0; u < 4; ++u) {
@@ -380,6 +397,7 @@ preprocess_bwd_kernel(int V, PreArgs a, const int32_t* __restrict__ radii,
               ga.x += pa[u].x; ga.y += pa[u].y; ga.z += pa[u].z; ga.w += pa[u].w;
               gb.x += pb[u].x; gb.y += pb[u].y; gb.z += pb[u].z; gb.w += pb[u].w;
               go += po[u];
+              if constexpr (ABS) { gq.x += pq[u].x; gq.y += pq[u].y; }
             }
           }
         }
@@ -388,9 +406,12 @@ preprocess_bwd_kernel(int V, PreArgs a, const int32_t* __restrict__ radii,
     // ---- statistics + projection VJP while the SH rows are in flight
     const float v_m2[2] = {ga.x, ga.y};
     if (mine && o.v_means2d_out) *reinterpret_cast<float2*>(o.v_means2d_out + 2 * (size_t)i) = make_float2(ga.x, ga.y);
+    if constexpr (ABS) {
+      if (mine && o.v_means2d_abs_out) *reinterpret_cast<float2*>(o.v_means2d_abs_out + 2 * (size_t)i) = gq;
+    }
     if (stat) {  // default: every filter row, as gsplat_add_densification_stats_exact_filter;
       // only_visible = the no_offload mask form
-      const float gx = v_m2[0] * (0.5f * a.width), gy = v_m2[1] * (0.5f * a.height);
+      const float gx = (ABS ? gq.x : v_m2[0]) * (0.5f * a.width), gy = (ABS ? gq.y : v_m2[1]) * (0.5f * a.height);
       if (o.packed_stats) {
         reinterpret_cast<float4*>(o.max_radii2D)[g] =
             make_float4(fmaxf(c_mr, (float)radius), c_ga + sqrtf(gx * gx + gy * gy), c_dn + 1.f, 0.f);
@@ -581,7 +602,12 @@ extern "C" int clmgs_preprocess_fwd(void* stream, int V, const int64_t* filter, 
   return 0;
 }
 
-extern "C" int clmgs_preprocess_bwd(void* stream, int V, const int64_t* filter, const float* xyz,
+template <bool ABS>
+static const PreGradsOf<ABS>& pre_grads_of(const PreGradsOf<false>& plain, const PreGradsOf<true>& abs) {
+  if constexpr (ABS) return abs; else return plain;
+}
+
+static int preprocess_bwd_impl(bool abs, float* v_means2d_abs_out, void* stream, int V, const int64_t* filter, const float* xyz,
                                     const float* opacity_raw, const float* scaling_raw,
                                     const float* rotation_raw, const float* sh_rows,
                                     int sh_by_filter, const float* viewmat_host,
@@ -619,14 +645,17 @@ extern "C" int clmgs_preprocess_bwd(void* stream, int V, const int64_t* filter, 
              sh_stamp, cur_step};
   const size_t lds = 0;
   const int grid = min(ceil_div(V, PP_ROWS), 256 * 12);
+  PreGradsOf<false> o0;
+  PreGradsOf<true> o1;
+  static_cast<PreGrads&>(o0) = o; static_cast<PreGrads&>(o1) = o; o1.v_means2d_abs_out = v_means2d_abs_out;
+#define CLMGS_PRE_BWD_K(D, PKD, A)                                                                \
+  hipLaunchKernelGGL((preprocess_bwd_kernel<D, PKD, A>), dim3(grid), dim3(PP_ROWS), lds,           \
+                     (hipStream_t)stream, V, a, radii, (const float4*)packed_grad, pre_grads_of<A>(o0, o1))
 #define CLMGS_PRE_BWD(D)                                                                          \
   do {                                                                                             \
-    if (pg)                                                                                        \
-      hipLaunchKernelGGL((preprocess_bwd_kernel<D, true>), dim3(grid), dim3(PP_ROWS), lds,         \
-                         (hipStream_t)stream, V, a, radii, (const float4*)packed_grad, o);         \
-    else                                                                                           \
-      hipLaunchKernelGGL((preprocess_bwd_kernel<D, false>), dim3(grid), dim3(PP_ROWS), lds,        \
-                         (hipStream_t)stream, V, a, radii, (const float4*)packed_grad, o);         \
+    if (abs) { if (pg) CLMGS_PRE_BWD_K(D, true, true); else CLMGS_PRE_BWD_K(D, false, true); }     \
+    else if (pg) CLMGS_PRE_BWD_K(D, true, false);                                                  \
+    else CLMGS_PRE_BWD_K(D, false, false);                                                         \
   } while (0)
   switch (degree) {
     case 0: CLMGS_PRE_BWD(0); break;
@@ -635,6 +664,48 @@ extern "C" int clmgs_preprocess_bwd(void* stream, int V, const int64_t* filter, 
     default: CLMGS_PRE_BWD(3); break;
   }
 #undef CLMGS_PRE_BWD
+#undef CLMGS_PRE_BWD_K
   CLMGS_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int clmgs_preprocess_bwd(void* stream, int V, const int64_t* filter, const float* xyz,
+                                    const float* opacity_raw, const float* scaling_raw,
+                                    const float* rotation_raw, const float* sh_rows,
+                                    int sh_by_filter, const float* viewmat_host,
+                                    const float* K_host, const float* campos_host, int width,
+                                    int height, int degree, float eps2d, const int32_t* radii,
+                                    const void* packed_grad, float* g_xyz, float* g_opacity,
+                                    float* g_scaling, float* g_rotation, float* g_sh_rows,
+                                    float* max_radii2D, float* grad_accum, float* denom,
+                                    float* v_means2d_out, int stats_only_visible,
+                                    const void* partials, const int64_t* row_cum,
+                                    const int32_t* sh_index, int32_t* sh_stamp, int cur_step) {
+  return preprocess_bwd_impl(false, nullptr, stream, V, filter, xyz, opacity_raw, scaling_raw, rotation_raw, sh_rows,
+                             sh_by_filter, viewmat_host, K_host, campos_host, width, height, degree, eps2d, radii,
+                             packed_grad, g_xyz, g_opacity, g_scaling, g_rotation, g_sh_rows, max_radii2D, grad_accum,
+                             denom, v_means2d_out, stats_only_visible, partials, row_cum, sh_index, sh_stamp, cur_step);
+}
+
+// gsplat's absgrad (DefaultStrategy(absgrad=True); AbsGS): clmgs_preprocess_bwd on the lines of clmgs_rasterize_abs_bwd,
+//   x y ca cb | cc r g b | o - ax ay.  Words 10 and 11 are summed per row in the same ascending slot order and the
+// densification statistic becomes  grad_accum += sqrt((ax W/2)^2 + (ay H/2)^2);  every gradient, denom and max_radii2D are
+// the plain entry's.  v_means2d_abs_out [V,2] (optional) mirrors v_means2d_out.
+extern "C" int clmgs_preprocess_abs_bwd(void* stream, int V, const int64_t* filter, const float* xyz,
+                                        const float* opacity_raw, const float* scaling_raw,
+                                        const float* rotation_raw, const float* sh_rows,
+                                        int sh_by_filter, const float* viewmat_host,
+                                        const float* K_host, const float* campos_host, int width,
+                                        int height, int degree, float eps2d, const int32_t* radii,
+                                        const void* packed_grad, float* g_xyz, float* g_opacity,
+                                        float* g_scaling, float* g_rotation, float* g_sh_rows,
+                                        float* max_radii2D, float* grad_accum, float* denom,
+                                        float* v_means2d_out, int stats_only_visible,
+                                        const void* partials, const int64_t* row_cum,
+                                        const int32_t* sh_index, int32_t* sh_stamp, int cur_step,
+                                        float* v_means2d_abs_out) {
+  return preprocess_bwd_impl(true, v_means2d_abs_out, stream, V, filter, xyz, opacity_raw, scaling_raw, rotation_raw,
+                             sh_rows, sh_by_filter, viewmat_host, K_host, campos_host, width, height, degree, eps2d, radii,
+                             packed_grad, g_xyz, g_opacity, g_scaling, g_rotation, g_sh_rows, max_radii2D, grad_accum,
+                             denom, v_means2d_out, stats_only_visible, partials, row_cum, sh_index, sh_stamp, cur_step);
 }

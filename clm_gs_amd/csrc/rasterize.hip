@@ -25,6 +25,9 @@
 //     spare word, takes one more accumulator per pixel in the forward and a tenth wave-wide sum (a second DPP chain) and
 //     a tenth atomic in the backward's atomic route; the 3-channel instantiations are, instruction for instruction, the
 //     kernels they were without the parameter ("Depth");
+//   * the backward is also a template on ABS, gsplat's absgrad (clmgs_rasterize_abs_bwd / _abs_bwd_dev): two more per-lane
+//     accumulators of the per-pixel |dL_p/dmean2d|, two more DPP chains per entry, words 10 and 11 of the 64 B line; the
+//     plain instantiations are, instruction for instruction, the kernels they were ("Absgrad");
 //   * blockIdx -> tile mapping is XCD-aware: each XCD's L2 sees a contiguous stripe of tiles,
 //     so neighbouring tiles' shared Gaussians hit in L2.
 #include "common.h"
@@ -80,7 +83,7 @@ raster_pack_kernel(int64_t n, const float* __restrict__ means2d, const float* __
   }
 }
 
-// packed_grad line: x y ca cb | cc r g b | o d - - | -   (d: NCH = 4 only)
+// packed_grad line: x y ca cb | cc r g b | o d ax ay | -   (d: NCH = 4 only; ax ay: ABS only, the absgrad pair)
 template <int NCH>
 __global__ void __launch_bounds__(256)
 raster_unpack_grad_kernel(int64_t n, const float4* __restrict__ packed_grad,
@@ -95,6 +98,16 @@ raster_unpack_grad_kernel(int64_t n, const float4* __restrict__ packed_grad,
     v_colors[NCH * i] = b.y; v_colors[NCH * i + 1] = b.z; v_colors[NCH * i + 2] = b.w;
     if constexpr (NCH == 4) v_colors[NCH * i + 3] = c.y;
     v_opacities[i] = c.x;
+  }
+}
+// ... and the absgrad pair of the same lines to v_means2d_abs [n,2].  Its own kernel: one more argument, or a shared
+// body, moved the plain kernel's instructions.
+__global__ void __launch_bounds__(256)
+raster_unpack_abs_kernel(int64_t n, const float4* __restrict__ packed_grad, float* __restrict__ v_means2d_abs) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const float4 c = packed_grad[REC_F4 * i + 2];
+    *reinterpret_cast<float2*>(v_means2d_abs + 2 * i) = make_float2(c.z, c.w);
   }
 }
 
@@ -377,7 +390,12 @@ struct TileLdsBwd : TileLds<NCH> {
 // (zeros for culled / unreached entries, so every line is written exactly once per launch) and
 // raster_partials_sum_kernel adds each row's contiguous range.
 // NCH = 4: the atomic route only (a tenth sum g_d = sum fac * vd, a tenth atomic at word 9 of the gradient line).
-template <bool PART, int NCH>
+// ABS (NCH = 3, both routes): gsplat's absgrad.  The kernel reduces MOMENTS of w = v_sigma and forms g_x = ca Sx + cb Sy
+// once per entry, so the per-pixel |dL_p/dmean2d| = |w (ca dx + cb dy)|, |w (cb dx + cc dy)| is new arithmetic in the pass:
+// two FMA pairs whose results enter their accumulators through the |.| input modifier, on the pre-scaled conic
+// (a log2(e)/2, b log2(e)/2, c log2(e)/2: the positive factor 2/log2(e) is applied once, after the wave-wide sum).  The
+// pair takes two more DPP chains next to g_o's and lands in words 10 and 11 of the line: x y ca cb | cc r g b | o - ax ay.
+template <bool PART, int NCH, bool ABS = false>
 __global__ void __launch_bounds__(64, CLMGS_BWD_WAVES)
 rasterize_bwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ packed,
                      const float* __restrict__ backgrounds,
@@ -389,6 +407,7 @@ rasterize_bwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
                      const int32_t* __restrict__ emit_slot, float4* __restrict__ partials,
                      const int64_t* __restrict__ n_dev) {
   static_assert(NCH == 3 || (NCH == 4 && !PART), "4 channels: atomic route only");
+  static_assert(!ABS || NCH == 3, "absgrad: three channels only (word 9 stays the fourth channel's)");
   __shared__ TileLdsBwd<NCH> sm;
   if (n_dev) n_isects = min(n_isects, *n_dev);
   const TileGeom g(C, tile_w, tile_h);
@@ -501,6 +520,8 @@ rasterize_bwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
       // moments of w = v_sigma over the tile: the five screen-space gradients are linear in them
       // (g_x = a Sx + b Sy, g_y = b Sx + c Sy, g_conic = Sxx/2, Sxy, Syy/2), applied at the flush
       float g_d = 0.f;  // NCH = 4: sum fac * vd
+      float ax = 0.f, ay = 0.f, cbh = 0.f;  // ABS: sum |v_xy| on the pre-scaled conic, and its off-diagonal word halved
+      if constexpr (ABS) cbh = 0.5f * RB.x;
       float g_r = 0.f, g_g = 0.f, g_b = 0.f, Sx = 0.f, Sy = 0.f, Sxx = 0.f, Sxy = 0.f, Syy = 0.f,
             g_o = 0.f;
       // OR of the passes' valid masks, kept as scalar mask arithmetic on the compares' results (a per-lane flag costs a
@@ -538,6 +559,7 @@ rasterize_bwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
               const float wdx = w * dx, wdy = w * dy;
               Sx += wdx; Sy += wdy;
               Sxx += wdx * dx; Sxy += wdx * dy; Syy += wdy * dy;
+              if constexpr (ABS) { ax += fabsf(fmaf(RA.w, wdx, cbh * wdy)); ay += fabsf(fmaf(cbh, wdx, RB.y * wdy)); }
               g_o += gex * v_alpha;
               Bk[k] += fac * cv;
             }
@@ -562,6 +584,7 @@ rasterize_bwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
       const float4 r0 = rp[0], r1 = rp[8];
       g_o = wave_sum_to_lane63(g_o);
       if constexpr (NCH == 4) g_d = wave_sum_to_lane63(g_d);  // the transpose carries eight values: a second chain
+      if constexpr (ABS) { ax = wave_sum_to_lane63(ax); ay = wave_sum_to_lane63(ay); }  // ... and a third and fourth
       float u = ((r0.x + r0.y) + (r0.z + r0.w)) + ((r1.x + r1.y) + (r1.z + r1.w));
       u = dpp_add<0x111>(u);
       u = dpp_add<0x112>(u);
@@ -571,6 +594,7 @@ rasterize_bwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
       if ((lane & 7) == 7) sm.acc[t][lane >> 3] = u;   // Sx Sy Sxx Sxy | Syy r g b | o
       if (lane == 63) sm.acc[t][8] = g_o;
       if constexpr (NCH == 4) { if (lane == 63) sm.acc[t][9] = g_d; }
+      if constexpr (ABS) { if (lane == 63) { sm.acc[t][10] = ax * CONIC_DIAG_INV; sm.acc[t][11] = ay * CONIC_DIAG_INV; } }
       touched |= (1ull << t);
     }
     __syncthreads();
@@ -586,6 +610,7 @@ rasterize_bwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
           r0 = sm.grad_xy_conic(lane, g_cc);
           r1 = make_float4(g_cc, m1.y, m1.z, m1.w);
           r2 = make_float4(a[2].x, 0.f, 0.f, 0.f);
+          if constexpr (ABS) { r2.z = a[2].z; r2.w = a[2].w; }  // x y ca cb | cc r g b | o - ax ay
         }
         float4* dst = partials + PART_F4 * (size_t)sm.id[lane];
         dst[0] = r0; dst[1] = r1; dst[2] = r2;
@@ -604,6 +629,7 @@ rasterize_bwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
       atomicAdd(dst + 4, g_cc);  // conic c
 #pragma unroll
       for (int c = 5; c < 6 + NCH; ++c) atomicAdd(dst + c, a[c]);
+      if constexpr (ABS) { atomicAdd(dst + 10, a[10]); atomicAdd(dst + 11, a[11]); }
     }
   }
 }
@@ -611,7 +637,8 @@ rasterize_bwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
 // Per-row sum of the tile partials (API surface: the engine path folds this sum into
 // clmgs_preprocess_bwd).  Row i owns the contiguous slot range [row_cum[i-1], row_cum[i]); ranges and
 // gradient lines are both walked sequentially; fixed order (ascending slot).
-// partials line = gradient line: x y ca cb | cc r g b | o - - - | -
+// partials line = gradient line: x y ca cb | cc r g b | o - - - | -   (ABS: o - ax ay, summed in the same order)
+template <bool ABS = false>
 __global__ void __launch_bounds__(256)
 raster_partials_sum_kernel(int64_t n_rows, const int64_t* __restrict__ row_cum,
                            const float4* __restrict__ partials, float4* __restrict__ packed_grad) {
@@ -641,6 +668,12 @@ raster_partials_sum_kernel(int64_t n_rows, const int64_t* __restrict__ row_cum,
     }
     float4* dst = packed_grad + REC_F4 * r;
     dst[0] = a; dst[1] = b; dst[2] = make_float4(o, 0.f, 0.f, 0.f);
+    if constexpr (ABS) {  // the absgrad pair, same ascending order, in a pass of its own over lines the loop above just
+      // read (API surface, cache hits): folded into that loop it permuted the plain kernel's registers
+      float ax = 0.f, ay = 0.f;
+      for (int t = 0; t < cnt; ++t) { const float4 c = src[PART_F4 * t + 2]; ax += c.z; ay += c.w; }
+      *reinterpret_cast<float2*>(reinterpret_cast<float*>(dst) + 10) = make_float2(ax, ay);
+    }
   }
 }
 
@@ -731,7 +764,13 @@ static int rasterize_bwd_impl(int nch, void* stream, int C, int N, int64_t n_ise
                               const float* v_render_alphas, void* packed_grad,
                               float* v_means2d, float* v_conics, float* v_colors,
                               float* v_opacities, const int32_t* emit_slot,
-                              const int64_t* row_cum, void* partials, const int64_t* n_dev) {
+                              const int64_t* row_cum, void* partials, const int64_t* n_dev,
+                              bool abs = false, float* v_means2d_abs = nullptr) {
+  if (abs && nch != 3) {  // before anything is written
+    clmgs::set_error("clmgs_rasterize_abs_bwd: absgrad blends three channels only (word 9 of the gradient line is the "
+                     "fourth channel's, words 10 and 11 the absgrad pair's)");
+    return CLMGS_EINVAL;
+  }
   if (nch == 4 && (partials || emit_slot)) {  // before anything is written
     clmgs::set_error("clmgs_rasterize4_bwd: the slot route (emit_slot / partials) blends three channels only; "
                      "pass emit_slot = partials = NULL for the atomic route");
@@ -741,6 +780,7 @@ static int rasterize_bwd_impl(int nch, void* stream, int C, int N, int64_t n_ise
   CLMGS_CHECK_ARG(C >= 1 && width > 0 && height > 0 && tile_width * TILE >= width &&
                   tile_height * TILE >= height);
   CLMGS_CHECK_ARG(!v_means2d || (v_conics && v_colors && v_opacities));
+  CLMGS_CHECK_ARG(!v_means2d_abs || (abs && v_means2d));  // the abs pair leaves with the unpack
   hipStream_t s = (hipStream_t)stream;
   const int64_t CN = (int64_t)C * N;
   if (CN == 0) return 0;  // nothing to differentiate: no argument below is required to exist
@@ -755,14 +795,16 @@ static int rasterize_bwd_impl(int nch, void* stream, int C, int N, int64_t n_ise
   if (n_isects > 0) {
     CLMGS_CHECK_ARG(packed && offsets && flatten_ids && render_alphas && last_ids && v_render_colors);
     const int n_blocks = C * tile_width * tile_height;
-    const auto kernel = part ? rasterize_bwd_kernel<true, 3>
-                             : nch == 4 ? rasterize_bwd_kernel<false, 4> : rasterize_bwd_kernel<false, 3>;
+    const auto kernel = abs ? (part ? rasterize_bwd_kernel<true, 3, true> : rasterize_bwd_kernel<false, 3, true>)
+                        : part ? rasterize_bwd_kernel<true, 3>
+                               : nch == 4 ? rasterize_bwd_kernel<false, 4> : rasterize_bwd_kernel<false, 3>;
     hipLaunchKernelGGL(kernel, dim3(n_blocks), dim3(64), 0, s, C, N, n_isects, (const float4*)packed, backgrounds, width,
                        height, tile_width, tile_height, offsets, flatten_ids, render_alphas, last_ids, v_render_colors,
                        v_render_alphas, (float*)packed_grad, emit_slot, (float4*)partials, n_dev);
     CLMGS_LAUNCH_CHECK();
     if (part && packed_grad) {
-      hipLaunchKernelGGL(raster_partials_sum_kernel, dim3(min(ceil_div(CN, 256), 256 * 16)), dim3(256),
+      hipLaunchKernelGGL(abs ? raster_partials_sum_kernel<true> : raster_partials_sum_kernel<false>,
+                         dim3(min(ceil_div(CN, 256), 256 * 16)), dim3(256),
                          0, s, CN, row_cum, (const float4*)partials, (float4*)packed_grad);
       CLMGS_LAUNCH_CHECK();
     }
@@ -771,6 +813,9 @@ static int rasterize_bwd_impl(int nch, void* stream, int C, int N, int64_t n_ise
     const dim3 grid(min(ceil_div(CN, 256), 256 * 8));
     hipLaunchKernelGGL(nch == 4 ? raster_unpack_grad_kernel<4> : raster_unpack_grad_kernel<3>, grid, dim3(256), 0, s, CN,
                        (const float4*)packed_grad, v_means2d, v_conics, v_colors, v_opacities);
+    CLMGS_LAUNCH_CHECK();
+    if (v_means2d_abs)
+      hipLaunchKernelGGL(raster_unpack_abs_kernel, grid, dim3(256), 0, s, CN, (const float4*)packed_grad, v_means2d_abs);
     CLMGS_LAUNCH_CHECK();
   }
   return 0;
@@ -821,4 +866,39 @@ extern "C" int clmgs_rasterize_bwd_dev(void* stream, int C, int N, int64_t capac
                             tile_height, offsets, flatten_ids, render_alphas, last_ids, v_render_colors,
                             v_render_alphas, nullptr, nullptr, nullptr, nullptr, nullptr, emit_slot, row_cum,
                             partials, n_isects_dev);
+}
+
+// gsplat's absgrad (rasterize_to_pixels(absgrad=True) -> means2d.absgrad; AbsGS): clmgs_rasterize_bwd with
+// sum_p |dL_p/dmean2d| next to the signed sums.  Three channels, both routes.  The gradient line and the slot route's
+// partial line become  x y ca cb | cc r g b | o - ax ay  (words 10 and 11; word 9 stays the fourth channel's); every other
+// word is the plain entry's.  v_means2d_abs [C*N,2] (optional) is written with the unpack.
+extern "C" int clmgs_rasterize_abs_bwd(void* stream, int C, int N, int64_t n_isects, const void* packed,
+                                       const float* backgrounds, int width, int height, int tile_size,
+                                       int tile_width, int tile_height, const int32_t* offsets,
+                                       const int32_t* flatten_ids, const float* render_alphas,
+                                       const int32_t* last_ids, const float* v_render_colors,
+                                       const float* v_render_alphas, void* packed_grad,
+                                       float* v_means2d, float* v_conics, float* v_colors,
+                                       float* v_opacities, const int32_t* emit_slot,
+                                       const int64_t* row_cum, void* partials, float* v_means2d_abs) {
+  return rasterize_bwd_impl(3, stream, C, N, n_isects, packed, backgrounds, width, height, tile_size, tile_width,
+                            tile_height, offsets, flatten_ids, render_alphas, last_ids, v_render_colors,
+                            v_render_alphas, packed_grad, v_means2d, v_conics, v_colors, v_opacities, emit_slot,
+                            row_cum, partials, nullptr, true, v_means2d_abs);
+}
+
+// Device-count form of the slot mode with the absgrad pair in words 10 and 11 of every partial line
+// (clmgs_preprocess_abs_bwd sums them with the row).
+extern "C" int clmgs_rasterize_abs_bwd_dev(void* stream, int C, int N, int64_t capacity, const int64_t* n_isects_dev,
+                                           const void* packed, const float* backgrounds, int width, int height,
+                                           int tile_size, int tile_width, int tile_height, const int32_t* offsets,
+                                           const int32_t* flatten_ids, const float* render_alphas,
+                                           const int32_t* last_ids, const float* v_render_colors,
+                                           const float* v_render_alphas, const int32_t* emit_slot,
+                                           const int64_t* row_cum, void* partials) {
+  CLMGS_CHECK_ARG(n_isects_dev && capacity > 0 && emit_slot && partials);
+  return rasterize_bwd_impl(3, stream, C, N, capacity, packed, backgrounds, width, height, tile_size, tile_width,
+                            tile_height, offsets, flatten_ids, render_alphas, last_ids, v_render_colors,
+                            v_render_alphas, nullptr, nullptr, nullptr, nullptr, nullptr, emit_slot, row_cum,
+                            partials, n_isects_dev, true, nullptr);
 }

@@ -319,16 +319,21 @@ def camera_backward(gaussians, p, g_sh_rows, small_grad=None, update_stats=True,
         partials = empty_bucketed(max(n_isects, 1), (_partial_line_floats(),), F32, dev)
     if p.ev_loss is not None:
         s_raster.wait_event(p.ev_loss)
+    # gsplat's absgrad (args.absgrad, read once): the three abs entries, whose lines carry sum_p |dL_p/dmean2d| in words
+    # 10 and 11 and whose row kernel takes the densification statistic from that pair
+    absgrad = bool(getattr(args, "absgrad", False))
+    raster_bwd, raster_bwd_dev = (L.clmgs_rasterize_abs_bwd, L.clmgs_rasterize_abs_bwd_dev) if absgrad else \
+        (L.clmgs_rasterize_bwd, L.clmgs_rasterize_bwd_dev)
     if p.n_dev is None:
-        check(L.clmgs_rasterize_bwd(_sptr(s_raster), 1, V, n_isects, dptr(p.packed), dptr(p.bg, F32, True), W, H,
-                                    TILE, tw, th, dptr(p.offsets), dptr(p.fids), dptr(p.alphas), dptr(p.last_ids),
-                                    dptr(p.v_out), None, None, None, None, None, None,
-                                    dptr(p.emit_slot), dptr(p.row_cum), dptr(partials)))
+        check(raster_bwd(_sptr(s_raster), 1, V, n_isects, dptr(p.packed), dptr(p.bg, F32, True), W, H,
+                         TILE, tw, th, dptr(p.offsets), dptr(p.fids), dptr(p.alphas), dptr(p.last_ids),
+                         dptr(p.v_out), None, None, None, None, None, None,
+                         dptr(p.emit_slot), dptr(p.row_cum), dptr(partials), *((None,) if absgrad else ())))
     else:
-        check(L.clmgs_rasterize_bwd_dev(_sptr(s_raster), 1, V, n_isects, dptr(p.n_dev), dptr(p.packed),
-                                        dptr(p.bg, F32, True), W, H, TILE, tw, th, dptr(p.offsets), dptr(p.fids),
-                                        dptr(p.alphas), dptr(p.last_ids), dptr(p.v_out), None,
-                                        dptr(p.emit_slot), dptr(p.row_cum), dptr(partials)))
+        check(raster_bwd_dev(_sptr(s_raster), 1, V, n_isects, dptr(p.n_dev), dptr(p.packed),
+                             dptr(p.bg, F32, True), W, H, TILE, tw, th, dptr(p.offsets), dptr(p.fids),
+                             dptr(p.alphas), dptr(p.last_ids), dptr(p.v_out), None,
+                             dptr(p.emit_slot), dptr(p.row_cum), dptr(partials)))
     if s_mem is not s_raster:
         ev = torch.cuda.Event()
         ev.record(s_raster)
@@ -346,12 +351,12 @@ def camera_backward(gaussians, p, g_sh_rows, small_grad=None, update_stats=True,
             s_mem.wait_event(accumulate_after)
         if visibility_out is not None:
             visibility_out |= (p.radii.reshape(-1) > 0)
-        check(L.clmgs_preprocess_bwd(
+        check((L.clmgs_preprocess_abs_bwd if absgrad else L.clmgs_preprocess_bwd)(
             _sptr(s_mem), V, dptr(p.filt, torch.int64, True), *p.small_in, dptr(p.sh_rows, F32, allow_host=True),
             int(p.sh_by_filter), _np(vm), _np(K), _np(campos), W, H, p.deg, 0.3, dptr(p.radii),
             None, *small_out, dptr(g_sh_rows, F32, allow_host=True),
             *stat_ptrs, None, int(bool(stats_only_visible)), dptr(partials), dptr(p.row_cum),
-            dptr(p.sh_index, I32, True), dptr(sh_stamp, I32, True), int(cur_step)))
+            dptr(p.sh_index, I32, True), dptr(sh_stamp, I32, True), int(cur_step), *((None,) if absgrad else ())))
     # partials (64 B per intersection, 576 MB at 4K) and the loss cotangent image are dead once the two
     # kernels above have run: hand them back now instead of at the next batch.  Each was used on a second
     # stream (partials: written on s_raster, read on s_mem; v_out: written on s_mem, read on s_raster), so

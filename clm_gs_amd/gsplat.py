@@ -466,10 +466,11 @@ def isect_tiles_two_level(means2d, radii, depths, tile_size, tile_width, tile_he
 class _Rasterize(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means2d, conics, colors, opacities, backgrounds, width, height, tile_size,
-                isect_offsets, flatten_ids):
+                isect_offsets, flatten_ids, absgrad=False):
         L = _lib.lib()
         C, N = opacities.shape
         dev = means2d.device
+        ctx.absgrad_of = means2d if absgrad else None  # the tensor the caller passed in: backward sets .absgrad on it
         means2d, conics, colors, opacities = (t.contiguous() for t in (means2d, conics, colors, opacities))
         bg = backgrounds.contiguous() if backgrounds is not None else None
         offsets = isect_offsets.contiguous()
@@ -509,12 +510,18 @@ class _Rasterize(torch.autograd.Function):
         v_opacities = torch.empty(s_op, dtype=F32, device=dev)
         packed_grad = torch.empty_like(packed)
         bwd = L.clmgs_rasterize4_bwd if s_col[-1] == 4 else L.clmgs_rasterize_bwd
+        extra = ()
+        if ctx.absgrad_of is not None:  # gsplat's absgrad: sum_p |dL_p/dmean2d| next to the signed sum (atomic route)
+            v_abs = torch.empty(s_m2, dtype=F32, device=dev)
+            bwd, extra = L.clmgs_rasterize_abs_bwd, (dptr(v_abs),)
         check(bwd(
             stream(), C, N, fids.numel(), dptr(packed), dptr(bg, F32, True), width, height,
             tile_size, tw, th, dptr(offsets), dptr(fids), dptr(alphas), dptr(last_ids),
             dptr(v_out, F32), dptr(v_alphas, F32, True), dptr(packed_grad), dptr(v_means2d),
-            dptr(v_conics), dptr(v_colors), dptr(v_opacities), None, None, None))
-        return v_means2d, v_conics, v_colors, v_opacities, None, None, None, None, None, None
+            dptr(v_conics), dptr(v_colors), dptr(v_opacities), None, None, None, *extra))
+        if ctx.absgrad_of is not None:
+            ctx.absgrad_of.absgrad = v_abs
+        return v_means2d, v_conics, v_colors, v_opacities, None, None, None, None, None, None, None
 
 
 def rasterize_to_pixels(means2d, conics, colors, opacities, image_width, image_height, tile_size,
@@ -523,12 +530,16 @@ def rasterize_to_pixels(means2d, conics, colors, opacities, image_width, image_h
     """-> (render_colors[C,H,W,3], render_alphas[C,H,W,1]).  backgrounds: None, [3] or [C,3]
     (the reference passes both shapes: no_offload/engine.py:96 vs base_engine.py:189-191).
     colors[..., 4] (gsplat's render_mode="RGB+D": the camera-space depth as a fourth colour) -> render_colors[C,H,W,4],
-    backgrounds None, [4] or [C,4]; channels 0..2 and the alphas are bit-identical to the 3-channel call."""
-    if packed or absgrad or masks is not None:
-        raise NotImplementedError("packed/absgrad/masks are not used by the CLM-GS engines")
+    backgrounds None, [4] or [C,4]; channels 0..2 and the alphas are bit-identical to the 3-channel call.
+    absgrad=True (gsplat's, AbsGS; three channels only): the backward also sets `means2d.absgrad`, shaped like means2d, on
+    the tensor passed in: sum over the pixels each Gaussian contributes to of |dL_p/dmean2d|, componentwise."""
+    if packed or masks is not None:
+        raise NotImplementedError("packed/masks are not used by the CLM-GS engines")
     nch = colors.shape[-1]
     if nch not in (3, 4):
         raise NotImplementedError("3 or 4 colour channels only")
+    if absgrad and nch != 3:
+        raise NotImplementedError("absgrad blends three channels only (no absgrad with a depth channel)")
     C = opacities.shape[0]
     if backgrounds is not None:
         if backgrounds.shape[-1] != nch:
@@ -537,4 +548,4 @@ def rasterize_to_pixels(means2d, conics, colors, opacities, image_width, image_h
         if backgrounds.shape[0] != C:
             backgrounds = backgrounds.expand(C, nch)
     return _Rasterize.apply(means2d, conics, colors, opacities, backgrounds, int(image_width),
-                            int(image_height), int(tile_size), isect_offsets, flatten_ids)
+                            int(image_height), int(tile_size), isect_offsets, flatten_ids, bool(absgrad))

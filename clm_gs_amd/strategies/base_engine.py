@@ -144,7 +144,8 @@ def pipeline_forward_one_step(filtered_opacity_gpu, filtered_scaling_gpu, filter
     rendered_image, alphas = rasterize_to_pixels(
         means2d=means2D, conics=conics, colors=colors, opacities=opacities,
         image_width=image_width, image_height=image_height, tile_size=TILE_SIZE,
-        isect_offsets=isect_offsets, flatten_ids=flatten_ids, backgrounds=backgrounds)
+        isect_offsets=isect_offsets, flatten_ids=flatten_ids, backgrounds=backgrounds,
+        absgrad=not eval and bool(getattr(utils.get_args(), "absgrad", False)))  # -> means2D.absgrad after backward
     if render_mode != "RGB":
         rendered_image, depth, alpha = split_depth(rendered_image, alphas, render_mode)
         return (rendered_image, means2D, radiis, depth) + ((alpha,) if return_alpha else ())

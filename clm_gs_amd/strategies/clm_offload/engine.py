@@ -75,7 +75,8 @@ def pipeline_forward_one_step_shs_inplace(filtered_opacity_gpu, filtered_scaling
     rendered_image, _ = rasterize_to_pixels(
         means2d=means2D, conics=conics, colors=colors, opacities=opacities,
         image_width=image_width, image_height=image_height, tile_size=TILE_SIZE,
-        isect_offsets=isect_offsets, flatten_ids=flatten_ids, backgrounds=backgrounds)
+        isect_offsets=isect_offsets, flatten_ids=flatten_ids, backgrounds=backgrounds,
+        absgrad=bool(getattr(utils.get_args(), "absgrad", False)))  # -> means2D.absgrad after backward
     rendered_image = rendered_image.squeeze(0).permute(2, 0, 1)  # [3,H,W] view, no copy
     return rendered_image, means2D, radiis, colors_detached, dirs
 
@@ -195,9 +196,11 @@ def _render_and_backward(gaussians, scene, camera, background, pipe_args, this_f
         v_coeffs=shs_grad, v_colors=colors_detached.grad)
     dirs.backward(v_dirs)
     _scatter_small_grads(gaussians, this_filter, xyz, opa_raw, sca_raw, rot_raw)
+    # gsplat's absgrad: the statistic is built from sum_p |dL_p/dmean2d| instead of the signed sum
+    m2_grad = means2D.absgrad if getattr(utils.get_args(), "absgrad", False) else means2D.grad
     update_densification_stats_offload_accum_grads(
         scene, gaussians, int(utils.get_img_height()), int(utils.get_img_width()), this_filter,
-        means2D.grad.squeeze(0), radiis.squeeze(0))
+        m2_grad.squeeze(0), radiis.squeeze(0))
     return loss.detach()
 
 

@@ -47,7 +47,8 @@ def baseline_accumGrads_micro_step(means3D, opacities, scales, rotations, shs, s
     rendered_image, alphas = rasterize_to_pixels(
         means2d=means2D, conics=conics, colors=colors, opacities=opacities.squeeze(1).unsqueeze(0),
         image_width=image_width, image_height=image_height, tile_size=tile_size,
-        isect_offsets=isect_offsets, flatten_ids=flatten_ids, backgrounds=background)
+        isect_offsets=isect_offsets, flatten_ids=flatten_ids, backgrounds=background,
+        absgrad=mode == "train" and bool(getattr(args, "absgrad", False)))  # -> means2D.absgrad after backward
     if render_mode != "RGB":
         rendered_image, depth, alpha = split_depth(rendered_image, alphas, render_mode)
         return (rendered_image, means2D, radiis, None, depth) + ((alpha,) if return_alpha else ())
@@ -83,7 +84,9 @@ def baseline_accumGrads_impl(gaussians, scene, batched_cameras, background, scal
         loss.backward()
         losses.append(loss.detach())
         with torch.no_grad():
-            update_densification_stats_baseline_accum_grads(scene, gaussians, H, W, means2D.grad,
+            # gsplat's absgrad: the statistic is built from sum_p |dL_p/dmean2d| instead of the signed sum
+            m2_grad = means2D.absgrad if getattr(utils.get_args(), "absgrad", False) else means2D.grad
+            update_densification_stats_baseline_accum_grads(scene, gaussians, H, W, m2_grad,
                                                             radiis, gaussian_ids)
         if sparse_adam:
             visibility = visibility | (radiis > 0).squeeze()

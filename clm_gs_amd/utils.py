@@ -37,6 +37,10 @@ def default_args(**over):
         rotation_lr=0.001, percent_dense=0.01, lambda_dssim=0.2, densification_interval=100,
         opacity_reset_interval=3000, densify_from_iter=500, densify_until_iter=15_000,
         densify_grad_threshold=0.0002, disable_auto_densification=False, min_opacity=0.005,
+        # this build: gsplat's absgrad (DefaultStrategy(absgrad=True), AbsGS): xyz_gradient_accum is built from the per-pixel
+        # magnitudes sum_p |dL_p/dmean2d| instead of the signed sum; the threshold stays densify_grad_threshold (gsplat's
+        # recipe raises it to 8e-4 with absgrad)
+        absgrad=False,
         lr_scale_mode="sqrt", bsz=1, exact_filter=True, log_cpu_adam_trailing_overhead=False,
         # Debug
         stop_update_param=False, drop_initial_3dgs_p=0.0,

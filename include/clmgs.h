@@ -192,6 +192,23 @@ int clmgs_rasterize4_bwd(void* stream, int C, int N, int64_t n_isects, const voi
                          float* v_conics, float* v_colors, float* v_opacities,
                          const int32_t* emit_slot, const int64_t* row_cum, void* partials);
 
+/* ---- gsplat.rasterize_to_pixels(absgrad=True) -> means2d.absgrad  (AbsGS; consumed by gsplat's
+ * DefaultStrategy(absgrad=True)): next to the signed screen-space gradient, the sum over the pixels p at which the
+ * Gaussian contributes of the per-pixel magnitudes,  absgrad = sum_p ( |dL_p/dmean2d.x| , |dL_p/dmean2d.y| ).
+ * Same contract and arguments as clmgs_rasterize_bwd, three channels, both accumulation modes.  The 64 B gradient line
+ * and the slot route's partial line become   x y ca cb | cc r g b | o - ax ay   (words 10 and 11 hold the pair; word 9
+ * stays the fourth channel's); every other word is what clmgs_rasterize_bwd writes.  v_means2d_abs[C*N,2] (optional,
+ * needs v_means2d) is OVERWRITTEN with the unpack. */
+int clmgs_rasterize_abs_bwd(void* stream, int C, int N, int64_t n_isects, const void* packed,
+                            const float* backgrounds, int width, int height, int tile_size,
+                            int tile_width, int tile_height, const int32_t* offsets,
+                            const int32_t* flatten_ids, const float* render_alphas,
+                            const int32_t* last_ids, const float* v_render_colors,
+                            const float* v_render_alphas, void* packed_grad, float* v_means2d,
+                            float* v_conics, float* v_colors, float* v_opacities,
+                            const int32_t* emit_slot, const int64_t* row_cum, void* partials,
+                            float* v_means2d_abs);
+
 /* ---- device-count forms (engine fast path): the data-dependent size I of a camera need not reach the host
  * before the consumers of the list are enqueued.  The reference reads it back synchronously
  * (strategies/base_engine.py:64-69 `counts.cpu()`, gsplat.isect_tiles' cum[-1].item()); here `capacity` (a
@@ -245,6 +262,16 @@ int clmgs_rasterize_bwd_dev(void* stream, int C, int N, int64_t capacity, const 
                             const float* v_render_alphas, const int32_t* emit_slot,
                             const int64_t* row_cum, void* partials);
 
+/* gsplat's absgrad, device-count form of the slot mode: clmgs_rasterize_bwd_dev whose partial lines carry the pair in
+ * words 10 and 11 (x y ca cb | cc r g b | o - ax ay), for clmgs_preprocess_abs_bwd to sum. */
+int clmgs_rasterize_abs_bwd_dev(void* stream, int C, int N, int64_t capacity, const int64_t* n_isects_dev,
+                                const void* packed, const float* backgrounds, int width, int height,
+                                int tile_size, int tile_width, int tile_height, const int32_t* offsets,
+                                const int32_t* flatten_ids, const float* render_alphas,
+                                const int32_t* last_ids, const float* v_render_colors,
+                                const float* v_render_alphas, const int32_t* emit_slot,
+                                const int64_t* row_cum, void* partials);
+
 /* ---- fused per-camera front end (engine-internal fast path; same arithmetic as the op chain
  * strategies/clm_offload/engine.py:650-691 forward and :703-742 + densification.py:59-102 backward)
  * For i < V, row g = filter ? filter[i] : i of the RAW parameter tensors (xyz[N,3], opacity_raw[N],
@@ -292,6 +319,23 @@ int clmgs_preprocess_bwd(void* stream, int V, const int64_t* filter, const float
                          float* denom, float* v_means2d_out, int stats_only_visible,
                          const void* partials, const int64_t* row_cum, const int32_t* sh_index,
                          int32_t* sh_stamp, int cur_step);
+
+/* gsplat's absgrad (DefaultStrategy(absgrad=True); AbsGS): clmgs_preprocess_bwd on the lines of clmgs_rasterize_abs_bwd /
+ * _abs_bwd_dev,  x y ca cb | cc r g b | o - ax ay  (packed_grad[V,16] or the partial lines).  Words 10 and 11 are summed
+ * per row in the same ascending slot order as the rest of the line, and the densification statistic becomes
+ *   grad_accum += sqrt((ax * width / 2)^2 + (ay * height / 2)^2)
+ * in place of the same norm of the signed x y.  Every gradient, denom and max_radii2D are clmgs_preprocess_bwd's bit for
+ * bit.  v_means2d_abs_out[V,2] (optional) mirrors v_means2d_out. */
+int clmgs_preprocess_abs_bwd(void* stream, int V, const int64_t* filter, const float* xyz,
+                             const float* opacity_raw, const float* scaling_raw,
+                             const float* rotation_raw, const float* sh_rows, int sh_by_filter,
+                             const float* viewmat_host, const float* K_host, const float* campos_host,
+                             int width, int height, int degree, float eps2d, const int32_t* radii,
+                             const void* packed_grad, float* g_xyz, float* g_opacity, float* g_scaling,
+                             float* g_rotation, float* g_sh_rows, float* max_radii2D, float* grad_accum,
+                             float* denom, float* v_means2d_out, int stats_only_visible,
+                             const void* partials, const int64_t* row_cum, const int32_t* sh_index,
+                             int32_t* sh_stamp, int cur_step, float* v_means2d_abs_out);
 
 /* ---- clm_kernels.fused_ssim  (base_engine.py:5,93; definition utils/loss_utils.py:26-85)
  * img1,img2 [B,CH,H,W].  fwd adds per-block SSIM-map sums into ssim_sum[1024] (caller zeroes
