@@ -76,6 +76,7 @@ struct ProjMid {
   float tx, ty;
   bool clamp_x, clamp_y;
   float c00, c01, c11, det;  // blurred 2D covariance
+  float det_orig;            // determinant of J Sc J^T before eps2d is added (antialiased mode)
 };
 
 CLMGS_HD bool project_mid(const Cam& cam, const float m[3], const float q[4], const float s[3],
@@ -127,14 +128,23 @@ CLMGS_HD bool project_mid(const Cam& cam, const float m[3], const float q[4], co
   o.c11 = c11 + eps2d;
   o.c01 = c01;
   o.det = o.c00 * o.c11 - o.c01 * o.c01;
+  o.det_orig = c00 * c11 - c01 * c01;  // from the un-blurred entries: eps2d is never subtracted back out
   return o.det > 0.f;
 }
 
+// Mip-Splatting opacity compensation (gsplat's calc_compensations / rasterize_mode="antialiased"): the eps2d
+// low-pass widens the footprint, the opacity is scaled by the square root of the determinants' ratio.
+CLMGS_HD float compensation_of(const ProjMid& o) { return sqrtf(fmaxf(0.f, o.det_orig / o.det)); }
+
+// AA (project_fwd_aa): also *compensation, 0 for a culled pair.  The plain form is this function itself and not a
+// wrapper around it: one more call level, although inlined, changes the instructions of the plain backward kernels.
+template <bool AA = false>
 CLMGS_HD Proj project_fwd(const Cam& cam, const float m[3], const float q[4], const float s[3],
                           float W, float H, float eps2d, float near_plane, float far_plane,
-                          float radius_clip) {
+                          float radius_clip, float* compensation = nullptr) {
   Proj r;
   r.radius = 0; r.mx = r.my = r.depth = r.ca = r.cb = r.cc = 0.f;
+  if (AA) *compensation = 0.f;
   ProjMid o;
   if (!project_mid(cam, m, q, s, W, H, eps2d, near_plane, far_plane, o)) return r;
   float rz = 1.f / o.p[2];
@@ -149,15 +159,26 @@ CLMGS_HD Proj project_fwd(const Cam& cam, const float m[3], const float q[4], co
   r.radius = (int)radius;
   r.mx = mx; r.my = my; r.depth = o.p[2];
   r.ca = o.c11 * idet; r.cb = -o.c01 * idet; r.cc = o.c00 * idet;
+  if (AA) *compensation = compensation_of(o);
   return r;
+}
+
+CLMGS_HD Proj project_fwd_aa(const Cam& cam, const float m[3], const float q[4], const float s[3],
+                             float W, float H, float eps2d, float near_plane, float far_plane,
+                             float radius_clip, float& compensation) {
+  return project_fwd<true>(cam, m, q, s, W, H, eps2d, near_plane, far_plane, radius_clip, &compensation);
 }
 
 // VJP of project_fwd for one (camera, Gaussian); caller guarantees radius > 0.
 // v_m / v_q / v_s are OVERWRITTEN with this camera's contribution.
+// AA (project_bwd_aa): v_compensation is one more cotangent, in gsplat's guarded form (the square root's derivative is
+// 0.5 / (compensation + 1e-6)), and *compensation receives the forward's value.
+template <bool AA = false>
 CLMGS_HD void project_bwd(const Cam& cam, const float m[3], const float q[4], const float s[3],
                           float W, float H, float eps2d,
                           const float v_mean2d[2], float v_depth, const float v_conic[3],
-                          float v_m[3], float v_q[4], float v_s[3]) {
+                          float v_m[3], float v_q[4], float v_s[3],
+                          float v_compensation = 0.f, float* compensation = nullptr) {
   ProjMid o;
   project_mid(cam, m, q, s, W, H, eps2d, -1e30f, 1e30f, o);
   float idet = 1.f / o.det;
@@ -173,6 +194,14 @@ CLMGS_HD void project_bwd(const Cam& cam, const float m[3], const float q[4], co
   float g11 = -(b * t01 + c * t11);
   // symmetrise: cov2d's off-diagonal appears twice
   float G00 = g00, G11 = g11, G01 = 0.5f * (g01 + g10);
+  if (AA) {  // d comp^2 / d cov2d = (1 - comp^2) conic - eps2d / det * I
+    const float comp = compensation_of(o);
+    *compensation = comp;
+    const float k = v_compensation * 0.5f / (comp + 1e-6f), w = 1.f - comp * comp;
+    G00 += k * (w * a - eps2d * idet);
+    G11 += k * (w * c - eps2d * idet);
+    G01 += k * w * b;
+  }
 
   float sxx = o.Sc[0], sxy = o.Sc[1], sxz = o.Sc[2], syy = o.Sc[3], syz = o.Sc[4], szz = o.Sc[5];
   float J00 = o.J00, J02 = o.J02, J11 = o.J11, J12 = o.J12;
@@ -242,6 +271,15 @@ CLMGS_HD void project_bwd(const Cam& cam, const float m[3], const float q[4], co
     for (int i = 0; i < 3; ++i) vR[i * 3 + j] = vM[i * 3 + j] * s[j];
   }
   quat_to_rotmat_vjp(q, vR, v_q);
+}
+
+CLMGS_HD float project_bwd_aa(const Cam& cam, const float m[3], const float q[4], const float s[3],
+                              float W, float H, float eps2d,
+                              const float v_mean2d[2], float v_depth, const float v_conic[3],
+                              float v_compensation, float v_m[3], float v_q[4], float v_s[3]) {
+  float comp;
+  project_bwd<true>(cam, m, q, s, W, H, eps2d, v_mean2d, v_depth, v_conic, v_m, v_q, v_s, v_compensation, &comp);
+  return comp;
 }
 
 // ----------------------------------------------------- spherical harmonics

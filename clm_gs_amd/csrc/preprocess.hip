@@ -113,7 +113,9 @@ __device__ __forceinline__ void wave_lds_sync() {
 //   * backward: the current values of every read-modify-write target are requested up front
 //     together with the inputs, and the SH gradient rows while the SH VJP computes.
 // OVERLAP = false (no filter: most rows are culled) projects first and stages only live rows.
-template <int DEG, bool OVERLAP, bool PK>
+// AA (clmgs_preprocess_aa_fwd, gsplat's rasterize_mode="antialiased"): the opacity of the record and of opacities[V]
+// is sigmoid(o_raw) * compensation; every other output is the plain kernel's bit for bit.
+template <int DEG, bool OVERLAP, bool PK, bool AA = false>
 __global__ void __launch_bounds__(PP_ROWS, 3)
 preprocess_fwd_kernel(int V, PreArgs a, int32_t* __restrict__ radii, float* __restrict__ means2d,
                       float* __restrict__ depths, float* __restrict__ conics,
@@ -166,8 +168,15 @@ preprocess_fwd_kernel(int V, PreArgs a, int32_t* __restrict__ radii, float* __re
       const float q[4] = {q4.x, q4.y, q4.z, q4.w};
       const float se[3] = {__expf(s[0]), __expf(s[1]), __expf(s[2])};
       o = sigmoidf(oraw);
-      p = project_fwd(cam, m, q, se, (float)a.width, (float)a.height, a.eps2d, a.near_plane,
-                      a.far_plane, a.radius_clip);
+      if constexpr (AA) {
+        float comp;
+        p = project_fwd_aa(cam, m, q, se, (float)a.width, (float)a.height, a.eps2d, a.near_plane,
+                           a.far_plane, a.radius_clip, comp);
+        o *= comp;
+      } else {
+        p = project_fwd(cam, m, q, se, (float)a.width, (float)a.height, a.eps2d, a.near_plane,
+                        a.far_plane, a.radius_clip);
+      }
     }
     wave_lds_sync();  // the previous chunk's LDS rows are consumed
     if (OVERLAP) {
@@ -258,7 +267,10 @@ struct PreGrads {
 template <bool ABS> struct PreGradsOf : PreGrads {};
 template <> struct PreGradsOf<true> : PreGrads { float* v_means2d_abs_out; };
 
-template <int DEG, bool PK, bool ABS = false>
+// AA (clmgs_preprocess_aa_bwd / _aa_abs_bwd): the record's opacity was sigmoid(o_raw) * compensation, so the opacity word
+// go of the line feeds  g_opacity += go * compensation * op (1 - op)  and  v_compensation = go * op,  one more cotangent
+// of the projection VJP (gs_math.h project_bwd_aa).  No argument is added: the compensation is recomputed.
+template <int DEG, bool PK, bool ABS = false, bool AA = false>
 __global__ void __launch_bounds__(PP_ROWS, 2)
 preprocess_bwd_kernel(int V, PreArgs a, const int32_t* __restrict__ radii,
                       const float4* __restrict__ packed_grad, PreGradsOf<ABS> o) {
@@ -431,10 +443,14 @@ preprocess_bwd_kernel(int V, PreArgs a, const int32_t* __restrict__ radii,
       const float v_con[3] = {ga.z, ga.w, gb.x};
       float vq[4], vs[3];
       const Cam camL = launder_cam(cam);
-      project_bwd(camL, m, q, se, (float)a.width, (float)a.height, a.eps2d, v_m2, 0.f, v_con, vm, vq, vs);
+      float gk = go;  // AA: go * compensation
+      if constexpr (AA)
+        gk *= project_bwd_aa(camL, m, q, se, (float)a.width, (float)a.height, a.eps2d, v_m2, 0.f, v_con, go * op, vm, vq, vs);
+      else
+        project_bwd(camL, m, q, se, (float)a.width, (float)a.height, a.eps2d, v_m2, 0.f, v_con, vm, vq, vs);
       n_sc[0] = c_sc[0] + vs[0] * se[0]; n_sc[1] = c_sc[1] + vs[1] * se[1]; n_sc[2] = c_sc[2] + vs[2] * se[2];
       n_rot = make_float4(c_rot.x + vq[0], c_rot.y + vq[1], c_rot.z + vq[2], c_rot.w + vq[3]);
-      n_op = c_op + go * op * (1.f - op);
+      n_op = c_op + gk * op * (1.f - op);
       if (!PK) {
         o.g_scaling[3 * g] = n_sc[0]; o.g_scaling[3 * g + 1] = n_sc[1]; o.g_scaling[3 * g + 2] = n_sc[2];
         *reinterpret_cast<float4*>(o.g_rotation + 4 * g) = n_rot;
@@ -555,7 +571,8 @@ static void fill_args(PreArgs& a, const int64_t* filter, const float* xyz, const
   a.eps2d = eps2d; a.near_plane = near_plane; a.far_plane = far_plane; a.radius_clip = radius_clip;
 }
 
-extern "C" int clmgs_preprocess_fwd(void* stream, int V, const int64_t* filter, const float* xyz,
+template <bool AA>
+static int preprocess_fwd_impl(void* stream, int V, const int64_t* filter, const float* xyz,
                                     const float* opacity_raw, const float* scaling_raw,
                                     const float* rotation_raw, const float* sh_rows,
                                     int sh_by_filter, const float* viewmat_host,
@@ -582,11 +599,11 @@ extern "C" int clmgs_preprocess_fwd(void* stream, int V, const int64_t* filter, 
 #define CLMGS_PRE_FWD(D, O)                                                                        \
   do {                                                                                             \
     if (a.packed_small)                                                                            \
-      hipLaunchKernelGGL((preprocess_fwd_kernel<D, O, true>), dim3(grid), dim3(PP_ROWS), lds,      \
+      hipLaunchKernelGGL((preprocess_fwd_kernel<D, O, true, AA>), dim3(grid), dim3(PP_ROWS), lds,      \
                          (hipStream_t)stream, V, a, radii, means2d, depths, conics, colors,        \
                          opacities, (float4*)packed);                                              \
     else                                                                                           \
-      hipLaunchKernelGGL((preprocess_fwd_kernel<D, O, false>), dim3(grid), dim3(PP_ROWS), lds,     \
+      hipLaunchKernelGGL((preprocess_fwd_kernel<D, O, false, AA>), dim3(grid), dim3(PP_ROWS), lds,     \
                          (hipStream_t)stream, V, a, radii, means2d, depths, conics, colors,        \
                          opacities, (float4*)packed);                                              \
   } while (0)
@@ -602,11 +619,30 @@ extern "C" int clmgs_preprocess_fwd(void* stream, int V, const int64_t* filter, 
   return 0;
 }
 
+#define CLMGS_PRE_FWD_PARAMS                                                                       \
+  void* stream, int V, const int64_t* filter, const float* xyz, const float* opacity_raw,          \
+  const float* scaling_raw, const float* rotation_raw, const float* sh_rows, int sh_by_filter,     \
+  const float* viewmat_host, const float* K_host, const float* campos_host, int width, int height, \
+  int degree, float eps2d, float near_plane, float far_plane, float radius_clip, int32_t* radii,   \
+  float* means2d, float* depths, float* conics, float* colors, float* opacities, void* packed,     \
+  const int32_t* sh_index
+#define CLMGS_PRE_FWD_ARGS                                                                         \
+  stream, V, filter, xyz, opacity_raw, scaling_raw, rotation_raw, sh_rows, sh_by_filter,           \
+  viewmat_host, K_host, campos_host, width, height, degree, eps2d, near_plane, far_plane,          \
+  radius_clip, radii, means2d, depths, conics, colors, opacities, packed, sh_index
+
+extern "C" int clmgs_preprocess_fwd(CLMGS_PRE_FWD_PARAMS) { return preprocess_fwd_impl<false>(CLMGS_PRE_FWD_ARGS); }
+
+// gsplat's rasterization(rasterize_mode="antialiased"): clmgs_preprocess_fwd with the opacity of the record and of
+// opacities[V] multiplied by the Mip-Splatting compensation; every other output is the plain entry's.
+extern "C" int clmgs_preprocess_aa_fwd(CLMGS_PRE_FWD_PARAMS) { return preprocess_fwd_impl<true>(CLMGS_PRE_FWD_ARGS); }
+
 template <bool ABS>
 static const PreGradsOf<ABS>& pre_grads_of(const PreGradsOf<false>& plain, const PreGradsOf<true>& abs) {
   if constexpr (ABS) return abs; else return plain;
 }
 
+template <bool AA>
 static int preprocess_bwd_impl(bool abs, float* v_means2d_abs_out, void* stream, int V, const int64_t* filter, const float* xyz,
                                     const float* opacity_raw, const float* scaling_raw,
                                     const float* rotation_raw, const float* sh_rows,
@@ -649,7 +685,7 @@ static int preprocess_bwd_impl(bool abs, float* v_means2d_abs_out, void* stream,
   PreGradsOf<true> o1;
   static_cast<PreGrads&>(o0) = o; static_cast<PreGrads&>(o1) = o; o1.v_means2d_abs_out = v_means2d_abs_out;
 #define CLMGS_PRE_BWD_K(D, PKD, A)                                                                \
-  hipLaunchKernelGGL((preprocess_bwd_kernel<D, PKD, A>), dim3(grid), dim3(PP_ROWS), lds,           \
+  hipLaunchKernelGGL((preprocess_bwd_kernel<D, PKD, A, AA>), dim3(grid), dim3(PP_ROWS), lds,           \
                      (hipStream_t)stream, V, a, radii, (const float4*)packed_grad, pre_grads_of<A>(o0, o1))
 #define CLMGS_PRE_BWD(D)                                                                          \
   do {                                                                                             \
@@ -681,7 +717,7 @@ extern "C" int clmgs_preprocess_bwd(void* stream, int V, const int64_t* filter, 
                                     float* v_means2d_out, int stats_only_visible,
                                     const void* partials, const int64_t* row_cum,
                                     const int32_t* sh_index, int32_t* sh_stamp, int cur_step) {
-  return preprocess_bwd_impl(false, nullptr, stream, V, filter, xyz, opacity_raw, scaling_raw, rotation_raw, sh_rows,
+  return preprocess_bwd_impl<false>(false, nullptr, stream, V, filter, xyz, opacity_raw, scaling_raw, rotation_raw, sh_rows,
                              sh_by_filter, viewmat_host, K_host, campos_host, width, height, degree, eps2d, radii,
                              packed_grad, g_xyz, g_opacity, g_scaling, g_rotation, g_sh_rows, max_radii2D, grad_accum,
                              denom, v_means2d_out, stats_only_visible, partials, row_cum, sh_index, sh_stamp, cur_step);
@@ -704,8 +740,51 @@ extern "C" int clmgs_preprocess_abs_bwd(void* stream, int V, const int64_t* filt
                                         const void* partials, const int64_t* row_cum,
                                         const int32_t* sh_index, int32_t* sh_stamp, int cur_step,
                                         float* v_means2d_abs_out) {
-  return preprocess_bwd_impl(true, v_means2d_abs_out, stream, V, filter, xyz, opacity_raw, scaling_raw, rotation_raw,
+  return preprocess_bwd_impl<false>(true, v_means2d_abs_out, stream, V, filter, xyz, opacity_raw, scaling_raw, rotation_raw,
                              sh_rows, sh_by_filter, viewmat_host, K_host, campos_host, width, height, degree, eps2d, radii,
                              packed_grad, g_xyz, g_opacity, g_scaling, g_rotation, g_sh_rows, max_radii2D, grad_accum,
                              denom, v_means2d_out, stats_only_visible, partials, row_cum, sh_index, sh_stamp, cur_step);
+}
+
+// gsplat's rasterization(rasterize_mode="antialiased"), backward: clmgs_preprocess_bwd for records written by
+// clmgs_preprocess_aa_fwd.  With go the row's summed opacity word:  g_opacity += go * compensation * op (1 - op)  and
+// v_compensation = go * op  enters the projection VJP.  Statistics are the plain entry's.
+extern "C" int clmgs_preprocess_aa_bwd(void* stream, int V, const int64_t* filter, const float* xyz,
+                                       const float* opacity_raw, const float* scaling_raw,
+                                       const float* rotation_raw, const float* sh_rows,
+                                       int sh_by_filter, const float* viewmat_host,
+                                       const float* K_host, const float* campos_host, int width,
+                                       int height, int degree, float eps2d, const int32_t* radii,
+                                       const void* packed_grad, float* g_xyz, float* g_opacity,
+                                       float* g_scaling, float* g_rotation, float* g_sh_rows,
+                                       float* max_radii2D, float* grad_accum, float* denom,
+                                       float* v_means2d_out, int stats_only_visible,
+                                       const void* partials, const int64_t* row_cum,
+                                       const int32_t* sh_index, int32_t* sh_stamp, int cur_step) {
+  return preprocess_bwd_impl<true>(false, nullptr, stream, V, filter, xyz, opacity_raw, scaling_raw, rotation_raw, sh_rows,
+                                   sh_by_filter, viewmat_host, K_host, campos_host, width, height, degree, eps2d, radii,
+                                   packed_grad, g_xyz, g_opacity, g_scaling, g_rotation, g_sh_rows, max_radii2D, grad_accum,
+                                   denom, v_means2d_out, stats_only_visible, partials, row_cum, sh_index, sh_stamp, cur_step);
+}
+
+// Antialiased + absgrad: clmgs_preprocess_aa_bwd's gradients bit for bit, the statistic from the abs pair as in
+// clmgs_preprocess_abs_bwd.
+extern "C" int clmgs_preprocess_aa_abs_bwd(void* stream, int V, const int64_t* filter, const float* xyz,
+                                           const float* opacity_raw, const float* scaling_raw,
+                                           const float* rotation_raw, const float* sh_rows,
+                                           int sh_by_filter, const float* viewmat_host,
+                                           const float* K_host, const float* campos_host, int width,
+                                           int height, int degree, float eps2d, const int32_t* radii,
+                                           const void* packed_grad, float* g_xyz, float* g_opacity,
+                                           float* g_scaling, float* g_rotation, float* g_sh_rows,
+                                           float* max_radii2D, float* grad_accum, float* denom,
+                                           float* v_means2d_out, int stats_only_visible,
+                                           const void* partials, const int64_t* row_cum,
+                                           const int32_t* sh_index, int32_t* sh_stamp, int cur_step,
+                                           float* v_means2d_abs_out) {
+  return preprocess_bwd_impl<true>(true, v_means2d_abs_out, stream, V, filter, xyz, opacity_raw, scaling_raw, rotation_raw,
+                                   sh_rows, sh_by_filter, viewmat_host, K_host, campos_host, width, height, degree, eps2d,
+                                   radii, packed_grad, g_xyz, g_opacity, g_scaling, g_rotation, g_sh_rows, max_radii2D,
+                                   grad_accum, denom, v_means2d_out, stats_only_visible, partials, row_cum, sh_index,
+                                   sh_stamp, cur_step);
 }

@@ -60,7 +60,7 @@ class _CameraPass:
     __slots__ = ("V", "cam", "filt", "sh_rows", "sh_by_filter", "small_in", "small_packed", "radii",
                  "packed", "fids", "offsets", "emit_slot", "row_cum", "out", "alphas", "last_ids",
                  "bg", "v_out", "maps", "loss", "ev_loss", "streams", "deg", "aux", "loss_partials",
-                 "lambda_dssim", "gt_u8", "background", "isect", "sh_index", "means2d", "n_dev")
+                 "lambda_dssim", "gt_u8", "background", "isect", "sh_index", "means2d", "n_dev", "antialiased")
 
 
 def _sptr(torch_stream):
@@ -147,6 +147,7 @@ def camera_front(gaussians, camera, this_filter, sh_rows, sh_by_filter, backgrou
     p.sh_rows, p.sh_by_filter, p.small_packed = sh_rows, sh_by_filter, small_packed
     p.sh_index = sh_index  # int32[V]: SH row of position i in a staging table (host-resident mode)
     p.gt_u8, p.lambda_dssim, p.background = gt_u8, float(lambda_dssim), background
+    p.antialiased = utils.antialiased()  # the backward follows the mode its forward ran in
     filt = p.filt = this_filter.contiguous() if this_filter is not None else None  # None: all rows
     if small_packed is not None:
         small_in = (dptr(small_packed, F32), None, None, None)
@@ -164,7 +165,9 @@ def camera_front(gaussians, camera, this_filter, sh_rows, sh_by_filter, backgrou
         means2d = empty_bucketed(V, (2,), F32, dev).reshape(1, V, 2)
         depths = empty_bucketed(V, (), F32, dev).reshape(1, V)
         packed = p.packed = empty_bucketed(V, (16,), F32, dev)
-        check(L.clmgs_preprocess_fwd(
+        # gsplat's rasterize_mode="antialiased" (args.rasterize_mode, read once per camera): the aa entries, whose records
+        # carry sigmoid(opacity) * compensation
+        check((L.clmgs_preprocess_aa_fwd if p.antialiased else L.clmgs_preprocess_fwd)(
             _sptr(s_front), V, dptr(filt, torch.int64, True), *small_in,
             dptr(sh_rows, F32, allow_host=True), int(sh_by_filter), _np(vm), _np(K), _np(campos), W, H, deg,
             0.3, 0.01, 1e10, float(getattr(args, "radius_clip", 0.0)), dptr(radii), dptr(means2d),
@@ -351,7 +354,11 @@ def camera_backward(gaussians, p, g_sh_rows, small_grad=None, update_stats=True,
             s_mem.wait_event(accumulate_after)
         if visibility_out is not None:
             visibility_out |= (p.radii.reshape(-1) > 0)
-        check((L.clmgs_preprocess_abs_bwd if absgrad else L.clmgs_preprocess_bwd)(
+        if p.antialiased:
+            pre_bwd = L.clmgs_preprocess_aa_abs_bwd if absgrad else L.clmgs_preprocess_aa_bwd
+        else:
+            pre_bwd = L.clmgs_preprocess_abs_bwd if absgrad else L.clmgs_preprocess_bwd
+        check(pre_bwd(
             _sptr(s_mem), V, dptr(p.filt, torch.int64, True), *p.small_in, dptr(p.sh_rows, F32, allow_host=True),
             int(p.sh_by_filter), _np(vm), _np(K), _np(campos), W, H, p.deg, 0.3, dptr(p.radii),
             None, *small_out, dptr(g_sh_rows, F32, allow_host=True),

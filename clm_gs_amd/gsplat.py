@@ -64,20 +64,81 @@ class _Projection(torch.autograd.Function):
         return v_means, v_quats, v_scales, None, None, None, None, None, None, None, None
 
 
+class _ProjectionAA(torch.autograd.Function):
+    """_Projection with the opacity compensations (clmgs_projection_aa_fwd / _aa_bwd) as a fifth, differentiable output."""
+
+    @staticmethod
+    def forward(ctx, means, quats, scales, viewmats, Ks, width, height, eps2d, near_plane,
+                far_plane, radius_clip):
+        L = _lib.lib()
+        means, quats, scales = means.contiguous(), quats.contiguous(), scales.contiguous()
+        viewmats, Ks = viewmats.contiguous(), Ks.contiguous()
+        C, N = viewmats.shape[0], means.shape[0]
+        dev = means.device
+        radii = torch.empty((C, N), dtype=I32, device=dev)
+        means2d = torch.empty((C, N, 2), dtype=F32, device=dev)
+        depths = torch.empty((C, N), dtype=F32, device=dev)
+        conics = torch.empty((C, N, 3), dtype=F32, device=dev)
+        comps = torch.empty((C, N), dtype=F32, device=dev)
+        check(L.clmgs_projection_aa_fwd(
+            stream(), C, N, dptr(means, F32), dptr(quats, F32), dptr(scales, F32),
+            dptr(viewmats, F32), dptr(Ks, F32), int(width), int(height), float(eps2d),
+            float(near_plane), float(far_plane), float(radius_clip), dptr(radii), dptr(means2d),
+            dptr(depths), dptr(conics), dptr(comps)))
+        ctx.save_for_backward(means, quats, scales, viewmats, Ks, radii)
+        ctx.cfg = (int(width), int(height), float(eps2d))
+        ctx.mark_non_differentiable(radii)
+        return radii, means2d, depths, conics, comps
+
+    @staticmethod
+    def backward(ctx, _v_radii, v_means2d, v_depths, v_conics, v_comps):
+        L = _lib.lib()
+        means, quats, scales, viewmats, Ks, radii = ctx.saved_tensors
+        width, height, eps2d = ctx.cfg
+        C, N = radii.shape
+        dev = means.device
+        if v_means2d is None:
+            v_means2d = torch.zeros((C, N, 2), dtype=F32, device=dev)
+        if v_conics is None:
+            v_conics = torch.zeros((C, N, 3), dtype=F32, device=dev)
+        v_means2d, v_conics = v_means2d.contiguous(), v_conics.contiguous()
+        v_depths = v_depths.contiguous() if v_depths is not None else None
+        v_comps = v_comps.contiguous() if v_comps is not None else None
+        v_means = torch.empty_like(means)
+        v_quats = torch.empty_like(quats)
+        v_scales = torch.empty_like(scales)
+        check(L.clmgs_projection_aa_bwd(
+            stream(), C, N, dptr(means), dptr(quats), dptr(scales), dptr(viewmats), dptr(Ks),
+            width, height, eps2d, dptr(radii), dptr(v_means2d, F32), dptr(v_depths, F32, True),
+            dptr(v_conics, F32), dptr(v_comps, F32, True), dptr(v_means), dptr(v_quats), dptr(v_scales)))
+        return v_means, v_quats, v_scales, None, None, None, None, None, None, None, None
+
+
 def fully_fused_projection(means, covars, quats, scales, viewmats, Ks, width, height, eps2d=0.3,
                            near_plane=0.01, far_plane=1e10, radius_clip=0.0, packed=False,
                            sparse_grad=False, calc_compensations=False):
     """EWA projection of N Gaussians into C cameras.
 
-    Unpacked -> (radii[C,N] i32, means2d[C,N,2], depths[C,N], conics[C,N,3], None).
+    Unpacked -> (radii[C,N] i32, means2d[C,N,2], depths[C,N], conics[C,N,3], compensations).
     Packed (no grad; strategies/base_engine.py:36-47 uses it under no_grad only)
-    -> (camera_ids, gaussian_ids, radii, means2d, depths, conics, None), ordered
+    -> (camera_ids, gaussian_ids, radii, means2d, depths, conics, compensations), ordered
     by (camera, gaussian).
+    compensations: None, or with calc_compensations=True (gsplat's; Mip-Splatting) the differentiable opacity
+    factors sqrt(max(0, det(cov2d) / det(cov2d + eps2d I))), [C,N] with 0 where culled (packed: [nnz]).
     """
     if covars is not None:
         raise NotImplementedError("the CLM-GS engines always pass covars=None")
     if calc_compensations:
-        raise NotImplementedError("compensations are never requested by the CLM-GS engines")
+        if not packed:
+            return _ProjectionAA.apply(means, quats, scales, viewmats, Ks, width, height, eps2d, near_plane,
+                                       far_plane, radius_clip)
+        with torch.no_grad():
+            radii, means2d, depths, conics, comps = _ProjectionAA.apply(
+                means, quats, scales, viewmats, Ks, width, height, eps2d, near_plane, far_plane, radius_clip)
+            camera_ids, gaussian_ids = torch.nonzero(radii > 0, as_tuple=True)
+            return (camera_ids, gaussian_ids, radii[camera_ids, gaussian_ids],
+                    means2d[camera_ids, gaussian_ids], depths[camera_ids, gaussian_ids],
+                    conics[camera_ids, gaussian_ids], comps[camera_ids, gaussian_ids])
     if not packed:
         radii, means2d, depths, conics = _Projection.apply(
             means, quats, scales, viewmats, Ks, width, height, eps2d, near_plane, far_plane,

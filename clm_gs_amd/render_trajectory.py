@@ -187,6 +187,8 @@ def main(argv=None):
     ap.add_argument("--save_video", action="store_true", help="skip the per-frame PNGs (no video writer in this image)")
     ap.add_argument("--render_depth", action="store_true",
                     help="also write depth_%%05d.npy (float32 expected depth) and depth_%%05d.png (grey) per frame")
+    ap.add_argument("--antialiased", action="store_true",
+                    help="gsplat's rasterize_mode=\"antialiased\": for a model trained with trainer --antialiased")
     g = ap.add_mutually_exclusive_group()
     g.add_argument("--clm_offload", action="store_true")
     g.add_argument("--naive_offload", action="store_true")
@@ -194,7 +196,7 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if not (a.clm_offload or a.naive_offload or a.no_offload):
         a.clm_offload = True
-    args = utils.default_args(bsz=4)
+    args = utils.default_args(bsz=4, rasterize_mode="antialiased" if a.antialiased else "classic")
     for k in ("clm_offload", "naive_offload", "no_offload", "save_video", "render_depth"):
         setattr(args, k, getattr(a, k))
     utils.set_args(args)

@@ -122,10 +122,10 @@ def pipeline_forward_one_step(filtered_opacity_gpu, filtered_scaling_gpu, filter
                      device=filtered_xyz_gpu.device)
     viewmat = camera.world_view_transform.transpose(0, 1)
     n_selected = filtered_xyz_gpu.shape[0]
-    radiis, means2D, depths, conics, _ = fully_fused_projection(
+    radiis, means2D, depths, conics, compensations = fully_fused_projection(
         means=filtered_xyz_gpu, covars=None, quats=filtered_rotation_gpu,
         scales=filtered_scaling_gpu, viewmats=viewmat.unsqueeze(0), Ks=K.unsqueeze(0),
-        width=image_width, height=image_height, packed=False)
+        width=image_width, height=image_height, packed=False, calc_compensations=utils.antialiased())
     if not eval:
         means2D.retain_grad()
     camtoworlds = torch.inverse(viewmat.unsqueeze(0))
@@ -134,6 +134,8 @@ def pipeline_forward_one_step(filtered_opacity_gpu, filtered_scaling_gpu, filter
                                  coeffs=filtered_shs.reshape(1, n_selected, 16, 3))
     colors = torch.clamp_min(colors + 0.5, 0.0)
     opacities = filtered_opacity_gpu.squeeze(1).unsqueeze(0)
+    if compensations is not None:  # rasterize_mode="antialiased"
+        opacities = opacities * compensations
     tile_width, tile_height = _tile_counts(image_width, image_height)
     _, isect_ids, flatten_ids = isect_tiles(means2d=means2D, radii=radiis, depths=depths,
                                             tile_size=TILE_SIZE, tile_width=tile_width,

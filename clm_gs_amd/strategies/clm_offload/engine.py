@@ -52,10 +52,10 @@ def pipeline_forward_one_step_shs_inplace(filtered_opacity_gpu, filtered_scaling
     K = camera.K
     n_selected = filtered_xyz_gpu.shape[0]
     image_width, image_height = int(utils.get_img_width()), int(utils.get_img_height())
-    radiis, means2D, depths, conics, _ = fully_fused_projection(
+    radiis, means2D, depths, conics, compensations = fully_fused_projection(
         means=filtered_xyz_gpu, covars=None, quats=filtered_rotation_gpu,
         scales=filtered_scaling_gpu, viewmats=viewmat.unsqueeze(0), Ks=K.unsqueeze(0),
-        width=image_width, height=image_height, packed=False)
+        width=image_width, height=image_height, packed=False, calc_compensations=utils.antialiased())
     means2D.retain_grad()
     dirs = filtered_xyz_gpu[None, :, :] - camera.camtoworlds[:, None, :3, 3]
     filtered_shs = filtered_shs.reshape(1, n_selected, 16, 3)
@@ -65,6 +65,8 @@ def pipeline_forward_one_step_shs_inplace(filtered_opacity_gpu, filtered_scaling
     colors_detached = colors_origin.detach().requires_grad_()
     colors = torch.clamp_min(colors_detached + 0.5, 0.0)
     opacities = filtered_opacity_gpu.squeeze(1).unsqueeze(0)
+    if compensations is not None:  # rasterize_mode="antialiased"
+        opacities = opacities * compensations
     tile_width = math.ceil(image_width / float(TILE_SIZE))
     tile_height = math.ceil(image_height / float(TILE_SIZE))
     _, isect_ids, flatten_ids = isect_tiles(means2d=means2D, radii=radiis, depths=depths,

@@ -26,10 +26,10 @@ def baseline_accumGrads_micro_step(means3D, opacities, scales, rotations, shs, s
     K = torch.tensor([[fx, 0, image_width / 2.0], [0, fy, image_height / 2.0], [0, 0, 1]],
                      device=means3D.device)
     viewmat = camera.world_view_transform.transpose(0, 1)
-    radiis, means2D, depths, conics, _ = fully_fused_projection(
+    radiis, means2D, depths, conics, compensations = fully_fused_projection(
         means=means3D, covars=None, quats=rotations, scales=scales, viewmats=viewmat.unsqueeze(0),
         Ks=K.unsqueeze(0), width=image_width, height=image_height, radius_clip=args.radius_clip,
-        packed=False)
+        packed=False, calc_compensations=utils.antialiased())
     if mode == "train":
         means2D.retain_grad()
     camtoworld = torch.inverse(viewmat.unsqueeze(0))
@@ -44,8 +44,11 @@ def baseline_accumGrads_micro_step(means3D, opacities, scales, rotations, shs, s
                                             tile_height=tile_height, packed=False)
     isect_offsets = isect_offset_encode(isect_ids, 1, tile_width, tile_height)
     colors, background = colors_with_depth(colors, depths, background, render_mode)
+    opacities = opacities.squeeze(1).unsqueeze(0)
+    if compensations is not None:  # rasterize_mode="antialiased"
+        opacities = opacities * compensations
     rendered_image, alphas = rasterize_to_pixels(
-        means2d=means2D, conics=conics, colors=colors, opacities=opacities.squeeze(1).unsqueeze(0),
+        means2d=means2D, conics=conics, colors=colors, opacities=opacities,
         image_width=image_width, image_height=image_height, tile_size=tile_size,
         isect_offsets=isect_offsets, flatten_ids=flatten_ids, backgrounds=background,
         absgrad=mode == "train" and bool(getattr(args, "absgrad", False)))  # -> means2D.absgrad after backward

@@ -462,9 +462,11 @@ if __name__ == "__main__":  # python -m clm_gs_amd.trainer -s <colmap dir> -m <o
                     help="sh_residency=host: HBM that keeps the first rows of the Z-ordered SH table resident (768 B per row)")
     ap.add_argument("--absgrad", action="store_true",
                     help="densify on sum_p |dL_p/dmean2d| (gsplat's absgrad); gsplat's recipe raises the threshold to 8e-4")
+    ap.add_argument("--antialiased", action="store_true",
+                    help="gsplat's rasterize_mode=\"antialiased\" (Mip-Splatting opacity compensation); render the model with it too")
     a = ap.parse_args()
     strat = "no_offload" if a.no_offload else ("naive_offload" if a.naive_offload else "clm_offload")
     _, _, t = train_from_colmap(a.source_path, a.model_path, strategy=strat, iterations=a.iterations, eval=a.eval,
                                 resolution=a.resolution, images=a.images, test_iterations=tuple(a.test_iterations),
                                 bsz=a.bsz, sh_residency=a.sh_residency, sh_hbm_budget_gb=a.sh_hbm_budget_gb,
-                                absgrad=a.absgrad)
+                                absgrad=a.absgrad, rasterize_mode="antialiased" if a.antialiased else "classic")

@@ -41,6 +41,10 @@ def default_args(**over):
         # magnitudes sum_p |dL_p/dmean2d| instead of the signed sum; the threshold stays densify_grad_threshold (gsplat's
         # recipe raises it to 8e-4 with absgrad)
         absgrad=False,
+        # this build: gsplat's rasterize_mode.  "antialiased" (Mip-Splatting) multiplies every opacity by the compensation
+        # sqrt(det(cov2d) / det(cov2d + eps2d I)) of the projection's low-pass filter; a property of the trained model (a
+        # model trained with it must be rendered with it).  Read once per camera (antialiased() below)
+        rasterize_mode="classic",
         lr_scale_mode="sqrt", bsz=1, exact_filter=True, log_cpu_adam_trailing_overhead=False,
         # Debug
         stop_update_param=False, drop_initial_3dgs_p=0.0,
@@ -93,6 +97,17 @@ def default_args(**over):
     for k, v in over.items():
         setattr(a, k, v)
     return a
+
+
+RASTERIZE_MODES = ("classic", "antialiased")
+
+
+def antialiased():
+    """args.rasterize_mode == "antialiased"; any value outside RASTERIZE_MODES raises ValueError."""
+    mode = getattr(ARGS, "rasterize_mode", "classic")
+    if mode not in RASTERIZE_MODES:
+        raise ValueError(f"rasterize_mode must be one of {RASTERIZE_MODES}, got {mode!r}")
+    return mode == "antialiased"
 
 
 class _NullLog(io.StringIO):

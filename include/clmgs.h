@@ -80,6 +80,23 @@ int clmgs_projection_bwd(void* stream, int C, int N, const float* means, const f
                          const float* v_depths, const float* v_conics, float* v_means,
                          float* v_quats, float* v_scales);
 
+/* ---- gsplat.fully_fused_projection(calc_compensations=True): clmgs_projection_fwd plus the Mip-Splatting opacity
+ * compensation of every pair, compensations[C,N] = sqrt(max(0, det(cov2d) / det(cov2d + eps2d I))), 0 where culled; the
+ * determinant of cov2d is formed from the un-blurred entries.  radii, means2d, depths and conics are clmgs_projection_fwd's
+ * bit for bit; here every output is required. */
+int clmgs_projection_aa_fwd(void* stream, int C, int N, const float* means, const float* quats,
+                            const float* scales, const float* viewmats, const float* Ks, int width,
+                            int height, float eps2d, float near_plane, float far_plane,
+                            float radius_clip, int32_t* radii, float* means2d, float* depths,
+                            float* conics, float* compensations);
+/* Its VJP: clmgs_projection_bwd with one more cotangent, v_compensations[C,N] (NULL = zeros), in gsplat's guarded form:
+ * the square root's derivative is taken as 0.5 / (compensation + 1e-6). */
+int clmgs_projection_aa_bwd(void* stream, int C, int N, const float* means, const float* quats,
+                            const float* scales, const float* viewmats, const float* Ks, int width,
+                            int height, float eps2d, const int32_t* radii, const float* v_means2d,
+                            const float* v_depths, const float* v_conics, const float* v_compensations,
+                            float* v_means, float* v_quats, float* v_scales);
+
 /* ---- gsplat.spherical_harmonics  (base_engine.py:161-163; no_offload/engine.py:67-69;
  *      clm_offload/engine.py:73-76)
  * dirs[n,3] (un-normalised), coeffs[n,16,3], masks[n] u8 or NULL -> colors[n,3]. */
@@ -336,6 +353,43 @@ int clmgs_preprocess_abs_bwd(void* stream, int V, const int64_t* filter, const f
                              float* denom, float* v_means2d_out, int stats_only_visible,
                              const void* partials, const int64_t* row_cum, const int32_t* sh_index,
                              int32_t* sh_stamp, int cur_step, float* v_means2d_abs_out);
+
+/* gsplat's rasterization(rasterize_mode="antialiased") (Mip-Splatting): the fused front end with the opacity compensation
+ * of clmgs_projection_aa_fwd.  Argument lists are those of the plain counterparts.
+ * fwd: the opacity word of the record and opacities[V] are sigmoid(opacity_raw) * compensation (the binning's tile-mask
+ * test reads the record, so it follows); radii, means2d, depths, conics and colours are clmgs_preprocess_fwd's bit for bit.
+ * bwd (records written by _aa_fwd): with go the row's summed opacity word and op = sigmoid(opacity_raw),
+ *   g_opacity += go * compensation * op (1 - op),   v_compensation = go * op
+ * and v_compensation enters the projection VJP as in clmgs_projection_aa_bwd.  Statistics are the plain entry's.
+ * _aa_abs_bwd: _aa_bwd's gradients bit for bit, the statistic from the abs pair as in clmgs_preprocess_abs_bwd. */
+int clmgs_preprocess_aa_fwd(void* stream, int V, const int64_t* filter, const float* xyz,
+                            const float* opacity_raw, const float* scaling_raw,
+                            const float* rotation_raw, const float* sh_rows, int sh_by_filter,
+                            const float* viewmat_host, const float* K_host, const float* campos_host,
+                            int width, int height, int degree, float eps2d, float near_plane,
+                            float far_plane, float radius_clip, int32_t* radii, float* means2d,
+                            float* depths, float* conics, float* colors, float* opacities, void* packed,
+                            const int32_t* sh_index);
+int clmgs_preprocess_aa_bwd(void* stream, int V, const int64_t* filter, const float* xyz,
+                            const float* opacity_raw, const float* scaling_raw,
+                            const float* rotation_raw, const float* sh_rows, int sh_by_filter,
+                            const float* viewmat_host, const float* K_host, const float* campos_host,
+                            int width, int height, int degree, float eps2d, const int32_t* radii,
+                            const void* packed_grad, float* g_xyz, float* g_opacity, float* g_scaling,
+                            float* g_rotation, float* g_sh_rows, float* max_radii2D, float* grad_accum,
+                            float* denom, float* v_means2d_out, int stats_only_visible,
+                            const void* partials, const int64_t* row_cum, const int32_t* sh_index,
+                            int32_t* sh_stamp, int cur_step);
+int clmgs_preprocess_aa_abs_bwd(void* stream, int V, const int64_t* filter, const float* xyz,
+                                const float* opacity_raw, const float* scaling_raw,
+                                const float* rotation_raw, const float* sh_rows, int sh_by_filter,
+                                const float* viewmat_host, const float* K_host, const float* campos_host,
+                                int width, int height, int degree, float eps2d, const int32_t* radii,
+                                const void* packed_grad, float* g_xyz, float* g_opacity, float* g_scaling,
+                                float* g_rotation, float* g_sh_rows, float* max_radii2D, float* grad_accum,
+                                float* denom, float* v_means2d_out, int stats_only_visible,
+                                const void* partials, const int64_t* row_cum, const int32_t* sh_index,
+                                int32_t* sh_stamp, int cur_step, float* v_means2d_abs_out);
 
 /* ---- clm_kernels.fused_ssim  (base_engine.py:5,93; definition utils/loss_utils.py:26-85)
  * img1,img2 [B,CH,H,W].  fwd adds per-block SSIM-map sums into ssim_sum[1024] (caller zeroes
