@@ -70,6 +70,8 @@ SIGNATURES = {
     "clmgs_loss_slots": (_i, []),
     "clmgs_l1_ssim_loss_fwd": (_i, [_vp, _i, _i, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "clmgs_l1_ssim_loss_bwd": (_i, [_vp, _i, _i, _vp, _i64, _i64, _i64, _vp, _vp, _f, _vp, _vp, _vp, _vp]),
+    "clmgs_l1_ssim_loss_masked_fwd": (_i, [_vp, _i, _i, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "clmgs_l1_ssim_loss_masked_bwd": (_i, [_vp, _i, _i, _vp, _i64, _i64, _i64, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp]),
     "clmgs_rows_gather": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _i]),
     "clmgs_rows_scatter_add": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _i]),
     "clmgs_scatter_to_bit": (_i, [_vp, _vp, _i, _vp, _i64, _i]),

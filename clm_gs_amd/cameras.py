@@ -1,16 +1,30 @@
 """Camera objects exposing what the engines read (scene/cameras.py:39-126,
 train.py:278-312): FoVx, FoVy, world_view_transform (row-vector convention,
 i.e. the TRANSPOSE of the 4x4 world->camera matrix), K, camtoworlds,
-original_image (uint8 [3,H,W] on the GPU), image_name, create_k_on_gpu()."""
+original_image (uint8 [3,H,W] on the GPU), image_name, create_k_on_gpu(); plus loss_mask (uint8 [H,W] or None)
+and loss_mask_count, the per-pixel ignore mask of the training loss."""
 import math
 
 import numpy as np
 import torch
 
 
+def camera_loss_mask(camera):
+    """(mask, count) of a camera's per-pixel ignore mask of the loss (Camera.loss_mask: uint8 [H,W], 0 =
+    ignored), or (None, None).  The count is a host integer the camera carries (taken once, before the upload); a
+    camera object that only has the tensor gets it counted here, once."""
+    mask = getattr(camera, "loss_mask", None)
+    if mask is None:
+        return None, None
+    count = getattr(camera, "loss_mask_count", None)
+    if count is None:
+        count = camera.loss_mask_count = int(torch.count_nonzero(mask).item())
+    return mask, int(count)
+
+
 class Camera:
     def __init__(self, uid, world_to_cam, FoVx, FoVy, width, height, image_u8=None,
-                 image_name=None, device="cuda"):
+                 image_name=None, device="cuda", loss_mask=None):
         self.uid = uid
         self.FoVx, self.FoVy = float(FoVx), float(FoVy)
         self.image_width, self.image_height = int(width), int(height)
@@ -20,6 +34,19 @@ class Camera:
         # planar and contiguous, as the reference keeps it (scene/cameras.py:74 "image.contiguous()"): the loss
         # kernels read it in place; a strided image would cost fused.camera_forward_finish a copy per camera
         self.original_image = image_u8.to(device).contiguous() if image_u8 is not None else None
+        # per-pixel ignore mask of the training loss: uint8 [H,W], 0 = ignored, anything else = counted; None = every
+        # pixel.  The count of counted pixels is taken HERE, on the host, before the upload: the loss value needs it
+        # at every step and must not read the device back for it.
+        self.loss_mask, self.loss_mask_count = None, None
+        if loss_mask is not None:
+            m = torch.as_tensor(loss_mask)
+            if m.dtype == torch.bool:
+                m = m.to(torch.uint8)
+            if m.dtype != torch.uint8 or tuple(m.shape) != (self.image_height, self.image_width):
+                raise ValueError(f"loss_mask must be uint8 [{self.image_height}, {self.image_width}], "
+                                 f"got {m.dtype} {tuple(m.shape)}")
+            self.loss_mask_count = int(torch.count_nonzero(m))
+            self.loss_mask = m.to(device).contiguous()
         self.K = self.create_k_on_gpu(device)
         c2w = torch.inverse(w2c)
         self.camtoworlds = c2w[None].to(device)  # [1,4,4] as train.py:293-301

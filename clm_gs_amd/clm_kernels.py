@@ -89,11 +89,65 @@ class _FusedL1SSIMLoss(torch.autograd.Function):
         return v_img, None, None
 
 
-def fused_l1_ssim_loss(image, gt_u8, lambda_dssim=0.2):
+class _FusedL1SSIMLossMasked(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, image, gt_u8, lambda_dssim, mask, mask_count):
+        L = _lib.lib()
+        assert image.dim() == 3 and image.shape[0] == 3 and image.dtype == F32 and image.is_cuda
+        _, H, W = image.shape
+        gt_u8, mask = gt_u8.contiguous(), mask.contiguous()
+        assert gt_u8.dtype == U8 and gt_u8.shape == image.shape
+        assert mask.dtype == U8 and tuple(mask.shape) == (H, W) and mask.device == image.device
+        need = image.requires_grad
+        slots = L.clmgs_loss_slots()
+        partials = torch.zeros((slots, 2), dtype=F32, device=image.device)
+        maps = torch.empty((3, 3, H, W), dtype=F32, device=image.device) if need else None
+        sc, sy, sx = image.stride()
+        check(L.clmgs_l1_ssim_loss_masked_fwd(stream(), H, W, ctypes.c_void_p(image.data_ptr()), sc, sy, sx,
+                                              dptr(gt_u8, U8), dptr(partials),
+                                              dptr(maps[0] if need else None, F32, True),
+                                              dptr(maps[1] if need else None, F32, True),
+                                              dptr(maps[2] if need else None, F32, True), dptr(mask, U8)))
+        tot = partials.sum(dim=0)
+        ctx.lam = float(lambda_dssim)
+        if need:
+            ctx.save_for_backward(image, gt_u8, maps, mask)
+        return masked_loss_value(tot[0], tot[1], ctx.lam, mask_count, H, W)
+
+    @staticmethod
+    def backward(ctx, v):
+        L = _lib.lib()
+        image, gt_u8, maps, mask = ctx.saved_tensors
+        _, H, W = image.shape
+        v = v.reshape(1).to(F32).contiguous()
+        v_img = torch.empty_strided(image.shape, image.stride(), dtype=F32, device=image.device)
+        sc, sy, sx = image.stride()
+        check(L.clmgs_l1_ssim_loss_masked_bwd(stream(), H, W, ctypes.c_void_p(image.data_ptr()), sc, sy, sx,
+                                              dptr(gt_u8, U8), dptr(v, F32), ctx.lam, dptr(maps[0]),
+                                              dptr(maps[1]), dptr(maps[2]),
+                                              ctypes.c_void_p(v_img.data_ptr()), dptr(mask, U8)))
+        return v_img, None, None, None, None
+
+
+def masked_loss_value(l1_sum, ssim_sum, lambda_dssim, mask_count, H, W):
+    """The masked loss from the masked forward's two partial sums (over counted pixels) and the HOST count of
+    counted pixels: ((1-lambda) * l1 + lambda * (3 * count - ss)) / (3 H W)."""
+    return ((1.0 - lambda_dssim) * l1_sum + lambda_dssim * (float(3 * int(mask_count)) - ssim_sum)) / float(3 * H * W)
+
+
+def fused_l1_ssim_loss(image, gt_u8, lambda_dssim=0.2, mask=None, mask_count=None):
     """(1-lambda) * L1 + lambda * (1 - SSIM) of image [3,H,W] (any strides, e.g. a permuted view
     of the rasterizer's [H,W,3] output) against a uint8 [3,H,W] ground truth; one forward and one
-    backward kernel (strategies/base_engine.py:79-103 semantics)."""
-    return _FusedL1SSIMLoss.apply(image, gt_u8, lambda_dssim)
+    backward kernel (strategies/base_engine.py:79-103 semantics).
+    mask: uint8 [H,W] on the image's device, 0 = ignored pixel, anything else = counted (None: every pixel, the
+    unmasked kernels).  Ignored pixels add nothing to either term; the SSIM statistics are those of the whole images
+    and the divisor stays 3 H W ("Masked loss").  mask_count: the number of counted pixels as a
+    host integer (Camera.loss_mask_count); counted here, with one read-back, when not given."""
+    if mask is None:
+        return _FusedL1SSIMLoss.apply(image, gt_u8, lambda_dssim)
+    if mask_count is None:
+        mask_count = int(torch.count_nonzero(mask).item())
+    return _FusedL1SSIMLossMasked.apply(image, gt_u8, lambda_dssim, mask, int(mask_count))
 
 
 # ------------------------------------------------------------- SH row movement

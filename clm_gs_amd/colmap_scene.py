@@ -170,14 +170,47 @@ def scene_radius(world_to_cams):
     return -mean, 1.1 * float(np.linalg.norm(centres - mean, axis=1).max())
 
 
-def _decode_image(path, resolution):
+def _decode_image(path, resolution, want_alpha=False):
+    """-> uint8 [3,H,W]; with want_alpha -> (image, alpha) where alpha is the uint8 [H,W] alpha channel of an image
+    that has one -- as a band, or as the transparency entry of a palette / grey / RGB PNG -- (resized with nearest
+    neighbour, like a mask file) and None otherwise."""
     from PIL import Image
     with Image.open(path) as im:
+        alpha = None
+        if want_alpha and "A" in im.getbands():
+            alpha = im.getchannel("A")
+        elif want_alpha and "transparency" in im.info:  # palette / grey / RGB PNG with a tRNS chunk: no A band of its own
+            alpha = im.convert("RGBA").getchannel("A")
         im = im.convert("RGB")
         if resolution not in (1, None):
             im = im.resize((round(im.width / resolution), round(im.height / resolution)))
+            if alpha is not None:
+                alpha = alpha.resize(im.size, Image.NEAREST)
         a = np.array(im, dtype=np.uint8)  # a writable copy
-    return torch.from_numpy(a).permute(2, 0, 1).contiguous()
+        if alpha is not None:
+            alpha = torch.from_numpy(np.array(alpha, dtype=np.uint8))
+    img = torch.from_numpy(a).permute(2, 0, 1).contiguous()
+    return (img, alpha) if want_alpha else img
+
+
+def _mask_path(mask_dir, image_file):
+    """COLMAP's convention first (`NAME.EXT.png` for image `NAME.EXT`), then `NAME.png`; None if neither exists."""
+    for cand in (image_file + ".png", os.path.splitext(image_file)[0] + ".png"):
+        p = os.path.join(mask_dir, cand)
+        if os.path.exists(p):
+            return p
+    return None
+
+
+def _decode_mask(path, size_wh):
+    """A mask file as 8-bit grey -> uint8 [H,W] (non-zero = counted), resized with nearest neighbour to the decoded
+    image's size when the images were scaled (`resolution`)."""
+    from PIL import Image
+    with Image.open(path) as im:
+        im = im.convert("L")
+        if size_wh is not None and im.size != size_wh:
+            im = im.resize(size_wh, Image.NEAREST)
+        return torch.from_numpy(np.array(im, dtype=np.uint8))
 
 
 def read_model(sparse_dir):
@@ -199,10 +232,15 @@ def read_model(sparse_dir):
 
 
 def load_colmap_scene(source_path, images="images", eval=False, llffhold=10, resolution=1, device="cuda",
-                      load_images=True):
+                      load_images=True, masks=None, alpha_mask=False):
     """-> namespace(train_cameras, test_cameras, point_cloud(points, colors in [0,1]) or None,
     cameras_extent, nerf_normalization).  `cameras_extent` is what the trainer passes as
-    `spatial_lr_scale` and what densification compares scales with (train.py:118-131)."""
+    `spatial_lr_scale` and what densification compares scales with (train.py:118-131).
+    Per-pixel ignore masks of the loss (Camera.loss_mask): `masks` is a directory (relative to `source_path`, or
+    absolute) holding `NAME.EXT.png` (COLMAP's convention) or `NAME.png` for image `NAME.EXT`, read as 8-bit grey,
+    non-zero = counted; with `resolution` it is resized (nearest neighbour) to the decoded image's size, a mask of
+    another size raises, an image without a mask file stays unmasked.  `alpha_mask`: an image with transparency (an
+    alpha band, or a PNG `tRNS` entry) and without a mask file takes `alpha > 0`.  Without both, nothing changes."""
     cams, imgs, (xyz, rgb) = read_model(os.path.join(source_path, "sparse", "0"))
     folder = os.path.join(source_path, images or "images")
     recs = []
@@ -223,16 +261,34 @@ def load_colmap_scene(source_path, images="images", eval=False, llffhold=10, res
         train, test = recs, []
     translate, radius = scene_radius([r.w2c for r in train])
 
+    mask_dir = None
+    if masks:
+        mask_dir = masks if os.path.isabs(masks) else os.path.join(source_path, masks)
+        if not os.path.isdir(mask_dir):
+            raise FileNotFoundError(f"mask directory {mask_dir} does not exist")
+
     def build(r):
-        img = None
+        img, mask = None, None
         w, h = r.width, r.height
         if load_images:
-            img = _decode_image(r.path, resolution)
+            if alpha_mask:
+                img, alpha = _decode_image(r.path, resolution, want_alpha=True)
+            else:
+                img, alpha = _decode_image(r.path, resolution), None
             h, w = int(img.shape[1]), int(img.shape[2])  # the decoded size wins, as upstream (image.size)
         elif resolution not in (1, None):
             w, h = round(w / resolution), round(h / resolution)
+        if load_images:
+            mpath = _mask_path(mask_dir, os.path.basename(r.path)) if mask_dir else None
+            if mpath is not None:
+                mask = _decode_mask(mpath, (w, h) if resolution not in (1, None) else None)
+                if tuple(mask.shape) != (h, w):
+                    raise ValueError(f"mask {mpath} is {tuple(mask.shape)[1]}x{tuple(mask.shape)[0]}, "
+                                     f"image {r.path} is {w}x{h}")
+            elif alpha is not None:
+                mask = (alpha > 0).to(torch.uint8)
         return Camera(r.uid, torch.from_numpy(r.w2c).float(), r.fovx, r.fovy, w, h, image_u8=img,
-                      image_name=r.name, device=device)
+                      image_name=r.name, device=device, loss_mask=mask)
 
     pcd = None
     if xyz is not None and len(xyz):

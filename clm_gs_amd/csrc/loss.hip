@@ -88,9 +88,16 @@ __device__ __forceinline__ bool strip_of_block(int H, int W, int& c, int& x0, in
 #ifndef CLMGS_LOSS_FWD_WAVES
 #define CLMGS_LOSS_FWD_WAVES 3
 #endif
+// MASKED (per-pixel ignore mask, uint8 [H,W], 0 = ignored): the window statistics are those of the whole, unmasked
+// images; the mask byte of the OUTPUT pixel rides the row prefetch like the backward's px / py (an unconditional load
+// at clamped coordinates, requested LP rows before its row is finished, consumed as a select).  An ignored pixel adds
+// nothing to the two sums and gets ZEROS in its three derivative maps (the backward convolves them).  `mask` is not
+// read by the unmasked instantiation, whose code is the unparametrised kernel's.
+template <bool MASKED>
 __global__ void __launch_bounds__(64, CLMGS_LOSS_FWD_WAVES)
 loss_fwd_kernel(int H, int W, ImgView img, const uint8_t* __restrict__ gt, float* __restrict__ partials,
-                float* __restrict__ m1, float* __restrict__ m2, float* __restrict__ m3) {
+                float* __restrict__ m1, float* __restrict__ m2, float* __restrict__ m3,
+                const uint8_t* __restrict__ mask) {
   __shared__ float la[LS_RING][LS_PITCH], lb[LS_RING][LS_PITCH];
   const int lane = threadIdx.x;
   int c, x0, y0, slot;
@@ -115,12 +122,18 @@ loss_fwd_kernel(int H, int W, ImgView img, const uint8_t* __restrict__ gt, float
   const unsigned xs_off = xs_c * (unsigned)img.sx, xh_off = xh_c * (unsigned)img.sx;
   float pa[LP], ha[LP];                                  // rows in flight
   unsigned pb[LP], hb[LP];                               // (raw ground-truth bytes)
+  [[maybe_unused]] unsigned pm[LP];                      // MASKED: raw mask byte of the output pixel finished by the row
+  [[maybe_unused]] const unsigned xo_c = (unsigned)min(xo, W - 1);
   auto fetch = [&](int r, int s) {  // request input row r into slot s
     const int y = min(max(y0 - LR + min(r, n_rows - 1), 0), H - 1);  // wave-uniform
     const float* ir = img_c + y * img.sy;
     const uint8_t* gr = gt_c + (size_t)y * W;
     pa[s] = ir[xs_off]; pb[s] = gr[xs_c];
     ha[s] = ir[xh_off]; hb[s] = gr[xh_c];
+    if constexpr (MASKED) {
+      const int yo = min(max(y0 + min(r, n_rows - 1) - 2 * LR, 0), H - 1);  // output row finished at iteration r
+      pm[s] = (mask + (size_t)yo * W)[xo_c];
+    }
   };
 #pragma unroll
   for (int s = 0; s < LP; ++s) fetch(s, s);
@@ -143,6 +156,9 @@ loss_fwd_kernel(int H, int W, ImgView img, const uint8_t* __restrict__ gt, float
             la[buf][LS_W + lane] = okh ? ha[s] : 0.f; lb[buf][LS_W + lane] = okh ? gt_from_byte(hb[s]) : 0.f;
           }
         }
+        [[maybe_unused]] bool counted = true;
+        [[maybe_unused]] unsigned keep = ~0u;
+        if constexpr (MASKED) { counted = pm[s] != 0u; keep = counted ? ~0u : 0u; }
         fetch(r + LP, s);
         wave_sync();
         float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
@@ -173,15 +189,24 @@ loss_fwd_kernel(int H, int W, ImgView img, const uint8_t* __restrict__ gt, float
             const float D = mu1sq + mu2sq + L_C1, E = sgs + L_C2;
             const float iDE = __builtin_amdgcn_rcpf(D * E);  // 1-ulp reciprocals: three IEEE divides
             const float val = A * B * iDE;                   // per pixel were a tenth of the kernel
-            ss += out_ok ? val : 0.f;
+            const bool sum_ok = MASKED ? (out_ok && counted) : out_ok;
+            ss += sum_ok ? val : 0.f;
             const int cbuf = (r - LR) & (LS_RING - 1);  // centre: input row r - 5, still in the ring
-            l1 += out_ok ? fabsf(la[cbuf][lane + LR] - lb[cbuf][lane + LR]) : 0.f;
+            l1 += sum_ok ? fabsf(la[cbuf][lane + LR] - lb[cbuf][lane + LR]) : 0.f;
             if (m1 && out_ok) {
               const float d_mu1 = 2.f * mu2 * B * iDE - val * 2.f * mu1 * __builtin_amdgcn_rcpf(D);
               const float d_s1 = -val * __builtin_amdgcn_rcpf(E), d_s12 = 2.f * A * iDE;
               const size_t orow = c * plane + (size_t)y * W;  // wave-uniform
-              (m1 + orow)[(unsigned)xo] = d_mu1 - 2.f * mu1 * d_s1 - mu2 * d_s12;
-              (m2 + orow)[(unsigned)xo] = d_s1; (m3 + orow)[(unsigned)xo] = d_s12;
+              if constexpr (MASKED) {
+                // zeros at ignored pixels as an AND with `keep` (all ones / all zeros): three selects under this branch
+                // cost 21 VGPRs and four spills
+                auto kept = [&](float x) { return __uint_as_float(__float_as_uint(x) & keep); };
+                (m1 + orow)[(unsigned)xo] = kept(d_mu1 - 2.f * mu1 * d_s1 - mu2 * d_s12);
+                (m2 + orow)[(unsigned)xo] = kept(d_s1); (m3 + orow)[(unsigned)xo] = kept(d_s12);
+              } else {
+                (m1 + orow)[(unsigned)xo] = d_mu1 - 2.f * mu1 * d_s1 - mu2 * d_s12;
+                (m2 + orow)[(unsigned)xo] = d_s1; (m3 + orow)[(unsigned)xo] = d_s12;
+              }
             }
           }
         }
@@ -200,14 +225,21 @@ loss_fwd_kernel(int H, int W, ImgView img, const uint8_t* __restrict__ gt, float
 // LP rows before they are used, so every wait is for the oldest outstanding load), and the cotangent row leaves as one
 // run per row (planar images: 256 contiguous bytes).
 // v_img (strides of vimg) = v * ( w_l1 * sign(x - y) - w_ssim * dSSIMsum/dx ) / numel
+// MASKED: the maps already hold zeros at ignored pixels, so the mask is needed for the L1 sign term alone; its byte is
+// a third passenger of the output pixel (px, py, pk).  Every pixel of the image is written, ignored ones included.
+// The unmasked kernel sits exactly at the 168 VGPRs of 3 waves/SIMD, and the four mask bytes in flight do not fit: at 3
+// waves the masked kernel spills 4 VGPRs (20 B of scratch) and drains all loads twice per 12-row round to reload them,
+// measured 6-10 % slower than the unmasked kernel at 4608x3456.  Compiled for 2 waves/SIMD it takes 180 VGPRs, no
+// scratch, and measures 0.96-1.01 x the unmasked kernel (profiles/loss_masked_microbench.txt): that is what is built.
 #ifndef CLMGS_LOSS_BWD_WAVES
 #define CLMGS_LOSS_BWD_WAVES 3
 #endif
-__global__ void __launch_bounds__(64, CLMGS_LOSS_BWD_WAVES)
+template <bool MASKED>
+__global__ void __launch_bounds__(64, MASKED ? 2 : CLMGS_LOSS_BWD_WAVES)
 loss_bwd_kernel(int H, int W, ImgView img, const uint8_t* __restrict__ gt, const float* __restrict__ v,
                 float w_l1_over_numel, float w_ssim_over_numel, const float* __restrict__ m1,
                 const float* __restrict__ m2, const float* __restrict__ m3, float* __restrict__ v_img,
-                int64_t vsc, int64_t vsy, int64_t vsx) {
+                int64_t vsc, int64_t vsy, int64_t vsx, const uint8_t* __restrict__ mask) {
   __shared__ float lm[2][3][LS_PITCH];
   const int lane = threadIdx.x;
   int c, x0, y0, slot;
@@ -238,6 +270,7 @@ loss_bwd_kernel(int H, int W, ImgView img, const uint8_t* __restrict__ gt, const
   const unsigned xo_voff = (unsigned)xo * (unsigned)vsx;
   float p1[LP], p2[LP], p3[LP], ph[LP], px[LP];
   unsigned py[LP];
+  [[maybe_unused]] unsigned pk[LP];
   auto fetch = [&](int r, int s) {
     const int rc = min(r, n_rows - 1);
     const int y = min(max(y0 - LR + rc, 0), H - 1);         // input row of the maps (wave-uniform)
@@ -247,6 +280,7 @@ loss_bwd_kernel(int H, int W, ImgView img, const uint8_t* __restrict__ gt, const
     ph[s] = (mh + o)[xh_c];
     px[s] = (img_c + yo * img.sy)[xo_off];
     py[s] = (gt_c + (size_t)yo * W)[xo_c];
+    if constexpr (MASKED) pk[s] = (mask + (size_t)yo * W)[xo_c];
   };
 #pragma unroll
   for (int s = 0; s < LP; ++s) fetch(s, s);
@@ -266,6 +300,8 @@ loss_bwd_kernel(int H, int W, ImgView img, const uint8_t* __restrict__ gt, const
           if (hg < 3 && hl < 2 * LR) lm[buf][hg][LS_W + hl] = (row_ok && h_ok) ? ph[s] : 0.f;
         }
         const float xv = px[s], yv = gt_from_byte(py[s]);
+        [[maybe_unused]] bool counted = true;
+        if constexpr (MASKED) counted = pk[s] != 0u;
         fetch(r + LP, s);
         wave_sync();
         float s0 = 0.f, s1 = 0.f, s2 = 0.f;
@@ -287,7 +323,8 @@ loss_bwd_kernel(int H, int W, ImgView img, const uint8_t* __restrict__ gt, const
           }
           const int y = y0 + r - 2 * LR;
           if (r >= 2 * LR && r < n_rows && xo < W) {
-            const float sgn = (xv > yv) ? 1.f : ((xv < yv) ? -1.f : 0.f);
+            float sgn = (xv > yv) ? 1.f : ((xv < yv) ? -1.f : 0.f);
+            if constexpr (MASKED) sgn = counted ? sgn : 0.f;
             const float dss = g[0] + 2.f * xv * g[1] + yv * g[2];
             (v_img + (c * vsc + y * vsy))[xo_voff] = vv * (w_l1_over_numel * sgn - w_ssim_over_numel * dss);
           }
@@ -304,32 +341,65 @@ using namespace clmgs;
 
 extern "C" int clmgs_loss_slots(void) { return LOSS_SLOTS; }
 
-extern "C" int clmgs_l1_ssim_loss_fwd(void* stream, int H, int W, const float* img, int64_t stride_c,
-                                      int64_t stride_y, int64_t stride_x, const uint8_t* gt_u8,
-                                      float* partials, float* m1, float* m2, float* m3) {
+template <bool MASKED>
+static int launch_loss_fwd(void* stream, int H, int W, const float* img, int64_t stride_c, int64_t stride_y,
+                           int64_t stride_x, const uint8_t* gt_u8, float* partials, float* m1, float* m2, float* m3,
+                           const uint8_t* mask) {
   CLMGS_CHECK_ARG(H >= 1 && W >= 1 && img && gt_u8 && partials);
   CLMGS_CHECK_ARG((m1 && m2 && m3) || (!m1 && !m2 && !m3));
   ImgView v{img, stride_c, stride_y, stride_x};
   const int64_t strips = (int64_t)ceil_div(W, LS_W) * ceil_div(H, LS_ROWS);
   dim3 grid((unsigned)(24 * ceil_div(strips, 8)));
-  hipLaunchKernelGGL(loss_fwd_kernel, grid, dim3(64), 0, (hipStream_t)stream, H, W, v, gt_u8,
-                     partials, m1, m2, m3);
+  hipLaunchKernelGGL(loss_fwd_kernel<MASKED>, grid, dim3(64), 0, (hipStream_t)stream, H, W, v, gt_u8,
+                     partials, m1, m2, m3, mask);
   CLMGS_LAUNCH_CHECK();
   return 0;
+}
+
+template <bool MASKED>
+static int launch_loss_bwd(void* stream, int H, int W, const float* img, int64_t stride_c, int64_t stride_y,
+                           int64_t stride_x, const uint8_t* gt_u8, const float* v_loss, float lambda_dssim,
+                           const float* m1, const float* m2, const float* m3, float* v_img, const uint8_t* mask) {
+  CLMGS_CHECK_ARG(H >= 1 && W >= 1 && img && gt_u8 && v_loss && m1 && m2 && m3 && v_img);
+  ImgView v{img, stride_c, stride_y, stride_x};
+  const double numel = 3.0 * (double)H * (double)W;  // masked too: the divisor is the image's, not the counted pixels'
+  const int64_t strips = (int64_t)ceil_div(W, LS_W) * ceil_div(H, LS_ROWS);
+  dim3 grid((unsigned)(24 * ceil_div(strips, 8)));
+  hipLaunchKernelGGL(loss_bwd_kernel<MASKED>, grid, dim3(64), 0, (hipStream_t)stream, H, W, v, gt_u8, v_loss,
+                     (float)((1.0 - lambda_dssim) / numel), (float)(lambda_dssim / numel), m1, m2, m3,
+                     v_img, stride_c, stride_y, stride_x, mask);
+  CLMGS_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int clmgs_l1_ssim_loss_fwd(void* stream, int H, int W, const float* img, int64_t stride_c,
+                                      int64_t stride_y, int64_t stride_x, const uint8_t* gt_u8,
+                                      float* partials, float* m1, float* m2, float* m3) {
+  return launch_loss_fwd<false>(stream, H, W, img, stride_c, stride_y, stride_x, gt_u8, partials, m1, m2, m3, nullptr);
 }
 
 extern "C" int clmgs_l1_ssim_loss_bwd(void* stream, int H, int W, const float* img, int64_t stride_c,
                                       int64_t stride_y, int64_t stride_x, const uint8_t* gt_u8,
                                       const float* v_loss, float lambda_dssim, const float* m1,
                                       const float* m2, const float* m3, float* v_img) {
-  CLMGS_CHECK_ARG(H >= 1 && W >= 1 && img && gt_u8 && v_loss && m1 && m2 && m3 && v_img);
-  ImgView v{img, stride_c, stride_y, stride_x};
-  const double numel = 3.0 * (double)H * (double)W;
-  const int64_t strips = (int64_t)ceil_div(W, LS_W) * ceil_div(H, LS_ROWS);
-  dim3 grid((unsigned)(24 * ceil_div(strips, 8)));
-  hipLaunchKernelGGL(loss_bwd_kernel, grid, dim3(64), 0, (hipStream_t)stream, H, W, v, gt_u8, v_loss,
-                     (float)((1.0 - lambda_dssim) / numel), (float)(lambda_dssim / numel), m1, m2, m3,
-                     v_img, stride_c, stride_y, stride_x);
-  CLMGS_LAUNCH_CHECK();
-  return 0;
+  return launch_loss_bwd<false>(stream, H, W, img, stride_c, stride_y, stride_x, gt_u8, v_loss, lambda_dssim, m1, m2, m3,
+                                v_img, nullptr);
+}
+
+extern "C" int clmgs_l1_ssim_loss_masked_fwd(void* stream, int H, int W, const float* img, int64_t stride_c,
+                                             int64_t stride_y, int64_t stride_x, const uint8_t* gt_u8,
+                                             float* partials, float* m1, float* m2, float* m3,
+                                             const uint8_t* mask) {
+  CLMGS_CHECK_ARG(mask);
+  return launch_loss_fwd<true>(stream, H, W, img, stride_c, stride_y, stride_x, gt_u8, partials, m1, m2, m3, mask);
+}
+
+extern "C" int clmgs_l1_ssim_loss_masked_bwd(void* stream, int H, int W, const float* img, int64_t stride_c,
+                                             int64_t stride_y, int64_t stride_x, const uint8_t* gt_u8,
+                                             const float* v_loss, float lambda_dssim, const float* m1,
+                                             const float* m2, const float* m3, float* v_img,
+                                             const uint8_t* mask) {
+  CLMGS_CHECK_ARG(mask);
+  return launch_loss_bwd<true>(stream, H, W, img, stride_c, stride_y, stride_x, gt_u8, v_loss, lambda_dssim, m1, m2, m3,
+                               v_img, mask);
 }

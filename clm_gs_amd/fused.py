@@ -13,6 +13,8 @@ import torch
 
 from . import _lib, utils
 from ._lib import check, dptr
+from .cameras import camera_loss_mask
+from .clm_kernels import masked_loss_value
 from .gsplat import (_record_counts, bucket_size, empty_bucketed, isect2_begin, isect2_counts, isect2_finish, isect3_begin,
                      isect3_finish)
 
@@ -60,7 +62,8 @@ class _CameraPass:
     __slots__ = ("V", "cam", "filt", "sh_rows", "sh_by_filter", "small_in", "small_packed", "radii",
                  "packed", "fids", "offsets", "emit_slot", "row_cum", "out", "alphas", "last_ids",
                  "bg", "v_out", "maps", "loss", "ev_loss", "streams", "deg", "aux", "loss_partials",
-                 "lambda_dssim", "gt_u8", "background", "isect", "sh_index", "means2d", "n_dev", "antialiased")
+                 "lambda_dssim", "gt_u8", "background", "isect", "sh_index", "means2d", "n_dev", "antialiased",
+                 "loss_mask", "mask_count")
 
 
 def _sptr(torch_stream):
@@ -147,6 +150,7 @@ def camera_front(gaussians, camera, this_filter, sh_rows, sh_by_filter, backgrou
     p.sh_rows, p.sh_by_filter, p.small_packed = sh_rows, sh_by_filter, small_packed
     p.sh_index = sh_index  # int32[V]: SH row of position i in a staging table (host-resident mode)
     p.gt_u8, p.lambda_dssim, p.background = gt_u8, float(lambda_dssim), background
+    p.loss_mask, p.mask_count = camera_loss_mask(camera)  # a mask on the camera selects the masked loss kernels
     p.antialiased = utils.antialiased()  # the backward follows the mode its forward ran in
     filt = p.filt = this_filter.contiguous() if this_filter is not None else None  # None: all rows
     if small_packed is not None:
@@ -236,8 +240,15 @@ def camera_forward_finish(gaussians, p, exact=False):
         sc, sy, sx = 1, 3 * W, 3
         gt = gt_u8.contiguous()
         sm = _sptr(s_mem)
-        check(L.clmgs_l1_ssim_loss_fwd(sm, H, W, dptr(p.out), sc, sy, sx, dptr(gt, U8), dptr(partials),
-                                       dptr(maps[0]), dptr(maps[1]), dptr(maps[2])))
+        mask = p.loss_mask
+        if mask is None:
+            check(L.clmgs_l1_ssim_loss_fwd(sm, H, W, dptr(p.out), sc, sy, sx, dptr(gt, U8), dptr(partials),
+                                           dptr(maps[0]), dptr(maps[1]), dptr(maps[2])))
+        else:
+            if tuple(mask.shape) != (H, W):
+                raise _lib.ClmgsError(f"loss_mask is {tuple(mask.shape)}, the image is {(H, W)}")
+            check(L.clmgs_l1_ssim_loss_masked_fwd(sm, H, W, dptr(p.out), sc, sy, sx, dptr(gt, U8), dptr(partials),
+                                                  dptr(maps[0]), dptr(maps[1]), dptr(maps[2]), dptr(mask, U8)))
         # the loss VALUE is not needed by the backward (d loss / d loss = 1): its handful of tiny
         # reduction kernels is enqueued by camera_loss(), off the forward -> backward chain
         p.loss_partials, p.loss = partials, None
@@ -245,14 +256,19 @@ def camera_forward_finish(gaussians, p, exact=False):
         if one is None or one.device != dev:
             one = gaussians._clmgs_one = torch.ones((1,), dtype=F32, device=dev)
         p.v_out = torch.empty_like(p.out)
-        check(L.clmgs_l1_ssim_loss_bwd(sm, H, W, dptr(p.out), sc, sy, sx, dptr(gt, U8), dptr(one),
-                                       float(lambda_dssim), dptr(maps[0]), dptr(maps[1]), dptr(maps[2]),
-                                       dptr(p.v_out)))
+        if mask is None:
+            check(L.clmgs_l1_ssim_loss_bwd(sm, H, W, dptr(p.out), sc, sy, sx, dptr(gt, U8), dptr(one),
+                                           float(lambda_dssim), dptr(maps[0]), dptr(maps[1]), dptr(maps[2]),
+                                           dptr(p.v_out)))
+        else:
+            check(L.clmgs_l1_ssim_loss_masked_bwd(sm, H, W, dptr(p.out), sc, sy, sx, dptr(gt, U8), dptr(one),
+                                                  float(lambda_dssim), dptr(maps[0]), dptr(maps[1]), dptr(maps[2]),
+                                                  dptr(p.v_out), dptr(mask, U8)))
         p.ev_loss = None
         if s_raster is not s_mem:
             p.ev_loss = torch.cuda.Event()
             p.ev_loss.record(s_mem)
-        p.aux = p.aux + (gt, one, partials)
+        p.aux = p.aux + (gt, one, partials) + ((mask,) if mask is not None else ())
         # the three derivative maps (573 MB at 4K) were allocated, written and read on s_mem only: dropping
         # them here hands the block back to that stream's pool, where the next camera's maps reuse it in
         # stream order (they used to stay alive until the next batch: 4 x 573 MB)
@@ -266,8 +282,12 @@ def camera_loss(p):
     the CURRENT stream, which must be ordered after the camera's loss kernel."""
     if p.loss is None:
         W, H = int(utils.get_img_width()), int(utils.get_img_height())
-        tot = p.loss_partials.sum(dim=0) / float(3 * H * W)
-        p.loss = ((1.0 - p.lambda_dssim) * tot[0] + p.lambda_dssim * (1.0 - tot[1])).detach()
+        if p.loss_mask is None:
+            tot = p.loss_partials.sum(dim=0) / float(3 * H * W)
+            p.loss = ((1.0 - p.lambda_dssim) * tot[0] + p.lambda_dssim * (1.0 - tot[1])).detach()
+        else:  # sums over counted pixels; the count is a host integer
+            tot = p.loss_partials.sum(dim=0)
+            p.loss = masked_loss_value(tot[0], tot[1], p.lambda_dssim, p.mask_count, H, W).detach()
     return p.loss
 
 

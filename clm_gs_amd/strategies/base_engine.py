@@ -69,12 +69,17 @@ def loss_combined(image, image_gt, ssim_loss):
     return (1.0 - LAMBDA_DSSIM) * Ll1 + LAMBDA_DSSIM * (1.0 - ssim_loss)
 
 
-def torch_compiled_loss(image, image_gt_original):
+def torch_compiled_loss(image, image_gt_original, loss_mask=None, loss_mask_count=None):
     """0.8 * L1 + 0.2 * (1 - SSIM) against clamp(u8/255) (base_engine.py:79-103).  The
     reference torch.compile's the L1 mix next to a fused SSIM kernel; here the whole loss
-    (u8 -> float GT, L1, SSIM, mix) is one fused HIP kernel each way when the GT is uint8."""
+    (u8 -> float GT, L1, SSIM, mix) is one fused HIP kernel each way when the GT is uint8.
+    loss_mask (uint8 [H,W], 0 = ignored; a camera's `loss_mask`) selects the masked kernels."""
     if image_gt_original.dtype == torch.uint8:
+        if loss_mask is not None:
+            return fused_l1_ssim_loss(image, image_gt_original, LAMBDA_DSSIM, loss_mask, loss_mask_count)
         return fused_l1_ssim_loss(image, image_gt_original, LAMBDA_DSSIM)
+    if loss_mask is not None:
+        raise ValueError("a loss mask needs the uint8 ground-truth image (the masked loss exists as the fused kernels only)")
     image_gt = torch.clamp(image_gt_original / 255.0, 0.0, 1.0)
     ssim_loss = fused_ssim(image.unsqueeze(0), image_gt.unsqueeze(0))
     return loss_combined(image, image_gt, ssim_loss)

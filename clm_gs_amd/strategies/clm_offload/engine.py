@@ -30,6 +30,7 @@ import os
 import torch
 
 from ... import _lib, clm_kernels, dp, fast_tsp, utils
+from ...cameras import camera_loss_mask
 from ...clm_kernels import (send_shs2cpu_grad_buffer_stream, send_shs2gpu_stream,
                             spherical_harmonics_bwd_inplace)
 from ...densification import update_densification_stats_offload_accum_grads
@@ -189,7 +190,7 @@ def _render_and_backward(gaussians, scene, camera, background, pipe_args, this_f
     rot = gaussians.rotation_activation(rot_raw)
     image, means2D, radiis, colors_detached, dirs = pipeline_forward_one_step_shs_inplace(
         opa, sca, rot, xyz, shs, camera, scene, gaussians, background, pipe_args)
-    loss = torch_compiled_loss(image, camera.original_image)
+    loss = torch_compiled_loss(image, camera.original_image, *camera_loss_mask(camera))
     loss.backward()
     if before_sh_backward is not None:
         before_sh_backward()

@@ -6,6 +6,7 @@ import math
 import torch
 
 from ... import utils
+from ...cameras import camera_loss_mask
 from ...densification import update_densification_stats_baseline_accum_grads
 from ...gsplat import (fully_fused_projection, isect_offset_encode, isect_tiles,
                        rasterize_to_pixels, spherical_harmonics)
@@ -83,7 +84,7 @@ def baseline_accumGrads_impl(gaussians, scene, batched_cameras, background, scal
     for camera in batched_cameras:
         rendered_image, means2D, radiis, gaussian_ids = baseline_accumGrads_micro_step(
             means3D, opacities, scales, rotations, shs, sh_degree, camera, background)
-        loss = torch_compiled_loss(rendered_image, camera.original_image)
+        loss = torch_compiled_loss(rendered_image, camera.original_image, *camera_loss_mask(camera))
         loss.backward()
         losses.append(loss.detach())
         with torch.no_grad():

@@ -17,6 +17,7 @@ import time
 import torch
 
 from . import dp, utils
+from .cameras import camera_loss_mask
 from .densification import gsplat_densification
 
 
@@ -73,14 +74,25 @@ def memory_line(iteration, bsz, gaussians, what="densify_and_prune"):
 
 @torch.no_grad()
 def evaluate(name, iteration, cameras, render_fn, log_file, max_images=10 ** 9):
-    """train.py:669-846 in essence: mean L1 / PSNR over a camera set."""
+    """train.py:669-846 in essence: mean L1 / PSNR over a camera set.  A camera with a loss mask is measured over its
+    counted pixels only; one whose mask counts no pixel at all has nothing to measure and is left out of the means."""
     l1s, ps = [], []
     for cam in cameras[:max_images]:
+        mask, count = camera_loss_mask(cam)
+        if mask is not None and count == 0:
+            continue
         img = torch.clamp(render_fn(cam), 0.0, 1.0)
         gt = torch.clamp(cam.original_image.float() / 255.0, 0.0, 1.0)
-        l1s.append((img - gt).abs().mean().item())
-        ps.append(psnr(img[None], gt[None]).mean().item())
-    l1, p = sum(l1s) / len(l1s), sum(ps) / len(ps)
+        if mask is None:
+            l1s.append((img - gt).abs().mean().item())
+            ps.append(psnr(img[None], gt[None]).mean().item())
+        else:  # a reported metric: sums over the counted pixels, divided by their number (3 * count values)
+            m = (mask != 0).to(img.dtype)[None]
+            n = float(3 * count)
+            l1s.append((((img - gt).abs() * m).sum() / n).item())
+            mse = (((img - gt) ** 2) * m).sum() / n
+            ps.append((20 * torch.log10(1.0 / torch.sqrt(mse))).item())
+    l1, p = sum(l1s) / max(len(l1s), 1), sum(ps) / max(len(ps), 1)
     log_file.write("[ITER {}] Evaluating {}: L1 {} PSNR {}\n".format(iteration, name, l1, p))
     return l1, p
 
@@ -395,13 +407,14 @@ def training(gaussians, scene, train_cameras, test_cameras, log_file, iterations
 
 
 def train_from_colmap(source_path, model_path, strategy="clm_offload", iterations=None, eval=False, resolution=1,
-                      images="images", test_iterations=(), save=True, **arg_overrides):
+                      images="images", test_iterations=(), save=True, masks=None, alpha_mask=False, **arg_overrides):
     """A COLMAP directory -> trained model (row f1): `colmap_scene.load_colmap_scene` (cameras, held-out
     split, scene radius, sparse points) -> `create_from_pcd` with `spatial_lr_scale = cameras_extent` ->
     `training_setup` -> `training` (log lines of the reference in `<model_path>/python_ws=1_rk=0.log`) ->
     `point_cloud/iteration_N/point_cloud.ply` (scene/__init__.py:41-143, train.py:60-131 for the order of
     these steps).  `strategy`: clm_offload | no_offload | naive_offload; `arg_overrides`: any flag of
-    `utils.default_args`.  Returns (gaussians, scene, timer)."""
+    `utils.default_args`.  `masks` / `alpha_mask`: per-pixel ignore masks of the loss (colmap_scene.load_colmap_scene).
+    Returns (gaussians, scene, timer)."""
     from .colmap_scene import load_colmap_scene
     from .strategies.clm_offload import GaussianModelCLMOffload
     from .strategies.naive_offload import GaussianModelNaiveOffload
@@ -413,7 +426,8 @@ def train_from_colmap(source_path, model_path, strategy="clm_offload", iteration
     if iterations is not None:
         args.iterations = int(iterations)
     utils.set_args(args)
-    scene = load_colmap_scene(source_path, images=images, eval=eval, resolution=resolution, device="cuda")
+    scene = load_colmap_scene(source_path, images=images, eval=eval, resolution=resolution, device="cuda",
+                              masks=masks, alpha_mask=alpha_mask)
     if scene.point_cloud is None:
         raise ValueError(f"{source_path}/sparse/0 holds no points3D.bin / points3D.txt to initialise from")
     sizes = {(c.image_height, c.image_width) for c in scene.train_cameras + scene.test_cameras}
@@ -464,9 +478,15 @@ if __name__ == "__main__":  # python -m clm_gs_amd.trainer -s <colmap dir> -m <o
                     help="densify on sum_p |dL_p/dmean2d| (gsplat's absgrad); gsplat's recipe raises the threshold to 8e-4")
     ap.add_argument("--antialiased", action="store_true",
                     help="gsplat's rasterize_mode=\"antialiased\" (Mip-Splatting opacity compensation); render the model with it too")
+    ap.add_argument("--masks", default=None, metavar="DIR",
+                    help="directory of per-image loss masks (NAME.EXT.png or NAME.png, 0 = pixel ignored by the loss), "
+                         "relative to the source path or absolute")
+    ap.add_argument("--alpha_mask", action="store_true",
+                    help="images with an alpha channel and no mask file: the loss ignores pixels with alpha 0")
     a = ap.parse_args()
     strat = "no_offload" if a.no_offload else ("naive_offload" if a.naive_offload else "clm_offload")
     _, _, t = train_from_colmap(a.source_path, a.model_path, strategy=strat, iterations=a.iterations, eval=a.eval,
                                 resolution=a.resolution, images=a.images, test_iterations=tuple(a.test_iterations),
                                 bsz=a.bsz, sh_residency=a.sh_residency, sh_hbm_budget_gb=a.sh_hbm_budget_gb,
-                                absgrad=a.absgrad, rasterize_mode="antialiased" if a.antialiased else "classic")
+                                absgrad=a.absgrad, rasterize_mode="antialiased" if a.antialiased else "classic",
+                                masks=a.masks, alpha_mask=a.alpha_mask)

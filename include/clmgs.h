@@ -418,6 +418,22 @@ int clmgs_l1_ssim_loss_bwd(void* stream, int H, int W, const float* img, int64_t
                            int64_t stride_y, int64_t stride_x, const uint8_t* gt_u8,
                            const float* v_loss, float lambda_dssim, const float* m1,
                            const float* m2, const float* m3, float* v_img);
+/* Masked forms: the same loss with a per-pixel ignore mask, mask[H,W] uint8 planar (0 = ignored, any other value =
+ * counted; required non-NULL), shared by the three channels:
+ *   loss = (1 - lambda) * sum m |img - gt| / (3 H W) + lambda * sum m (1 - ssim_map) / (3 H W).
+ * The SSIM window statistics are those of the whole, unmasked images and the divisor stays 3 H W.  fwd adds the two
+ * sums over COUNTED pixels only (the caller forms sum m (1 - ssim_map) as 3 * count - partial) and writes ZEROS into
+ * m1..m3 at ignored pixels; bwd writes every element of v_img (exactly 0 farther than 5 pixels from any counted
+ * pixel).  With an all-counted mask both compute what the unmasked entries compute. */
+int clmgs_l1_ssim_loss_masked_fwd(void* stream, int H, int W, const float* img, int64_t stride_c,
+                                  int64_t stride_y, int64_t stride_x, const uint8_t* gt_u8,
+                                  float* partials, float* m1, float* m2, float* m3,
+                                  const uint8_t* mask);
+int clmgs_l1_ssim_loss_masked_bwd(void* stream, int H, int W, const float* img, int64_t stride_c,
+                                  int64_t stride_y, int64_t stride_x, const uint8_t* gt_u8,
+                                  const float* v_loss, float lambda_dssim, const float* m1,
+                                  const float* m2, const float* m3, float* v_img,
+                                  const uint8_t* mask);
 
 /* ---- clm_kernels row movers  (clm_offload/engine.py:499-505, 622-636, 789-802, 815-822)
  * dst/src may be device memory or pinned (mapped) host memory.
