@@ -2,7 +2,8 @@
 train.py:278-312): FoVx, FoVy, world_view_transform (row-vector convention,
 i.e. the TRANSPOSE of the 4x4 world->camera matrix), K, camtoworlds,
 original_image (uint8 [3,H,W] on the GPU), image_name, create_k_on_gpu(); plus loss_mask (uint8 [H,W] or None)
-and loss_mask_count, the per-pixel ignore mask of the training loss."""
+and loss_mask_count, the per-pixel ignore mask of the training loss.  A training camera may also carry `exposure` /
+`exposure_grad`, float32 [3,4] views of its rows in an exposure.ExposureModel (camera_exposure below)."""
 import math
 
 import numpy as np
@@ -20,6 +21,16 @@ def camera_loss_mask(camera):
     if count is None:
         count = camera.loss_mask_count = int(torch.count_nonzero(mask).item())
     return mask, int(count)
+
+
+def camera_exposure(camera):
+    """(row, grad_row) of a camera's exposure transform -- float32 [3,4] views into the tables of an
+    exposure.ExposureModel (`camera.exposure`, `camera.exposure_grad`) -- or (None, None): a camera without the
+    attribute, or with None, is rendered and trained as the model is."""
+    row = getattr(camera, "exposure", None)
+    if row is None:
+        return None, None
+    return row, getattr(camera, "exposure_grad", None)
 
 
 class Camera:

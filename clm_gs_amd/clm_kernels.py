@@ -150,6 +150,63 @@ def fused_l1_ssim_loss(image, gt_u8, lambda_dssim=0.2, mask=None, mask_count=Non
     return _FusedL1SSIMLossMasked.apply(image, gt_u8, lambda_dssim, mask, int(mask_count))
 
 
+# ------------------------------------------------------- exposure compensation
+def _view_ptr(t):
+    return ctypes.c_void_p(t.data_ptr())
+
+
+class _ApplyExposure(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, image, exposure):
+        L = _lib.lib()
+        assert image.dim() == 3 and image.shape[0] == 3 and image.dtype == F32 and image.is_cuda
+        assert tuple(exposure.shape) == (3, 4) and exposure.dtype == F32 and exposure.device == image.device
+        _, H, W = image.shape
+        E = exposure.detach().contiguous()
+        out = torch.empty_strided(image.shape, image.stride(), dtype=F32, device=image.device)
+        check(L.clmgs_exposure_fwd(stream(), H, W, _view_ptr(image), *image.stride(), dptr(E, F32),
+                                   _view_ptr(out), *out.stride()))
+        ctx.save_for_backward(image, E)
+        return out
+
+    @staticmethod
+    def backward(ctx, v):
+        L = _lib.lib()
+        image, E = ctx.saved_tensors
+        _, H, W = image.shape
+        assert v.dtype == F32 and v.shape == image.shape
+        v_img = torch.empty_strided(image.shape, image.stride(), dtype=F32, device=image.device)
+        rows = int(L.clmgs_exposure_partials_rows(H, W))
+        partials = torch.empty((rows, 12), dtype=F32, device=image.device)
+        v_E = torch.zeros((3, 4), dtype=F32, device=image.device)
+        check(L.clmgs_exposure_bwd(stream(), H, W, _view_ptr(image), *image.stride(), dptr(E, F32), _view_ptr(v),
+                                   *v.stride(), _view_ptr(v_img), *v_img.stride(), dptr(partials)))
+        check(L.clmgs_exposure_grad_finish(stream(), rows, dptr(partials), dptr(v_E)))
+        return v_img, v_E
+
+
+def apply_exposure(image, exposure):
+    """A camera's exposure transform on a rendered image: image [3,H,W] float32 (any strides, e.g. the permuted view of
+    the rasterizer's [H,W,3] output), exposure float32 [3,4] on the same device ->
+    y[c] = x[0] E[0][c] + x[1] E[1][c] + x[2] E[2][c] + E[c][3] in the image's layout, unclamped; differentiable in
+    both (csrc/exposure.hip; DESIGN.md section 3, "Exposure")."""
+    return _ApplyExposure.apply(image, exposure)
+
+
+def apply_camera_exposure(image, camera):
+    """apply_exposure with the camera's row, the row's gradient ADDED into `camera.exposure_grad` by the backward; the
+    image itself for a camera without an exposure.  What the op-by-op engines and the evaluation renders call."""
+    from .cameras import camera_exposure
+    row, grad_row = camera_exposure(camera)
+    if row is None:
+        return image
+    if not (torch.is_grad_enabled() and image.requires_grad) or grad_row is None:
+        return apply_exposure(image, row.detach())
+    leaf = row.detach().requires_grad_(True)
+    leaf.register_hook(lambda g: (grad_row.add_(g), None)[1])
+    return apply_exposure(image, leaf)
+
+
 # ------------------------------------------------------------- SH row movement
 def _idx64(t):
     return 1 if t is not None and t.dtype == I64 else 0

@@ -13,7 +13,7 @@ import torch
 
 from . import _lib, utils
 from ._lib import check, dptr
-from .cameras import camera_loss_mask
+from .cameras import camera_exposure, camera_loss_mask
 from .clm_kernels import masked_loss_value
 from .gsplat import (_record_counts, bucket_size, empty_bucketed, isect2_begin, isect2_counts, isect2_finish, isect3_begin,
                      isect3_finish)
@@ -63,7 +63,7 @@ class _CameraPass:
                  "packed", "fids", "offsets", "emit_slot", "row_cum", "out", "alphas", "last_ids",
                  "bg", "v_out", "maps", "loss", "ev_loss", "streams", "deg", "aux", "loss_partials",
                  "lambda_dssim", "gt_u8", "background", "isect", "sh_index", "means2d", "n_dev", "antialiased",
-                 "loss_mask", "mask_count")
+                 "loss_mask", "mask_count", "exposure", "exposure_grad", "exp_partials")
 
 
 def _sptr(torch_stream):
@@ -151,6 +151,8 @@ def camera_front(gaussians, camera, this_filter, sh_rows, sh_by_filter, backgrou
     p.sh_index = sh_index  # int32[V]: SH row of position i in a staging table (host-resident mode)
     p.gt_u8, p.lambda_dssim, p.background = gt_u8, float(lambda_dssim), background
     p.loss_mask, p.mask_count = camera_loss_mask(camera)  # a mask on the camera selects the masked loss kernels
+    # an exposure row on the camera puts the affine colour transform between the tile kernel and the loss
+    (p.exposure, p.exposure_grad), p.exp_partials = camera_exposure(camera), None
     p.antialiased = utils.antialiased()  # the backward follows the mode its forward ran in
     filt = p.filt = this_filter.contiguous() if this_filter is not None else None  # None: all rows
     if small_packed is not None:
@@ -241,13 +243,21 @@ def camera_forward_finish(gaussians, p, exact=False):
         gt = gt_u8.contiguous()
         sm = _sptr(s_mem)
         mask = p.loss_mask
+        img = p.out  # what the loss sees
+        if p.exposure is not None:
+            # the camera's exposure transform into a second [H,W,3] buffer, allocated and used on s_mem only (like the
+            # maps); p.out stays: the transform's backward reads it
+            if tuple(p.exposure.shape) != (3, 4) or p.exposure.dtype != F32:
+                raise _lib.ClmgsError(f"camera.exposure must be float32 [3,4], got {p.exposure.dtype} {tuple(p.exposure.shape)}")
+            img = torch.empty_like(p.out)
+            check(L.clmgs_exposure_fwd(sm, H, W, dptr(p.out), sc, sy, sx, dptr(p.exposure, F32), dptr(img), sc, sy, sx))
         if mask is None:
-            check(L.clmgs_l1_ssim_loss_fwd(sm, H, W, dptr(p.out), sc, sy, sx, dptr(gt, U8), dptr(partials),
+            check(L.clmgs_l1_ssim_loss_fwd(sm, H, W, dptr(img), sc, sy, sx, dptr(gt, U8), dptr(partials),
                                            dptr(maps[0]), dptr(maps[1]), dptr(maps[2])))
         else:
             if tuple(mask.shape) != (H, W):
                 raise _lib.ClmgsError(f"loss_mask is {tuple(mask.shape)}, the image is {(H, W)}")
-            check(L.clmgs_l1_ssim_loss_masked_fwd(sm, H, W, dptr(p.out), sc, sy, sx, dptr(gt, U8), dptr(partials),
+            check(L.clmgs_l1_ssim_loss_masked_fwd(sm, H, W, dptr(img), sc, sy, sx, dptr(gt, U8), dptr(partials),
                                                   dptr(maps[0]), dptr(maps[1]), dptr(maps[2]), dptr(mask, U8)))
         # the loss VALUE is not needed by the backward (d loss / d loss = 1): its handful of tiny
         # reduction kernels is enqueued by camera_loss(), off the forward -> backward chain
@@ -257,13 +267,21 @@ def camera_forward_finish(gaussians, p, exact=False):
             one = gaussians._clmgs_one = torch.ones((1,), dtype=F32, device=dev)
         p.v_out = torch.empty_like(p.out)
         if mask is None:
-            check(L.clmgs_l1_ssim_loss_bwd(sm, H, W, dptr(p.out), sc, sy, sx, dptr(gt, U8), dptr(one),
+            check(L.clmgs_l1_ssim_loss_bwd(sm, H, W, dptr(img), sc, sy, sx, dptr(gt, U8), dptr(one),
                                            float(lambda_dssim), dptr(maps[0]), dptr(maps[1]), dptr(maps[2]),
                                            dptr(p.v_out)))
         else:
-            check(L.clmgs_l1_ssim_loss_masked_bwd(sm, H, W, dptr(p.out), sc, sy, sx, dptr(gt, U8), dptr(one),
+            check(L.clmgs_l1_ssim_loss_masked_bwd(sm, H, W, dptr(img), sc, sy, sx, dptr(gt, U8), dptr(one),
                                                   float(lambda_dssim), dptr(maps[0]), dptr(maps[1]), dptr(maps[2]),
                                                   dptr(p.v_out), dptr(mask, U8)))
+        if p.exposure is not None:
+            # dL/dy -> dL/dx IN PLACE on p.v_out (no third image buffer) + one row of 12 partial sums per workgroup; the
+            # rows wait on the pass: camera_backward adds them to the camera's gradient row once camera_verify has
+            # accepted THIS forward (a forward repeated for capacity replaces them)
+            rows = int(L.clmgs_exposure_partials_rows(H, W))
+            p.exp_partials = torch.empty((rows, 12), dtype=F32, device=dev)
+            check(L.clmgs_exposure_bwd(sm, H, W, dptr(p.out), sc, sy, sx, dptr(p.exposure, F32), dptr(p.v_out), sc, sy, sx,
+                                       dptr(p.v_out), sc, sy, sx, dptr(p.exp_partials)))
         p.ev_loss = None
         if s_raster is not s_mem:
             p.ev_loss = torch.cuda.Event()
@@ -271,9 +289,10 @@ def camera_forward_finish(gaussians, p, exact=False):
         p.aux = p.aux + (gt, one, partials) + ((mask,) if mask is not None else ())
         # the three derivative maps (573 MB at 4K) were allocated, written and read on s_mem only: dropping
         # them here hands the block back to that stream's pool, where the next camera's maps reuse it in
-        # stream order (they used to stay alive until the next batch: 4 x 573 MB)
+        # stream order (they used to stay alive until the next batch: 4 x 573 MB).  The exposure-corrected image goes
+        # the same way: nothing after the loss backward reads it.
         p.maps = None
-        del maps
+        del maps, img
     return p
 
 
@@ -325,6 +344,13 @@ def camera_backward(gaussians, p, g_sh_rows, small_grad=None, update_stats=True,
     dev = gaussians._xyz.device
     camera_verify(gaussians, p)
     s_front, s_mem, s_raster = p.streams
+    if p.exp_partials is not None:
+        # the exposure gradient of the forward camera_verify has just accepted (an overflowed forward was repeated exactly
+        # and left its own rows): added ONCE, on the stream that wrote the rows.  Allocated, written and read on s_mem only.
+        if p.exposure_grad is not None:
+            check(L.clmgs_exposure_grad_finish(_sptr(s_mem), int(p.exp_partials.shape[0]), dptr(p.exp_partials),
+                                               dptr(p.exposure_grad, F32)))
+        p.exp_partials = None
     V = p.V
     vm, K, campos = p.cam
     tw, th = math.ceil(W / float(TILE)), math.ceil(H / float(TILE))

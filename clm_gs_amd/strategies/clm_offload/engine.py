@@ -31,7 +31,7 @@ import torch
 
 from ... import _lib, clm_kernels, dp, fast_tsp, utils
 from ...cameras import camera_loss_mask
-from ...clm_kernels import (send_shs2cpu_grad_buffer_stream, send_shs2gpu_stream,
+from ...clm_kernels import (apply_camera_exposure, send_shs2cpu_grad_buffer_stream, send_shs2gpu_stream,
                             spherical_harmonics_bwd_inplace)
 from ...densification import update_densification_stats_offload_accum_grads
 from ...gsplat import (fully_fused_projection, isect_offset_encode, isect_tiles,
@@ -190,6 +190,7 @@ def _render_and_backward(gaussians, scene, camera, background, pipe_args, this_f
     rot = gaussians.rotation_activation(rot_raw)
     image, means2D, radiis, colors_detached, dirs = pipeline_forward_one_step_shs_inplace(
         opa, sca, rot, xyz, shs, camera, scene, gaussians, background, pipe_args)
+    image = apply_camera_exposure(image, camera)  # the camera's exposure transform, if it has one
     loss = torch_compiled_loss(image, camera.original_image, *camera_loss_mask(camera))
     loss.backward()
     if before_sh_backward is not None:
@@ -915,4 +916,5 @@ def clm_offload_eval_one_cam(camera, gaussians, background, scene, render_mode="
         res = pipeline_forward_one_step(opa, sca, rot, xyz, shs, camera, scene, gaussians,
                                         background, None, eval=True, render_mode=render_mode,
                                         return_alpha=return_alpha)
-    return res[0] if render_mode == "RGB" else (res[0],) + tuple(res[3:])
+        image = apply_camera_exposure(res[0], camera)  # a training camera is rendered as it was trained
+    return image if render_mode == "RGB" else (image,) + tuple(res[3:])

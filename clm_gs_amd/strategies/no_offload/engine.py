@@ -7,6 +7,7 @@ import torch
 
 from ... import utils
 from ...cameras import camera_loss_mask
+from ...clm_kernels import apply_camera_exposure
 from ...densification import update_densification_stats_baseline_accum_grads
 from ...gsplat import (fully_fused_projection, isect_offset_encode, isect_tiles,
                        rasterize_to_pixels, spherical_harmonics)
@@ -84,6 +85,7 @@ def baseline_accumGrads_impl(gaussians, scene, batched_cameras, background, scal
     for camera in batched_cameras:
         rendered_image, means2D, radiis, gaussian_ids = baseline_accumGrads_micro_step(
             means3D, opacities, scales, rotations, shs, sh_degree, camera, background)
+        rendered_image = apply_camera_exposure(rendered_image, camera)  # the camera's exposure transform, if it has one
         loss = torch_compiled_loss(rendered_image, camera.original_image, *camera_loss_mask(camera))
         loss.backward()
         losses.append(loss.detach())

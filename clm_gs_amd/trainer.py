@@ -18,6 +18,7 @@ import torch
 
 from . import dp, utils
 from .cameras import camera_loss_mask
+from .clm_kernels import apply_camera_exposure
 from .densification import gsplat_densification
 
 
@@ -202,9 +203,25 @@ def _warm_structural_ops(device, n=70_000):
     torch.cuda.synchronize()
 
 
+def build_exposure(train_cameras, iterations, device="cuda", lr_init=0.01, lr_final=0.001):
+    """`--exposure`: an exposure.ExposureModel with one row per TRAINING camera, attached to the cameras (test cameras and
+    novel views carry no exposure and are rendered as the model is).  Refused under camera-DP: every rank would step its
+    own copy of the table; the all-reduce of the table's gradient is a later change."""
+    if dp.world_size() > 1:
+        raise ValueError("--exposure is not supported with camera-DP (world_size {}): the exposure table is not reduced "
+                         "across ranks; train on one GPU or without --exposure".format(dp.world_size()))
+    from .exposure import ExposureModel
+    model = ExposureModel(len(train_cameras), device, lr_init=lr_init, lr_final=lr_final, max_steps=int(iterations))
+    model.attach(train_cameras)
+    return model
+
+
 def training(gaussians, scene, train_cameras, test_cameras, log_file, iterations=None,
-             test_iterations=(), background=None, shuffle_seed=0, phase_times=None):
+             test_iterations=(), background=None, shuffle_seed=0, phase_times=None, exposure=None):
     """Runs `iterations` images of training; returns the End2endTimer.
+    `exposure` (optional exposure.ExposureModel, attached to the training cameras): stepped at the scheduled learning
+    rate and zeroed after every batch, on the current stream -- every engine has joined its camera streams into it by
+    the time it returns.  A row's gradient is its camera's alone and is not divided by the batch size.
     `phase_times` (optional dict): host wall time per phase inside the end-to-end clock is accumulated into it
     ("engine" = enqueueing the batches, "densify" = gsplat_densification incl. the device work it waits for,
     "resort" = the Z-order re-sort after a densification, "log" = waiting for loss values, "final_sync"); a callable under
@@ -218,6 +235,8 @@ def training(gaussians, scene, train_cameras, test_cameras, log_file, iterations
     bsz = args.bsz
     ws, rk = dp.world_size(), dp.rank()
     gbsz = bsz * ws
+    if ws > 1 and exposure is not None:
+        raise ValueError("an exposure model cannot be trained under camera-DP (see build_exposure)")
     if ws > 1:
         assert clm_hbm_only(args), "camera-DP trains clm_offload with sh_residency='hbm'"
         if getattr(gaussians, "split_generator", None) is None:
@@ -242,7 +261,7 @@ def training(gaussians, scene, train_cameras, test_cameras, log_file, iterations
             img, _, _, _ = baseline_accumGrads_micro_step(
                 gaussians.get_xyz, gaussians.get_opacity, gaussians.get_scaling, gaussians.get_rotation,
                 gaussians.get_features, gaussians.active_sh_degree, cam, background, mode="test")
-            return img
+            return apply_camera_exposure(img, cam)  # a training camera is rendered as it was trained
     spatial = bool(getattr(args, "spatial_row_order", True)) and hasattr(gaussians, "spatial_sort") and not naive
     if spatial:
         gaussians.spatial_sort()  # rows along a Z-order curve: a camera's rows become contiguous runs
@@ -390,6 +409,9 @@ def training(gaussians, scene, train_cameras, test_cameras, log_file, iterations
             else:
                 gaussians.optimizer.step()
             gaussians.optimizer.zero_grad(set_to_none=True)
+        if exposure is not None:
+            exposure.step(iteration)
+            exposure.zero_grad()
         if not defer:
             torch.cuda.synchronize()
         if iter_hook is not None:
@@ -414,7 +436,9 @@ def train_from_colmap(source_path, model_path, strategy="clm_offload", iteration
     `point_cloud/iteration_N/point_cloud.ply` (scene/__init__.py:41-143, train.py:60-131 for the order of
     these steps).  `strategy`: clm_offload | no_offload | naive_offload; `arg_overrides`: any flag of
     `utils.default_args`.  `masks` / `alpha_mask`: per-pixel ignore masks of the loss (colmap_scene.load_colmap_scene).
-    Returns (gaussians, scene, timer)."""
+    `exposure=True` (with `exposure_lr_init` / `exposure_lr_final`): per-camera exposure compensation of the training
+    cameras (build_exposure); the table is written to `<model_path>/exposure.json` next to the ply and stays reachable as
+    `scene.exposure`.  Returns (gaussians, scene, timer)."""
     from .colmap_scene import load_colmap_scene
     from .strategies.clm_offload import GaussianModelCLMOffload
     from .strategies.naive_offload import GaussianModelNaiveOffload
@@ -426,6 +450,8 @@ def train_from_colmap(source_path, model_path, strategy="clm_offload", iteration
     if iterations is not None:
         args.iterations = int(iterations)
     utils.set_args(args)
+    if getattr(args, "exposure", False) and dp.world_size() > 1:
+        build_exposure([], args.iterations)  # raises: before anything is loaded
     scene = load_colmap_scene(source_path, images=images, eval=eval, resolution=resolution, device="cuda",
                               masks=masks, alpha_mask=alpha_mask)
     if scene.point_cloud is None:
@@ -439,12 +465,16 @@ def train_from_colmap(source_path, model_path, strategy="clm_offload", iteration
                  "naive_offload": GaussianModelNaiveOffload}[strategy](args.sh_degree)
     gaussians.create_from_pcd(scene.point_cloud, scene.cameras_extent)
     gaussians.training_setup(args)
+    scene.exposure = None
+    if getattr(args, "exposure", False):
+        scene.exposure = build_exposure(scene.train_cameras, args.iterations, "cuda",
+                                        float(args.exposure_lr_init), float(args.exposure_lr_final))
     os.makedirs(model_path, exist_ok=True)
     prev_log = utils.get_log_file()
     try:
         with open(os.path.join(model_path, "python_ws=1_rk=0.log"), "w") as log_file:
             timer = training(gaussians, scene, scene.train_cameras, scene.test_cameras, log_file,
-                             iterations=args.iterations, test_iterations=test_iterations)
+                             iterations=args.iterations, test_iterations=test_iterations, exposure=scene.exposure)
     finally:
         utils.set_log_file(prev_log)  # never leave a closed file as the process-wide log
     if save:
@@ -452,12 +482,13 @@ def train_from_colmap(source_path, model_path, strategy="clm_offload", iteration
             gaussians.flush_lazy_rows()  # ALL ranks (a collective under owner-computes / locality camera-DP) ...
         if dp.rank() == 0:               # ... then rank-0-only I/O (no collective left inside save_ply: nothing is dirty)
             gaussians.save_ply(os.path.join(model_path, "point_cloud", f"iteration_{args.iterations}", "point_cloud.ply"))
+            if scene.exposure is not None:  # {image_name: 3x4}, the INRIA code base's exposure.json
+                scene.exposure.save_json(os.path.join(model_path, "exposure.json"), scene.train_cameras)
     return gaussians, scene, timer
 
 
-if __name__ == "__main__":  # python -m clm_gs_amd.trainer -s <colmap dir> -m <output dir> [--clm_offload] ...
-    # (clm_gs_amd/__init__.py has applied runtime_env.single_gpu_runtime_defaults() before torch was imported: the
-    # hardware-queue default bench.py runs with is the trainer's too)
+def build_arg_parser():
+    """The command line of `python -m clm_gs_amd.trainer`."""
     import argparse
     ap = argparse.ArgumentParser(description="train a 3DGS model from a COLMAP directory (flag names of train.py)")
     ap.add_argument("-s", "--source_path", required=True)
@@ -483,10 +514,22 @@ if __name__ == "__main__":  # python -m clm_gs_amd.trainer -s <colmap dir> -m <o
                          "relative to the source path or absolute")
     ap.add_argument("--alpha_mask", action="store_true",
                     help="images with an alpha channel and no mask file: the loss ignores pixels with alpha 0")
-    a = ap.parse_args()
+    ap.add_argument("--exposure", action="store_true",
+                    help="per-camera exposure compensation: a learnable 3x4 affine colour transform per training image, "
+                         "written to <model_path>/exposure.json (single GPU)")
+    ap.add_argument("--exposure_lr_init", type=float, default=0.01)
+    ap.add_argument("--exposure_lr_final", type=float, default=0.001)
+    return ap
+
+
+if __name__ == "__main__":  # python -m clm_gs_amd.trainer -s <colmap dir> -m <output dir> [--clm_offload] ...
+    # (clm_gs_amd/__init__.py has applied runtime_env.single_gpu_runtime_defaults() before torch was imported: the
+    # hardware-queue default bench.py runs with is the trainer's too)
+    a = build_arg_parser().parse_args()
     strat = "no_offload" if a.no_offload else ("naive_offload" if a.naive_offload else "clm_offload")
     _, _, t = train_from_colmap(a.source_path, a.model_path, strategy=strat, iterations=a.iterations, eval=a.eval,
                                 resolution=a.resolution, images=a.images, test_iterations=tuple(a.test_iterations),
                                 bsz=a.bsz, sh_residency=a.sh_residency, sh_hbm_budget_gb=a.sh_hbm_budget_gb,
                                 absgrad=a.absgrad, rasterize_mode="antialiased" if a.antialiased else "classic",
-                                masks=a.masks, alpha_mask=a.alpha_mask)
+                                masks=a.masks, alpha_mask=a.alpha_mask, exposure=a.exposure,
+                                exposure_lr_init=a.exposure_lr_init, exposure_lr_final=a.exposure_lr_final)

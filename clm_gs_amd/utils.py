@@ -45,6 +45,9 @@ def default_args(**over):
         # sqrt(det(cov2d) / det(cov2d + eps2d I)) of the projection's low-pass filter; a property of the trained model (a
         # model trained with it must be rendered with it).  Read once per camera (antialiased() below)
         rasterize_mode="classic",
+        # this build: per-camera exposure compensation (exposure.ExposureModel; the INRIA code base's --exposure_lr_init /
+        # --exposure_lr_final): a learnable 3x4 affine colour transform per TRAINING image, between the rasterizer and the loss
+        exposure=False, exposure_lr_init=0.01, exposure_lr_final=0.001,
         lr_scale_mode="sqrt", bsz=1, exact_filter=True, log_cpu_adam_trailing_overhead=False,
         # Debug
         stop_update_param=False, drop_initial_3dgs_p=0.0,

@@ -435,6 +435,26 @@ int clmgs_l1_ssim_loss_masked_bwd(void* stream, int H, int W, const float* img, 
                                   const float* m2, const float* m3, float* v_img,
                                   const uint8_t* mask);
 
+/* ---- per-camera exposure compensation (csrc/exposure.hip; the convention of the INRIA 3DGS exposure.json)
+ * E_dev: DEVICE pointer to float32 [3][4], row-major.  x, y, g, v_x are [3,H,W] VIEWS given by their element strides
+ * (c, y, x), like img of the loss entries: the rasterizer's [H,W,3] buffer and a planar image alike.
+ *   fwd:  y[c] = x[0] E[0][c] + x[1] E[1][c] + x[2] E[2][c] + E[c][3]            (y must not alias x)
+ *   bwd:  v_x[k] = E[k][0] g[0] + E[k][1] g[1] + E[k][2] g[2], g = dL/dy; v_x MAY BE g itself (same pointer and
+ *         strides: in place).  Each workgroup STORES one row of 12 floats, laid out like E, into
+ *         partials[clmgs_exposure_partials_rows(H, W)][12] (every row is written; nothing to zero):
+ *         their column sums are dL/dE[k][c] = sum_p x[k] g[c] (c < 3) and dL/dE[c][3] = sum_p g[c].
+ *   grad_finish: one wave sums the `rows` rows of partials in a fixed order and ADDS the 12 sums into grad12.
+ * No float atomics: the same inputs give the same bits on every run. */
+int clmgs_exposure_partials_rows(int H, int W);
+int clmgs_exposure_fwd(void* stream, int H, int W, const float* x, int64_t stride_c, int64_t stride_y,
+                       int64_t stride_x, const float* E_dev, float* y, int64_t ystride_c, int64_t ystride_y,
+                       int64_t ystride_x);
+int clmgs_exposure_bwd(void* stream, int H, int W, const float* x, int64_t stride_c, int64_t stride_y,
+                       int64_t stride_x, const float* E_dev, const float* g, int64_t gstride_c,
+                       int64_t gstride_y, int64_t gstride_x, float* v_x, int64_t vstride_c, int64_t vstride_y,
+                       int64_t vstride_x, float* partials);
+int clmgs_exposure_grad_finish(void* stream, int rows, const float* partials, float* grad12);
+
 /* ---- clm_kernels row movers  (clm_offload/engine.py:499-505, 622-636, 789-802, 815-822)
  * dst/src may be device memory or pinned (mapped) host memory.
  * gather:      dst[dst_idx ? dst_idx[i] : i] = src[src_idx ? src_idx[i] : i]
