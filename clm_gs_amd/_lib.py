@@ -52,6 +52,10 @@ SIGNATURES = {
     "clmgs_rasterize_bwd": (_i, [_vp, _i, _i, _i64, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "clmgs_rasterize4_fwd": (_i, [_vp, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "clmgs_rasterize4_bwd": (_i, [_vp, _i, _i, _i64, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # four channels on the slot route and in the device-count forms: the argument lists of the 3-channel entries
+    "clmgs_rasterize4_slot_bwd": (_i, [_vp, _i, _i, _i64, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "clmgs_rasterize4_fwd_dev": (_i, [_vp, _i, _i, _i64, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "clmgs_rasterize4_bwd_dev": (_i, [_vp, _i, _i, _i64, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "clmgs_preprocess_fwd": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "clmgs_preprocess_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i]),
     # gsplat's absgrad: the plain entries' arguments (+ one trailing optional output where the plain entry unpacks)
@@ -76,6 +80,11 @@ SIGNATURES = {
     "clmgs_exposure_fwd": (_i, [_vp, _i, _i, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i64]),
     "clmgs_exposure_bwd": (_i, [_vp, _i, _i, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp]),
     "clmgs_exposure_grad_finish": (_i, [_vp, _i, _vp, _vp]),
+    "clmgs_invdepth_partials_rows": (_i, [_i, _i]),
+    "clmgs_invdepth_pack": (_i, [_vp, _i, _vp, _vp, _vp]),
+    "clmgs_invdepth_l1_fwd_bwd": (_i, [_vp, _i, _i, _vp, _i64, _i64, _vp, _f, _f, _vp, _f, _vp, _i64, _i64, _vp]),
+    "clmgs_invdepth_finish": (_i, [_vp, _i, _vp, _vp]),
+    "clmgs_invdepth_rows_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
     "clmgs_rows_gather": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _i]),
     "clmgs_rows_scatter_add": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _i]),
     "clmgs_scatter_to_bit": (_i, [_vp, _vp, _i, _vp, _i64, _i]),
@@ -146,7 +155,7 @@ class _Namespace:
     pass
 
 
-_NO_STREAM = {"clmgs_version", "clmgs_loss_slots", "clmgs_exposure_partials_rows", "clmgs_small_deferred_kmax", "clmgs_isect3_front_temp_bytes",
+_NO_STREAM = {"clmgs_version", "clmgs_loss_slots", "clmgs_exposure_partials_rows", "clmgs_invdepth_partials_rows", "clmgs_small_deferred_kmax", "clmgs_isect3_front_temp_bytes",
               "clmgs_isect3_bin_temp_bytes", "clmgs_last_error", "clmgs_isect_count_temp_bytes",
               "clmgs_isect_sort_temp_bytes", "clmgs_host_groups_temp_bytes", "clmgs_isect2_order_temp_bytes", "clmgs_isect2_sort_temp_bytes", "clmgs_visibility_select_temp_bytes", "clmgs_rasterize_pack_bytes", "clmgs_rasterize_partials_bytes", "clmgs_host_adam_rows", "clmgs_host_pool_start", "clmgs_host_usable_cpus", "clmgs_host_rows_prepare", "clmgs_tsp_tour",
               "clmgs_pinned_alloc", "clmgs_pinned_free", "clmgs_device_errors"}

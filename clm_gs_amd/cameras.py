@@ -3,7 +3,8 @@ train.py:278-312): FoVx, FoVy, world_view_transform (row-vector convention,
 i.e. the TRANSPOSE of the 4x4 world->camera matrix), K, camtoworlds,
 original_image (uint8 [3,H,W] on the GPU), image_name, create_k_on_gpu(); plus loss_mask (uint8 [H,W] or None)
 and loss_mask_count, the per-pixel ignore mask of the training loss.  A training camera may also carry `exposure` /
-`exposure_grad`, float32 [3,4] views of its rows in an exposure.ExposureModel (camera_exposure below)."""
+`exposure_grad`, float32 [3,4] views of its rows in an exposure.ExposureModel (camera_exposure below), and `invdepth`
+(uint16 [H,W]) with `invdepth_scale` / `invdepth_offset`, its monocular inverse-depth prior (camera_invdepth below)."""
 import math
 
 import numpy as np
@@ -33,9 +34,20 @@ def camera_exposure(camera):
     return row, getattr(camera, "exposure_grad", None)
 
 
+def camera_invdepth(camera):
+    """(raw, scale, offset) of a camera's inverse-depth prior -- raw uint16 [H,W] on the device, two host floats; the
+    prior is raw / 65536 * scale + offset, the INRIA 3DGS 16-bit PNG + depth_params.json convention -- or None: a camera
+    without the attribute, or with None, is rendered with three channels and trained without the depth term."""
+    raw = getattr(camera, "invdepth", None)
+    if raw is None:
+        return None
+    return raw, float(getattr(camera, "invdepth_scale", 1.0)), float(getattr(camera, "invdepth_offset", 0.0))
+
+
 class Camera:
     def __init__(self, uid, world_to_cam, FoVx, FoVy, width, height, image_u8=None,
-                 image_name=None, device="cuda", loss_mask=None):
+                 image_name=None, device="cuda", loss_mask=None, invdepth=None, invdepth_scale=1.0,
+                 invdepth_offset=0.0):
         self.uid = uid
         self.FoVx, self.FoVy = float(FoVx), float(FoVy)
         self.image_width, self.image_height = int(width), int(height)
@@ -58,6 +70,16 @@ class Camera:
                                  f"got {m.dtype} {tuple(m.shape)}")
             self.loss_mask_count = int(torch.count_nonzero(m))
             self.loss_mask = m.to(device).contiguous()
+        # monocular inverse-depth prior of the depth regularisation: uint16 [H,W], prior = raw / 65536 * scale + offset
+        self.invdepth, self.invdepth_scale, self.invdepth_offset = None, float(invdepth_scale), float(invdepth_offset)
+        if invdepth is not None:
+            d = torch.as_tensor(invdepth)
+            if d.dtype != torch.uint16 or tuple(d.shape) != (self.image_height, self.image_width):
+                raise ValueError(f"invdepth must be uint16 [{self.image_height}, {self.image_width}], "
+                                 f"got {d.dtype} {tuple(d.shape)}")
+            if not (math.isfinite(self.invdepth_scale) and math.isfinite(self.invdepth_offset)):
+                raise ValueError(f"invdepth_scale / invdepth_offset must be finite, got {invdepth_scale} {invdepth_offset}")
+            self.invdepth = d.to(device).contiguous()
         self.K = self.create_k_on_gpu(device)
         c2w = torch.inverse(w2c)
         self.camtoworlds = c2w[None].to(device)  # [1,4,4] as train.py:293-301

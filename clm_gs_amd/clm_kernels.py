@@ -150,6 +150,62 @@ def fused_l1_ssim_loss(image, gt_u8, lambda_dssim=0.2, mask=None, mask_count=Non
     return _FusedL1SSIMLossMasked.apply(image, gt_u8, lambda_dssim, mask, int(mask_count))
 
 
+# ------------------------------------------------------- depth regularisation
+class _InvDepthL1(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, I, raw, scale, offset, weight, mask):
+        L = _lib.lib()
+        assert I.dim() == 2 and I.dtype == F32 and I.is_cuda
+        H, W = I.shape
+        raw = raw.contiguous()
+        assert raw.dtype == torch.uint16 and tuple(raw.shape) == (H, W) and raw.device == I.device
+        if mask is not None:
+            mask = mask.contiguous()
+            assert mask.dtype == U8 and tuple(mask.shape) == (H, W) and mask.device == I.device
+        rows = int(L.clmgs_invdepth_partials_rows(H, W))
+        partials = torch.empty((rows,), dtype=F32, device=I.device)
+        total = torch.empty((1,), dtype=F32, device=I.device)
+        v_I = torch.empty((H, W), dtype=F32, device=I.device)
+        check(L.clmgs_invdepth_l1_fwd_bwd(stream(), H, W, ctypes.c_void_p(I.data_ptr()), *I.stride(),
+                                          dptr(raw, torch.uint16), float(scale), float(offset), dptr(mask, U8, True),
+                                          float(weight), dptr(v_I), *v_I.stride(), dptr(partials)))
+        check(L.clmgs_invdepth_finish(stream(), rows, dptr(partials), dptr(total)))
+        ctx.save_for_backward(v_I)
+        return total[0] * (float(weight) / float(H * W))
+
+    @staticmethod
+    def backward(ctx, v):
+        (v_I,) = ctx.saved_tensors
+        return v_I * v, None, None, None, None, None
+
+
+def invdepth_l1_loss(I, raw, scale, offset, weight, mask=None):
+    """The depth term of a camera: weight * sum_p m_p |I_p - prior_p| / (H*W) with prior = raw / 65536 * scale + offset.
+    I [H,W] float32 (any strides, e.g. channel 3 of the rasterizer's [1,H,W,4] output: the rendered inverse depth),
+    raw uint16 [H,W], mask uint8 [H,W] (0 = ignored) or None; differentiable in I, d|x|/dx = 0 at 0.  One kernel computes
+    the partial sums and the cotangent (csrc/invdepth.hip; DESIGN.md section 3, "Depth regularisation")."""
+    return _InvDepthL1.apply(I, raw, float(scale), float(offset), float(weight), mask)
+
+
+def camera_depth_term(inv_depth, camera):
+    """invdepth_l1_loss of a rendered inverse-depth map [H,W] against the camera's prior (cameras.camera_invdepth), with
+    the camera's loss mask and the current iteration's weight.  What the op-by-op engines add to the camera's loss."""
+    from .cameras import camera_invdepth, camera_loss_mask
+    raw, scale, offset = camera_invdepth(camera)
+    return invdepth_l1_loss(inv_depth, raw, scale, offset, utils.depth_l1_weight(), camera_loss_mask(camera)[0])
+
+
+def check_depth_prior_args(camera):
+    """A camera with an inverse-depth prior under absgrad: refused before anything runs (absgrad blends three channels
+    only).  -> whether the camera has a prior."""
+    if getattr(camera, "invdepth", None) is None:
+        return False
+    if bool(getattr(utils.get_args(), "absgrad", False)):
+        raise ValueError("absgrad with an inverse-depth prior is not built (absgrad blends three channels only): train "
+                         "without absgrad or without depth priors")
+    return True
+
+
 # ------------------------------------------------------- exposure compensation
 def _view_ptr(t):
     return ctypes.c_void_p(t.data_ptr())

@@ -213,6 +213,45 @@ def _decode_mask(path, size_wh):
         return torch.from_numpy(np.array(im, dtype=np.uint8))
 
 
+def _decode_invdepth(path, size_wh):
+    """A 16-bit grey PNG -> uint16 [H,W] (the raw inverse-depth prior: prior = raw / 65536 * scale + offset).  A map of
+    another size than the training image (`resolution`) is resampled to it: bilinear on float32, then rounded back to
+    uint16."""
+    from PIL import Image
+    with Image.open(path) as im:
+        a = np.array(im)
+    if a.ndim != 2 or a.dtype != np.uint16:
+        raise ValueError(f"depth map {path} must be a 16-bit grey PNG, got {a.dtype} {a.shape}")
+    if size_wh is not None and (a.shape[1], a.shape[0]) != tuple(size_wh):
+        f = Image.fromarray(a.astype(np.float32)).resize(tuple(size_wh), Image.BILINEAR)
+        a = np.clip(np.rint(np.array(f, dtype=np.float32)), 0, 65535).astype(np.uint16)
+    return torch.from_numpy(np.ascontiguousarray(a))
+
+
+def read_depth_params(path):
+    """`depth_params.json` ({NAME: {"scale": s, "offset": o}}) -> ({NAME: (scale, offset)}, median of the positive
+    scales or None); a missing file gives ({}, None)."""
+    import json
+    if not os.path.exists(path):
+        return {}, None
+    with open(path) as f:
+        raw = json.load(f)
+    params = {k: (float(v["scale"]), float(v["offset"])) for k, v in raw.items()}
+    pos = [s for s, _ in params.values() if s > 0]
+    return params, (float(np.median(pos)) if pos else None)
+
+
+def reliable_depth_params(params, med_scale, name):
+    """(scale, offset) of image `name`, or None by the INRIA code base's reliability rule: no json entry, scale <= 0, or a
+    scale outside [0.2, 5] x the median scale."""
+    if name not in params or med_scale is None:
+        return None
+    scale, offset = params[name]
+    if scale <= 0 or scale < 0.2 * med_scale or scale > 5.0 * med_scale:
+        return None
+    return scale, offset
+
+
 def read_model(sparse_dir):
     """(cameras, images, (xyz, rgb)) from a `sparse/0` directory: binary files first, text as the fallback."""
     def pick(stem, rb, rt):
@@ -232,7 +271,7 @@ def read_model(sparse_dir):
 
 
 def load_colmap_scene(source_path, images="images", eval=False, llffhold=10, resolution=1, device="cuda",
-                      load_images=True, masks=None, alpha_mask=False):
+                      load_images=True, masks=None, alpha_mask=False, depths=None):
     """-> namespace(train_cameras, test_cameras, point_cloud(points, colors in [0,1]) or None,
     cameras_extent, nerf_normalization).  `cameras_extent` is what the trainer passes as
     `spatial_lr_scale` and what densification compares scales with (train.py:118-131).
@@ -240,7 +279,13 @@ def load_colmap_scene(source_path, images="images", eval=False, llffhold=10, res
     absolute) holding `NAME.EXT.png` (COLMAP's convention) or `NAME.png` for image `NAME.EXT`, read as 8-bit grey,
     non-zero = counted; with `resolution` it is resized (nearest neighbour) to the decoded image's size, a mask of
     another size raises, an image without a mask file stays unmasked.  `alpha_mask`: an image with transparency (an
-    alpha band, or a PNG `tRNS` entry) and without a mask file takes `alpha > 0`.  Without both, nothing changes."""
+    alpha band, or a PNG `tRNS` entry) and without a mask file takes `alpha > 0`.  Without both, nothing changes.
+    Inverse-depth priors of the depth regularisation (Camera.invdepth, TRAINING cameras only): `depths` is a directory
+    (relative to `source_path`, or absolute) of 16-bit grey PNGs `NAME.png` for image `NAME.EXT`, with
+    `sparse/0/depth_params.json` = {NAME: {"scale": s, "offset": o}} (prior = raw / 65536 * scale + offset); a map of
+    another size than the training image is resampled to it (bilinear on float32, rounded back to uint16).  An image gets
+    no prior when its PNG or its json entry is missing, its scale is <= 0, or its scale lies outside [0.2, 5] x the median
+    scale (reliable_depth_params)."""
     cams, imgs, (xyz, rgb) = read_model(os.path.join(source_path, "sparse", "0"))
     folder = os.path.join(source_path, images or "images")
     recs = []
@@ -267,7 +312,18 @@ def load_colmap_scene(source_path, images="images", eval=False, llffhold=10, res
         if not os.path.isdir(mask_dir):
             raise FileNotFoundError(f"mask directory {mask_dir} does not exist")
 
-    def build(r):
+    depth_dir, depth_params, med_scale = None, {}, None
+    if depths:
+        depth_dir = depths if os.path.isabs(depths) else os.path.join(source_path, depths)
+        if not os.path.isdir(depth_dir):
+            raise FileNotFoundError(f"depth directory {depth_dir} does not exist")
+        params_path = os.path.join(source_path, "sparse", "0", "depth_params.json")
+        if not os.path.exists(params_path):  # a depth directory without its scales: stop, as the INRIA code base does
+            raise FileNotFoundError(f"depths={depths!r} was asked for but {params_path} does not exist (the per-image "
+                                    "scale and offset of the inverse-depth maps)")
+        depth_params, med_scale = read_depth_params(params_path)
+
+    def build(r, training=True):
         img, mask = None, None
         w, h = r.width, r.height
         if load_images:
@@ -287,13 +343,27 @@ def load_colmap_scene(source_path, images="images", eval=False, llffhold=10, res
                                      f"image {r.path} is {w}x{h}")
             elif alpha is not None:
                 mask = (alpha > 0).to(torch.uint8)
+        prior = {}
+        if depth_dir and training:
+            so = reliable_depth_params(depth_params, med_scale, r.name)
+            dpath = os.path.join(depth_dir, r.name + ".png")
+            if so is not None and os.path.exists(dpath):
+                prior = dict(invdepth=_decode_invdepth(dpath, (w, h)), invdepth_scale=so[0], invdepth_offset=so[1])
         return Camera(r.uid, torch.from_numpy(r.w2c).float(), r.fovx, r.fovy, w, h, image_u8=img,
-                      image_name=r.name, device=device, loss_mask=mask)
+                      image_name=r.name, device=device, loss_mask=mask, **prior)
 
     pcd = None
     if xyz is not None and len(xyz):
         pcd = SimpleNamespace(points=xyz.astype(np.float32), colors=rgb.astype(np.float32) / 255.0,
                               normals=np.zeros_like(xyz, dtype=np.float32))
-    return SimpleNamespace(train_cameras=[build(r) for r in train], test_cameras=[build(r) for r in test],
+    train_cameras = [build(r) for r in train]
+    if depth_dir:  # said aloud: a run whose priors were all dropped must not look like a run with priors
+        n_prior = sum(c.invdepth is not None for c in train_cameras)
+        print(f"depth priors: {n_prior} of {len(train_cameras)} training cameras ({depth_dir}; an image without a PNG, "
+              "without a depth_params.json entry or with an unreliable scale gets none)")
+        if n_prior == 0:
+            raise ValueError(f"depths={depths!r}: no training camera received an inverse-depth prior (no PNG matches, or "
+                             "every scale of depth_params.json is unreliable)")
+    return SimpleNamespace(train_cameras=train_cameras, test_cameras=[build(r, False) for r in test],
                            point_cloud=pcd, cameras_extent=radius,
                            nerf_normalization={"translate": translate, "radius": radius})

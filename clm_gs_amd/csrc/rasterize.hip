@@ -23,8 +23,9 @@
 //   * both tile kernels are templates on the number of blended channels: 3, or 4 for gsplat's depth modes
 //     (rasterize_to_pixels with colors[..., 4]: clmgs_rasterize4_fwd / _bwd).  The fourth channel rides in the record's
 //     spare word, takes one more accumulator per pixel in the forward and a tenth wave-wide sum (a second DPP chain) and
-//     a tenth atomic in the backward's atomic route; the 3-channel instantiations are, instruction for instruction, the
-//     kernels they were without the parameter ("Depth");
+//     a tenth atomic (atomic route) or word 9 of the stored line (slot route) in the backward; the 3-channel
+//     instantiations are, instruction for instruction, the kernels they were without the parameter (DESIGN.md section 3,
+//     "Depth");
 //   * the backward is also a template on ABS, gsplat's absgrad (clmgs_rasterize_abs_bwd / _abs_bwd_dev): two more per-lane
 //     accumulators of the per-pixel |dL_p/dmean2d|, two more DPP chains per entry, words 10 and 11 of the 64 B line; the
 //     plain instantiations are, instruction for instruction, the kernels they were ("Absgrad");
@@ -389,7 +390,8 @@ struct TileLdsBwd : TileLds<NCH> {
 // (slot = its emit index, see isect2_emit_kernel); the tile's wave STORES the reduced sums there
 // (zeros for culled / unreached entries, so every line is written exactly once per launch) and
 // raster_partials_sum_kernel adds each row's contiguous range.
-// NCH = 4: the atomic route only (a tenth sum g_d = sum fac * vd, a tenth atomic at word 9 of the gradient line).
+// NCH = 4, both routes: a tenth sum g_d = sum fac * vd, at word 9 of the line: a tenth atomic, or the slot route's stored
+// line  x y ca cb | cc r g b | o d - -  (zero lines stay zero).
 // ABS (NCH = 3, both routes): gsplat's absgrad.  The kernel reduces MOMENTS of w = v_sigma and forms g_x = ca Sx + cb Sy
 // once per entry, so the per-pixel |dL_p/dmean2d| = |w (ca dx + cb dy)|, |w (cb dx + cc dy)| is new arithmetic in the pass:
 // two FMA pairs whose results enter their accumulators through the |.| input modifier, on the pre-scaled conic
@@ -406,7 +408,7 @@ rasterize_bwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
                      const float* __restrict__ v_render_alphas, float* __restrict__ packed_grad,
                      const int32_t* __restrict__ emit_slot, float4* __restrict__ partials,
                      const int64_t* __restrict__ n_dev) {
-  static_assert(NCH == 3 || (NCH == 4 && !PART), "4 channels: atomic route only");
+  static_assert(NCH == 3 || NCH == 4, "3 or 4 blended channels");
   static_assert(!ABS || NCH == 3, "absgrad: three channels only (word 9 stays the fourth channel's)");
   __shared__ TileLdsBwd<NCH> sm;
   if (n_dev) n_isects = min(n_isects, *n_dev);
@@ -610,6 +612,7 @@ rasterize_bwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
           r0 = sm.grad_xy_conic(lane, g_cc);
           r1 = make_float4(g_cc, m1.y, m1.z, m1.w);
           r2 = make_float4(a[2].x, 0.f, 0.f, 0.f);
+          if constexpr (NCH == 4) r2.y = a[2].y;                 // x y ca cb | cc r g b | o d
           if constexpr (ABS) { r2.z = a[2].z; r2.w = a[2].w; }  // x y ca cb | cc r g b | o - ax ay
         }
         float4* dst = partials + PART_F4 * (size_t)sm.id[lane];
@@ -637,8 +640,8 @@ rasterize_bwd_kernel(int C, int N, int64_t n_isects, const float4* __restrict__ 
 // Per-row sum of the tile partials (API surface: the engine path folds this sum into
 // clmgs_preprocess_bwd).  Row i owns the contiguous slot range [row_cum[i-1], row_cum[i]); ranges and
 // gradient lines are both walked sequentially; fixed order (ascending slot).
-// partials line = gradient line: x y ca cb | cc r g b | o - - - | -   (ABS: o - ax ay, summed in the same order)
-template <bool ABS = false>
+// partials line = gradient line: x y ca cb | cc r g b | o - - - | -   (ABS: o - ax ay, D4: o d, summed in the same order)
+template <bool ABS = false, bool D4 = false>
 __global__ void __launch_bounds__(256)
 raster_partials_sum_kernel(int64_t n_rows, const int64_t* __restrict__ row_cum,
                            const float4* __restrict__ partials, float4* __restrict__ packed_grad) {
@@ -673,6 +676,11 @@ raster_partials_sum_kernel(int64_t n_rows, const int64_t* __restrict__ row_cum,
       float ax = 0.f, ay = 0.f;
       for (int t = 0; t < cnt; ++t) { const float4 c = src[PART_F4 * t + 2]; ax += c.z; ay += c.w; }
       *reinterpret_cast<float2*>(reinterpret_cast<float*>(dst) + 10) = make_float2(ax, ay);
+    }
+    if constexpr (D4) {  // the fourth channel's word, likewise in a pass of its own
+      float d = 0.f;
+      for (int t = 0; t < cnt; ++t) d += src[PART_F4 * t + 2].y;
+      reinterpret_cast<float*>(dst)[9] = d;
     }
   }
 }
@@ -756,6 +764,19 @@ extern "C" int clmgs_rasterize_fwd_dev(void* stream, int C, int N, int64_t capac
                             render_alphas, last_ids, n_isects_dev);
 }
 
+// Four channels, device-count form: the records are the caller's packed [N,16] lines with the fourth colour in word 9
+// (clmgs_invdepth_pack writes it into the lines clmgs_preprocess_fwd left); render_colors rows of 4.
+extern "C" int clmgs_rasterize4_fwd_dev(void* stream, int C, int N, int64_t capacity, const int64_t* n_isects_dev,
+                                        const float* backgrounds, int width, int height, int tile_size,
+                                        int tile_width, int tile_height, const int32_t* offsets,
+                                        const int32_t* flatten_ids, void* packed, float* render_colors,
+                                        float* render_alphas, int32_t* last_ids) {
+  CLMGS_CHECK_ARG(n_isects_dev && capacity > 0);
+  return rasterize_fwd_impl(4, stream, C, N, capacity, nullptr, nullptr, nullptr, nullptr, backgrounds, width, height,
+                            tile_size, tile_width, tile_height, offsets, flatten_ids, packed, render_colors,
+                            render_alphas, last_ids, n_isects_dev);
+}
+
 static int rasterize_bwd_impl(int nch, void* stream, int C, int N, int64_t n_isects, const void* packed,
                               const float* backgrounds, int width, int height, int tile_size,
                               int tile_width, int tile_height, const int32_t* offsets,
@@ -765,15 +786,16 @@ static int rasterize_bwd_impl(int nch, void* stream, int C, int N, int64_t n_ise
                               float* v_means2d, float* v_conics, float* v_colors,
                               float* v_opacities, const int32_t* emit_slot,
                               const int64_t* row_cum, void* partials, const int64_t* n_dev,
-                              bool abs = false, float* v_means2d_abs = nullptr) {
+                              bool abs = false, float* v_means2d_abs = nullptr, bool slot4 = false) {
   if (abs && nch != 3) {  // before anything is written
     clmgs::set_error("clmgs_rasterize_abs_bwd: absgrad blends three channels only (word 9 of the gradient line is the "
                      "fourth channel's, words 10 and 11 the absgrad pair's)");
     return CLMGS_EINVAL;
   }
-  if (nch == 4 && (partials || emit_slot)) {  // before anything is written
-    clmgs::set_error("clmgs_rasterize4_bwd: the slot route (emit_slot / partials) blends three channels only; "
-                     "pass emit_slot = partials = NULL for the atomic route");
+  if (nch == 4 && !slot4 && (partials || emit_slot)) {  // before anything is written
+    clmgs::set_error("clmgs_rasterize4_bwd: the slot route (emit_slot / partials) of four channels is "
+                     "clmgs_rasterize4_slot_bwd / clmgs_rasterize4_bwd_dev; pass emit_slot = partials = NULL for the "
+                     "atomic route");
     return CLMGS_EINVAL;
   }
   CLMGS_CHECK_ARG(tile_size == TILE);
@@ -796,15 +818,16 @@ static int rasterize_bwd_impl(int nch, void* stream, int C, int N, int64_t n_ise
     CLMGS_CHECK_ARG(packed && offsets && flatten_ids && render_alphas && last_ids && v_render_colors);
     const int n_blocks = C * tile_width * tile_height;
     const auto kernel = abs ? (part ? rasterize_bwd_kernel<true, 3, true> : rasterize_bwd_kernel<false, 3, true>)
-                        : part ? rasterize_bwd_kernel<true, 3>
+                        : part ? (nch == 4 ? rasterize_bwd_kernel<true, 4> : rasterize_bwd_kernel<true, 3>)
                                : nch == 4 ? rasterize_bwd_kernel<false, 4> : rasterize_bwd_kernel<false, 3>;
     hipLaunchKernelGGL(kernel, dim3(n_blocks), dim3(64), 0, s, C, N, n_isects, (const float4*)packed, backgrounds, width,
                        height, tile_width, tile_height, offsets, flatten_ids, render_alphas, last_ids, v_render_colors,
                        v_render_alphas, (float*)packed_grad, emit_slot, (float4*)partials, n_dev);
     CLMGS_LAUNCH_CHECK();
     if (part && packed_grad) {
-      hipLaunchKernelGGL(abs ? raster_partials_sum_kernel<true> : raster_partials_sum_kernel<false>,
-                         dim3(min(ceil_div(CN, 256), 256 * 16)), dim3(256),
+      const auto sum_kernel = abs ? raster_partials_sum_kernel<true>
+                              : nch == 4 ? raster_partials_sum_kernel<false, true> : raster_partials_sum_kernel<false>;
+      hipLaunchKernelGGL(sum_kernel, dim3(min(ceil_div(CN, 256), 256 * 16)), dim3(256),
                          0, s, CN, row_cum, (const float4*)partials, (float4*)packed_grad);
       CLMGS_LAUNCH_CHECK();
     }
@@ -836,7 +859,8 @@ extern "C" int clmgs_rasterize_bwd(void* stream, int C, int N, int64_t n_isects,
                             row_cum, partials, nullptr);
 }
 
-// Four blended channels, atomic route only: emit_slot / partials != NULL is refused before anything is written.
+// Four blended channels, atomic route only: emit_slot / partials != NULL is refused before anything is written (the slot
+// route of four channels is clmgs_rasterize4_slot_bwd below).
 extern "C" int clmgs_rasterize4_bwd(void* stream, int C, int N, int64_t n_isects, const void* packed,
                                     const float* backgrounds, int width, int height, int tile_size,
                                     int tile_width, int tile_height, const int32_t* offsets,
@@ -850,6 +874,40 @@ extern "C" int clmgs_rasterize4_bwd(void* stream, int C, int N, int64_t n_isects
                             tile_height, offsets, flatten_ids, render_alphas, last_ids, v_render_colors,
                             v_render_alphas, packed_grad, v_means2d, v_conics, v_colors, v_opacities, emit_slot,
                             row_cum, partials, nullptr);
+}
+
+// Four blended channels, slot route: clmgs_rasterize_bwd's contract with emit_slot / partials (partials is required).
+// The stored line is  x y ca cb | cc r g b | o d - -;  with packed_grad + row_cum the per-row sum carries word 9 too, and
+// the unpack writes v_colors rows of 4.
+extern "C" int clmgs_rasterize4_slot_bwd(void* stream, int C, int N, int64_t n_isects, const void* packed,
+                                         const float* backgrounds, int width, int height, int tile_size,
+                                         int tile_width, int tile_height, const int32_t* offsets,
+                                         const int32_t* flatten_ids, const float* render_alphas,
+                                         const int32_t* last_ids, const float* v_render_colors,
+                                         const float* v_render_alphas, void* packed_grad,
+                                         float* v_means2d, float* v_conics, float* v_colors,
+                                         float* v_opacities, const int32_t* emit_slot,
+                                         const int64_t* row_cum, void* partials) {
+  CLMGS_CHECK_ARG(partials);
+  return rasterize_bwd_impl(4, stream, C, N, n_isects, packed, backgrounds, width, height, tile_size, tile_width,
+                            tile_height, offsets, flatten_ids, render_alphas, last_ids, v_render_colors,
+                            v_render_alphas, packed_grad, v_means2d, v_conics, v_colors, v_opacities, emit_slot,
+                            row_cum, partials, nullptr, false, nullptr, true);
+}
+
+// ... and its device-count form (clmgs_rasterize_bwd_dev's contract; word 9 of every line is the fourth channel's).
+extern "C" int clmgs_rasterize4_bwd_dev(void* stream, int C, int N, int64_t capacity, const int64_t* n_isects_dev,
+                                        const void* packed, const float* backgrounds, int width, int height,
+                                        int tile_size, int tile_width, int tile_height, const int32_t* offsets,
+                                        const int32_t* flatten_ids, const float* render_alphas,
+                                        const int32_t* last_ids, const float* v_render_colors,
+                                        const float* v_render_alphas, const int32_t* emit_slot,
+                                        const int64_t* row_cum, void* partials) {
+  CLMGS_CHECK_ARG(n_isects_dev && capacity > 0 && emit_slot && partials);
+  return rasterize_bwd_impl(4, stream, C, N, capacity, packed, backgrounds, width, height, tile_size, tile_width,
+                            tile_height, offsets, flatten_ids, render_alphas, last_ids, v_render_colors,
+                            v_render_alphas, nullptr, nullptr, nullptr, nullptr, nullptr, emit_slot, row_cum,
+                            partials, n_isects_dev, false, nullptr, true);
 }
 
 // Device-count form of the slot mode (one 64 B partial line per intersection, summed by the caller):

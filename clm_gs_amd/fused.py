@@ -13,12 +13,12 @@ import torch
 
 from . import _lib, utils
 from ._lib import check, dptr
-from .cameras import camera_exposure, camera_loss_mask
-from .clm_kernels import masked_loss_value
+from .cameras import camera_exposure, camera_invdepth, camera_loss_mask
+from .clm_kernels import check_depth_prior_args, masked_loss_value
 from .gsplat import (_record_counts, bucket_size, empty_bucketed, isect2_begin, isect2_counts, isect2_finish, isect3_begin,
                      isect3_finish)
 
-F32, I32, U8 = torch.float32, torch.int32, torch.uint8
+F32, I32, U8, U16 = torch.float32, torch.int32, torch.uint8, torch.uint16
 TILE = 16
 
 
@@ -63,7 +63,8 @@ class _CameraPass:
                  "packed", "fids", "offsets", "emit_slot", "row_cum", "out", "alphas", "last_ids",
                  "bg", "v_out", "maps", "loss", "ev_loss", "streams", "deg", "aux", "loss_partials",
                  "lambda_dssim", "gt_u8", "background", "isect", "sh_index", "means2d", "n_dev", "antialiased",
-                 "loss_mask", "mask_count", "exposure", "exposure_grad", "exp_partials")
+                 "loss_mask", "mask_count", "exposure", "exposure_grad", "exp_partials",
+                 "invdepth", "depth_weight", "depths", "id_partials", "id_term")
 
 
 def _sptr(torch_stream):
@@ -153,6 +154,16 @@ def camera_front(gaussians, camera, this_filter, sh_rows, sh_by_filter, backgrou
     p.loss_mask, p.mask_count = camera_loss_mask(camera)  # a mask on the camera selects the masked loss kernels
     # an exposure row on the camera puts the affine colour transform between the tile kernel and the loss
     (p.exposure, p.exposure_grad), p.exp_partials = camera_exposure(camera), None
+    # an inverse-depth prior on the camera (depth regularisation): the camera is rendered with a fourth channel, the
+    # inverse depth, and trained with the L1 term; without one, not one launch differs.  Refused with absgrad, here,
+    # before anything is enqueued.
+    p.invdepth = camera_invdepth(camera) if check_depth_prior_args(camera) else None
+    p.depth_weight, p.id_partials, p.id_term, p.depths = 0.0, None, None, None
+    if p.invdepth is not None:
+        raw = p.invdepth[0]
+        if tuple(raw.shape) != (H, W) or raw.dtype != U16:
+            raise _lib.ClmgsError(f"camera.invdepth must be uint16 [{H}, {W}], got {raw.dtype} {tuple(raw.shape)}")
+        p.depth_weight = utils.depth_l1_weight()  # of the current iteration, read once per camera
     p.antialiased = utils.antialiased()  # the backward follows the mode its forward ran in
     filt = p.filt = this_filter.contiguous() if this_filter is not None else None  # None: all rows
     if small_packed is not None:
@@ -179,6 +190,9 @@ def camera_front(gaussians, camera, this_filter, sh_rows, sh_by_filter, backgrou
             0.3, 0.01, 1e10, float(getattr(args, "radius_clip", 0.0)), dptr(radii), dptr(means2d),
             dptr(depths), None, None, None, dptr(packed),  # conics/colours/opacities live in `packed`
             dptr(sh_index, I32, True)))
+        if p.invdepth is not None:  # 1/z into the records' spare word: the fourth colour of the 4-channel tile kernels
+            check(L.clmgs_invdepth_pack(_sptr(s_front), V, dptr(radii), dptr(depths), dptr(packed)))
+            p.depths = depths
         # binning route: "tile" (default, csrc/isect3.hip: no global sort) | "sort" (csrc/isect.hip: depth sort + tile sort);
         # identical lists (tests/test_gpu_ops.py)
         begin = isect3_begin if getattr(args, "binning", "tile") == "tile" else isect2_begin
@@ -215,31 +229,36 @@ def camera_forward_finish(gaussians, p, exact=False):
                 _observe_count(_cap_key(gaussians, W, H), p.fids.numel())
         else:
             p.n_dev = p.isect.totals  # int64[2] on the device: {emitted, reference}; p.isect stays for camera_verify
-        p.out = torch.empty((H, W, 3), dtype=F32, device=dev)
+        nch = 4 if p.invdepth is not None else 3  # with a prior: [H,W,4], channel 3 = the inverse depth
+        p.out = torch.empty((H, W, nch), dtype=F32, device=dev)
         p.alphas = torch.empty((H, W), dtype=F32, device=dev)
         p.last_ids = torch.empty((H, W), dtype=I32, device=dev)
         p.bg = background.reshape(1, 3).to(F32).contiguous() if background is not None else None
+        if nch == 4 and p.bg is not None:  # the inverse depth's background is 0
+            p.bg = torch.cat([p.bg, p.bg.new_zeros((1, 1))], dim=1).contiguous()
     if s_raster is not s_front:
         s_raster.wait_stream(s_front)
     n_isects = p.fids.numel()
+    raster_fwd, raster_fwd_dev = (L.clmgs_rasterize4_fwd, L.clmgs_rasterize4_fwd_dev) if nch == 4 else \
+        (L.clmgs_rasterize_fwd, L.clmgs_rasterize_fwd_dev)
     if p.n_dev is None:
-        check(L.clmgs_rasterize_fwd(_sptr(s_raster), 1, V, n_isects, None, None, None, None, dptr(p.bg, F32, True),
-                                    W, H, TILE, tw, th, dptr(p.offsets), dptr(p.fids), dptr(packed), dptr(p.out),
-                                    dptr(p.alphas), dptr(p.last_ids)))
+        check(raster_fwd(_sptr(s_raster), 1, V, n_isects, None, None, None, None, dptr(p.bg, F32, True),
+                         W, H, TILE, tw, th, dptr(p.offsets), dptr(p.fids), dptr(packed), dptr(p.out),
+                         dptr(p.alphas), dptr(p.last_ids)))
     else:
-        check(L.clmgs_rasterize_fwd_dev(_sptr(s_raster), 1, V, n_isects, dptr(p.n_dev), dptr(p.bg, F32, True),
-                                        W, H, TILE, tw, th, dptr(p.offsets), dptr(p.fids), dptr(packed), dptr(p.out),
-                                        dptr(p.alphas), dptr(p.last_ids)))
+        check(raster_fwd_dev(_sptr(s_raster), 1, V, n_isects, dptr(p.n_dev), dptr(p.bg, F32, True),
+                             W, H, TILE, tw, th, dptr(p.offsets), dptr(p.fids), dptr(packed), dptr(p.out),
+                             dptr(p.alphas), dptr(p.last_ids)))
     if s_mem is not s_raster:
         ev = torch.cuda.Event()
         ev.record(s_raster)
         s_mem.wait_event(ev)
     with torch.cuda.stream(s_mem):
-        # loss forward + backward straight on the [H,W,3] buffer viewed as [3,H,W]
+        # loss forward + backward straight on the [H,W,3] ([H,W,4] with a prior) buffer viewed as [3,H,W]
         slots = L.clmgs_loss_slots()
         partials = torch.zeros((slots, 2), dtype=F32, device=dev)
         maps = p.maps = torch.empty((3, 3, H, W), dtype=F32, device=dev)
-        sc, sy, sx = 1, 3 * W, 3
+        sc, sy, sx = 1, nch * W, nch
         gt = gt_u8.contiguous()
         sm = _sptr(s_mem)
         mask = p.loss_mask
@@ -282,6 +301,17 @@ def camera_forward_finish(gaussians, p, exact=False):
             p.exp_partials = torch.empty((rows, 12), dtype=F32, device=dev)
             check(L.clmgs_exposure_bwd(sm, H, W, dptr(p.out), sc, sy, sx, dptr(p.exposure, F32), dptr(p.v_out), sc, sy, sx,
                                        dptr(p.v_out), sc, sy, sx, dptr(p.exp_partials)))
+        if p.invdepth is not None:
+            # the depth term, after the loss (and exposure) backward on the same stream, into the same [H,W,4] cotangent:
+            # they wrote words 0..2 of every pixel through their strides, this writes word 3.  One partial sum per
+            # workgroup; camera_loss finishes them (a forward repeated for capacity replaces the rows: counted once).
+            raw, scale, offset = p.invdepth
+            p.id_partials = torch.empty((int(L.clmgs_invdepth_partials_rows(H, W)),), dtype=F32, device=dev)
+            p.id_term = None
+            ch3 = 3 * p.out.element_size()
+            check(L.clmgs_invdepth_l1_fwd_bwd(sm, H, W, ctypes.c_void_p(p.out.data_ptr() + ch3), 4 * W, 4, dptr(raw, U16),
+                                              scale, offset, dptr(mask, U8, True), p.depth_weight,
+                                              ctypes.c_void_p(p.v_out.data_ptr() + ch3), 4 * W, 4, dptr(p.id_partials)))
         p.ev_loss = None
         if s_raster is not s_mem:
             p.ev_loss = torch.cuda.Event()
@@ -307,6 +337,12 @@ def camera_loss(p):
         else:  # sums over counted pixels; the count is a host integer
             tot = p.loss_partials.sum(dim=0)
             p.loss = masked_loss_value(tot[0], tot[1], p.lambda_dssim, p.mask_count, H, W).detach()
+        if p.id_partials is not None:  # L_rgb + L_depth: the partial sums of the forward that was accepted, finished once
+            L = _lib.lib()
+            total = torch.empty((1,), dtype=F32, device=p.id_partials.device)
+            check(L.clmgs_invdepth_finish(_lib.stream(), int(p.id_partials.numel()), dptr(p.id_partials), dptr(total)))
+            p.id_term = (total[0] * (p.depth_weight / float(H * W))).detach()
+            p.loss = p.loss + p.id_term
     return p.loss
 
 
@@ -373,6 +409,9 @@ def camera_backward(gaussians, p, g_sh_rows, small_grad=None, update_stats=True,
     absgrad = bool(getattr(args, "absgrad", False))
     raster_bwd, raster_bwd_dev = (L.clmgs_rasterize_abs_bwd, L.clmgs_rasterize_abs_bwd_dev) if absgrad else \
         (L.clmgs_rasterize_bwd, L.clmgs_rasterize_bwd_dev)
+    if p.invdepth is not None:  # four channels on the slot route: word 9 of every partial line is dL/d(1/z) of its tile
+        assert not absgrad  # refused by camera_front
+        raster_bwd, raster_bwd_dev = L.clmgs_rasterize4_slot_bwd, L.clmgs_rasterize4_bwd_dev
     if p.n_dev is None:
         check(raster_bwd(_sptr(s_raster), 1, V, n_isects, dptr(p.packed), dptr(p.bg, F32, True), W, H,
                          TILE, tw, th, dptr(p.offsets), dptr(p.fids), dptr(p.alphas), dptr(p.last_ids),
@@ -410,6 +449,13 @@ def camera_backward(gaussians, p, g_sh_rows, small_grad=None, update_stats=True,
             None, *small_out, dptr(g_sh_rows, F32, allow_host=True),
             *stat_ptrs, None, int(bool(stats_only_visible)), dptr(partials), dptr(p.row_cum),
             dptr(p.sh_index, I32, True), dptr(sh_stamp, I32, True), int(cur_step), *((None,) if absgrad else ())))
+        if p.invdepth is not None:
+            # dL/d(1/z) -> the xyz gradient, on the memory stream directly after the camera's preprocess backward: that
+            # kernel's first-touch store has initialised the row for this step (and accumulated into it otherwise), so
+            # a plain read-modify-write of the row's three xyz words is correct here
+            check(L.clmgs_invdepth_rows_bwd(_sptr(s_mem), V, dptr(p.filt, torch.int64, True), dptr(p.radii),
+                                            dptr(p.depths), _np(vm), dptr(partials), dptr(p.row_cum), None,
+                                            small_out[0], 1 if p.small_packed is not None else 0))
     # partials (64 B per intersection, 576 MB at 4K) and the loss cotangent image are dead once the two
     # kernels above have run: hand them back now instead of at the next batch.  Each was used on a second
     # stream (partials: written on s_raster, read on s_mem; v_out: written on s_mem, read on s_raster), so
@@ -424,7 +470,8 @@ def camera_backward(gaussians, p, g_sh_rows, small_grad=None, update_stats=True,
         # front stream and used on the tile and memory streams: tell the allocator, then drop them, so the next
         # cameras reuse the blocks in stream order instead of the whole batch's outputs staying alive until the
         # next batch (4 x 0.7 GB at 4K).  Only what camera_loss() needs is kept.
-        for name in ("radii", "packed", "fids", "offsets", "emit_slot", "row_cum", "out", "alphas", "last_ids", "n_dev"):
+        for name in ("radii", "packed", "fids", "offsets", "emit_slot", "row_cum", "out", "alphas", "last_ids", "n_dev",
+                     "depths"):
             t = getattr(p, name)
             if t is not None:
                 for st in {s_mem, s_raster} - {s_front}:

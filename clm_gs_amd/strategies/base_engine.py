@@ -85,16 +85,21 @@ def torch_compiled_loss(image, image_gt_original, loss_mask=None, loss_mask_coun
     return loss_combined(image, image_gt, ssim_loss)
 
 
-RENDER_MODES = ("RGB", "RGB+D", "RGB+ED")
+RENDER_MODES = ("RGB", "RGB+D", "RGB+ED", "RGB+ID")
 
 
 def colors_with_depth(colors, depths, backgrounds, render_mode):
     """The rasterizer's inputs for a render mode (gsplat's rasterization(render_mode=...)): with a depth mode the
-    camera-space depths[C,N] ride as a fourth colour channel whose background is 0."""
+    camera-space depths[C,N] ride as a fourth colour channel whose background is 0; with "RGB+ID" (the INRIA rasterizer's
+    inverse depth, the channel the depth regularisation reads) the fourth colour is 1 / depths, 0 for rows at or behind
+    the camera plane (they reach no tile list)."""
     if render_mode not in RENDER_MODES:
         raise ValueError(f"render_mode must be one of {RENDER_MODES}, got {render_mode!r}")
     if render_mode == "RGB":
         return colors, backgrounds
+    if render_mode == "RGB+ID":
+        front = depths > 0
+        depths = torch.where(front, 1.0 / torch.where(front, depths, torch.ones_like(depths)), torch.zeros_like(depths))
     colors = torch.cat([colors, depths.unsqueeze(-1)], dim=-1)
     if backgrounds is not None:
         backgrounds = torch.cat([backgrounds, backgrounds.new_zeros(backgrounds.shape[:-1] + (1,))], dim=-1)
@@ -103,7 +108,8 @@ def colors_with_depth(colors, depths, backgrounds, render_mode):
 
 def split_depth(rendered, alphas, render_mode):
     """rendered[1,H,W,4], alphas[1,H,W,1] -> (image[3,H,W] view, depth[1,H,W], alpha[1,H,W]): the accumulated depth
-    sum w_i z_i ("RGB+D") or the expected depth D / clamp(alpha, 1e-10) ("RGB+ED", gsplat's definition)."""
+    sum w_i z_i ("RGB+D"), the expected depth D / clamp(alpha, 1e-10) ("RGB+ED", gsplat's definition) or the blended
+    channel as it is ("RGB+ID": the inverse depth sum w_i / z_i, not normalised)."""
     depth, alpha = rendered[..., 3], alphas[..., 0]
     if render_mode == "RGB+ED":
         depth = depth / alpha.clamp(min=1e-10)

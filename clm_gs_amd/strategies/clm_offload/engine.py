@@ -31,24 +31,25 @@ import torch
 
 from ... import _lib, clm_kernels, dp, fast_tsp, utils
 from ...cameras import camera_loss_mask
-from ...clm_kernels import (apply_camera_exposure, send_shs2cpu_grad_buffer_stream, send_shs2gpu_stream,
-                            spherical_harmonics_bwd_inplace)
+from ...clm_kernels import (apply_camera_exposure, camera_depth_term, check_depth_prior_args,
+                            send_shs2cpu_grad_buffer_stream, send_shs2gpu_stream, spherical_harmonics_bwd_inplace)
 from ...densification import update_densification_stats_offload_accum_grads
 from ...gsplat import (fully_fused_projection, isect_offset_encode, isect_tiles,
                        rasterize_to_pixels, spherical_harmonics)
 from ...host import pinned_empty
-from ..base_engine import (select_filters, TILE_SIZE, calculate_filters, pipeline_forward_one_step,
-                           torch_compiled_loss)
+from ..base_engine import (select_filters, TILE_SIZE, calculate_filters, colors_with_depth, pipeline_forward_one_step,
+                           split_depth, torch_compiled_loss)
 
 _BITMAP_DTYPE = {4: torch.int8, 8: torch.int8, 16: torch.int16, 32: torch.int32, 64: torch.int64}
 
 
 def pipeline_forward_one_step_shs_inplace(filtered_opacity_gpu, filtered_scaling_gpu,
                                           filtered_rotation_gpu, filtered_xyz_gpu, filtered_shs,
-                                          camera, scene, gaussians, background, pipe_args):
+                                          camera, scene, gaussians, background, pipe_args, render_mode="RGB"):
     """One camera over the gathered rows; SH evaluated under no_grad and the colours re-leafed so
     the SH backward can later accumulate in place (engine.py:30-127).
-    Returns (image[3,H,W], means2D[1,V,2], radii[1,V], colors_detached[1,V,3], dirs[1,V,3])."""
+    Returns (image[3,H,W], means2D[1,V,2], radii[1,V], colors_detached[1,V,3], dirs[1,V,3]); with a depth render mode
+    (base_engine.colors_with_depth) a sixth result depth[1,H,W]."""
     viewmat = camera.world_view_transform.transpose(0, 1)
     K = camera.K
     n_selected = filtered_xyz_gpu.shape[0]
@@ -75,11 +76,15 @@ def pipeline_forward_one_step_shs_inplace(filtered_opacity_gpu, filtered_scaling
                                             tile_height=tile_height, packed=False)
     isect_offsets = isect_offset_encode(isect_ids, 1, tile_width, tile_height)
     backgrounds = background.reshape(1, 3) if background is not None else None
-    rendered_image, _ = rasterize_to_pixels(
+    colors, backgrounds = colors_with_depth(colors, depths, backgrounds, render_mode)
+    rendered_image, alphas = rasterize_to_pixels(
         means2d=means2D, conics=conics, colors=colors, opacities=opacities,
         image_width=image_width, image_height=image_height, tile_size=TILE_SIZE,
         isect_offsets=isect_offsets, flatten_ids=flatten_ids, backgrounds=backgrounds,
         absgrad=bool(getattr(utils.get_args(), "absgrad", False)))  # -> means2D.absgrad after backward
+    if render_mode != "RGB":
+        rendered_image, depth, _ = split_depth(rendered_image, alphas, render_mode)
+        return rendered_image, means2D, radiis, colors_detached, dirs, depth
     rendered_image = rendered_image.squeeze(0).permute(2, 0, 1)  # [3,H,W] view, no copy
     return rendered_image, means2D, radiis, colors_detached, dirs
 
@@ -184,14 +189,19 @@ def _render_and_backward(gaussians, scene, camera, background, pipe_args, this_f
             before_sh_backward()
         return train_one_camera(gaussians, camera, this_filter, shs, 0, shs_grad, background,
                                 camera.original_image)
+    has_prior = check_depth_prior_args(camera)  # refusal before anything runs
     xyz, opa_raw, sca_raw, rot_raw = _gather_small(gaussians, this_filter)
     opa = gaussians.opacity_activation(opa_raw)
     sca = gaussians.scaling_activation(sca_raw)
     rot = gaussians.rotation_activation(rot_raw)
-    image, means2D, radiis, colors_detached, dirs = pipeline_forward_one_step_shs_inplace(
-        opa, sca, rot, xyz, shs, camera, scene, gaussians, background, pipe_args)
+    # a camera with an inverse-depth prior is rendered with the inverse depth as fourth channel
+    image, means2D, radiis, colors_detached, dirs, *inv_depth = pipeline_forward_one_step_shs_inplace(
+        opa, sca, rot, xyz, shs, camera, scene, gaussians, background, pipe_args,
+        render_mode="RGB+ID" if has_prior else "RGB")
     image = apply_camera_exposure(image, camera)  # the camera's exposure transform, if it has one
     loss = torch_compiled_loss(image, camera.original_image, *camera_loss_mask(camera))
+    if has_prior:
+        loss = loss + camera_depth_term(inv_depth[0][0], camera)
     loss.backward()
     if before_sh_backward is not None:
         before_sh_backward()
@@ -880,6 +890,8 @@ def clm_offload_train_one_batch(gaussians, scene, batched_cameras, parameters_gr
     # the deferred SH-row step applies a batch's gradient later with the scale 1 / (args.bsz x ranks), the
     # small-attribute Adam of the same batch uses len(batched_cameras): they must be the same number
     assert bsz == args.bsz, f"batch of {bsz} cameras but args.bsz = {args.bsz} (optimizer hyper-parameters are scaled by args.bsz)"
+    for camera in batched_cameras:  # absgrad with a depth prior: refused for the whole batch, before any camera runs
+        check_depth_prior_args(camera)
     if gaussians._parameters.is_cuda:
         with _lib.host_region("batch_total"):
             return _train_one_batch_hbm(gaussians, scene, batched_cameras, parameters_grad_buffer,

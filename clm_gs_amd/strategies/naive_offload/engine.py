@@ -7,7 +7,7 @@ Same call signatures and return values as the reference."""
 import torch
 
 from ... import utils
-from ...clm_kernels import apply_camera_exposure
+from ...clm_kernels import apply_camera_exposure, check_depth_prior_args
 from ...fused import train_one_camera
 from ..base_engine import calculate_filters, pipeline_forward_one_step
 
@@ -37,6 +37,8 @@ class _DeviceReplica:
 def naive_offload_train_one_batch(gaussians, scene, batched_cameras, background, sparse_adam=False):
     args = utils.get_args()
     bsz = len(batched_cameras)
+    for camera in batched_cameras:  # absgrad with a depth prior: refused for the whole batch, before any camera runs
+        check_depth_prior_args(camera)
     rep = _DeviceReplica(gaussians)
     with torch.no_grad():
         filters, _, _ = calculate_filters(batched_cameras, rep._xyz, None, rep._scaling, rep._rotation,

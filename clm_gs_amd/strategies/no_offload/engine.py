@@ -7,7 +7,7 @@ import torch
 
 from ... import utils
 from ...cameras import camera_loss_mask
-from ...clm_kernels import apply_camera_exposure
+from ...clm_kernels import apply_camera_exposure, camera_depth_term, check_depth_prior_args
 from ...densification import update_densification_stats_baseline_accum_grads
 from ...gsplat import (fully_fused_projection, isect_offset_encode, isect_tiles,
                        rasterize_to_pixels, spherical_harmonics)
@@ -19,8 +19,8 @@ def baseline_accumGrads_micro_step(means3D, opacities, scales, rotations, shs, s
                                    return_alpha=False):
     """One camera: K from FoV, projection(N) -> SH(masked) -> +0.5 clamp -> tile binning ->
     rasterize -> [3,H,W].  Returns (image, means2D (grad retained), radii, None); with render_mode "RGB+D" /
-    "RGB+ED" a fifth result depth[1,H,W] (accumulated / expected depth, base_engine.split_depth), and with
-    return_alpha a sixth, alpha[1,H,W]."""
+    "RGB+ED" / "RGB+ID" a fifth result depth[1,H,W] (accumulated / expected / inverse depth, base_engine.split_depth), and
+    with return_alpha a sixth, alpha[1,H,W]."""
     args = utils.get_args()
     image_width, image_height = int(utils.get_img_width()), int(utils.get_img_height())
     fx = image_width / (2 * math.tan(camera.FoVx * 0.5))
@@ -67,6 +67,8 @@ def baseline_accumGrads_impl(gaussians, scene, batched_cameras, background, scal
     backward through the activations.  Returns (losses, visibility | None); .grad lands on the
     model's six parameters (the optimizer step is the caller's, train.py:533-578)."""
     if getattr(utils.get_args(), "fused_front_end", True) and scaling_modifier == 1.0:
+        for camera in batched_cameras:  # absgrad with a depth prior: refused for the whole batch, before any camera runs
+            check_depth_prior_args(camera)
         return _baseline_fused(gaussians, scene, batched_cameras, background, sparse_adam)
     losses = []
     means3D = gaussians.get_xyz
@@ -82,11 +84,16 @@ def baseline_accumGrads_impl(gaussians, scene, batched_cameras, background, scal
     visibility = (torch.zeros((means3D.shape[0],), dtype=torch.bool, device=means3D.device)
                   if sparse_adam else None)
     H, W = int(utils.get_img_height()), int(utils.get_img_width())
-    for camera in batched_cameras:
-        rendered_image, means2D, radiis, gaussian_ids = baseline_accumGrads_micro_step(
-            means3D, opacities, scales, rotations, shs, sh_degree, camera, background)
+    priors = [check_depth_prior_args(camera) for camera in batched_cameras]  # refusals before anything runs
+    for camera, has_prior in zip(batched_cameras, priors):
+        # a camera with an inverse-depth prior is rendered with the inverse depth as fourth channel
+        rendered_image, means2D, radiis, gaussian_ids, *inv_depth = baseline_accumGrads_micro_step(
+            means3D, opacities, scales, rotations, shs, sh_degree, camera, background,
+            render_mode="RGB+ID" if has_prior else "RGB")
         rendered_image = apply_camera_exposure(rendered_image, camera)  # the camera's exposure transform, if it has one
         loss = torch_compiled_loss(rendered_image, camera.original_image, *camera_loss_mask(camera))
+        if has_prior:
+            loss = loss + camera_depth_term(inv_depth[0][0], camera)
         loss.backward()
         losses.append(loss.detach())
         with torch.no_grad():

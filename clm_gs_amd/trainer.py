@@ -203,6 +203,14 @@ def _warm_structural_ops(device, n=70_000):
     torch.cuda.synchronize()
 
 
+def check_depth_flags(args, depth_priors):
+    """Depth regularisation with absgrad is refused (absgrad blends three channels only, the inverse depth is a fourth):
+    `depth_priors` = a depth directory was asked for, or a training camera carries a prior."""
+    if depth_priors and bool(getattr(args, "absgrad", False)):
+        raise ValueError("--absgrad together with --depths is not supported: absgrad blends three channels only, the depth "
+                         "regularisation renders the inverse depth as a fourth; drop one of the two")
+
+
 def build_exposure(train_cameras, iterations, device="cuda", lr_init=0.01, lr_final=0.001):
     """`--exposure`: an exposure.ExposureModel with one row per TRAINING camera, attached to the cameras (test cameras and
     novel views carry no exposure and are rendered as the model is).  Refused under camera-DP: every rank would step its
@@ -304,6 +312,8 @@ def training(gaussians, scene, train_cameras, test_cameras, log_file, iterations
         # small-attribute Adam) surfaces HERE, not at the end of the run with the model unsaved
         _lib.check_device_errors()
     defer = bool(getattr(args, "defer_loss_log", True))
+    depth_priors = any(getattr(c, "invdepth", None) is not None for c in train_cameras)
+    check_depth_flags(args, depth_priors)
     loss_log = _LossLog(log_file, defer)
     pt = phase_times if phase_times is not None else {}
     iter_hook = pt.pop("iter_hook", None)  # diagnosis only (bench.py --trainer-trace): called after every iteration
@@ -368,8 +378,10 @@ def training(gaussians, scene, train_cameras, test_cameras, log_file, iterations
             names, sparsity = [c.image_name for c in batch], None
         _acc("engine", _t)
         _t = time.perf_counter()
+        # with depth priors: the depth term's weight of this iteration, next to the losses it is part of
+        depth_note = " depth_l1_weight: {:.6f}".format(utils.depth_l1_weight(iteration)) if depth_priors else ""
         loss_log.push("iteration[{},{}) loss: ".format(iteration, iteration + gbsz), losses,
-                      " image: {}".format(names) + ((" sparsity: " + " ".join("%.4f" % s for s in sparsity) + "\n")
+                      depth_note + " image: {}".format(names) + ((" sparsity: " + " ".join("%.4f" % s for s in sparsity) + "\n")
                                                    if sparsity else "\n"))
         _acc("log", _t)
         if any(iteration <= t < iteration + gbsz for t in test_iterations):
@@ -429,7 +441,8 @@ def training(gaussians, scene, train_cameras, test_cameras, log_file, iterations
 
 
 def train_from_colmap(source_path, model_path, strategy="clm_offload", iterations=None, eval=False, resolution=1,
-                      images="images", test_iterations=(), save=True, masks=None, alpha_mask=False, **arg_overrides):
+                      images="images", test_iterations=(), save=True, masks=None, alpha_mask=False, depths=None,
+                      **arg_overrides):
     """A COLMAP directory -> trained model (row f1): `colmap_scene.load_colmap_scene` (cameras, held-out
     split, scene radius, sparse points) -> `create_from_pcd` with `spatial_lr_scale = cameras_extent` ->
     `training_setup` -> `training` (log lines of the reference in `<model_path>/python_ws=1_rk=0.log`) ->
@@ -438,7 +451,9 @@ def train_from_colmap(source_path, model_path, strategy="clm_offload", iteration
     `utils.default_args`.  `masks` / `alpha_mask`: per-pixel ignore masks of the loss (colmap_scene.load_colmap_scene).
     `exposure=True` (with `exposure_lr_init` / `exposure_lr_final`): per-camera exposure compensation of the training
     cameras (build_exposure); the table is written to `<model_path>/exposure.json` next to the ply and stays reachable as
-    `scene.exposure`.  Returns (gaussians, scene, timer)."""
+    `scene.exposure`.  `depths` (with `depth_l1_weight_init` / `depth_l1_weight_final`): the directory of the 16-bit
+    inverse-depth PNGs of the depth regularisation (colmap_scene.load_colmap_scene); refused with `absgrad=True`.
+    Returns (gaussians, scene, timer)."""
     from .colmap_scene import load_colmap_scene
     from .strategies.clm_offload import GaussianModelCLMOffload
     from .strategies.naive_offload import GaussianModelNaiveOffload
@@ -449,11 +464,13 @@ def train_from_colmap(source_path, model_path, strategy="clm_offload", iteration
     args.source_path, args.model_path, args.eval = source_path, model_path, bool(eval)
     if iterations is not None:
         args.iterations = int(iterations)
+    args.depths = depths or ""
+    check_depth_flags(args, bool(depths))  # raises: before anything is loaded
     utils.set_args(args)
     if getattr(args, "exposure", False) and dp.world_size() > 1:
         build_exposure([], args.iterations)  # raises: before anything is loaded
     scene = load_colmap_scene(source_path, images=images, eval=eval, resolution=resolution, device="cuda",
-                              masks=masks, alpha_mask=alpha_mask)
+                              masks=masks, alpha_mask=alpha_mask, depths=depths)
     if scene.point_cloud is None:
         raise ValueError(f"{source_path}/sparse/0 holds no points3D.bin / points3D.txt to initialise from")
     sizes = {(c.image_height, c.image_width) for c in scene.train_cameras + scene.test_cameras}
@@ -519,6 +536,12 @@ def build_arg_parser():
                          "written to <model_path>/exposure.json (single GPU)")
     ap.add_argument("--exposure_lr_init", type=float, default=0.01)
     ap.add_argument("--exposure_lr_final", type=float, default=0.001)
+    ap.add_argument("-d", "--depths", default=None, metavar="DIR",
+                    help="depth regularisation: directory (relative to the source path or absolute) of 16-bit inverse-depth "
+                         "PNGs NAME.png, scaled by sparse/0/depth_params.json; an L1 term on the rendered inverse depth "
+                         "of every training image with a reliable prior (not with --absgrad)")
+    ap.add_argument("--depth_l1_weight_init", type=float, default=1.0)
+    ap.add_argument("--depth_l1_weight_final", type=float, default=0.01)
     return ap
 
 
@@ -532,4 +555,6 @@ if __name__ == "__main__":  # python -m clm_gs_amd.trainer -s <colmap dir> -m <o
                                 bsz=a.bsz, sh_residency=a.sh_residency, sh_hbm_budget_gb=a.sh_hbm_budget_gb,
                                 absgrad=a.absgrad, rasterize_mode="antialiased" if a.antialiased else "classic",
                                 masks=a.masks, alpha_mask=a.alpha_mask, exposure=a.exposure,
-                                exposure_lr_init=a.exposure_lr_init, exposure_lr_final=a.exposure_lr_final)
+                                exposure_lr_init=a.exposure_lr_init, exposure_lr_final=a.exposure_lr_final,
+                                depths=a.depths, depth_l1_weight_init=a.depth_l1_weight_init,
+                                depth_l1_weight_final=a.depth_l1_weight_final)

@@ -48,6 +48,10 @@ def default_args(**over):
         # this build: per-camera exposure compensation (exposure.ExposureModel; the INRIA code base's --exposure_lr_init /
         # --exposure_lr_final): a learnable 3x4 affine colour transform per TRAINING image, between the rasterizer and the loss
         exposure=False, exposure_lr_init=0.01, exposure_lr_final=0.001,
+        # this build: depth regularisation (the INRIA code base's -d / --depths, --depth_l1_weight_init / _final): an L1 term
+        # between the rendered inverse depth and the inverse-depth prior of every training camera that carries one
+        # (cameras.camera_invdepth), weighted by depth_l1_weight() below.  depths: the directory of the 16-bit PNGs
+        depths="", depth_l1_weight_init=1.0, depth_l1_weight_final=0.01,
         lr_scale_mode="sqrt", bsz=1, exact_filter=True, log_cpu_adam_trailing_overhead=False,
         # Debug
         stop_update_param=False, drop_initial_3dgs_p=0.0,
@@ -111,6 +115,16 @@ def antialiased():
     if mode not in RASTERIZE_MODES:
         raise ValueError(f"rasterize_mode must be one of {RASTERIZE_MODES}, got {mode!r}")
     return mode == "antialiased"
+
+
+def depth_l1_weight(iteration=None):
+    """Weight of the depth term at `iteration` (default: the current one):
+    get_expon_lr_func(depth_l1_weight_init, depth_l1_weight_final, max_steps=iterations), the INRIA code base's schedule."""
+    a = get_args()
+    it = get_cur_iter() if iteration is None else iteration
+    return float(get_expon_lr_func(float(getattr(a, "depth_l1_weight_init", 1.0)),
+                                   float(getattr(a, "depth_l1_weight_final", 0.01)),
+                                   max_steps=int(getattr(a, "iterations", 30_000)))(int(it)))
 
 
 class _NullLog(io.StringIO):

@@ -193,7 +193,10 @@ int clmgs_rasterize_bwd(void* stream, int C, int N, int64_t n_isects, const void
  * gradient in word 9 of the gradient line (x y ca cb | cc r g b | o d).  Channels 0..2, render_alphas and last_ids
  * are bit-identical to clmgs_rasterize_fwd on the same inputs.  means2d == NULL: `packed` already holds 4-channel
  * records (an earlier clmgs_rasterize4_fwd; clmgs_preprocess_fwd writes 3-channel ones, fourth word 0).
- * Backward: the atomic route only -- emit_slot or partials != NULL returns CLMGS_EINVAL before anything is written. */
+ * clmgs_rasterize4_bwd: the atomic route only -- emit_slot or partials != NULL returns CLMGS_EINVAL before anything is
+ * written.  The slot route of four channels is clmgs_rasterize4_slot_bwd: clmgs_rasterize_bwd's slot contract (C == 1,
+ * emit_slot, partials required; packed_grad + row_cum optional), the stored line is  x y ca cb | cc r g b | o d - -
+ * (zero lines stay zero), and the optional per-row sum carries word 9.  Absgrad with four channels is not built. */
 int clmgs_rasterize4_fwd(void* stream, int C, int N, int64_t n_isects, const float* means2d,
                          const float* conics, const float* colors, const float* opacities,
                          const float* backgrounds, int width, int height, int tile_size,
@@ -208,6 +211,14 @@ int clmgs_rasterize4_bwd(void* stream, int C, int N, int64_t n_isects, const voi
                          const float* v_render_alphas, void* packed_grad, float* v_means2d,
                          float* v_conics, float* v_colors, float* v_opacities,
                          const int32_t* emit_slot, const int64_t* row_cum, void* partials);
+int clmgs_rasterize4_slot_bwd(void* stream, int C, int N, int64_t n_isects, const void* packed,
+                              const float* backgrounds, int width, int height, int tile_size,
+                              int tile_width, int tile_height, const int32_t* offsets,
+                              const int32_t* flatten_ids, const float* render_alphas,
+                              const int32_t* last_ids, const float* v_render_colors,
+                              const float* v_render_alphas, void* packed_grad, float* v_means2d,
+                              float* v_conics, float* v_colors, float* v_opacities,
+                              const int32_t* emit_slot, const int64_t* row_cum, void* partials);
 
 /* ---- gsplat.rasterize_to_pixels(absgrad=True) -> means2d.absgrad  (AbsGS; consumed by gsplat's
  * DefaultStrategy(absgrad=True)): next to the signed screen-space gradient, the sum over the pixels p at which the
@@ -278,6 +289,22 @@ int clmgs_rasterize_bwd_dev(void* stream, int C, int N, int64_t capacity, const 
                             const int32_t* last_ids, const float* v_render_colors,
                             const float* v_render_alphas, const int32_t* emit_slot,
                             const int64_t* row_cum, void* partials);
+
+/* Four channels, device-count forms: the contracts of clmgs_rasterize_fwd_dev / _bwd_dev with render_colors /
+ * v_render_colors rows of 4, backgrounds[C,4] or NULL, the fourth colour in word 9 of every record of `packed`
+ * (clmgs_invdepth_pack) and its gradient in word 9 of every partial line. */
+int clmgs_rasterize4_fwd_dev(void* stream, int C, int N, int64_t capacity, const int64_t* n_isects_dev,
+                             const float* backgrounds, int width, int height, int tile_size,
+                             int tile_width, int tile_height, const int32_t* offsets,
+                             const int32_t* flatten_ids, void* packed, float* render_colors,
+                             float* render_alphas, int32_t* last_ids);
+int clmgs_rasterize4_bwd_dev(void* stream, int C, int N, int64_t capacity, const int64_t* n_isects_dev,
+                             const void* packed, const float* backgrounds, int width, int height,
+                             int tile_size, int tile_width, int tile_height, const int32_t* offsets,
+                             const int32_t* flatten_ids, const float* render_alphas,
+                             const int32_t* last_ids, const float* v_render_colors,
+                             const float* v_render_alphas, const int32_t* emit_slot,
+                             const int64_t* row_cum, void* partials);
 
 /* gsplat's absgrad, device-count form of the slot mode: clmgs_rasterize_bwd_dev whose partial lines carry the pair in
  * words 10 and 11 (x y ca cb | cc r g b | o - ax ay), for clmgs_preprocess_abs_bwd to sum. */
@@ -454,6 +481,36 @@ int clmgs_exposure_bwd(void* stream, int H, int W, const float* x, int64_t strid
                        int64_t gstride_y, int64_t gstride_x, float* v_x, int64_t vstride_c, int64_t vstride_y,
                        int64_t vstride_x, float* partials);
 int clmgs_exposure_grad_finish(void* stream, int rows, const float* partials, float* grad12);
+
+/* ---- depth regularisation (csrc/invdepth.hip; the INRIA 3DGS convention: rendered inverse depth
+ * I = sum_i w_i / z_i, the fourth blended channel with 1/z as fourth colour and background 0, against a uint16 prior
+ * prior = raw / 65536 * scale + offset)
+ *   pack:     word 9 (the fourth colour) of record i of packed[V,16] = radii[i] > 0 ? 1 / depths[i] : 0; no other word
+ *             of the records clmgs_preprocess_fwd / _aa_fwd left is touched.
+ *   l1_fwd_bwd: one pass over the H*W pixels.  I and v_I are [H,W] VIEWS given by their element strides (y, x): channel
+ *             3 of an [H,W,4] buffer (strides 4W, 4) and a planar map alike.  prior_u16 [H,W] contiguous; mask uint8
+ *             [H,W] contiguous or NULL (0 = ignored).  v_I = weight * m * sign(I - prior) / (H*W) (0 at I == prior) is
+ *             STORED at every pixel -- that word only; each workgroup STORES one partial sum of m |I - prior| into
+ *             partials[clmgs_invdepth_partials_rows(H, W)] (every row is written; nothing to zero).
+ *   finish:   one wave sums the `rows` partial sums in a fixed order and STORES the total into sum_out[0]; the loss term
+ *             is weight * sum_out[0] / (H*W).
+ *   rows_bwd: for i < V with radii[i] > 0: g_d = the sum in ascending slot order of word 9 of the partial lines
+ *             [row_cum[i-1], row_cum[i]) (partials != NULL) or word 9 of packed_grad[i] (packed_grad != NULL; exactly
+ *             one of the two), and  g_xyz[g] += -g_d / depths[i]^2 * viewmat[2][0..2]  at row g = filter ? filter[i] : i
+ *             of the [N,3] table (packed_grads = 0) or words 0..2 of the [N,12] table (packed_grads = 1); viewmat is a
+ *             HOST pointer to the row-major world-to-camera matrix.  Other rows and words are not touched.  A plain
+ *             read-modify-write: run it on the stream of, and after, the camera's clmgs_preprocess*_bwd.
+ * No float atomics: the same inputs give the same bits on every run.  Bad arguments return CLMGS_EINVAL before
+ * anything is written. */
+int clmgs_invdepth_partials_rows(int H, int W);
+int clmgs_invdepth_pack(void* stream, int V, const int32_t* radii, const float* depths, void* packed);
+int clmgs_invdepth_l1_fwd_bwd(void* stream, int H, int W, const float* I, int64_t stride_y, int64_t stride_x,
+                              const uint16_t* prior_u16, float scale, float offset, const uint8_t* mask,
+                              float weight, float* v_I, int64_t vstride_y, int64_t vstride_x, float* partials);
+int clmgs_invdepth_finish(void* stream, int rows, const float* partials, float* sum_out);
+int clmgs_invdepth_rows_bwd(void* stream, int V, const int64_t* filter, const int32_t* radii, const float* depths,
+                            const float* viewmat, const void* partials, const int64_t* row_cum,
+                            const void* packed_grad, float* g_xyz, int packed_grads);
 
 /* ---- clm_kernels row movers  (clm_offload/engine.py:499-505, 622-636, 789-802, 815-822)
  * dst/src may be device memory or pinned (mapped) host memory.
