@@ -85,6 +85,9 @@ SIGNATURES = {
     "clmgs_invdepth_l1_fwd_bwd": (_i, [_vp, _i, _i, _vp, _i64, _i64, _vp, _f, _f, _vp, _f, _vp, _i64, _i64, _vp]),
     "clmgs_invdepth_finish": (_i, [_vp, _i, _vp, _vp]),
     "clmgs_invdepth_rows_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
+    "clmgs_mcmc_relocation": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "clmgs_mcmc_reg_grad": (_i, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _f, _f]),
+    "clmgs_mcmc_noise": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _f, _vp]),
     "clmgs_rows_gather": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _i]),
     "clmgs_rows_scatter_add": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _i]),
     "clmgs_scatter_to_bit": (_i, [_vp, _vp, _i, _vp, _i64, _i]),

@@ -263,6 +263,75 @@ def apply_camera_exposure(image, camera):
     return apply_exposure(image, leaf)
 
 
+# ------------------------------------------------------------ MCMC densification
+def _f32_dev(t, shape, what):
+    assert t.is_cuda and t.dtype == F32 and t.is_contiguous() and tuple(t.shape) == tuple(shape), \
+        f"{what}: contiguous float32 device tensor of shape {tuple(shape)} expected, got {t.dtype} {tuple(t.shape)}"
+
+
+@torch.no_grad()
+def mcmc_relocation(opacities, scales, ratios):
+    """gsplat's compute_relocation: ACTIVATED opacities [n] / [n,1] and scales [n,3] of Gaussians that will exist
+    ratios[i] times (int32 [n], clamped to 1..51) -> (new_opacities, new_scales) in the shapes given, with
+    o' = 1 - (1 - o)^(1/r) and the scales multiplied by o / D(o', r) (csrc/mcmc.hip; DESIGN.md section 3, "MCMC")."""
+    n = scales.shape[0]
+    _f32_dev(scales, (n, 3), "scales")
+    assert opacities.numel() == n
+    _f32_dev(opacities, opacities.shape, "opacities")
+    assert ratios.is_cuda and ratios.dtype == I32 and ratios.is_contiguous() and tuple(ratios.shape) == (n,)
+    new_o, new_s = torch.empty_like(opacities), torch.empty_like(scales)
+    check(_lib.lib().clmgs_mcmc_relocation(stream(), n, dptr(opacities, F32), dptr(scales, F32), dptr(ratios, I32),
+                                           dptr(new_o), dptr(new_s)))
+    return new_o, new_s
+
+
+def _col_ptr(t, col):
+    return ctypes.c_void_p(t.data_ptr() + 4 * col)
+
+
+@torch.no_grad()
+def mcmc_reg_grad_(c_o, c_s, opacity=None, scaling=None, g_opacity=None, g_scaling=None, packed=None, packed_grad=None):
+    """ADDS the gradients of the two MCMC regularisers: g_opacity += c_o * s (1 - s), s = sigmoid(opacity);
+    g_scaling += c_s * exp(scaling).  Either the four tensors (raw opacity [n,1], raw scaling [n,3] and their gradients)
+    or `packed` / `packed_grad`, the [n,12] parameter mirror and gradient table (columns 3 and 4..6).  The caller folds
+    1/N, 1/3 and any batch scale into c_o / c_s.  Writes nothing but those four gradient columns."""
+    L = _lib.lib()
+    if packed is not None:
+        assert opacity is None and scaling is None and g_opacity is None and g_scaling is None
+        n = packed.shape[0]
+        _f32_dev(packed, (n, 12), "packed")
+        _f32_dev(packed_grad, (n, 12), "packed_grad")
+        assert packed.data_ptr() != packed_grad.data_ptr()
+        check(L.clmgs_mcmc_reg_grad(stream(), n, _col_ptr(packed, 3), 12, _col_ptr(packed, 4), 12,
+                                    _col_ptr(packed_grad, 3), 12, _col_ptr(packed_grad, 4), 12, float(c_o), float(c_s)))
+        return
+    n = scaling.shape[0]
+    _f32_dev(opacity, (n, 1), "opacity")
+    _f32_dev(scaling, (n, 3), "scaling")
+    _f32_dev(g_opacity, (n, 1), "g_opacity")
+    _f32_dev(g_scaling, (n, 3), "g_scaling")
+    check(L.clmgs_mcmc_reg_grad(stream(), n, dptr(opacity, F32), 1, dptr(scaling, F32), 3, dptr(g_opacity, F32), 1,
+                                dptr(g_scaling, F32), 3, float(c_o), float(c_s)))
+
+
+@torch.no_grad()
+def mcmc_inject_noise_(xyz, opacity, scaling, rotation, noise, scaler, packed=None):
+    """In place: xyz += Sigma (noise * gate * scaler) with gate = 1 / (1 + exp(-100 ((1 - sigmoid(opacity)) - 0.995))) and
+    Sigma = R diag(exp(scaling))^2 R^T, R of the normalised raw rotation (gsplat's inject_noise_to_position).  Raw
+    parameter tensors [n,3] / [n,1] / [n,3] / [n,4]; noise [n,3] (torch.randn on the device).  packed: the [n,12] mirror
+    of the small attributes; its columns 0..2 then receive the new positions in the same pass."""
+    n = xyz.shape[0]
+    _f32_dev(xyz, (n, 3), "xyz")
+    _f32_dev(opacity, (n, 1), "opacity")
+    _f32_dev(scaling, (n, 3), "scaling")
+    _f32_dev(rotation, (n, 4), "rotation")
+    _f32_dev(noise, (n, 3), "noise")
+    if packed is not None:
+        _f32_dev(packed, (n, 12), "packed")
+    check(_lib.lib().clmgs_mcmc_noise(stream(), n, dptr(xyz, F32), dptr(opacity, F32), dptr(scaling, F32),
+                                      dptr(rotation, F32), dptr(noise, F32), float(scaler), dptr(packed, F32, True)))
+
+
 # ------------------------------------------------------------- SH row movement
 def _idx64(t):
     return 1 if t is not None and t.dtype == I64 else 0

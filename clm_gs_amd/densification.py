@@ -43,6 +43,55 @@ def gsplat_densification(iteration, scene, gaussians, batched_screenspace_pkg=No
     timers.stop("densification")
 
 
+def check_mcmc_args(args):
+    """MCMC densification runs on no_offload and on clm_offload with the SH rows in HBM and the fused front end; every
+    other combination is refused here, before training starts, with a message naming the flag."""
+    if not bool(getattr(args, "mcmc", False)):
+        return
+    why = None
+    if getattr(args, "sh_residency", "hbm") == "host":
+        why = 'sh_residency="host": relocation rewrites SH rows and their moments in place, in HBM'
+    elif float(getattr(args, "sh_hbm_budget_gb", 0.0) or 0.0) > 0.0:
+        why = "sh_hbm_budget_gb > 0: the HBM-resident prefix belongs to the host-resident mode"
+    elif bool(getattr(args, "naive_offload", False)):
+        why = "naive_offload: its model keeps the parameters in pinned host tables"
+    elif dp.world_size() > 1:
+        why = "camera-DP (world_size {}): sampling, noise and row surgery are not replicated across ranks".format(dp.world_size())
+    elif bool(getattr(args, "sparse_adam", False)):
+        why = "sparse_adam: the noise and the regularisers step every row, a visibility-masked optimizer does not"
+    elif bool(getattr(args, "stop_update_param", False)):
+        why = "stop_update_param: there is no optimizer step to add the regularisers to or to inject noise after"
+    elif bool(getattr(args, "clm_offload", False)) and not bool(getattr(args, "fused_front_end", True)):
+        why = "clm_offload with fused_front_end=False: the MCMC passes work on the packed tables of the fused front end"
+    if why:
+        raise ValueError("mcmc is not supported with " + why)
+
+
+def mcmc_in_window(args, iteration):
+    return args.mcmc_refine_start_iter < iteration < args.mcmc_refine_stop_iter
+
+
+def mcmc_refinement(iteration, scene, gaussians):
+    """MCMC mode's replacement of gsplat_densification (no clone / split, no pruning, no opacity reset, no densification
+    statistics): inside (mcmc_refine_start_iter, mcmc_refine_stop_iter), whenever the image counter crosses a multiple of
+    mcmc_refine_every (the bsz-stride test, so no multiple is skipped), dead Gaussians are relocated onto live ones and
+    the model grows by 5 % up to mcmc_cap_max.  -> whether it refined."""
+    args = utils.get_args()
+    gbsz = args.bsz * dp.world_size()
+    if not (mcmc_in_window(args, iteration)
+            and utils.check_update_at_this_iter(iteration, gbsz, args.mcmc_refine_every, 0)):
+        return False
+    timers = utils.get_timers()
+    timers.start("densification")
+    gen = getattr(gaussians, "split_generator", None)
+    dead, _ = gaussians.relocate_gs(args.mcmc_min_opacity, gen)
+    added = gaussians.add_new_gs(args.mcmc_cap_max, gen)
+    utils.get_log_file().write("MCMC refinement: relocated {} added {}\n".format(int(dead.numel()), int(added.numel())))
+    utils.inc_densify_iter()
+    timers.stop("densification")
+    return True
+
+
 def update_densification_stats_offload_accum_grads(scene, gaussians, image_height, image_width,
                                                    send2gpu_final_filter_indices, means2d_grad,
                                                    radii):

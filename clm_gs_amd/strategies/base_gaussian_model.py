@@ -14,6 +14,16 @@ from ..clm_kernels import densify_stats
 from ..utils import RGB2SH, build_rotation, get_expon_lr_func, inverse_sigmoid
 
 
+def mcmc_sample(p, n, generator=None):
+    """n draws (int64, with replacement) from the categories of `p` with probability proportional to p >= 0, by the inverse
+    CDF in float64.  torch.multinomial refuses more than 2^24 categories; this form has no such limit and is what every
+    model size uses.  `generator` lives on p's device.  side="right": a draw lands on the first category whose
+    cumulative weight EXCEEDS it, so a category of weight 0 is never drawn."""
+    cdf = torch.cumsum(p.detach().double().flatten(), 0)
+    u = torch.rand((int(n),), dtype=torch.float64, device=p.device, generator=generator) * cdf[-1]
+    return torch.searchsorted(cdf, u, right=True).clamp_(max=p.numel() - 1)
+
+
 class BaseGaussianModel(ABC):
     def setup_functions(self):
         self.scaling_activation = torch.exp
@@ -229,6 +239,88 @@ class BaseGaussianModel(ABC):
             self.prune_points(mask, resort=True)
         else:
             self.prune_points(mask)
+
+    # ------------------------------------------------- MCMC densification (gsplat's MCMCStrategy)
+    def _mcmc_tables(self):
+        """Every per-row optimisable table as (parameter data [N,...], exp_avg | None, exp_avg_sq | None), all groups:
+        what relocate_gs / add_new_gs copy rows of and zero moments in."""
+        raise NotImplementedError(f"{type(self).__name__} does not support MCMC densification")
+
+    def _shs48_take(self, idx):
+        """[k,48] device copy of the SH rows idx (int64)."""
+        return utils.take_rows(self._shs48_rows(None), idx)
+
+    def _mcmc_touched(self, rows):
+        """Rows were rewritten in place: whatever a model caches about its rows is dropped here."""
+
+    def _mcmc_resort(self):
+        """The Z-order re-sort densify_and_prune runs, where the model does one."""
+
+    def _mcmc_flush(self):
+        if hasattr(self, "flush_lazy_rows"):  # lazy / deferred rows, as gsplat_densification does
+            self.flush_lazy_rows()
+
+    def _mcmc_relocate_sources(self, src, min_opacity):
+        """The relocation written into the source rows `src` (int64, with repeats: a row drawn k times will exist k + 1
+        times): opacity and scale by clm_kernels.mcmc_relocation, the opacity clamped to [min_opacity, 1 - eps]."""
+        from ..clm_kernels import mcmc_relocation
+        n = self._xyz.shape[0]
+        ratios = (torch.bincount(src, minlength=n)[src] + 1).to(torch.int32)
+        o = torch.sigmoid(utils.take_rows(self._opacity.detach(), src)).contiguous()
+        s = torch.exp(utils.take_rows(self._scaling.detach(), src)).contiguous()
+        new_o, new_s = mcmc_relocation(o, s, ratios)
+        new_o = torch.clamp(new_o, float(min_opacity), 1.0 - torch.finfo(torch.float32).eps)
+        # (repeats of a row carry the same values: the scatter's result does not depend on its order)
+        utils.put_rows(self._opacity.data, src, inverse_sigmoid(new_o))
+        utils.put_rows(self._scaling.data, src, torch.log(new_s))
+
+    def _mcmc_zero_moments(self, rows):
+        for _, m, v in self._mcmc_tables():
+            for t in (m, v):
+                if t is not None:
+                    utils.fill_rows(t, rows, 0.0)
+
+    @torch.no_grad()
+    def relocate_gs(self, min_opacity=None, generator=None):
+        """Dead Gaussians (opacity <= min_opacity) are moved onto live ones drawn with probability proportional to
+        opacity: the source's opacity and scale are relocated for the copies it now has, every attribute of the source
+        row is copied into the dead row, and both Adam moments of the SOURCE rows are zeroed in every group.
+        -> (dead_idx, source_idx); the row count does not change."""
+        min_opacity = float(self.args.mcmc_min_opacity if min_opacity is None else min_opacity)
+        self._mcmc_flush()
+        opac = torch.sigmoid(self._opacity.detach()).flatten()
+        dead = opac <= min_opacity
+        dead_idx, live_idx = torch.nonzero(dead).flatten(), torch.nonzero(~dead).flatten()
+        if dead_idx.numel() == 0 or live_idx.numel() == 0:
+            return dead_idx[:0], dead_idx[:0]
+        src = utils.take_rows(live_idx, mcmc_sample(utils.take_rows(opac, live_idx), dead_idx.numel(), generator))
+        self._mcmc_relocate_sources(src, min_opacity)
+        for p, _, _ in self._mcmc_tables():
+            utils.put_rows(p, dead_idx, utils.take_rows(p, src))
+        self._mcmc_zero_moments(src)
+        self._mcmc_touched(torch.cat((dead_idx, src)))
+        return dead_idx, src
+
+    @torch.no_grad()
+    def add_new_gs(self, cap_max, generator=None, min_opacity=None):
+        """Growth by 5 % up to cap_max: sources drawn from all rows by opacity, relocated as in relocate_gs, their copies
+        appended with zero moments (densification_postfix, which resets the statistics), the sources' moments zeroed.
+        -> the source rows (int64; empty at the cap)."""
+        min_opacity = float(self.args.mcmc_min_opacity if min_opacity is None else min_opacity)
+        n = self._xyz.shape[0]
+        n_new = max(0, min(int(cap_max), int(1.05 * n)) - n)
+        if n_new == 0:
+            return torch.empty((0,), dtype=torch.int64, device=self._xyz.device)
+        self._mcmc_flush()
+        src = mcmc_sample(torch.sigmoid(self._opacity.detach()).flatten(), n_new, generator)
+        self._mcmc_relocate_sources(src, min_opacity)
+        self._mcmc_touched(src)
+        pick = lambda t: utils.take_rows(t.detach(), src)
+        self.densification_postfix(pick(self._xyz), self._shs48_take(src), pick(self._opacity),
+                                   pick(self._scaling), pick(self._rotation))
+        self._mcmc_zero_moments(src)  # (appended rows sit behind the old ones: the source ids still hold)
+        self._mcmc_resort()
+        return src
 
     # ----------------------------------------------------------- storage order
     def permute_rows(self, order):

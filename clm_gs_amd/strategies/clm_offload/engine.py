@@ -29,11 +29,11 @@ import os
 
 import torch
 
-from ... import _lib, clm_kernels, dp, fast_tsp, utils
+from ... import _lib, clm_kernels, dp, fast_tsp, mcmc, utils
 from ...cameras import camera_loss_mask
 from ...clm_kernels import (apply_camera_exposure, camera_depth_term, check_depth_prior_args,
                             send_shs2cpu_grad_buffer_stream, send_shs2gpu_stream, spherical_harmonics_bwd_inplace)
-from ...densification import update_densification_stats_offload_accum_grads
+from ...densification import check_mcmc_args, update_densification_stats_offload_accum_grads
 from ...gsplat import (fully_fused_projection, isect_offset_encode, isect_tiles,
                        rasterize_to_pixels, spherical_harmonics)
 from ...host import pinned_empty
@@ -722,14 +722,22 @@ def _stage_optimizer(b):
     elif b.use_packed:
         if getattr(gaussians, "small_deferred", False):
             gaussians.flush_small()  # (a batch in another mode: nothing may wait across it)
+        if mcmc.enabled(args):  # regulariser gradients into the packed table, which the step below scales by 1 / bsz
+            mcmc.add_reg_grads(gaussians, grad_div=bsz * dp.world_size(), packed=b.small_pk, packed_grad=b.small_gk)
         gaussians.optimizer.gpu_step_packed(b.small_pk, b.small_gk, 1.0 / (bsz * dp.world_size()),
                                             g_stamp=b.ft_stamp, cur_step=step,
                                             row_range=dp.owner_range(N) if (b.small_owner and b.locality) else None)
         if b.small_owner and b.locality:
             gaussians.small_after_step()
+        if mcmc.enabled(args):  # position noise after the step; the mirror's xyz columns follow in the same pass
+            mcmc.inject_noise(gaussians, packed=b.small_pk)
     else:
+        if mcmc.enabled(args):
+            mcmc.add_reg_grads(gaussians, grad_div=bsz * dp.world_size())
         _gpu_adam_step(gaussians, args, b.touched if args.sparse_adam else None,
                        grad_div=bsz * dp.world_size())
+        if mcmc.enabled(args):
+            mcmc.inject_noise(gaussians)
         gaussians.invalidate_small_packed()
     if b.lazy:
         # DEFERRED: the touched rows' Adam step of this batch is not run now.  Their (reduced) gradient
@@ -892,6 +900,7 @@ def clm_offload_train_one_batch(gaussians, scene, batched_cameras, parameters_gr
     assert bsz == args.bsz, f"batch of {bsz} cameras but args.bsz = {args.bsz} (optimizer hyper-parameters are scaled by args.bsz)"
     for camera in batched_cameras:  # absgrad with a depth prior: refused for the whole batch, before any camera runs
         check_depth_prior_args(camera)
+    check_mcmc_args(args)
     if gaussians._parameters.is_cuda:
         with _lib.host_region("batch_total"):
             return _train_one_batch_hbm(gaussians, scene, batched_cameras, parameters_grad_buffer,

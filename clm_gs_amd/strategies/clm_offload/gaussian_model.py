@@ -120,6 +120,8 @@ class GaussianModelCLMOffload(BaseGaussianModel):
                 self.flush_lazy_rows()
             if getattr(self, "_hbm_prefix", None) is not None:  # its moments belong to the optimizer that is going away
                 self.hbm_prefix_drop(writeback=True)
+        from ...densification import check_mcmc_args
+        check_mcmc_args(self.args)  # an MCMC model in a combination that is not built: refused before training starts
         self._small_def_dirty = False
         self._lazy_dirty = True
         self._mutations = getattr(self, "_mutations", 0) + 1
@@ -153,10 +155,12 @@ class GaussianModelCLMOffload(BaseGaussianModel):
         self._small_since, self._small_drift = 0, [0.0, 0.0]  # batches since all copies were current; drift bounds
         # single GPU: the dense Adam of the small attributes deferred per block of 256 Z-ordered rows (small_deferred)
         self._small_def = None
+        # (an MCMC model runs without the two deferrals: its noise and regularisers touch all N rows every step, so they
+        # need current parameters and a gradient table that is cleared each step -- first_touch_grads below)
         if ((not self.sh_on_host) and (not a.sparse_adam) and getattr(a, "lazy_dense_adam", True) and not dp.active()
                 and getattr(a, "deferred_small_adam", True) and getattr(a, "fused_front_end", True)
                 and getattr(a, "packed_small", True) and getattr(a, "first_touch_grads", True)
-                and not a.stop_update_param):
+                and not a.stop_update_param and not getattr(a, "mcmc", False)):
             self._small_def = {"hist": [], "blk_last": None, "n": -1}
         m_cap, m_n = cap, n
         if self._mom_sharded:
@@ -467,7 +471,7 @@ class GaussianModelCLMOffload(BaseGaussianModel):
         # rows must be zeros), so they keep the clearing policy; the locality exchange moves stamped rows only
         dp_ok = (not dp.active()) or bool(getattr(a, "dp_locality", False))
         return bool(self.lazy_rows and getattr(a, "fused_front_end", True) and getattr(a, "first_touch_grads", True)
-                    and dp_ok and not self.deferred_host_rows)
+                    and dp_ok and not self.deferred_host_rows and not getattr(a, "mcmc", False))
 
     @property
     def moments_sharded(self):
@@ -976,6 +980,37 @@ class GaussianModelCLMOffload(BaseGaussianModel):
             self._bind_rows(n)
         self.max_radii2D = pick(self.max_radii2D)
         self.invalidate_small_packed()
+
+    # ---------------------------------------------------- MCMC densification (base_gaussian_model.relocate_gs / add_new_gs)
+    def _mcmc_tables(self):
+        opt = self.optimizer
+        out = []
+        for _, attr in self._GPU_GROUPS:
+            p = getattr(self, attr)
+            st = opt.gpu_adam.state.get(p, {})
+            out.append((p.data, st.get("exp_avg"), st.get("exp_avg_sq")))
+        st = opt.cpu_adam.state.get(self._parameters, {})
+        out.append((self._parameters.data, st.get("exp_avg"), st.get("exp_avg_sq")))
+        return out
+
+    def _shs48_take(self, idx):
+        self.flush_lazy_rows()
+        return utils.take_rows(self._parameters.detach(), idx)
+
+    def _mcmc_touched(self, rows):
+        """Rows rewritten in place after a flush: the mirror is rebuilt, "sorted" ends, and the rows' deferred-step stamps
+        say what the flush left -- current as of the optimizer's step, no gradient waiting."""
+        self.invalidate_small_packed()
+        self._mutations = getattr(self, "_mutations", 0) + 1
+        self._sorted_tag = None
+        if self.lazy_rows and rows.numel():
+            utils.fill_rows(self._row_last_step, rows, int(self.optimizer.cpu_adam.global_step))
+            utils.fill_rows(self._row_g_step, rows, 0)
+
+    def _mcmc_resort(self):
+        if getattr(self, "fuse_sort_into_prune", False):  # (the trainer keeps the rows in Z-order: densify_and_prune's re-sort)
+            self.spatial_sort()
+            self._sorted_tag = (self._mutations, self._xyz.shape[0])
 
     def _shs48_rows(self, mask):
         self.flush_lazy_rows()

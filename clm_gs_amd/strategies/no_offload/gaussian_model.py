@@ -36,6 +36,8 @@ class GaussianModelNoOffload(BaseGaussianModel):
                 self._opacity]
 
     def training_setup(self, training_args):
+        from ...densification import check_mcmc_args
+        check_mcmc_args(self.args)  # an MCMC model in a combination that is not built: refused before training starts
         self.percent_dense = training_args.percent_dense
         n = self.get_xyz.shape[0]
         self.xyz_gradient_accum = torch.zeros((n, 1), device="cuda")
@@ -103,6 +105,19 @@ class GaussianModelNoOffload(BaseGaussianModel):
         self.xyz_gradient_accum = utils.gather_rows(self.xyz_gradient_accum, order)
         self.denom = utils.gather_rows(self.denom, order)
         self.max_radii2D = utils.gather_rows(self.max_radii2D, order)
+
+    def _mcmc_tables(self):
+        out = []
+        for g in self.optimizer.param_groups:
+            p = g["params"][0]
+            st = self.optimizer.state.get(p, {})
+            out.append((p.data, st.get("exp_avg"), st.get("exp_avg_sq")))
+        return out
+
+    def _shs48_take(self, idx):
+        k = idx.numel()
+        return torch.cat((utils.take_rows(self._features_dc.detach(), idx),
+                          utils.take_rows(self._features_rest.detach(), idx)), dim=1).reshape(k, 48)
 
     def _shs48_rows(self, mask):
         f = self.get_features.detach()

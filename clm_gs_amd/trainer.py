@@ -16,10 +16,10 @@ import time
 
 import torch
 
-from . import dp, utils
+from . import dp, mcmc, utils
 from .cameras import camera_loss_mask
 from .clm_kernels import apply_camera_exposure
-from .densification import gsplat_densification
+from .densification import check_mcmc_args, gsplat_densification, mcmc_refinement
 
 
 class End2endTimer:
@@ -211,6 +211,25 @@ def check_depth_flags(args, depth_priors):
                          "regularisation renders the inverse depth as a fourth; drop one of the two")
 
 
+def no_offload_optimizer_step(gaussians, args, bsz, visibility=None):
+    """The no_offload optimizer epilogue of a batch (train.py:533-578): gradients / bsz, step, zero_grad.  In MCMC mode
+    the two regulariser gradients are added before the step and the position noise is injected after it."""
+    use_mcmc = mcmc.enabled(args)
+    if args.lr_scale_mode != "accumu":
+        for p in gaussians.all_parameters():
+            if p.grad is not None:
+                p.grad /= bsz
+    if use_mcmc:  # (one regulariser term per optimizer step, added to what the step consumes: no batch scale)
+        mcmc.add_reg_grads(gaussians)
+    if args.sparse_adam:
+        gaussians.optimizer.step(visibility=visibility)
+    else:
+        gaussians.optimizer.step()
+    gaussians.optimizer.zero_grad(set_to_none=True)
+    if use_mcmc:
+        mcmc.inject_noise(gaussians)
+
+
 def build_exposure(train_cameras, iterations, device="cuda", lr_init=0.01, lr_final=0.001):
     """`--exposure`: an exposure.ExposureModel with one row per TRAINING camera, attached to the cameras (test cameras and
     novel views carry no exposure and are rendered as the model is).  Refused under camera-DP: every rank would step its
@@ -314,6 +333,8 @@ def training(gaussians, scene, train_cameras, test_cameras, log_file, iterations
     defer = bool(getattr(args, "defer_loss_log", True))
     depth_priors = any(getattr(c, "invdepth", None) is not None for c in train_cameras)
     check_depth_flags(args, depth_priors)
+    check_mcmc_args(args)
+    use_mcmc = mcmc.enabled(args)
     loss_log = _LossLog(log_file, defer)
     pt = phase_times if phase_times is not None else {}
     iter_hook = pt.pop("iter_hook", None)  # diagnosis only (bench.py --trainer-trace): called after every iteration
@@ -396,7 +417,14 @@ def training(gaussians, scene, train_cameras, test_cameras, log_file, iterations
             timer.start()
         n_before = gaussians.get_xyz.shape[0]
         _t = time.perf_counter()
-        gsplat_densification(iteration, scene, gaussians, None)
+        if use_mcmc:
+            # the batch's optimizer step and noise come first (clm_offload: inside the engine): a refinement moves rows of
+            # stepped parameters, and the gradients of a batch belong to the rows as they were rendered
+            if not clm and not naive:
+                no_offload_optimizer_step(gaussians, args, bsz, visibility)
+            mcmc_refinement(iteration, scene, gaussians)
+        else:
+            gsplat_densification(iteration, scene, gaussians, None)
         _acc("densify", _t)
         if gaussians.get_xyz.shape[0] != n_before:
             _check_device()  # (densify_and_prune read its counts back: the device is drained)
@@ -408,19 +436,11 @@ def training(gaussians, scene, train_cameras, test_cameras, log_file, iterations
                 deal()
                 next_batch = None  # drawn from the old pool
         if gaussians.get_xyz.shape[0] != n_before or utils.check_update_at_this_iter(
-                iteration, gbsz, args.densification_interval, 0):
+                iteration, gbsz, args.mcmc_refine_every if use_mcmc else args.densification_interval, 0):
             loss_log.flush()  # keep the reference's line order: the batch's loss line, then the memory line
             log_file.write(memory_line(iteration, gbsz, gaussians))
-        if not clm and not naive:  # train.py:533-578
-            if args.lr_scale_mode != "accumu":
-                for p in gaussians.all_parameters():
-                    if p.grad is not None:
-                        p.grad /= bsz
-            if args.sparse_adam:
-                gaussians.optimizer.step(visibility=visibility)
-            else:
-                gaussians.optimizer.step()
-            gaussians.optimizer.zero_grad(set_to_none=True)
+        if not clm and not naive and not use_mcmc:  # train.py:533-578
+            no_offload_optimizer_step(gaussians, args, bsz, visibility)
         if exposure is not None:
             exposure.step(iteration)
             exposure.zero_grad()
@@ -542,6 +562,18 @@ def build_arg_parser():
                          "of every training image with a reliable prior (not with --absgrad)")
     ap.add_argument("--depth_l1_weight_init", type=float, default=1.0)
     ap.add_argument("--depth_l1_weight_final", type=float, default=0.01)
+    ap.add_argument("--mcmc", action="store_true",
+                    help="3DGS-MCMC densification (gsplat's MCMCStrategy): a fixed budget of --cap_max Gaussians, dead ones "
+                         "relocated instead of pruned, 5 %% growth per refinement, position noise after every step "
+                         "(no_offload, or clm_offload with --sh_residency hbm; single GPU)")
+    ap.add_argument("--cap_max", type=int, default=1_000_000, help="--mcmc: the number of Gaussians the model grows to")
+    ap.add_argument("--mcmc_noise_lr", type=float, default=5e5)
+    ap.add_argument("--mcmc_refine_start_iter", type=int, default=500)
+    ap.add_argument("--mcmc_refine_stop_iter", type=int, default=25_000)
+    ap.add_argument("--mcmc_refine_every", type=int, default=100)
+    ap.add_argument("--mcmc_min_opacity", type=float, default=0.005)
+    ap.add_argument("--mcmc_opacity_reg", type=float, default=0.01)
+    ap.add_argument("--mcmc_scale_reg", type=float, default=0.01)
     return ap
 
 
@@ -557,4 +589,8 @@ if __name__ == "__main__":  # python -m clm_gs_amd.trainer -s <colmap dir> -m <o
                                 masks=a.masks, alpha_mask=a.alpha_mask, exposure=a.exposure,
                                 exposure_lr_init=a.exposure_lr_init, exposure_lr_final=a.exposure_lr_final,
                                 depths=a.depths, depth_l1_weight_init=a.depth_l1_weight_init,
-                                depth_l1_weight_final=a.depth_l1_weight_final)
+                                depth_l1_weight_final=a.depth_l1_weight_final, mcmc=a.mcmc, mcmc_cap_max=a.cap_max,
+                                mcmc_noise_lr=a.mcmc_noise_lr, mcmc_refine_start_iter=a.mcmc_refine_start_iter,
+                                mcmc_refine_stop_iter=a.mcmc_refine_stop_iter, mcmc_refine_every=a.mcmc_refine_every,
+                                mcmc_min_opacity=a.mcmc_min_opacity, mcmc_opacity_reg=a.mcmc_opacity_reg,
+                                mcmc_scale_reg=a.mcmc_scale_reg)

@@ -52,6 +52,13 @@ def default_args(**over):
         # between the rendered inverse depth and the inverse-depth prior of every training camera that carries one
         # (cameras.camera_invdepth), weighted by depth_l1_weight() below.  depths: the directory of the 16-bit PNGs
         depths="", depth_l1_weight_init=1.0, depth_l1_weight_final=0.01,
+        # this build: 3DGS-MCMC densification (gsplat's MCMCStrategy) -- a fixed Gaussian budget mcmc_cap_max: dead Gaussians
+        # (opacity <= mcmc_min_opacity) are relocated onto live ones, the model grows by 5 % per refinement up to the cap,
+        # an opacity-gated position noise (mcmc_noise_lr x the xyz learning rate) follows every optimizer step, and
+        # mcmc_opacity_reg * mean(opacity) + mcmc_scale_reg * mean(scale) is added to the loss.  Replaces the clone / split /
+        # prune heuristic and the opacity reset (densification.mcmc_refinement); refused combinations: check_mcmc_args
+        mcmc=False, mcmc_cap_max=1_000_000, mcmc_noise_lr=5e5, mcmc_refine_start_iter=500, mcmc_refine_stop_iter=25_000,
+        mcmc_refine_every=100, mcmc_min_opacity=0.005, mcmc_opacity_reg=0.01, mcmc_scale_reg=0.01,
         lr_scale_mode="sqrt", bsz=1, exact_filter=True, log_cpu_adam_trailing_overhead=False,
         # Debug
         stop_update_param=False, drop_initial_3dgs_p=0.0,

@@ -512,6 +512,33 @@ int clmgs_invdepth_rows_bwd(void* stream, int V, const int64_t* filter, const in
                             const float* viewmat, const void* partials, const int64_t* row_cum,
                             const void* packed_grad, float* g_xyz, int packed_grads);
 
+/* ---- MCMC densification (csrc/mcmc.hip; gsplat's MCMCStrategy, Kheradmand et al. 2024: a fixed Gaussian budget)
+ *   relocation: for i < n, r = clamp(ratios[i], 1, 51), o = opacities[i] (ACTIVATED, in (0, 1)):
+ *               new_opacities[i] = o' = 1 - (1 - o)^(1/r),
+ *               D = sum_{i=1..r} sum_{k=0..i-1} C(i-1,k) (-1)^k o'^(k+1) / sqrt(k+1),
+ *               new_scales[i][0..2] = (o / D) * scales[i][0..2]   (ACTIVATED scales, [n,3]).
+ *               Double arithmetic, each output rounded once to float.  Outputs must not alias inputs.
+ *   reg_grad:   the gradients of w_o * mean(sigmoid(opacity_raw)) + w_s * mean(exp(scaling_raw)), ADDED: for i < n
+ *               g_opacity[i * g_opacity_stride] += c_o * s (1 - s), s = sigmoid(opacity_raw[i * opacity_stride]);
+ *               g_scaling[i * g_scaling_stride + j] += c_s * exp(scaling_raw[i * scaling_stride + j]), j = 0..2.
+ *               Strides are in floats; the pointers address the first row's column: four separate tensors (strides 1
+ *               and 3) and the packed [N,12] tables (stride 12, pointers at columns 3 and 4) alike.  The caller folds
+ *               1/N, 1/3 and any batch scale into c_o / c_s.  Nothing but those four gradient columns is written.
+ *   noise:      in place on xyz[n,3]: gate = 1 / (1 + exp(-100 ((1 - sigmoid(opacity_raw[i])) - 0.995))),
+ *               Sigma = R diag(exp(scaling_raw[i]))^2 R^T with R of the NORMALISED rotation_raw[i] (w,x,y,z),
+ *               xyz[i] += Sigma (noise[i] * gate * scaler).  A zero increment leaves the stored bits.  packed_mirror
+ *               (optional, [n,12], 8 B aligned): columns 0..2 of row i receive the new xyz[i] in the same pass, columns
+ *               3..11 are not written.
+ * No atomics; the same inputs give the same bits on every run.  Bad arguments return CLMGS_EINVAL before anything is
+ * written. */
+int clmgs_mcmc_relocation(void* stream, int64_t n, const float* opacities, const float* scales, const int32_t* ratios,
+                          float* new_opacities, float* new_scales);
+int clmgs_mcmc_reg_grad(void* stream, int64_t n, const float* opacity_raw, int64_t opacity_stride,
+                        const float* scaling_raw, int64_t scaling_stride, float* g_opacity, int64_t g_opacity_stride,
+                        float* g_scaling, int64_t g_scaling_stride, float c_o, float c_s);
+int clmgs_mcmc_noise(void* stream, int64_t n, float* xyz, const float* opacity_raw, const float* scaling_raw,
+                     const float* rotation_raw, const float* noise, float scaler, float* packed_mirror);
+
 /* ---- clm_kernels row movers  (clm_offload/engine.py:499-505, 622-636, 789-802, 815-822)
  * dst/src may be device memory or pinned (mapped) host memory.
  * gather:      dst[dst_idx ? dst_idx[i] : i] = src[src_idx ? src_idx[i] : i]
