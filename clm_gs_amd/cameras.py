@@ -3,7 +3,8 @@ train.py:278-312): FoVx, FoVy, world_view_transform (row-vector convention,
 i.e. the TRANSPOSE of the 4x4 world->camera matrix), K, camtoworlds,
 original_image (uint8 [3,H,W] on the GPU), image_name, create_k_on_gpu(); plus loss_mask (uint8 [H,W] or None)
 and loss_mask_count, the per-pixel ignore mask of the training loss.  A training camera may also carry `exposure` /
-`exposure_grad`, float32 [3,4] views of its rows in an exposure.ExposureModel (camera_exposure below), and `invdepth`
+`exposure_grad`, float32 [3,4] views of its rows in an exposure.ExposureModel (camera_exposure below), or `bilagrid` /
+`bilagrid_grad`, float32 [L,Hg,Wg,12] views of its grids in a bilagrid.BilagridModel (camera_bilagrid), and `invdepth`
 (uint16 [H,W]) with `invdepth_scale` / `invdepth_offset`, its monocular inverse-depth prior (camera_invdepth below)."""
 import math
 
@@ -42,6 +43,20 @@ def camera_invdepth(camera):
     if raw is None:
         return None
     return raw, float(getattr(camera, "invdepth_scale", 1.0)), float(getattr(camera, "invdepth_offset", 0.0))
+
+
+def camera_bilagrid(camera):
+    """(grid, grad) of a camera's bilateral grid -- float32 [L,Hg,Wg,12] views into the tables of a
+    bilagrid.BilagridModel (`camera.bilagrid`, `camera.bilagrid_grad`) -- or (None, None): a camera without the
+    attribute, or with None, is rendered and trained as the model is.  A camera that carries an exposure row as well is
+    refused: the order in which the two transforms compose is not defined."""
+    grid = getattr(camera, "bilagrid", None)
+    if grid is None:
+        return None, None
+    if getattr(camera, "exposure", None) is not None:
+        raise ValueError("a camera carries both an exposure row and a bilateral grid: the order of composition is not "
+                         "defined; train with --exposure or with --bilagrid")
+    return grid, getattr(camera, "bilagrid_grad", None)
 
 
 class Camera:

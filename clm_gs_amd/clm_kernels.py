@@ -332,6 +332,60 @@ def mcmc_inject_noise_(xyz, opacity, scaling, rotation, noise, scaler, packed=No
                                       dptr(rotation, F32), dptr(noise, F32), float(scaler), dptr(packed, F32, True)))
 
 
+# ------------------------------------------------------- bilateral-grid colour correction
+class _ApplyBilagrid(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, image, grid):
+        L = _lib.lib()
+        assert image.dim() == 3 and image.shape[0] == 3 and image.dtype == F32 and image.is_cuda
+        assert grid.dim() == 4 and grid.shape[3] == 12 and grid.dtype == F32 and grid.device == image.device
+        _, H, W = image.shape
+        G = grid.detach().contiguous()
+        out = torch.empty_strided(image.shape, image.stride(), dtype=F32, device=image.device)
+        check(L.clmgs_bilagrid_fwd(stream(), H, W, _view_ptr(image), *image.stride(), dptr(G, F32), *G.shape[:3],
+                                   _view_ptr(out), *out.stride()))
+        ctx.save_for_backward(image, G)
+        return out
+
+    @staticmethod
+    def backward(ctx, v):
+        L = _lib.lib()
+        image, G = ctx.saved_tensors
+        _, H, W = image.shape
+        Lz, Hg, Wg = G.shape[:3]
+        assert v.dtype == F32 and v.shape == image.shape
+        v_img = torch.empty_strided(image.shape, image.stride(), dtype=F32, device=image.device)
+        rows = int(L.clmgs_bilagrid_partials_rows(H, W, Hg, Wg))
+        partials = torch.empty((rows, Lz * 48), dtype=F32, device=image.device)
+        v_G = torch.zeros_like(G)
+        check(L.clmgs_bilagrid_bwd(stream(), H, W, _view_ptr(image), *image.stride(), dptr(G, F32), Lz, Hg, Wg,
+                                   _view_ptr(v), *v.stride(), _view_ptr(v_img), *v_img.stride(), dptr(partials)))
+        check(L.clmgs_bilagrid_grad_finish(stream(), H, W, Lz, Hg, Wg, dptr(partials), dptr(v_G)))
+        return v_img, v_G
+
+
+def apply_bilagrid(image, grid):
+    """A camera's bilateral grid on a rendered image: image [3,H,W] float32 (any strides, e.g. the permuted view of the
+    rasterizer's [H,W,3] output), grid float32 [L,Hg,Wg,12] on the same device -> the image in the same layout, every
+    pixel through the 3x4 affine transform the grid gives at its position and luminance, unclamped; differentiable in
+    both, the gradient through the luminance included (csrc/bilagrid.hip; DESIGN.md section 3, "Bilateral grid")."""
+    return _ApplyBilagrid.apply(image, grid)
+
+
+def apply_camera_bilagrid(image, camera):
+    """apply_bilagrid with the camera's grid, the grid's gradient ADDED into `camera.bilagrid_grad` by the backward; the
+    image itself for a camera without a grid.  Called wherever apply_camera_exposure is (a camera carries one or the other)."""
+    from .cameras import camera_bilagrid
+    grid, grad = camera_bilagrid(camera)
+    if grid is None:
+        return image
+    if not (torch.is_grad_enabled() and image.requires_grad) or grad is None:
+        return apply_bilagrid(image, grid.detach())
+    leaf = grid.detach().requires_grad_(True)
+    leaf.register_hook(lambda g: (grad.add_(g), None)[1])
+    return apply_bilagrid(image, leaf)
+
+
 # ------------------------------------------------------------- SH row movement
 def _idx64(t):
     return 1 if t is not None and t.dtype == I64 else 0

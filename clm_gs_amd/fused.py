@@ -13,7 +13,7 @@ import torch
 
 from . import _lib, utils
 from ._lib import check, dptr
-from .cameras import camera_exposure, camera_invdepth, camera_loss_mask
+from .cameras import camera_bilagrid, camera_exposure, camera_invdepth, camera_loss_mask
 from .clm_kernels import check_depth_prior_args, masked_loss_value
 from .gsplat import (_record_counts, bucket_size, empty_bucketed, isect2_begin, isect2_counts, isect2_finish, isect3_begin,
                      isect3_finish)
@@ -64,6 +64,7 @@ class _CameraPass:
                  "bg", "v_out", "maps", "loss", "ev_loss", "streams", "deg", "aux", "loss_partials",
                  "lambda_dssim", "gt_u8", "background", "isect", "sh_index", "means2d", "n_dev", "antialiased",
                  "loss_mask", "mask_count", "exposure", "exposure_grad", "exp_partials",
+                 "bilagrid", "bilagrid_grad", "bg_partials",
                  "invdepth", "depth_weight", "depths", "id_partials", "id_term")
 
 
@@ -154,6 +155,9 @@ def camera_front(gaussians, camera, this_filter, sh_rows, sh_by_filter, backgrou
     p.loss_mask, p.mask_count = camera_loss_mask(camera)  # a mask on the camera selects the masked loss kernels
     # an exposure row on the camera puts the affine colour transform between the tile kernel and the loss
     (p.exposure, p.exposure_grad), p.exp_partials = camera_exposure(camera), None
+    # a bilateral grid on the camera takes the same place (a camera carrying both is refused, here, before anything is
+    # enqueued)
+    (p.bilagrid, p.bilagrid_grad), p.bg_partials = camera_bilagrid(camera), None
     # an inverse-depth prior on the camera (depth regularisation): the camera is rendered with a fourth channel, the
     # inverse depth, and trained with the L1 term; without one, not one launch differs.  Refused with absgrad, here,
     # before anything is enqueued.
@@ -270,6 +274,14 @@ def camera_forward_finish(gaussians, p, exact=False):
                 raise _lib.ClmgsError(f"camera.exposure must be float32 [3,4], got {p.exposure.dtype} {tuple(p.exposure.shape)}")
             img = torch.empty_like(p.out)
             check(L.clmgs_exposure_fwd(sm, H, W, dptr(p.out), sc, sy, sx, dptr(p.exposure, F32), dptr(img), sc, sy, sx))
+        if p.bilagrid is not None:
+            # the camera's bilateral grid, sliced per pixel, into a second buffer of p.out's shape on s_mem only; p.out
+            # stays: the slice's backward reads it.  With a depth prior the fourth word of a pixel is not touched.
+            if p.bilagrid.dim() != 4 or p.bilagrid.shape[3] != 12 or p.bilagrid.dtype != F32 or not p.bilagrid.is_contiguous():
+                raise _lib.ClmgsError(f"camera.bilagrid must be contiguous float32 [L,Hg,Wg,12], got {p.bilagrid.dtype} {tuple(p.bilagrid.shape)}")
+            img = torch.empty_like(p.out)
+            check(L.clmgs_bilagrid_fwd(sm, H, W, dptr(p.out), sc, sy, sx, dptr(p.bilagrid, F32), *p.bilagrid.shape[:3],
+                                       dptr(img), sc, sy, sx))
         if mask is None:
             check(L.clmgs_l1_ssim_loss_fwd(sm, H, W, dptr(img), sc, sy, sx, dptr(gt, U8), dptr(partials),
                                            dptr(maps[0]), dptr(maps[1]), dptr(maps[2])))
@@ -301,6 +313,14 @@ def camera_forward_finish(gaussians, p, exact=False):
             p.exp_partials = torch.empty((rows, 12), dtype=F32, device=dev)
             check(L.clmgs_exposure_bwd(sm, H, W, dptr(p.out), sc, sy, sx, dptr(p.exposure, F32), dptr(p.v_out), sc, sy, sx,
                                        dptr(p.v_out), sc, sy, sx, dptr(p.exp_partials)))
+        if p.bilagrid is not None:
+            # dL/dy -> dL/dx IN PLACE on p.v_out + one slab row per workgroup; the slab waits on the pass: camera_backward
+            # adds it to the camera's gradient grid once camera_verify has accepted THIS forward
+            Lz, Hg, Wg = p.bilagrid.shape[:3]
+            rows = int(L.clmgs_bilagrid_partials_rows(H, W, Hg, Wg))
+            p.bg_partials = torch.empty((rows, Lz * 48), dtype=F32, device=dev)
+            check(L.clmgs_bilagrid_bwd(sm, H, W, dptr(p.out), sc, sy, sx, dptr(p.bilagrid, F32), Lz, Hg, Wg, dptr(p.v_out),
+                                       sc, sy, sx, dptr(p.v_out), sc, sy, sx, dptr(p.bg_partials)))
         if p.invdepth is not None:
             # the depth term, after the loss (and exposure) backward on the same stream, into the same [H,W,4] cotangent:
             # they wrote words 0..2 of every pixel through their strides, this writes word 3.  One partial sum per
@@ -387,6 +407,12 @@ def camera_backward(gaussians, p, g_sh_rows, small_grad=None, update_stats=True,
             check(L.clmgs_exposure_grad_finish(_sptr(s_mem), int(p.exp_partials.shape[0]), dptr(p.exp_partials),
                                                dptr(p.exposure_grad, F32)))
         p.exp_partials = None
+    if p.bg_partials is not None:  # likewise the bilateral grid's slab: summed per node and added ONCE, on s_mem
+        if p.bilagrid_grad is not None:
+            Lz, Hg, Wg = p.bilagrid.shape[:3]
+            check(L.clmgs_bilagrid_grad_finish(_sptr(s_mem), H, W, Lz, Hg, Wg, dptr(p.bg_partials),
+                                               dptr(p.bilagrid_grad, F32)))
+        p.bg_partials = None
     V = p.V
     vm, K, campos = p.cam
     tw, th = math.ceil(W / float(TILE)), math.ceil(H / float(TILE))

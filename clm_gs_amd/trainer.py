@@ -18,7 +18,7 @@ import torch
 
 from . import dp, mcmc, utils
 from .cameras import camera_loss_mask
-from .clm_kernels import apply_camera_exposure
+from .clm_kernels import apply_camera_bilagrid, apply_camera_exposure
 from .densification import check_mcmc_args, gsplat_densification, mcmc_refinement
 
 
@@ -243,12 +243,41 @@ def build_exposure(train_cameras, iterations, device="cuda", lr_init=0.01, lr_fi
     return model
 
 
+def refuse_bilagrid_under_camera_dp():
+    """The one camera-DP refusal of the bilateral grid: every rank would step its own copy of the table."""
+    if dp.world_size() > 1:
+        raise ValueError("--bilagrid is not supported with camera-DP (world_size {}): the grid table is not reduced "
+                         "across ranks; train on one GPU or without --bilagrid".format(dp.world_size()))
+
+
+def check_appearance_flags(args):
+    """The refusals of the two appearance modes, by name, before anything is loaded."""
+    if getattr(args, "exposure", False) and getattr(args, "bilagrid", False):
+        raise ValueError("--exposure and --bilagrid together are refused: the order in which the exposure transform and "
+                         "the bilateral grid compose is not defined; choose one")
+    if getattr(args, "bilagrid", False):
+        refuse_bilagrid_under_camera_dp()
+
+
+def build_bilagrid(train_cameras, iterations, device="cuda", grid=(16, 16, 8), lr_init=2e-3, lr_final=2e-5, tv_weight=10.0):
+    """`--bilagrid`: a bilagrid.BilagridModel with one grid per TRAINING camera, attached to the cameras (test cameras and
+    novel views carry none and are rendered as the model is).  Refused under camera-DP, for the reason of build_exposure."""
+    refuse_bilagrid_under_camera_dp()
+    from .bilagrid import BilagridModel
+    model = BilagridModel(len(train_cameras), device, grid=tuple(grid), lr_init=lr_init, lr_final=lr_final,
+                          max_steps=int(iterations), tv_weight=tv_weight)
+    model.attach(train_cameras)
+    return model
+
+
 def training(gaussians, scene, train_cameras, test_cameras, log_file, iterations=None,
-             test_iterations=(), background=None, shuffle_seed=0, phase_times=None, exposure=None):
+             test_iterations=(), background=None, shuffle_seed=0, phase_times=None, exposure=None, bilagrid=None):
     """Runs `iterations` images of training; returns the End2endTimer.
     `exposure` (optional exposure.ExposureModel, attached to the training cameras): stepped at the scheduled learning
     rate and zeroed after every batch, on the current stream -- every engine has joined its camera streams into it by
     the time it returns.  A row's gradient is its camera's alone and is not divided by the batch size.
+    `bilagrid` (optional bilagrid.BilagridModel): likewise, next to the exposure step; its step adds the gradient of the
+    total-variation term before Adam.
     `phase_times` (optional dict): host wall time per phase inside the end-to-end clock is accumulated into it
     ("engine" = enqueueing the batches, "densify" = gsplat_densification incl. the device work it waits for,
     "resort" = the Z-order re-sort after a densification, "log" = waiting for loss values, "final_sync"); a callable under
@@ -264,6 +293,8 @@ def training(gaussians, scene, train_cameras, test_cameras, log_file, iterations
     gbsz = bsz * ws
     if ws > 1 and exposure is not None:
         raise ValueError("an exposure model cannot be trained under camera-DP (see build_exposure)")
+    if bilagrid is not None:
+        refuse_bilagrid_under_camera_dp()
     if ws > 1:
         assert clm_hbm_only(args), "camera-DP trains clm_offload with sh_residency='hbm'"
         if getattr(gaussians, "split_generator", None) is None:
@@ -288,7 +319,7 @@ def training(gaussians, scene, train_cameras, test_cameras, log_file, iterations
             img, _, _, _ = baseline_accumGrads_micro_step(
                 gaussians.get_xyz, gaussians.get_opacity, gaussians.get_scaling, gaussians.get_rotation,
                 gaussians.get_features, gaussians.active_sh_degree, cam, background, mode="test")
-            return apply_camera_exposure(img, cam)  # a training camera is rendered as it was trained
+            return apply_camera_bilagrid(apply_camera_exposure(img, cam), cam)  # a training camera is rendered as it was trained
     spatial = bool(getattr(args, "spatial_row_order", True)) and hasattr(gaussians, "spatial_sort") and not naive
     if spatial:
         gaussians.spatial_sort()  # rows along a Z-order curve: a camera's rows become contiguous runs
@@ -444,6 +475,9 @@ def training(gaussians, scene, train_cameras, test_cameras, log_file, iterations
         if exposure is not None:
             exposure.step(iteration)
             exposure.zero_grad()
+        if bilagrid is not None:
+            bilagrid.step(iteration)
+            bilagrid.zero_grad()
         if not defer:
             torch.cuda.synchronize()
         if iter_hook is not None:
@@ -471,7 +505,9 @@ def train_from_colmap(source_path, model_path, strategy="clm_offload", iteration
     `utils.default_args`.  `masks` / `alpha_mask`: per-pixel ignore masks of the loss (colmap_scene.load_colmap_scene).
     `exposure=True` (with `exposure_lr_init` / `exposure_lr_final`): per-camera exposure compensation of the training
     cameras (build_exposure); the table is written to `<model_path>/exposure.json` next to the ply and stays reachable as
-    `scene.exposure`.  `depths` (with `depth_l1_weight_init` / `depth_l1_weight_final`): the directory of the 16-bit
+    `scene.exposure`.  `bilagrid=True` (with `bilagrid_shape`, `bilagrid_lr_init`, `bilagrid_lr_final`,
+    `bilagrid_tv_weight`): bilateral-grid colour correction of the training cameras (build_bilagrid), written to
+    `<model_path>/bilagrid.npz`, reachable as `scene.bilagrid`; refused together with `exposure=True`.  `depths` (with `depth_l1_weight_init` / `depth_l1_weight_final`): the directory of the 16-bit
     inverse-depth PNGs of the depth regularisation (colmap_scene.load_colmap_scene); refused with `absgrad=True`.
     Returns (gaussians, scene, timer)."""
     from .colmap_scene import load_colmap_scene
@@ -486,6 +522,7 @@ def train_from_colmap(source_path, model_path, strategy="clm_offload", iteration
         args.iterations = int(iterations)
     args.depths = depths or ""
     check_depth_flags(args, bool(depths))  # raises: before anything is loaded
+    check_appearance_flags(args)  # raises: before anything is loaded
     utils.set_args(args)
     if getattr(args, "exposure", False) and dp.world_size() > 1:
         build_exposure([], args.iterations)  # raises: before anything is loaded
@@ -506,12 +543,18 @@ def train_from_colmap(source_path, model_path, strategy="clm_offload", iteration
     if getattr(args, "exposure", False):
         scene.exposure = build_exposure(scene.train_cameras, args.iterations, "cuda",
                                         float(args.exposure_lr_init), float(args.exposure_lr_final))
+    scene.bilagrid = None
+    if getattr(args, "bilagrid", False):
+        scene.bilagrid = build_bilagrid(scene.train_cameras, args.iterations, "cuda", tuple(args.bilagrid_shape),
+                                        float(args.bilagrid_lr_init), float(args.bilagrid_lr_final),
+                                        float(args.bilagrid_tv_weight))
     os.makedirs(model_path, exist_ok=True)
     prev_log = utils.get_log_file()
     try:
         with open(os.path.join(model_path, "python_ws=1_rk=0.log"), "w") as log_file:
             timer = training(gaussians, scene, scene.train_cameras, scene.test_cameras, log_file,
-                             iterations=args.iterations, test_iterations=test_iterations, exposure=scene.exposure)
+                             iterations=args.iterations, test_iterations=test_iterations, exposure=scene.exposure,
+                             bilagrid=scene.bilagrid)
     finally:
         utils.set_log_file(prev_log)  # never leave a closed file as the process-wide log
     if save:
@@ -521,6 +564,8 @@ def train_from_colmap(source_path, model_path, strategy="clm_offload", iteration
             gaussians.save_ply(os.path.join(model_path, "point_cloud", f"iteration_{args.iterations}", "point_cloud.ply"))
             if scene.exposure is not None:  # {image_name: 3x4}, the INRIA code base's exposure.json
                 scene.exposure.save_json(os.path.join(model_path, "exposure.json"), scene.train_cameras)
+            if scene.bilagrid is not None:  # grids in gsplat's [n,12,L,Hg,Wg] layout + image names
+                scene.bilagrid.save(os.path.join(model_path, "bilagrid.npz"), scene.train_cameras)
     return gaussians, scene, timer
 
 
@@ -556,6 +601,14 @@ def build_arg_parser():
                          "written to <model_path>/exposure.json (single GPU)")
     ap.add_argument("--exposure_lr_init", type=float, default=0.01)
     ap.add_argument("--exposure_lr_final", type=float, default=0.001)
+    ap.add_argument("--bilagrid", action="store_true",
+                    help="bilateral-grid colour correction (gsplat's use_bilateral_grid): a learnable lattice of 3x4 affine "
+                         "colour transforms per training image, sliced by position and luminance, written to "
+                         "<model_path>/bilagrid.npz (single GPU; not with --exposure)")
+    ap.add_argument("--bilagrid_shape", type=int, nargs=3, default=[16, 16, 8], metavar=("WG", "HG", "L"))
+    ap.add_argument("--bilagrid_lr_init", type=float, default=2e-3)
+    ap.add_argument("--bilagrid_lr_final", type=float, default=2e-5)
+    ap.add_argument("--bilagrid_tv_weight", type=float, default=10.0)
     ap.add_argument("-d", "--depths", default=None, metavar="DIR",
                     help="depth regularisation: directory (relative to the source path or absolute) of 16-bit inverse-depth "
                          "PNGs NAME.png, scaled by sparse/0/depth_params.json; an L1 term on the rendered inverse depth "
@@ -588,6 +641,9 @@ if __name__ == "__main__":  # python -m clm_gs_amd.trainer -s <colmap dir> -m <o
                                 absgrad=a.absgrad, rasterize_mode="antialiased" if a.antialiased else "classic",
                                 masks=a.masks, alpha_mask=a.alpha_mask, exposure=a.exposure,
                                 exposure_lr_init=a.exposure_lr_init, exposure_lr_final=a.exposure_lr_final,
+                                bilagrid=a.bilagrid, bilagrid_shape=tuple(a.bilagrid_shape),
+                                bilagrid_lr_init=a.bilagrid_lr_init, bilagrid_lr_final=a.bilagrid_lr_final,
+                                bilagrid_tv_weight=a.bilagrid_tv_weight,
                                 depths=a.depths, depth_l1_weight_init=a.depth_l1_weight_init,
                                 depth_l1_weight_final=a.depth_l1_weight_final, mcmc=a.mcmc, mcmc_cap_max=a.cap_max,
                                 mcmc_noise_lr=a.mcmc_noise_lr, mcmc_refine_start_iter=a.mcmc_refine_start_iter,

@@ -48,6 +48,10 @@ def default_args(**over):
         # this build: per-camera exposure compensation (exposure.ExposureModel; the INRIA code base's --exposure_lr_init /
         # --exposure_lr_final): a learnable 3x4 affine colour transform per TRAINING image, between the rasterizer and the loss
         exposure=False, exposure_lr_init=0.01, exposure_lr_final=0.001,
+        # this build: bilateral-grid colour correction (bilagrid.BilagridModel; gsplat's use_bilateral_grid): a learnable
+        # (Wg, Hg, L) lattice of 3x4 affine colour transforms per TRAINING image, sliced by position and luminance, between
+        # the rasterizer and the loss; bilagrid_tv_weight x its total variation is added to the objective
+        bilagrid=False, bilagrid_shape=(16, 16, 8), bilagrid_lr_init=2e-3, bilagrid_lr_final=2e-5, bilagrid_tv_weight=10.0,
         # this build: depth regularisation (the INRIA code base's -d / --depths, --depth_l1_weight_init / _final): an L1 term
         # between the rendered inverse depth and the inverse-depth prior of every training camera that carries one
         # (cameras.camera_invdepth), weighted by depth_l1_weight() below.  depths: the directory of the 16-bit PNGs

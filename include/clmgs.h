@@ -539,6 +539,32 @@ int clmgs_mcmc_reg_grad(void* stream, int64_t n, const float* opacity_raw, int64
 int clmgs_mcmc_noise(void* stream, int64_t n, float* xyz, const float* opacity_raw, const float* scaling_raw,
                      const float* rotation_raw, const float* noise, float scaler, float* packed_mirror);
 
+/* ---- bilateral-grid colour correction (csrc/bilagrid.hip; gsplat's use_bilateral_grid operator)
+ * grid_dev: DEVICE pointer to float32 [L][Hg][Wg][12], coefficient 4c + k = A[c][k]; 2 <= Wg, Hg <= 64, 2 <= L <= 32
+ * (anything else: CLMGS_EINVAL).  x, y, g, v_x are [3,H,W] VIEWS given by their element strides (c, y, x), as for the
+ * exposure entries.  With u = (px + .5) / W, v = (py + .5) / H, s = .299 x[0] + .587 x[1] + .114 x[2], A the trilinear
+ * interpolation (align_corners, border) of the grid at (u, v, clamp(s, 0, 1)), every lerp fmaf(t, b - a, a):
+ *   fwd:  y[c] = A[c][0] x[0] + A[c][1] x[1] + A[c][2] x[2] + A[c][3]             (y must not alias x)
+ *   bwd:  v_x[k] = sum_c A[c][k] g[c] + lum[k] (L - 1) [0 < s < 1] sum_{c,k'} (A_hi - A_lo)[c][k'] g[c] x[k'] (x[3] = 1);
+ *         v_x MAY BE g itself (same pointer and strides: in place).  Each workgroup STORES one row of L x 48 floats into
+ *         partials[clmgs_bilagrid_partials_rows(H, W, Hg, Wg)][L * 48] (every row is written; nothing to zero).
+ *   grad_finish: per grid element, the rows of its at most four cells summed in a fixed order and ADDED into
+ *         grad[L][Hg][Wg][12]: dL/dG[node][4c + k] = sum_p w_node(p) g[c] x[k].  H, W as given to bwd.
+ *   tv_grad: grad[n][L][Hg][Wg][12] += d(weight * tv)/dtable, tv = (1/n) sum_axis sum (G[i+1] - G[i])^2 / count_axis,
+ *         count_axis = 12 x the differences along the axis in one grid.  16-byte aligned tables.
+ * No float atomics: the same inputs give the same bits on every run. */
+int clmgs_bilagrid_partials_rows(int H, int W, int Hg, int Wg);
+int clmgs_bilagrid_fwd(void* stream, int H, int W, const float* x, int64_t stride_c, int64_t stride_y,
+                       int64_t stride_x, const float* grid_dev, int L, int Hg, int Wg, float* y, int64_t ystride_c,
+                       int64_t ystride_y, int64_t ystride_x);
+int clmgs_bilagrid_bwd(void* stream, int H, int W, const float* x, int64_t stride_c, int64_t stride_y,
+                       int64_t stride_x, const float* grid_dev, int L, int Hg, int Wg, const float* g,
+                       int64_t gstride_c, int64_t gstride_y, int64_t gstride_x, float* v_x, int64_t vstride_c,
+                       int64_t vstride_y, int64_t vstride_x, float* partials);
+int clmgs_bilagrid_grad_finish(void* stream, int H, int W, int L, int Hg, int Wg, const float* partials, float* grad);
+int clmgs_bilagrid_tv_grad(void* stream, const float* table, int64_t n, int L, int Hg, int Wg, float weight,
+                           float* grad);
+
 /* ---- clm_kernels row movers  (clm_offload/engine.py:499-505, 622-636, 789-802, 815-822)
  * dst/src may be device memory or pinned (mapped) host memory.
  * gather:      dst[dst_idx ? dst_idx[i] : i] = src[src_idx ? src_idx[i] : i]
