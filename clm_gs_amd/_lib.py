@@ -85,6 +85,12 @@ SIGNATURES = {
     "clmgs_bilagrid_bwd": (_i, [_vp, _i, _i, _vp, _i64, _i64, _i64, _vp, _i, _i, _i, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp]),
     "clmgs_bilagrid_grad_finish": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "clmgs_bilagrid_tv_grad": (_i, [_vp, _vp, _i64, _i, _i, _i, _f, _vp]),
+    # camera pose refinement: the inputs of clmgs_preprocess_bwd -> 16 floats per workgroup; the operator form
+    "clmgs_pose_grad_partials_rows": (_i, [_i]),
+    "clmgs_pose_grad": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "clmgs_pose_grad_finish": (_i, [_vp, _i, _vp, _vp]),
+    "clmgs_projection_viewmat_partials_rows": (_i, [_i]),
+    "clmgs_projection_viewmat_bwd": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "clmgs_invdepth_partials_rows": (_i, [_i, _i]),
     "clmgs_invdepth_pack": (_i, [_vp, _i, _vp, _vp, _vp]),
     "clmgs_invdepth_l1_fwd_bwd": (_i, [_vp, _i, _i, _vp, _i64, _i64, _vp, _f, _f, _vp, _f, _vp, _i64, _i64, _vp]),
@@ -163,7 +169,7 @@ class _Namespace:
     pass
 
 
-_NO_STREAM = {"clmgs_version", "clmgs_loss_slots", "clmgs_exposure_partials_rows", "clmgs_bilagrid_partials_rows", "clmgs_invdepth_partials_rows", "clmgs_small_deferred_kmax", "clmgs_isect3_front_temp_bytes",
+_NO_STREAM = {"clmgs_version", "clmgs_loss_slots", "clmgs_exposure_partials_rows", "clmgs_bilagrid_partials_rows", "clmgs_invdepth_partials_rows", "clmgs_pose_grad_partials_rows", "clmgs_projection_viewmat_partials_rows", "clmgs_small_deferred_kmax", "clmgs_isect3_front_temp_bytes",
               "clmgs_isect3_bin_temp_bytes", "clmgs_last_error", "clmgs_isect_count_temp_bytes",
               "clmgs_isect_sort_temp_bytes", "clmgs_host_groups_temp_bytes", "clmgs_isect2_order_temp_bytes", "clmgs_isect2_sort_temp_bytes", "clmgs_visibility_select_temp_bytes", "clmgs_rasterize_pack_bytes", "clmgs_rasterize_partials_bytes", "clmgs_host_adam_rows", "clmgs_host_pool_start", "clmgs_host_usable_cpus", "clmgs_host_rows_prepare", "clmgs_tsp_tour",
               "clmgs_pinned_alloc", "clmgs_pinned_free", "clmgs_device_errors"}

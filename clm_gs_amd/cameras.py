@@ -5,7 +5,9 @@ original_image (uint8 [3,H,W] on the GPU), image_name, create_k_on_gpu(); plus l
 and loss_mask_count, the per-pixel ignore mask of the training loss.  A training camera may also carry `exposure` /
 `exposure_grad`, float32 [3,4] views of its rows in an exposure.ExposureModel (camera_exposure below), or `bilagrid` /
 `bilagrid_grad`, float32 [L,Hg,Wg,12] views of its grids in a bilagrid.BilagridModel (camera_bilagrid), and `invdepth`
-(uint16 [H,W]) with `invdepth_scale` / `invdepth_offset`, its monocular inverse-depth prior (camera_invdepth below)."""
+(uint16 [H,W]) with `invdepth_scale` / `invdepth_offset`, its monocular inverse-depth prior (camera_invdepth below), and
+`pose_grad`, the float32 [15] buffer its pose gradient is added into (camera_pose_grad; pose.PoseModel rewrites
+world_view_transform, camtoworlds and the cached host triple of a camera whose pose it has moved)."""
 import math
 
 import numpy as np
@@ -57,6 +59,13 @@ def camera_bilagrid(camera):
         raise ValueError("a camera carries both an exposure row and a bilateral grid: the order of composition is not "
                          "defined; train with --exposure or with --bilagrid")
     return grid, getattr(camera, "bilagrid_grad", None)
+
+
+def camera_pose_grad(camera):
+    """The camera's pose-gradient buffer -- float32 [15] on the device, v_R 9 | v_t 3 | v_campos 3, a view of its row in a
+    pose.PoseModel (`camera.pose_grad`) that the kernels of csrc/pose.hip ADD into -- or None: a camera without the
+    attribute, or with None, is trained exactly as before (nothing more is launched)."""
+    return getattr(camera, "pose_grad", None)
 
 
 class Camera:

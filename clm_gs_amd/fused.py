@@ -13,7 +13,7 @@ import torch
 
 from . import _lib, utils
 from ._lib import check, dptr
-from .cameras import camera_bilagrid, camera_exposure, camera_invdepth, camera_loss_mask
+from .cameras import camera_bilagrid, camera_exposure, camera_invdepth, camera_loss_mask, camera_pose_grad
 from .clm_kernels import check_depth_prior_args, masked_loss_value
 from .gsplat import (_record_counts, bucket_size, empty_bucketed, isect2_begin, isect2_counts, isect2_finish, isect3_begin,
                      isect3_finish)
@@ -65,7 +65,7 @@ class _CameraPass:
                  "lambda_dssim", "gt_u8", "background", "isect", "sh_index", "means2d", "n_dev", "antialiased",
                  "loss_mask", "mask_count", "exposure", "exposure_grad", "exp_partials",
                  "bilagrid", "bilagrid_grad", "bg_partials",
-                 "invdepth", "depth_weight", "depths", "id_partials", "id_term")
+                 "invdepth", "depth_weight", "depths", "id_partials", "id_term", "pose_grad")
 
 
 def _sptr(torch_stream):
@@ -168,6 +168,19 @@ def camera_front(gaussians, camera, this_filter, sh_rows, sh_by_filter, backgrou
         if tuple(raw.shape) != (H, W) or raw.dtype != U16:
             raise _lib.ClmgsError(f"camera.invdepth must be uint16 [{H}, {W}], got {raw.dtype} {tuple(raw.shape)}")
         p.depth_weight = utils.depth_l1_weight()  # of the current iteration, read once per camera
+    # a pose-gradient buffer on the camera (pose refinement): camera_backward launches the camera-gradient kernel after the
+    # row backward; without one, not one launch differs.  Refused with a depth prior, here, before anything is enqueued:
+    # the fourth channel's cotangent reaches the positions outside the projection VJP.
+    p.pose_grad = camera_pose_grad(camera)
+    if p.pose_grad is not None:
+        if p.invdepth is not None:
+            raise ValueError("a camera carries both a pose-gradient buffer and an inverse-depth prior: pose refinement is not "
+                             "supported with the depth regularisation")
+        if tuple(p.pose_grad.shape) != (15,) or p.pose_grad.dtype != F32 or not p.pose_grad.is_contiguous():
+            raise _lib.ClmgsError(f"camera.pose_grad must be contiguous float32 [15], got {p.pose_grad.dtype} "
+                                  f"{tuple(p.pose_grad.shape)}")
+        if sh_index is not None or not sh_rows.is_cuda:
+            raise ValueError("pose refinement needs the SH rows in HBM (sh_residency=\"hbm\")")
     p.antialiased = utils.antialiased()  # the backward follows the mode its forward ran in
     filt = p.filt = this_filter.contiguous() if this_filter is not None else None  # None: all rows
     if small_packed is not None:
@@ -475,6 +488,17 @@ def camera_backward(gaussians, p, g_sh_rows, small_grad=None, update_stats=True,
             None, *small_out, dptr(g_sh_rows, F32, allow_host=True),
             *stat_ptrs, None, int(bool(stats_only_visible)), dptr(partials), dptr(p.row_cum),
             dptr(p.sh_index, I32, True), dptr(sh_stamp, I32, True), int(cur_step), *((None,) if absgrad else ())))
+        if p.pose_grad is not None:
+            # the camera's own gradient, from the same lines and rows, directly behind the row backward on the memory
+            # stream (partials, row_cum, radii and the row inputs are alive here): one row of 16 floats per workgroup,
+            # allocated, written and read on s_mem only, summed in a fixed order and added to the camera's buffer ONCE
+            pose_rows = torch.empty((int(L.clmgs_pose_grad_partials_rows(V)), 16), dtype=F32, device=dev)
+            check(L.clmgs_pose_grad(
+                _sptr(s_mem), V, dptr(p.filt, torch.int64, True), *p.small_in, dptr(p.sh_rows, F32),
+                int(p.sh_by_filter), _np(vm), _np(K), _np(campos), W, H, p.deg, 0.3, dptr(p.radii), None,
+                dptr(partials), dptr(p.row_cum), None, int(bool(p.antialiased)), dptr(pose_rows)))
+            check(L.clmgs_pose_grad_finish(_sptr(s_mem), int(pose_rows.shape[0]), dptr(pose_rows), dptr(p.pose_grad, F32)))
+            del pose_rows
         if p.invdepth is not None:
             # dL/d(1/z) -> the xyz gradient, on the memory stream directly after the camera's preprocess backward: that
             # kernel's first-touch store has initialised the row for this step (and accumulated into it otherwise), so

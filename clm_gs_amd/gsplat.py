@@ -17,6 +17,25 @@ from ._lib import check, dptr, stream
 F32, I32, I64 = torch.float32, torch.int32, torch.int64
 
 
+def _viewmats_grad(ctx, means, quats, scales, viewmats, Ks, radii, v_means2d, v_depths, v_conics, v_comps):
+    """gsplat's v_viewmats (fully_fused_projection with viewmats_requires_grad): [C,4,4], rows 0..2 = v_R | v_t, row 3
+    zero -- clmgs_projection_viewmat_bwd, launched only when the view matrices ask for a gradient."""
+    if not ctx.needs_input_grad[3]:
+        return None
+    L = _lib.lib()
+    width, height, eps2d = ctx.cfg
+    C, N = radii.shape
+    rows = int(L.clmgs_projection_viewmat_partials_rows(N))
+    partials = torch.empty((C * max(rows, 1), 16), dtype=F32, device=means.device)
+    v_viewmats = torch.empty((C, 4, 4), dtype=F32, device=means.device)
+    check(L.clmgs_projection_viewmat_bwd(
+        stream(), C, N, dptr(means), dptr(quats), dptr(scales), dptr(viewmats), dptr(Ks), width, height, eps2d,
+        dptr(radii), dptr(v_means2d, F32), dptr(v_depths, F32, True), dptr(v_conics, F32), dptr(v_comps, F32, True),
+        dptr(partials), dptr(v_viewmats)))
+    return v_viewmats
+
+
+
 # --------------------------------------------------------------------- projection
 class _Projection(torch.autograd.Function):
     @staticmethod
@@ -61,7 +80,8 @@ class _Projection(torch.autograd.Function):
             stream(), C, N, dptr(means), dptr(quats), dptr(scales), dptr(viewmats), dptr(Ks),
             width, height, eps2d, dptr(radii), dptr(v_means2d, F32), dptr(v_depths, F32, True),
             dptr(v_conics, F32), dptr(v_means), dptr(v_quats), dptr(v_scales)))
-        return v_means, v_quats, v_scales, None, None, None, None, None, None, None, None
+        v_viewmats = _viewmats_grad(ctx, means, quats, scales, viewmats, Ks, radii, v_means2d, v_depths, v_conics, None)
+        return v_means, v_quats, v_scales, v_viewmats, None, None, None, None, None, None, None
 
 
 class _ProjectionAA(torch.autograd.Function):
@@ -111,7 +131,8 @@ class _ProjectionAA(torch.autograd.Function):
             stream(), C, N, dptr(means), dptr(quats), dptr(scales), dptr(viewmats), dptr(Ks),
             width, height, eps2d, dptr(radii), dptr(v_means2d, F32), dptr(v_depths, F32, True),
             dptr(v_conics, F32), dptr(v_comps, F32, True), dptr(v_means), dptr(v_quats), dptr(v_scales)))
-        return v_means, v_quats, v_scales, None, None, None, None, None, None, None, None
+        v_viewmats = _viewmats_grad(ctx, means, quats, scales, viewmats, Ks, radii, v_means2d, v_depths, v_conics, v_comps)
+        return v_means, v_quats, v_scales, v_viewmats, None, None, None, None, None, None, None
 
 
 def fully_fused_projection(means, covars, quats, scales, viewmats, Ks, width, height, eps2d=0.3,
@@ -123,6 +144,8 @@ def fully_fused_projection(means, covars, quats, scales, viewmats, Ks, width, he
     Packed (no grad; strategies/base_engine.py:36-47 uses it under no_grad only)
     -> (camera_ids, gaussian_ids, radii, means2d, depths, conics, compensations), ordered
     by (camera, gaussian).
+    The view matrices receive a gradient ([C,4,4], gsplat's viewmats_requires_grad) when `viewmats.requires_grad`;
+    otherwise nothing more is launched.
     compensations: None, or with calc_compensations=True (gsplat's; Mip-Splatting) the differentiable opacity
     factors sqrt(max(0, det(cov2d) / det(cov2d + eps2d I))), [C,N] with 0 where culled (packed: [nnz]).
     """

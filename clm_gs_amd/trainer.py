@@ -20,6 +20,7 @@ from . import dp, mcmc, utils
 from .cameras import camera_loss_mask
 from .clm_kernels import apply_camera_bilagrid, apply_camera_exposure
 from .densification import check_mcmc_args, gsplat_densification, mcmc_refinement
+from .pose import check_pose_args
 
 
 class End2endTimer:
@@ -270,14 +271,29 @@ def build_bilagrid(train_cameras, iterations, device="cuda", grid=(16, 16, 8), l
     return model
 
 
+def build_pose(train_cameras, iterations, device="cuda", lr=1e-5, reg=1e-6, noise=0.0, defer=True, seed=0):
+    """`--pose_opt`: a pose.PoseModel with one row per TRAINING camera, attached to the cameras (test cameras carry no
+    buffer and are evaluated as loaded).  `noise` > 0: gsplat's pose_noise, a seeded perturbation of the training poses."""
+    from .pose import PoseModel
+    model = PoseModel(len(train_cameras), lr=lr, reg=reg, max_steps=int(iterations), defer=defer, device=device)
+    model.attach(train_cameras)
+    if noise:
+        model.perturb(float(noise), seed=seed)
+    return model
+
+
 def training(gaussians, scene, train_cameras, test_cameras, log_file, iterations=None,
-             test_iterations=(), background=None, shuffle_seed=0, phase_times=None, exposure=None, bilagrid=None):
+             test_iterations=(), background=None, shuffle_seed=0, phase_times=None, exposure=None, bilagrid=None,
+             pose=None):
     """Runs `iterations` images of training; returns the End2endTimer.
     `exposure` (optional exposure.ExposureModel, attached to the training cameras): stepped at the scheduled learning
     rate and zeroed after every batch, on the current stream -- every engine has joined its camera streams into it by
     the time it returns.  A row's gradient is its camera's alone and is not divided by the batch size.
     `bilagrid` (optional bilagrid.BilagridModel): likewise, next to the exposure step; its step adds the gradient of the
     total-variation term before Adam.
+    `pose` (optional pose.PoseModel, attached to the training cameras): stepped next to the exposure step with the
+    gradients of the batch's cameras; deferred by one batch unless the model was built with defer=False (pose.py).
+    Training cameras are evaluated at their refined pose, test cameras as loaded.
     `phase_times` (optional dict): host wall time per phase inside the end-to-end clock is accumulated into it
     ("engine" = enqueueing the batches, "densify" = gsplat_densification incl. the device work it waits for,
     "resort" = the Z-order re-sort after a densification, "log" = waiting for loss values, "final_sync"); a callable under
@@ -365,6 +381,8 @@ def training(gaussians, scene, train_cameras, test_cameras, log_file, iterations
     depth_priors = any(getattr(c, "invdepth", None) is not None for c in train_cameras)
     check_depth_flags(args, depth_priors)
     check_mcmc_args(args)
+    if pose is not None:
+        check_pose_args(args, depth_priors, enabled=True)  # a model handed in is refused like the flag
     use_mcmc = mcmc.enabled(args)
     loss_log = _LossLog(log_file, defer)
     pt = phase_times if phase_times is not None else {}
@@ -438,6 +456,8 @@ def training(gaussians, scene, train_cameras, test_cameras, log_file, iterations
         _acc("log", _t)
         if any(iteration <= t < iteration + gbsz for t in test_iterations):
             loss_log.flush()
+            if pose is not None:
+                pose.flush()  # training cameras are evaluated at their refined pose
             timer.stop()  # evaluation is excluded from the throughput figure
             _check_device()
             if hasattr(gaussians, "flush_lazy_rows"):  # deferred row steps (and, owner-computes DP, the exchange)
@@ -478,12 +498,16 @@ def training(gaussians, scene, train_cameras, test_cameras, log_file, iterations
         if bilagrid is not None:
             bilagrid.step(iteration)
             bilagrid.zero_grad()
+        if pose is not None:
+            pose.step(batch)
         if not defer:
             torch.cuda.synchronize()
         if iter_hook is not None:
             iter_hook(iteration)
     _t = time.perf_counter()
     loss_log.flush()
+    if pose is not None:
+        pose.flush()
     timer.stop()
     _acc("final_sync", _t)
     _check_device()
@@ -509,6 +533,9 @@ def train_from_colmap(source_path, model_path, strategy="clm_offload", iteration
     `bilagrid_tv_weight`): bilateral-grid colour correction of the training cameras (build_bilagrid), written to
     `<model_path>/bilagrid.npz`, reachable as `scene.bilagrid`; refused together with `exposure=True`.  `depths` (with `depth_l1_weight_init` / `depth_l1_weight_final`): the directory of the 16-bit
     inverse-depth PNGs of the depth regularisation (colmap_scene.load_colmap_scene); refused with `absgrad=True`.
+    `pose_opt=True` (with `pose_opt_lr`, `pose_opt_reg`, `pose_noise`, `defer_pose_step`): camera pose refinement of the
+    training cameras (build_pose), written to `<model_path>/poses.json`, reachable as `scene.pose`; refusals:
+    pose.check_pose_args.
     Returns (gaussians, scene, timer)."""
     from .colmap_scene import load_colmap_scene
     from .strategies.clm_offload import GaussianModelCLMOffload
@@ -523,6 +550,7 @@ def train_from_colmap(source_path, model_path, strategy="clm_offload", iteration
     args.depths = depths or ""
     check_depth_flags(args, bool(depths))  # raises: before anything is loaded
     check_appearance_flags(args)  # raises: before anything is loaded
+    check_pose_args(args, bool(depths))  # raises: before anything is loaded
     utils.set_args(args)
     if getattr(args, "exposure", False) and dp.world_size() > 1:
         build_exposure([], args.iterations)  # raises: before anything is loaded
@@ -548,13 +576,17 @@ def train_from_colmap(source_path, model_path, strategy="clm_offload", iteration
         scene.bilagrid = build_bilagrid(scene.train_cameras, args.iterations, "cuda", tuple(args.bilagrid_shape),
                                         float(args.bilagrid_lr_init), float(args.bilagrid_lr_final),
                                         float(args.bilagrid_tv_weight))
+    scene.pose = None
+    if getattr(args, "pose_opt", False):
+        scene.pose = build_pose(scene.train_cameras, args.iterations, "cuda", float(args.pose_opt_lr),
+                                float(args.pose_opt_reg), float(args.pose_noise), bool(args.defer_pose_step))
     os.makedirs(model_path, exist_ok=True)
     prev_log = utils.get_log_file()
     try:
         with open(os.path.join(model_path, "python_ws=1_rk=0.log"), "w") as log_file:
             timer = training(gaussians, scene, scene.train_cameras, scene.test_cameras, log_file,
                              iterations=args.iterations, test_iterations=test_iterations, exposure=scene.exposure,
-                             bilagrid=scene.bilagrid)
+                             bilagrid=scene.bilagrid, pose=scene.pose)
     finally:
         utils.set_log_file(prev_log)  # never leave a closed file as the process-wide log
     if save:
@@ -566,6 +598,8 @@ def train_from_colmap(source_path, model_path, strategy="clm_offload", iteration
                 scene.exposure.save_json(os.path.join(model_path, "exposure.json"), scene.train_cameras)
             if scene.bilagrid is not None:  # grids in gsplat's [n,12,L,Hg,Wg] layout + image names
                 scene.bilagrid.save(os.path.join(model_path, "bilagrid.npz"), scene.train_cameras)
+            if scene.pose is not None:  # {image_name: {"delta": [9], "world_to_camera": 4x4}}
+                scene.pose.save_json(os.path.join(model_path, "poses.json"), scene.train_cameras)
     return gaussians, scene, timer
 
 
@@ -615,6 +649,15 @@ def build_arg_parser():
                          "of every training image with a reliable prior (not with --absgrad)")
     ap.add_argument("--depth_l1_weight_init", type=float, default=1.0)
     ap.add_argument("--depth_l1_weight_final", type=float, default=0.01)
+    ap.add_argument("--pose_opt", action="store_true",
+                    help="camera pose refinement (gsplat's pose_opt): a learnable rigid correction per training image, "
+                         "written to <model_path>/poses.json (fused front end, SH rows in HBM, single GPU; not with --depths)")
+    ap.add_argument("--pose_opt_lr", type=float, default=1e-5)
+    ap.add_argument("--pose_opt_reg", type=float, default=1e-6)
+    ap.add_argument("--pose_noise", type=float, default=0.0,
+                    help="--pose_opt: seeded random perturbation of the training poses at the start (experiments)")
+    ap.add_argument("--immediate_pose_step", action="store_true",
+                    help="--pose_opt: apply a batch's pose step before the next batch is enqueued (the host waits)")
     ap.add_argument("--mcmc", action="store_true",
                     help="3DGS-MCMC densification (gsplat's MCMCStrategy): a fixed budget of --cap_max Gaussians, dead ones "
                          "relocated instead of pruned, 5 %% growth per refinement, position noise after every step "
@@ -649,4 +692,6 @@ if __name__ == "__main__":  # python -m clm_gs_amd.trainer -s <colmap dir> -m <o
                                 mcmc_noise_lr=a.mcmc_noise_lr, mcmc_refine_start_iter=a.mcmc_refine_start_iter,
                                 mcmc_refine_stop_iter=a.mcmc_refine_stop_iter, mcmc_refine_every=a.mcmc_refine_every,
                                 mcmc_min_opacity=a.mcmc_min_opacity, mcmc_opacity_reg=a.mcmc_opacity_reg,
-                                mcmc_scale_reg=a.mcmc_scale_reg)
+                                mcmc_scale_reg=a.mcmc_scale_reg, pose_opt=a.pose_opt, pose_opt_lr=a.pose_opt_lr,
+                                pose_opt_reg=a.pose_opt_reg, pose_noise=a.pose_noise,
+                                defer_pose_step=not a.immediate_pose_step)

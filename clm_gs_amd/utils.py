@@ -63,6 +63,12 @@ def default_args(**over):
         # prune heuristic and the opacity reset (densification.mcmc_refinement); refused combinations: check_mcmc_args
         mcmc=False, mcmc_cap_max=1_000_000, mcmc_noise_lr=5e5, mcmc_refine_start_iter=500, mcmc_refine_stop_iter=25_000,
         mcmc_refine_every=100, mcmc_min_opacity=0.005, mcmc_opacity_reg=0.01, mcmc_scale_reg=0.01,
+        # this build: camera pose refinement (pose.PoseModel; gsplat's pose_opt / pose_opt_lr / pose_opt_reg / pose_noise): a
+        # learnable rigid correction per TRAINING camera, trained by the gradient of the loss with respect to the camera
+        # (csrc/pose.hip), dense Adam with weight decay pose_opt_reg, learning rate pose_opt_lr decaying to 0.01 x over the
+        # run.  pose_noise: a seeded random perturbation of the training poses at the start (experiments).
+        # defer_pose_step: the step of batch b is applied once batch b+1 is enqueued (pose.py); refusals: pose.check_pose_args
+        pose_opt=False, pose_opt_lr=1e-5, pose_opt_reg=1e-6, pose_noise=0.0, defer_pose_step=True,
         lr_scale_mode="sqrt", bsz=1, exact_filter=True, log_cpu_adam_trailing_overhead=False,
         # Debug
         stop_update_param=False, drop_initial_3dgs_p=0.0,

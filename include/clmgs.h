@@ -565,6 +565,43 @@ int clmgs_bilagrid_grad_finish(void* stream, int H, int W, int L, int Hg, int Wg
 int clmgs_bilagrid_tv_grad(void* stream, const float* table, int64_t n, int L, int Hg, int Wg, float weight,
                            float* grad);
 
+/* ---- camera pose refinement (csrc/pose.hip, csrc/pose_math.h; gsplat's pose_opt: the gradient of the loss with
+ * respect to the camera).  For the world-to-camera matrix [Rv | t] and the camera centre c the front end was run
+ * with, over the rows i with radii[i] > 0:
+ *     v_R[9] = sum_i (vp_i m_i^T + 2 vS_i Rv Sigma_i)   v_t[3] = sum_i vp_i   v_campos[3] = -sum_i vd_i
+ * vp_i / vS_i: the camera-space mean / covariance cotangents of the projection VJP; vd_i: the direction cotangent of
+ * the SH VJP with the clamp mask applied (0 at degree 0).  c is NOT assumed to be -Rv^T t: the three stay apart and the
+ * host composes them.
+ *   pose_grad: replaces fully_fused_projection(viewmats_requires_grad=True)'s v_viewmats[:3, :4] (v_R | v_t) and the
+ *             autograd of dirs = means - camtoworlds[:3, 3] (v_campos) of gsplat's rasterization() for ONE camera of the
+ *             fused front end.  The inputs, and the argument checks, are those of clmgs_preprocess_bwd: rows, SH rows
+ *             (not read at degree 0, may be NULL there), HOST camera constants, radii, and the cotangent lines either as
+ *             packed_grad[V,16] or as partials + row_cum (exactly one; a row's lines are summed in ascending slot order,
+ *             as clmgs_preprocess_bwd sums them).  antialiased != 0: for records of clmgs_preprocess_aa_fwd
+ *             (v_compensation = go * op).  Each workgroup STORES one row of 16 floats  v_R | v_t | v_campos | 0  into
+ *             partials_out[clmgs_pose_grad_partials_rows(V)][16] (every row is written; nothing to zero).
+ *   pose_grad_finish: one wave sums the `rows` rows in ascending order and ADDS the 15 sums into grad15, once.
+ *   projection_viewmat_bwd: replaces the v_viewmats output of gsplat's fully_fused_projection backward
+ *             (viewmats_requires_grad=True), operator form: the arguments of clmgs_projection_aa_bwd (v_compensations
+ *             NULL: the plain projection; v_depths optional, added to vp_i[2]), partials
+ *             [C * clmgs_projection_viewmat_partials_rows(N)][16] scratch (one row per workgroup), and v_viewmats
+ *             [C,16], STORED: rows 0..2 of the 4x4 = v_R | v_t, row 3 = 0.
+ * No float atomics: the same inputs give the same bits on every run.  Bad arguments return CLMGS_EINVAL before
+ * anything is written. */
+int clmgs_pose_grad_partials_rows(int V);
+int clmgs_pose_grad(void* stream, int V, const int64_t* filter, const float* xyz, const float* opacity_raw,
+                    const float* scaling_raw, const float* rotation_raw, const float* sh_rows, int sh_by_filter,
+                    const float* viewmat_host, const float* K_host, const float* campos_host, int width, int height,
+                    int degree, float eps2d, const int32_t* radii, const void* packed_grad, const void* partials,
+                    const int64_t* row_cum, const int32_t* sh_index, int antialiased, float* partials_out);
+int clmgs_pose_grad_finish(void* stream, int rows, const float* partials, float* grad15);
+int clmgs_projection_viewmat_partials_rows(int N);
+int clmgs_projection_viewmat_bwd(void* stream, int C, int N, const float* means, const float* quats,
+                                 const float* scales, const float* viewmats, const float* Ks, int width, int height,
+                                 float eps2d, const int32_t* radii, const float* v_means2d, const float* v_depths,
+                                 const float* v_conics, const float* v_compensations, float* partials,
+                                 float* v_viewmats);
+
 /* ---- clm_kernels row movers  (clm_offload/engine.py:499-505, 622-636, 789-802, 815-822)
  * dst/src may be device memory or pinned (mapped) host memory.
  * gather:      dst[dst_idx ? dst_idx[i] : i] = src[src_idx ? src_idx[i] : i]
