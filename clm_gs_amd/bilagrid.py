@@ -6,8 +6,8 @@ luminance and regularised by a total-variation term.
 
 The model holds the two tables [n, L, Hg, Wg, 12] and their optimizer; the slice, its gradients and the gradient of the
 total-variation term are the kernels of csrc/bilagrid.hip, reached through fused.camera_forward_finish (the engines) and
-clm_kernels.apply_bilagrid (the op-by-op path, evaluation).  A camera takes part by carrying views of its rows
-(`attach`); cameras.camera_bilagrid reads them.
+clm_kernels.apply_bilagrid (the op-by-op path, evaluation), both through the one description clm_kernels.COLOUR["bilagrid"].
+A camera takes part by carrying views of its rows (colour_model.ColourModel.attach); cameras.camera_colour reads them.
 
 Optimizer: a dense torch.optim.Adam with eps 1e-15 (gsplat's).  The learning rate comes from this project's
 utils.get_expon_lr_func(lr_init, lr_final, lr_delay_steps=1000, lr_delay_mult=0.01) -- a log-linear decay with a sine
@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import utils
+from .colour_model import ColourModel
 
 IDENTITY = (1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0)
 
@@ -30,29 +31,19 @@ def tv_value(table):
             + (dx * dx).sum() / (12 * L * Hg * (Wg - 1))) / n
 
 
-class BilagridModel:
+class BilagridModel(ColourModel):
+    KIND = "bilagrid"
+
     def __init__(self, n_cameras, device, grid=(16, 16, 8), lr_init=2e-3, lr_final=2e-5, max_steps=30000, tv_weight=10.0):
-        self.n_cameras = int(n_cameras)
         Wg, Hg, L = (int(v) for v in grid)  # gsplat's order: grid_X, grid_Y, grid_W (the guidance axis)
         if not (2 <= Wg <= 64 and 2 <= Hg <= 64 and 2 <= L <= 32):
             raise ValueError(f"bilateral grid shape (Wg, Hg, L) = {(Wg, Hg, L)}: 2 <= Wg, Hg <= 64 and 2 <= L <= 32")
         self.shape = (L, Hg, Wg)
         self.tv_weight = float(tv_weight)
-        # the leaf the optimizer steps; cameras get views of its storage that carry no autograd history
-        eye = torch.tensor(IDENTITY, dtype=torch.float32)
-        self.param = eye.repeat(self.n_cameras, L, Hg, Wg, 1).to(device).contiguous().requires_grad_(True)
-        self.grad = torch.zeros_like(self.param)
-        self.param.grad = self.grad  # the kernels ADD into rows of this table; zero_grad() clears it in place
+        super().__init__(torch.tensor(IDENTITY, dtype=torch.float32).repeat(int(n_cameras), L, Hg, Wg, 1).to(device))
         self.optimizer = torch.optim.Adam([self.param], lr=float(lr_init), eps=1e-15)
         self.lr_func = utils.get_expon_lr_func(lr_init, lr_final, lr_delay_steps=1000, lr_delay_mult=0.01,
                                                max_steps=max_steps)
-
-    def attach(self, cameras):
-        """camera i of the list trains grid i: `camera.bilagrid` / `camera.bilagrid_grad` are VIEWS of the tables."""
-        assert len(cameras) == self.n_cameras, (len(cameras), self.n_cameras)
-        rows = self.param.detach()
-        for i, c in enumerate(cameras):
-            c.bilagrid, c.bilagrid_grad = rows[i], self.grad[i]
 
     def tv(self):
         """The total-variation value (0-dim tensor), in torch: for logging and tests only; the training step takes the
@@ -73,21 +64,9 @@ class BilagridModel:
         else:
             self.grad += tv_grad_reference(self.param.detach(), self.tv_weight)
 
-    def step(self, iteration):
-        """The total-variation gradient into the table, then one Adam step at the scheduled learning rate; enqueued on
-        the current stream, which must be ordered after the streams the cameras' gradient kernels ran on (the engines
-        join them at the end of a batch)."""
-        lr = float(self.lr_func(iteration))
-        for group in self.optimizer.param_groups:
-            group["lr"] = lr
-        if self.param.grad is not self.grad:
-            self.param.grad = self.grad
+    def before_step(self):
+        """ColourModel.step: the total-variation gradient into the table, then the Adam step."""
         self.tv_grad()
-        self.optimizer.step()
-        return lr
-
-    def zero_grad(self):
-        self.grad.zero_()
 
     def save(self, path, cameras):
         """An .npz: `grids` float32 [n, 12, L, Hg, Wg] (gsplat's layout, a permutation of the table) and `image_names`."""

@@ -2,9 +2,9 @@
 train.py:278-312): FoVx, FoVy, world_view_transform (row-vector convention,
 i.e. the TRANSPOSE of the 4x4 world->camera matrix), K, camtoworlds,
 original_image (uint8 [3,H,W] on the GPU), image_name, create_k_on_gpu(); plus loss_mask (uint8 [H,W] or None)
-and loss_mask_count, the per-pixel ignore mask of the training loss.  A training camera may also carry `exposure` /
-`exposure_grad`, float32 [3,4] views of its rows in an exposure.ExposureModel (camera_exposure below), or `bilagrid` /
-`bilagrid_grad`, float32 [L,Hg,Wg,12] views of its grids in a bilagrid.BilagridModel (camera_bilagrid), and `invdepth`
+and loss_mask_count, the per-pixel ignore mask of the training loss.  A training camera may also carry ONE colour stage
+(camera_colour below) -- `exposure` / `exposure_grad`, float32 [3,4] views of its rows in an exposure.ExposureModel, or
+`bilagrid` / `bilagrid_grad`, float32 [L,Hg,Wg,12] views of its grids in a bilagrid.BilagridModel -- and `invdepth`
 (uint16 [H,W]) with `invdepth_scale` / `invdepth_offset`, its monocular inverse-depth prior (camera_invdepth below), and
 `pose_grad`, the float32 [15] buffer its pose gradient is added into (camera_pose_grad; pose.PoseModel rewrites
 world_view_transform, camtoworlds and the cached host triple of a camera whose pose it has moved)."""
@@ -27,14 +27,34 @@ def camera_loss_mask(camera):
     return mask, int(count)
 
 
+def camera_colour(camera):
+    """The colour stage a camera carries between the rasterizer and the loss: (kind, param, grad) with kind "exposure"
+    (param float32 [3,4]) or "bilagrid" (param float32 [L,Hg,Wg,12]) -- views into the tables of a colour_model.ColourModel
+    (`camera.<kind>`, `camera.<kind>_grad`; grad may be None) -- or None: a camera without the attributes, or with None, is
+    rendered and trained as the model is.  A camera that carries both is refused: the order in which the two transforms
+    compose is not defined."""
+    row, grid = getattr(camera, "exposure", None), getattr(camera, "bilagrid", None)
+    if row is not None and grid is not None:
+        raise ValueError("a camera carries both an exposure row and a bilateral grid: the order of composition is not "
+                         "defined; train with --exposure or with --bilagrid")
+    if row is not None:
+        return "exposure", row, getattr(camera, "exposure_grad", None)
+    if grid is not None:
+        return "bilagrid", grid, getattr(camera, "bilagrid_grad", None)
+    return None
+
+
 def camera_exposure(camera):
-    """(row, grad_row) of a camera's exposure transform -- float32 [3,4] views into the tables of an
-    exposure.ExposureModel (`camera.exposure`, `camera.exposure_grad`) -- or (None, None): a camera without the
-    attribute, or with None, is rendered and trained as the model is."""
-    row = getattr(camera, "exposure", None)
-    if row is None:
-        return None, None
-    return row, getattr(camera, "exposure_grad", None)
+    """(row, grad_row) of camera_colour for a camera whose stage is an exposure row, else (None, None); for callers
+    outside the stage (the scene tests)."""
+    c = camera_colour(camera)
+    return c[1:] if c is not None and c[0] == "exposure" else (None, None)
+
+
+def camera_bilagrid(camera):
+    """(grid, grad) of camera_colour for a camera whose stage is a bilateral grid, else (None, None)."""
+    c = camera_colour(camera)
+    return c[1:] if c is not None and c[0] == "bilagrid" else (None, None)
 
 
 def camera_invdepth(camera):
@@ -45,20 +65,6 @@ def camera_invdepth(camera):
     if raw is None:
         return None
     return raw, float(getattr(camera, "invdepth_scale", 1.0)), float(getattr(camera, "invdepth_offset", 0.0))
-
-
-def camera_bilagrid(camera):
-    """(grid, grad) of a camera's bilateral grid -- float32 [L,Hg,Wg,12] views into the tables of a
-    bilagrid.BilagridModel (`camera.bilagrid`, `camera.bilagrid_grad`) -- or (None, None): a camera without the
-    attribute, or with None, is rendered and trained as the model is.  A camera that carries an exposure row as well is
-    refused: the order in which the two transforms compose is not defined."""
-    grid = getattr(camera, "bilagrid", None)
-    if grid is None:
-        return None, None
-    if getattr(camera, "exposure", None) is not None:
-        raise ValueError("a camera carries both an exposure row and a bilateral grid: the order of composition is not "
-                         "defined; train with --exposure or with --bilagrid")
-    return grid, getattr(camera, "bilagrid_grad", None)
 
 
 def camera_pose_grad(camera):

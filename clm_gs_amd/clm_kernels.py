@@ -206,39 +206,79 @@ def check_depth_prior_args(camera):
     return True
 
 
-# ------------------------------------------------------- exposure compensation
+# ------------------------------------------- colour stages: exposure compensation, bilateral grid
 def _view_ptr(t):
     return ctypes.c_void_p(t.data_ptr())
 
 
-class _ApplyExposure(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, image, exposure):
+class _ColourStage:
+    """One kind of colour stage between the rasterizer and the loss, as the library offers it: the parameter check, the
+    forward entry, the backward entry with its partial rows, the finish entry that ADDS the rows into a gradient in the
+    fixed order of csrc/rowsum.h.  An image travels as a pointer and its (sc, sy, sx) element strides.  Driven by
+    _ApplyColour below (op by op) and by fused.camera_forward_finish / camera_backward (the engines)."""
+
+    def __init__(self, kind, expected, ok, dims, rows, width, finish_args):
+        self.kind, self.expected, self.ok = kind, expected, ok  # ok(P): the shape the kernels take; `expected` names it
+        self.dims = dims                # P -> what the forward and backward entries take behind the parameter pointer
+        self.rows, self.width = rows, width  # (L, H, W, P) -> partial rows of a backward; P -> floats per row
+        self.finish_args = finish_args  # (H, W, P, rows) -> what the finish entry takes before `partials, grad`
+
+    def check(self, P, what):
+        if P.dtype != F32 or not self.ok(P):
+            raise _lib.ClmgsError(f"{what} must be {self.expected}, got {P.dtype} {tuple(P.shape)}")
+
+    def forward(self, s, H, W, x, xs, P, y, ys):
+        check(getattr(_lib.lib(), f"clmgs_{self.kind}_fwd")(s, H, W, x, *xs, dptr(P, F32), *self.dims(P), y, *ys))
+
+    def backward(self, s, H, W, x, xs, P, g, gs, v, vs, device):
+        """v = dL/dx from g = dL/dy (v may be g itself, as the same view) -> the partial rows of dL/dP, for finish()."""
         L = _lib.lib()
+        partials = torch.empty((self.rows(L, H, W, P), self.width(P)), dtype=F32, device=device)
+        check(getattr(L, f"clmgs_{self.kind}_bwd")(s, H, W, x, *xs, dptr(P, F32), *self.dims(P), g, *gs, v, *vs,
+                                                   dptr(partials)))
+        return partials
+
+    def finish(self, s, H, W, P, partials, grad):
+        check(getattr(_lib.lib(), f"clmgs_{self.kind}_grad_finish")(
+            s, *self.finish_args(H, W, P, int(partials.shape[0])), dptr(partials), dptr(grad, F32)))
+
+
+COLOUR = {
+    "exposure": _ColourStage(
+        "exposure", "float32 [3,4]", lambda E: tuple(E.shape) == (3, 4), lambda E: (),
+        lambda L, H, W, E: int(L.clmgs_exposure_partials_rows(H, W)), lambda E: 12, lambda H, W, E, rows: (rows,)),
+    "bilagrid": _ColourStage(
+        "bilagrid", "contiguous float32 [L,Hg,Wg,12]", lambda G: G.dim() == 4 and G.shape[3] == 12 and G.is_contiguous(),
+        lambda G: tuple(G.shape[:3]), lambda L, H, W, G: int(L.clmgs_bilagrid_partials_rows(H, W, G.shape[1], G.shape[2])),
+        lambda G: 48 * G.shape[0], lambda H, W, G, rows: (H, W, *G.shape[:3])),
+}
+
+
+class _ApplyColour(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, image, param, kind):
+        stage = COLOUR[kind]
         assert image.dim() == 3 and image.shape[0] == 3 and image.dtype == F32 and image.is_cuda
-        assert tuple(exposure.shape) == (3, 4) and exposure.dtype == F32 and exposure.device == image.device
+        P = param.detach().contiguous()
+        assert P.dtype == F32 and P.device == image.device and stage.ok(P)
         _, H, W = image.shape
-        E = exposure.detach().contiguous()
         out = torch.empty_strided(image.shape, image.stride(), dtype=F32, device=image.device)
-        check(L.clmgs_exposure_fwd(stream(), H, W, _view_ptr(image), *image.stride(), dptr(E, F32),
-                                   _view_ptr(out), *out.stride()))
-        ctx.save_for_backward(image, E)
+        stage.forward(stream(), H, W, _view_ptr(image), image.stride(), P, _view_ptr(out), out.stride())
+        ctx.stage = stage
+        ctx.save_for_backward(image, P)
         return out
 
     @staticmethod
     def backward(ctx, v):
-        L = _lib.lib()
-        image, E = ctx.saved_tensors
+        stage, (image, P) = ctx.stage, ctx.saved_tensors
         _, H, W = image.shape
         assert v.dtype == F32 and v.shape == image.shape
         v_img = torch.empty_strided(image.shape, image.stride(), dtype=F32, device=image.device)
-        rows = int(L.clmgs_exposure_partials_rows(H, W))
-        partials = torch.empty((rows, 12), dtype=F32, device=image.device)
-        v_E = torch.zeros((3, 4), dtype=F32, device=image.device)
-        check(L.clmgs_exposure_bwd(stream(), H, W, _view_ptr(image), *image.stride(), dptr(E, F32), _view_ptr(v),
-                                   *v.stride(), _view_ptr(v_img), *v_img.stride(), dptr(partials)))
-        check(L.clmgs_exposure_grad_finish(stream(), rows, dptr(partials), dptr(v_E)))
-        return v_img, v_E
+        partials = stage.backward(stream(), H, W, _view_ptr(image), image.stride(), P, _view_ptr(v), v.stride(),
+                                  _view_ptr(v_img), v_img.stride(), image.device)
+        v_P = torch.zeros_like(P)
+        stage.finish(stream(), H, W, P, partials, v_P)
+        return v_img, v_P, None
 
 
 def apply_exposure(image, exposure):
@@ -246,21 +286,31 @@ def apply_exposure(image, exposure):
     the rasterizer's [H,W,3] output), exposure float32 [3,4] on the same device ->
     y[c] = x[0] E[0][c] + x[1] E[1][c] + x[2] E[2][c] + E[c][3] in the image's layout, unclamped; differentiable in
     both (csrc/exposure.hip; DESIGN.md section 3, "Exposure")."""
-    return _ApplyExposure.apply(image, exposure)
+    return _ApplyColour.apply(image, exposure, "exposure")
 
 
-def apply_camera_exposure(image, camera):
-    """apply_exposure with the camera's row, the row's gradient ADDED into `camera.exposure_grad` by the backward; the
-    image itself for a camera without an exposure.  What the op-by-op engines and the evaluation renders call."""
-    from .cameras import camera_exposure
-    row, grad_row = camera_exposure(camera)
-    if row is None:
+def apply_bilagrid(image, grid):
+    """A camera's bilateral grid on a rendered image: image [3,H,W] float32 (any strides, e.g. the permuted view of the
+    rasterizer's [H,W,3] output), grid float32 [L,Hg,Wg,12] on the same device -> the image in the same layout, every
+    pixel through the 3x4 affine transform the grid gives at its position and luminance, unclamped; differentiable in
+    both, the gradient through the luminance included (csrc/bilagrid.hip; DESIGN.md section 3, "Bilateral grid")."""
+    return _ApplyColour.apply(image, grid, "bilagrid")
+
+
+def apply_camera_colour(image, camera):
+    """The camera's colour stage (cameras.camera_colour: an exposure row or a bilateral grid) on a rendered image, the
+    parameter's gradient ADDED into the camera's gradient view by the backward; the image itself for a camera without a
+    stage.  What the op-by-op engines and the evaluation renders call."""
+    from .cameras import camera_colour
+    colour = camera_colour(camera)
+    if colour is None:
         return image
-    if not (torch.is_grad_enabled() and image.requires_grad) or grad_row is None:
-        return apply_exposure(image, row.detach())
-    leaf = row.detach().requires_grad_(True)
-    leaf.register_hook(lambda g: (grad_row.add_(g), None)[1])
-    return apply_exposure(image, leaf)
+    kind, param, grad = colour
+    if not (torch.is_grad_enabled() and image.requires_grad) or grad is None:
+        return _ApplyColour.apply(image, param.detach(), kind)
+    leaf = param.detach().requires_grad_(True)
+    leaf.register_hook(lambda g: (grad.add_(g), None)[1])
+    return _ApplyColour.apply(image, leaf, kind)
 
 
 # ------------------------------------------------------------ MCMC densification
@@ -330,60 +380,6 @@ def mcmc_inject_noise_(xyz, opacity, scaling, rotation, noise, scaler, packed=No
         _f32_dev(packed, (n, 12), "packed")
     check(_lib.lib().clmgs_mcmc_noise(stream(), n, dptr(xyz, F32), dptr(opacity, F32), dptr(scaling, F32),
                                       dptr(rotation, F32), dptr(noise, F32), float(scaler), dptr(packed, F32, True)))
-
-
-# ------------------------------------------------------- bilateral-grid colour correction
-class _ApplyBilagrid(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, image, grid):
-        L = _lib.lib()
-        assert image.dim() == 3 and image.shape[0] == 3 and image.dtype == F32 and image.is_cuda
-        assert grid.dim() == 4 and grid.shape[3] == 12 and grid.dtype == F32 and grid.device == image.device
-        _, H, W = image.shape
-        G = grid.detach().contiguous()
-        out = torch.empty_strided(image.shape, image.stride(), dtype=F32, device=image.device)
-        check(L.clmgs_bilagrid_fwd(stream(), H, W, _view_ptr(image), *image.stride(), dptr(G, F32), *G.shape[:3],
-                                   _view_ptr(out), *out.stride()))
-        ctx.save_for_backward(image, G)
-        return out
-
-    @staticmethod
-    def backward(ctx, v):
-        L = _lib.lib()
-        image, G = ctx.saved_tensors
-        _, H, W = image.shape
-        Lz, Hg, Wg = G.shape[:3]
-        assert v.dtype == F32 and v.shape == image.shape
-        v_img = torch.empty_strided(image.shape, image.stride(), dtype=F32, device=image.device)
-        rows = int(L.clmgs_bilagrid_partials_rows(H, W, Hg, Wg))
-        partials = torch.empty((rows, Lz * 48), dtype=F32, device=image.device)
-        v_G = torch.zeros_like(G)
-        check(L.clmgs_bilagrid_bwd(stream(), H, W, _view_ptr(image), *image.stride(), dptr(G, F32), Lz, Hg, Wg,
-                                   _view_ptr(v), *v.stride(), _view_ptr(v_img), *v_img.stride(), dptr(partials)))
-        check(L.clmgs_bilagrid_grad_finish(stream(), H, W, Lz, Hg, Wg, dptr(partials), dptr(v_G)))
-        return v_img, v_G
-
-
-def apply_bilagrid(image, grid):
-    """A camera's bilateral grid on a rendered image: image [3,H,W] float32 (any strides, e.g. the permuted view of the
-    rasterizer's [H,W,3] output), grid float32 [L,Hg,Wg,12] on the same device -> the image in the same layout, every
-    pixel through the 3x4 affine transform the grid gives at its position and luminance, unclamped; differentiable in
-    both, the gradient through the luminance included (csrc/bilagrid.hip; DESIGN.md section 3, "Bilateral grid")."""
-    return _ApplyBilagrid.apply(image, grid)
-
-
-def apply_camera_bilagrid(image, camera):
-    """apply_bilagrid with the camera's grid, the grid's gradient ADDED into `camera.bilagrid_grad` by the backward; the
-    image itself for a camera without a grid.  Called wherever apply_camera_exposure is (a camera carries one or the other)."""
-    from .cameras import camera_bilagrid
-    grid, grad = camera_bilagrid(camera)
-    if grid is None:
-        return image
-    if not (torch.is_grad_enabled() and image.requires_grad) or grad is None:
-        return apply_bilagrid(image, grid.detach())
-    leaf = grid.detach().requires_grad_(True)
-    leaf.register_hook(lambda g: (grad.add_(g), None)[1])
-    return apply_bilagrid(image, leaf)
 
 
 # ------------------------------------------------------------- SH row movement

@@ -22,6 +22,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "rowsum.h"
 
 // Every fused multiply-add in this file is written as fmaf; nothing else may be fused.  Left to itself the compiler
 // contracts tx = fx - x0 into one fma in some places and not in others, and the forward, the backward and the cell
@@ -38,11 +39,6 @@ constexpr int BG_MAX_L = 32, BG_MAX_XY = 64;
 constexpr int BG_LEVEL = 52;                   // LDS floats per level: 4 corners x 12 + 4 of padding (level z starts at bank
                                                // 20 z mod 32: lanes on different levels read different banks)
 constexpr int BG_ROW = 48;                     // slab floats per level and workgroup
-
-struct BgView {
-  float* p;
-  int64_t sc, sy, sx;
-};
 
 // THE float32 lattice coordinate of pixel p on an axis of n pixels and m nodes; used by the cell search and by every pixel
 __device__ __forceinline__ float bg_coord(int p, int n, int m) { return ((float)p + 0.5f) / (float)n * (float)(m - 1); }
@@ -113,7 +109,7 @@ __device__ __forceinline__ void bg_stage(float* nodes, const float* __restrict__
 }
 
 __global__ void __launch_bounds__(BG_THREADS)
-bilagrid_fwd_kernel(int H, int W, BgView xv, const float* __restrict__ G, int L, int Hg, int Wg, BgView yv) {
+bilagrid_fwd_kernel(int H, int W, ImgView xv, const float* __restrict__ G, int L, int Hg, int Wg, ImgView yv) {
   __shared__ __attribute__((aligned(16))) float nodes[BG_MAX_L * BG_LEVEL];
   const BgCell c = bg_cell(blockIdx.y, H, W, Hg, Wg);
   if ((int64_t)blockIdx.x * BG_CHUNK >= c.npx) return;  // block-uniform
@@ -150,7 +146,7 @@ bilagrid_fwd_kernel(int H, int W, BgView xv, const float* __restrict__ G, int L,
 // v_x may alias g (the same view): a lane reads the g of its own pixels before it writes their v_x and no lane reads
 // another lane's pixels, so g and v_x carry no __restrict__.
 __global__ void __launch_bounds__(BG_THREADS)
-bilagrid_bwd_kernel(int H, int W, BgView xv, const float* __restrict__ G, int L, int Hg, int Wg, BgView gv, BgView vv,
+bilagrid_bwd_kernel(int H, int W, ImgView xv, const float* __restrict__ G, int L, int Hg, int Wg, ImgView gv, ImgView vv,
                     float* __restrict__ partials) {
   __shared__ __attribute__((aligned(16))) float nodes[BG_MAX_L * BG_LEVEL];
   __shared__ float wsum[BG_WAVES][BG_MAX_L * BG_ROW];  // per wave: its running L x 48 block
@@ -280,16 +276,7 @@ bilagrid_grad_finish_kernel(int chunks, int L, int Hg, int Wg, const float* __re
       const int cx = x - dx;
       if (cx < 0 || cx > Wg - 2) continue;
       const float* src = partials + (int64_t)(cy * (Wg - 1) + cx) * chunks * row_floats + z * BG_ROW + (dy * 2 + dx) * 12 + j;
-      constexpr int B = 8;
-      int r = 0;
-      for (; r + B <= chunks; r += B) {
-        float t[B];
-#pragma unroll
-        for (int i = 0; i < B; ++i) t[i] = src[(int64_t)(r + i) * row_floats];
-#pragma unroll
-        for (int i = 0; i < B; ++i) acc += t[i];
-      }
-      for (; r < chunks; ++r) acc += src[(int64_t)r * row_floats];
+      acc = serial_sum8(acc, src, 0, 1, chunks, row_floats);  // rowsum.h: the chain goes on from cell to cell
     }
   }
   grad[e] += acc;
@@ -356,7 +343,7 @@ extern "C" int clmgs_bilagrid_fwd(void* stream, int H, int W, const float* x, in
                                   int64_t ystride_c, int64_t ystride_y, int64_t ystride_x) {
   CLMGS_CHECK_ARG(bg_image_ok(H, W) && x && grid_dev && y && x != y);
   CLMGS_CHECK_ARG(bg_shape_ok(L, Hg, Wg));
-  BgView xv{const_cast<float*>(x), stride_c, stride_y, stride_x}, yv{y, ystride_c, ystride_y, ystride_x};
+  ImgView xv{const_cast<float*>(x), stride_c, stride_y, stride_x}, yv{y, ystride_c, ystride_y, ystride_x};
   const dim3 grid((unsigned)bg_chunks(H, W, Hg, Wg), (unsigned)((Hg - 1) * (Wg - 1)));
   hipLaunchKernelGGL(bilagrid_fwd_kernel, grid, dim3(BG_THREADS), 0, (hipStream_t)stream, H, W, xv, grid_dev, L, Hg, Wg, yv);
   CLMGS_LAUNCH_CHECK();
@@ -369,10 +356,9 @@ extern "C" int clmgs_bilagrid_bwd(void* stream, int H, int W, const float* x, in
                                   int64_t vstride_y, int64_t vstride_x, float* partials) {
   CLMGS_CHECK_ARG(bg_image_ok(H, W) && x && grid_dev && g && v_x && partials && x != v_x);
   CLMGS_CHECK_ARG(bg_shape_ok(L, Hg, Wg));
-  // in place is allowed only as the SAME view: a lane then overwrites exactly the elements it has read
-  CLMGS_CHECK_ARG(g != v_x || (gstride_c == vstride_c && gstride_y == vstride_y && gstride_x == vstride_x));
-  BgView xv{const_cast<float*>(x), stride_c, stride_y, stride_x};
-  BgView gv{const_cast<float*>(g), gstride_c, gstride_y, gstride_x}, vv{v_x, vstride_c, vstride_y, vstride_x};
+  ImgView xv{const_cast<float*>(x), stride_c, stride_y, stride_x};
+  ImgView gv{const_cast<float*>(g), gstride_c, gstride_y, gstride_x}, vv{v_x, vstride_c, vstride_y, vstride_x};
+  CLMGS_CHECK_ARG(distinct_or_same_view(gv, vv));
   const dim3 grid((unsigned)bg_chunks(H, W, Hg, Wg), (unsigned)((Hg - 1) * (Wg - 1)));
   hipLaunchKernelGGL(bilagrid_bwd_kernel, grid, dim3(BG_THREADS), 0, (hipStream_t)stream, H, W, xv, grid_dev, L, Hg, Wg, gv,
                      vv, partials);

@@ -50,6 +50,19 @@ __device__ __forceinline__ void lds_barrier() {
 // one).  Kept at 4; the constant is the single place to change it (clmgs_rasterize_partials_bytes reports it).
 constexpr int PART_F4 = 4;
 
+// An image [3,H,W] by element strides: what the colour stages between the rasterizer and the loss (exposure.hip,
+// bilagrid.hip) read and write -- planar, interleaved [H,W,3] or [H,W,4], an offset view.
+struct ImgView {
+  float* p;
+  int64_t sc, sy, sx;
+};
+
+// A backward in place (the cotangent g overwritten by v_x) is allowed only as the SAME view: a lane then overwrites
+// exactly the elements it has read.
+static inline bool distinct_or_same_view(const ImgView& g, const ImgView& v) {
+  return g.p != v.p || (g.sc == v.sc && g.sy == v.sy && g.sx == v.sx);
+}
+
 static inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 

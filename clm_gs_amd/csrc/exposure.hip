@@ -16,6 +16,7 @@
 // The pixels [0, n_fast) go through fast workgroups, [n_fast, H*W) -- the last H*W mod 4 pixels of an eligible
 // layout, everything of any other layout -- through generic ones.
 #include "common.h"
+#include "rowsum.h"
 
 namespace clmgs {
 
@@ -25,12 +26,6 @@ constexpr int EXP_FWD_GROUPS = 4;                                 // forward: 4-
 constexpr int EXP_FWD_PIXELS = EXP_THREADS * 4 * EXP_FWD_GROUPS;  // pixels per forward workgroup (4096)
 constexpr int EXP_LANE_PIXELS = 64;                               // backward: pixels one lane accumulates, at most
 constexpr int EXP_BWD_PIXELS = EXP_THREADS * EXP_LANE_PIXELS;     // pixels per backward workgroup = per partial row
-constexpr int EXP_FINISH_SLICES = 4;                              // grad_finish: serial row chains, joined by a fixed tree
-
-struct ExpView {
-  float* p;
-  int64_t sc, sy, sx;
-};
 
 struct ExpE {
   float m[3][4];
@@ -76,7 +71,7 @@ __device__ __forceinline__ void exposure_accumulate(float acc[12], const float x
   for (int c = 0; c < 3; ++c) acc[c * 4 + 3] += g[c];
 }
 
-__device__ __forceinline__ int64_t pixel_offset(const ExpView& v, int64_t p, int W) {
+__device__ __forceinline__ int64_t pixel_offset(const ImgView& v, int64_t p, int W) {
   const int64_t y = p / W, x = p - y * W;
   return y * v.sy + x * v.sx;
 }
@@ -96,7 +91,7 @@ __device__ __forceinline__ void pack4(const float px[4][3], float4& a, float4& b
 }
 
 __global__ void __launch_bounds__(EXP_THREADS)
-exposure_fwd_kernel(int64_t n_pix, int W, ExpView xv, const float* __restrict__ E_dev, ExpView yv, int64_t n_fast,
+exposure_fwd_kernel(int64_t n_pix, int W, ImgView xv, const float* __restrict__ E_dev, ImgView yv, int64_t n_fast,
                     int fast_blocks) {
   const ExpE e = load_E(E_dev);
   const int tid = threadIdx.x;
@@ -150,7 +145,7 @@ exposure_fwd_kernel(int64_t n_pix, int W, ExpView xv, const float* __restrict__ 
 // v_x may alias g (equal strides): a lane reads the g of its own pixels before it writes their v_x, and no lane reads
 // another lane's pixels, so g and v_x carry no __restrict__.
 __global__ void __launch_bounds__(EXP_THREADS)
-exposure_bwd_kernel(int64_t n_pix, int W, ExpView xv, const float* __restrict__ E_dev, ExpView gv, ExpView vv,
+exposure_bwd_kernel(int64_t n_pix, int W, ImgView xv, const float* __restrict__ E_dev, ImgView gv, ImgView vv,
                     float* __restrict__ partials, int64_t n_fast, int fast_blocks) {
   __shared__ float red[EXP_WAVES][12];
   const ExpE e = load_E(E_dev);
@@ -203,44 +198,8 @@ exposure_bwd_kernel(int64_t n_pix, int W, ExpView xv, const float* __restrict__ 
       for (int k = 0; k < 3; ++k) vv.p[vo + k * vv.sc] = v[k];
     }
   }
-  // lane -> wave (6 DPP steps) -> workgroup (waves 0..3 in order, through LDS) -> one stored row
-  const int wave = tid >> 6, lane = tid & 63;
-#pragma unroll
-  for (int j = 0; j < 12; ++j) {
-    const float s = wave_sum(acc[j]);
-    if (lane == 0) red[wave][j] = s;
-  }
-  __syncthreads();
-  if (tid < 12) {
-    float s = red[0][tid];
-#pragma unroll
-    for (int w = 1; w < EXP_WAVES; ++w) s += red[w][tid];
-    partials[(int64_t)blockIdx.x * 12 + tid] = s;
-  }
-}
-
-// One wave.  Lane l = 16 * slice + j: slice s sums rows s, s+4, s+8, ... of element j serially, the four slices are
-// joined by a fixed two-step tree, lane j < 12 ADDS the total into grad12[j].
-__global__ void __launch_bounds__(64)
-exposure_grad_finish_kernel(int rows, const float* __restrict__ partials, float* __restrict__ grad12) {
-  const int lane = threadIdx.x, j = lane & 15, s = lane >> 4;
-  float acc = 0.f;
-  if (j < 12) {
-    // eight loads in flight, added in row order: the chain of a slice is one latency per 8 rows, not per row
-    constexpr int B = 8;
-    int r = s;
-    for (; r + (B - 1) * EXP_FINISH_SLICES < rows; r += B * EXP_FINISH_SLICES) {
-      float t[B];
-#pragma unroll
-      for (int i = 0; i < B; ++i) t[i] = partials[(int64_t)(r + i * EXP_FINISH_SLICES) * 12 + j];
-#pragma unroll
-      for (int i = 0; i < B; ++i) acc += t[i];
-    }
-    for (; r < rows; r += EXP_FINISH_SLICES) acc += partials[(int64_t)r * 12 + j];
-  }
-  acc += __shfl_xor(acc, 16, 64);
-  acc += __shfl_xor(acc, 32, 64);
-  if (lane < 12) grad12[lane] += acc;
+  const float s = workgroup_row<EXP_WAVES, 12>(acc, red);  // rowsum.h: one stored row per workgroup
+  if (tid < 12) partials[(int64_t)blockIdx.x * 12 + tid] = s;
 }
 
 static bool fast_layout(const void* base, int W, int64_t sc, int64_t sy, int64_t sx) {
@@ -268,7 +227,7 @@ extern "C" int clmgs_exposure_fwd(void* stream, int H, int W, const float* x, in
   const int64_t n_fast = fast ? (n_pix & ~(int64_t)3) : 0;
   const int fast_blocks = ceil_div(n_fast, EXP_FWD_PIXELS);
   const int blocks = fast_blocks + ceil_div(n_pix - n_fast, EXP_FWD_PIXELS);
-  ExpView xv{const_cast<float*>(x), stride_c, stride_y, stride_x}, yv{y, ystride_c, ystride_y, ystride_x};
+  ImgView xv{const_cast<float*>(x), stride_c, stride_y, stride_x}, yv{y, ystride_c, ystride_y, ystride_x};
   hipLaunchKernelGGL(exposure_fwd_kernel, dim3((unsigned)blocks), dim3(EXP_THREADS), 0, (hipStream_t)stream, n_pix, W,
                      xv, E_dev, yv, n_fast, fast_blocks);
   CLMGS_LAUNCH_CHECK();
@@ -280,8 +239,9 @@ extern "C" int clmgs_exposure_bwd(void* stream, int H, int W, const float* x, in
                                   int64_t gstride_y, int64_t gstride_x, float* v_x, int64_t vstride_c,
                                   int64_t vstride_y, int64_t vstride_x, float* partials) {
   CLMGS_CHECK_ARG(H >= 1 && W >= 1 && x && E_dev && g && v_x && partials && x != v_x);
-  // in place is allowed only as the SAME view: a lane then overwrites exactly the elements it has read
-  CLMGS_CHECK_ARG(g != v_x || (gstride_c == vstride_c && gstride_y == vstride_y && gstride_x == vstride_x));
+  ImgView xv{const_cast<float*>(x), stride_c, stride_y, stride_x};
+  ImgView gv{const_cast<float*>(g), gstride_c, gstride_y, gstride_x}, vv{v_x, vstride_c, vstride_y, vstride_x};
+  CLMGS_CHECK_ARG(distinct_or_same_view(gv, vv));
   const int64_t n_pix = (int64_t)H * W;
   const bool fast = fast_layout(x, W, stride_c, stride_y, stride_x) && fast_layout(g, W, gstride_c, gstride_y, gstride_x) &&
                     fast_layout(v_x, W, vstride_c, vstride_y, vstride_x);
@@ -289,8 +249,6 @@ extern "C" int clmgs_exposure_bwd(void* stream, int H, int W, const float* x, in
   const int fast_blocks = ceil_div(n_fast, EXP_BWD_PIXELS);
   const int rows = clmgs_exposure_partials_rows(H, W);  // workgroups without pixels store a row of zeros
   CLMGS_CHECK_ARG(fast_blocks + ceil_div(n_pix - n_fast, EXP_BWD_PIXELS) <= rows);
-  ExpView xv{const_cast<float*>(x), stride_c, stride_y, stride_x};
-  ExpView gv{const_cast<float*>(g), gstride_c, gstride_y, gstride_x}, vv{v_x, vstride_c, vstride_y, vstride_x};
   hipLaunchKernelGGL(exposure_bwd_kernel, dim3((unsigned)rows), dim3(EXP_THREADS), 0, (hipStream_t)stream, n_pix, W, xv,
                      E_dev, gv, vv, partials, n_fast, fast_blocks);
   CLMGS_LAUNCH_CHECK();
@@ -299,7 +257,8 @@ extern "C" int clmgs_exposure_bwd(void* stream, int H, int W, const float* x, in
 
 extern "C" int clmgs_exposure_grad_finish(void* stream, int rows, const float* partials, float* grad12) {
   CLMGS_CHECK_ARG(rows >= 0 && partials && grad12);
-  hipLaunchKernelGGL(exposure_grad_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, rows, partials, grad12);
+  hipLaunchKernelGGL((rows_finish_kernel<16, 12, true>), dim3(1), dim3(64), 0, (hipStream_t)stream, rows, partials, grad12,
+                     12);
   CLMGS_LAUNCH_CHECK();
   return 0;
 }

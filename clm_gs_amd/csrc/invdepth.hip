@@ -10,6 +10,7 @@
 //                       dL/dz * R[2,:]  (z = R[2,:] . xyz + t[2], third row of the world-to-camera matrix).
 // No float atomics anywhere: a workgroup STORES one partial sum, clmgs_invdepth_finish adds the rows in a fixed order.
 #include "common.h"
+#include "rowsum.h"
 
 namespace clmgs {
 
@@ -41,10 +42,10 @@ __global__ void __launch_bounds__(INV_THREADS)
 invdepth_l1_kernel(int64_t n_pix, int W, const float* __restrict__ I, int64_t sy, int64_t sx,
                    const uint16_t* __restrict__ prior, float scale, float offset, const uint8_t* __restrict__ mask,
                    float coef, float* __restrict__ v_I, int64_t vsy, int64_t vsx, float* __restrict__ partials) {
-  __shared__ float red[INV_WAVES];
+  __shared__ float red[INV_WAVES][1];
   const int tid = threadIdx.x;
   const int64_t p0 = (int64_t)blockIdx.x * INV_WG_PIXELS + tid;
-  float acc = 0.f;
+  float acc[1] = {0.f};
 #pragma unroll 1
   for (int t0 = 0; t0 < INV_LANE_PIXELS; t0 += INV_UNROLL) {
     float x[INV_UNROLL];
@@ -74,42 +75,14 @@ invdepth_l1_kernel(int64_t n_pix, int W, const float* __restrict__ I, int64_t sy
       if (p < n_pix) {
         const float d = x[u] - prior_of(raw[u], scale, offset);
         const bool on = m[u] != 0u;
-        acc += on ? fabsf(d) : 0.f;
+        acc[0] += on ? fabsf(d) : 0.f;
         const float sg = d > 0.f ? coef : (d < 0.f ? -coef : 0.f);  // d|x|/dx at 0 is 0
         v_I[vo[u]] = on ? sg : 0.f;
       }
     }
   }
-  // lane -> wave (DPP) -> workgroup (waves 0..3 in order, through LDS) -> one stored row
-  const float s = wave_sum(acc);
-  if ((tid & 63) == 0) red[tid >> 6] = s;
-  __syncthreads();
-  if (tid == 0) {
-    float r = red[0];
-#pragma unroll
-    for (int w = 1; w < INV_WAVES; ++w) r += red[w];
-    partials[blockIdx.x] = r;
-  }
-}
-
-// One wave: lane l sums rows l, l + 64, ... serially (eight loads in flight, added in row order), then a fixed tree.
-__global__ void __launch_bounds__(64)
-invdepth_finish_kernel(int rows, const float* __restrict__ partials, float* __restrict__ sum_out) {
-  const int lane = threadIdx.x;
-  float acc = 0.f;
-  constexpr int B = 8;
-  int r = lane;
-  for (; r + (B - 1) * 64 < rows; r += B * 64) {
-    float t[B];
-#pragma unroll
-    for (int i = 0; i < B; ++i) t[i] = partials[r + i * 64];
-#pragma unroll
-    for (int i = 0; i < B; ++i) acc += t[i];
-  }
-  for (; r < rows; r += 64) acc += partials[r];
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) acc += __shfl_xor(acc, o, 64);
-  if (lane == 0) sum_out[0] = acc;
+  const float r = workgroup_row<INV_WAVES, 1>(acc, red);  // rowsum.h: one stored row per workgroup
+  if (tid == 0) partials[blockIdx.x] = r;
 }
 
 // One lane per position i.  pitch 12: the [N,12] packed gradient table (words 0..2 of a row); pitch 3: [N,3].
@@ -187,7 +160,7 @@ extern "C" int clmgs_invdepth_l1_fwd_bwd(void* stream, int H, int W, const float
 
 extern "C" int clmgs_invdepth_finish(void* stream, int rows, const float* partials, float* sum_out) {
   CLMGS_CHECK_ARG(rows >= 0 && partials && sum_out);
-  hipLaunchKernelGGL(invdepth_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, rows, partials, sum_out);
+  hipLaunchKernelGGL((rows_finish_kernel<1, 1, false>), dim3(1), dim3(64), 0, (hipStream_t)stream, rows, partials, sum_out, 1);
   CLMGS_LAUNCH_CHECK();
   return 0;
 }

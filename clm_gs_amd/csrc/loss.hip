@@ -52,8 +52,6 @@ constexpr float l_win[11] = {
     0.0010283801f, 0.0075987582f, 0.0360007721f, 0.1093606895f, 0.2130055377f, 0.2660117249f,
     0.2130055377f, 0.1093606895f, 0.0360007721f, 0.0075987582f, 0.0010283801f};
 
-struct ImgView { const float* p; int64_t sc, sy, sx; };
-
 __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
@@ -347,7 +345,7 @@ static int launch_loss_fwd(void* stream, int H, int W, const float* img, int64_t
                            const uint8_t* mask) {
   CLMGS_CHECK_ARG(H >= 1 && W >= 1 && img && gt_u8 && partials);
   CLMGS_CHECK_ARG((m1 && m2 && m3) || (!m1 && !m2 && !m3));
-  ImgView v{img, stride_c, stride_y, stride_x};
+  ImgView v{const_cast<float*>(img), stride_c, stride_y, stride_x};  // read only
   const int64_t strips = (int64_t)ceil_div(W, LS_W) * ceil_div(H, LS_ROWS);
   dim3 grid((unsigned)(24 * ceil_div(strips, 8)));
   hipLaunchKernelGGL(loss_fwd_kernel<MASKED>, grid, dim3(64), 0, (hipStream_t)stream, H, W, v, gt_u8,
@@ -361,7 +359,7 @@ static int launch_loss_bwd(void* stream, int H, int W, const float* img, int64_t
                            int64_t stride_x, const uint8_t* gt_u8, const float* v_loss, float lambda_dssim,
                            const float* m1, const float* m2, const float* m3, float* v_img, const uint8_t* mask) {
   CLMGS_CHECK_ARG(H >= 1 && W >= 1 && img && gt_u8 && v_loss && m1 && m2 && m3 && v_img);
-  ImgView v{img, stride_c, stride_y, stride_x};
+  ImgView v{const_cast<float*>(img), stride_c, stride_y, stride_x};  // read only
   const double numel = 3.0 * (double)H * (double)W;  // masked too: the divisor is the image's, not the counted pixels'
   const int64_t strips = (int64_t)ceil_div(W, LS_W) * ceil_div(H, LS_ROWS);
   dim3 grid((unsigned)(24 * ceil_div(strips, 8)));

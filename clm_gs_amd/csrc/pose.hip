@@ -15,13 +15,13 @@
 
 #include "common.h"
 #include "pose_math.h"
+#include "rowsum.h"
 
 namespace clmgs {
 
 constexpr int POSE_ROWS = 64;        // rows per chunk = lanes per wavefront = threads per workgroup
 constexpr int POSE_PITCH = 52;       // floats per LDS row (see sh.hip)
 constexpr int POSE_GRID_CAP = 3072;  // the front end's 256 * 12: above 196 608 rows a wave runs a second chunk
-constexpr int POSE_FINISH_SLICES = 4;
 constexpr int VM_THREADS = 256;      // operator form: one thread per Gaussian, four waves per workgroup
 constexpr int VM_GRID_CAP = 1024;
 
@@ -266,34 +266,6 @@ pose_grad_kernel(int V, PoseArgs a, const int32_t* __restrict__ radii, float* __
   if (t < 16) out[(size_t)blockIdx.x * 16 + t] = mine_out;
 }
 
-// One wave per camera slot c = blockIdx.x.  Lane l = 16 * slice + j: slice s sums rows s, s+4, s+8, ... of column j
-// serially in ascending order, the four slices are joined by a fixed two-step tree.  ADD: lane j < n_out adds into
-// dst[j]; otherwise it stores (the operator form: a fresh gradient, pad words 0).
-template <bool ADD>
-__global__ void __launch_bounds__(64)
-pose_finish_kernel(int rows, const float* __restrict__ partials, float* __restrict__ dst, int n_out) {
-  const int lane = threadIdx.x, j = lane & 15, s = lane >> 4;
-  const float* src = partials + (size_t)blockIdx.x * rows * 16;
-  float acc = 0.f;
-  constexpr int B = 8;  // eight loads in flight, added in row order
-  int r = s;
-  for (; r + (B - 1) * POSE_FINISH_SLICES < rows; r += B * POSE_FINISH_SLICES) {
-    float v[B];
-#pragma unroll
-    for (int u = 0; u < B; ++u) v[u] = src[(size_t)(r + u * POSE_FINISH_SLICES) * 16 + j];
-#pragma unroll
-    for (int u = 0; u < B; ++u) acc += v[u];
-  }
-  for (; r < rows; r += POSE_FINISH_SLICES) acc += src[(size_t)r * 16 + j];
-  acc += __shfl_xor(acc, 16, 64);
-  acc += __shfl_xor(acc, 32, 64);
-  if (ADD) {
-    if (lane < n_out) dst[lane] += acc;
-  } else {
-    if (lane < 16) dst[(size_t)blockIdx.x * 16 + lane] = lane < n_out ? acc : 0.f;
-  }
-}
-
 // Operator form: v_viewmats of fully_fused_projection.  Thread n walks the Gaussians n, n + stride, ... of camera
 // blockIdx.y and keeps its 12 sums in registers; the four waves of the workgroup are joined through LDS in wave order
 // and the workgroup stores one row: partials[(c * gridDim.x + blockIdx.x)][16], rows 0..2 of the 4x4 (v_R[i] | v_t[i]) | 0.
@@ -331,21 +303,8 @@ projection_viewmat_bwd_kernel(int N, const float* __restrict__ means, const floa
       acc[4 * i + 3] += vt[i];
     }
   }
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-  for (int k = 0; k < 12; ++k) {
-    const float s = wave_sum(acc[k]);
-    if (lane == 0) red[wave][k] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < 16) {
-    float s = 0.f;
-    if (threadIdx.x < 12) {
-#pragma unroll
-      for (int w = 0; w < VM_THREADS / 64; ++w) s += red[w][threadIdx.x];
-    }
-    partials[((size_t)c * gridDim.x + blockIdx.x) * 16 + threadIdx.x] = s;
-  }
+  const float s = workgroup_row<VM_THREADS / 64, 12>(acc, red);  // rowsum.h; threads 12..15 hold 0.f: the pad words
+  if (threadIdx.x < 16) partials[((size_t)c * gridDim.x + blockIdx.x) * 16 + threadIdx.x] = s;
 }
 
 }  // namespace clmgs
@@ -409,7 +368,7 @@ extern "C" int clmgs_pose_grad(void* stream, int V, const int64_t* filter, const
 extern "C" int clmgs_pose_grad_finish(void* stream, int rows, const float* partials, float* grad15) {
   CLMGS_CHECK_ARG(rows >= 0 && (partials || rows == 0) && grad15);
   if (rows == 0) return 0;
-  hipLaunchKernelGGL(pose_finish_kernel<true>, dim3(1), dim3(64), 0, (hipStream_t)stream, rows, partials, grad15, 15);
+  hipLaunchKernelGGL((rows_finish_kernel<16, 16, true>), dim3(1), dim3(64), 0, (hipStream_t)stream, rows, partials, grad15, 15);
   CLMGS_LAUNCH_CHECK();
   return 0;
 }
@@ -440,7 +399,7 @@ extern "C" int clmgs_projection_viewmat_bwd(void* stream, int C, int N, const fl
     CLMGS_LAUNCH_CHECK();
   }
   // rows == 0: nothing is read, every camera's 16 words are stored as zeros
-  hipLaunchKernelGGL(pose_finish_kernel<false>, dim3(C), dim3(64), 0, (hipStream_t)stream, rows, partials, v_viewmats, 12);
+  hipLaunchKernelGGL((rows_finish_kernel<16, 16, false>), dim3(C), dim3(64), 0, (hipStream_t)stream, rows, partials, v_viewmats, 12);
   CLMGS_LAUNCH_CHECK();
   return 0;
 }

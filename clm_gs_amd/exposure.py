@@ -6,49 +6,27 @@ the rasterizer and the loss (the INRIA 3DGS code base's `--exposure_lr_init` / `
 
 The model holds the two tables and their optimizer; the transform and its gradients are the kernels of
 csrc/exposure.hip, reached through fused.camera_forward_finish (the engines) and clm_kernels.apply_exposure (the
-op-by-op path, evaluation).  A camera takes part by carrying views of its rows (`attach`); cameras.camera_exposure
-reads them."""
+op-by-op path, evaluation), both through the one description clm_kernels.COLOUR["exposure"].  A camera takes part by
+carrying views of its rows (colour_model.ColourModel.attach); cameras.camera_colour reads them."""
 import json
 
 import torch
 
 from . import utils
+from .colour_model import ColourModel
 
 
-class ExposureModel:
+class ExposureModel(ColourModel):
+    KIND = "exposure"
+
     def __init__(self, n_cameras, device, lr_init=0.01, lr_final=0.001, lr_delay_steps=0, lr_delay_mult=0.0,
                  max_steps=30000):
-        self.n_cameras = int(n_cameras)
-        # the leaf the optimizer steps; cameras get views of its storage that carry no autograd history
-        self.param = torch.eye(3, 4, dtype=torch.float32).repeat(self.n_cameras, 1, 1).to(device).contiguous().requires_grad_(True)
-        self.grad = torch.zeros_like(self.param)
-        self.param.grad = self.grad  # the kernels ADD into rows of this table; zero_grad() clears it in place
+        super().__init__(torch.eye(3, 4, dtype=torch.float32).repeat(int(n_cameras), 1, 1).to(device))
         # dense Adam over the whole table, torch's default eps: rows of cameras outside the batch see a zero gradient
         # (their moments decay and keep moving them), as in the INRIA code base
         self.optimizer = torch.optim.Adam([self.param], lr=float(lr_init))
         self.lr_func = utils.get_expon_lr_func(lr_init, lr_final, lr_delay_steps=lr_delay_steps,
                                                lr_delay_mult=lr_delay_mult, max_steps=max_steps)
-
-    def attach(self, cameras):
-        """camera i of the list trains row i: `camera.exposure` / `camera.exposure_grad` are VIEWS of the tables."""
-        assert len(cameras) == self.n_cameras, (len(cameras), self.n_cameras)
-        rows = self.param.detach()
-        for i, c in enumerate(cameras):
-            c.exposure, c.exposure_grad = rows[i], self.grad[i]
-
-    def step(self, iteration):
-        """One Adam step at the scheduled learning rate; enqueued on the current stream, which must be ordered after the
-        streams the cameras' gradient kernels ran on (the engines join them at the end of a batch)."""
-        lr = float(self.lr_func(iteration))
-        for group in self.optimizer.param_groups:
-            group["lr"] = lr
-        if self.param.grad is not self.grad:
-            self.param.grad = self.grad
-        self.optimizer.step()
-        return lr
-
-    def zero_grad(self):
-        self.grad.zero_()
 
     def save_json(self, path, cameras):
         """{image_name: 3x4 list}.  A float32 survives the trip through its shortest decimal form exactly."""

@@ -13,8 +13,8 @@ import torch
 
 from . import _lib, utils
 from ._lib import check, dptr
-from .cameras import camera_bilagrid, camera_exposure, camera_invdepth, camera_loss_mask, camera_pose_grad
-from .clm_kernels import check_depth_prior_args, masked_loss_value
+from .cameras import camera_colour, camera_invdepth, camera_loss_mask, camera_pose_grad
+from .clm_kernels import COLOUR, check_depth_prior_args, masked_loss_value
 from .gsplat import (_record_counts, bucket_size, empty_bucketed, isect2_begin, isect2_counts, isect2_finish, isect3_begin,
                      isect3_finish)
 
@@ -63,8 +63,7 @@ class _CameraPass:
                  "packed", "fids", "offsets", "emit_slot", "row_cum", "out", "alphas", "last_ids",
                  "bg", "v_out", "maps", "loss", "ev_loss", "streams", "deg", "aux", "loss_partials",
                  "lambda_dssim", "gt_u8", "background", "isect", "sh_index", "means2d", "n_dev", "antialiased",
-                 "loss_mask", "mask_count", "exposure", "exposure_grad", "exp_partials",
-                 "bilagrid", "bilagrid_grad", "bg_partials",
+                 "loss_mask", "mask_count", "colour", "colour_partials",
                  "invdepth", "depth_weight", "depths", "id_partials", "id_term", "pose_grad")
 
 
@@ -153,11 +152,9 @@ def camera_front(gaussians, camera, this_filter, sh_rows, sh_by_filter, backgrou
     p.sh_index = sh_index  # int32[V]: SH row of position i in a staging table (host-resident mode)
     p.gt_u8, p.lambda_dssim, p.background = gt_u8, float(lambda_dssim), background
     p.loss_mask, p.mask_count = camera_loss_mask(camera)  # a mask on the camera selects the masked loss kernels
-    # an exposure row on the camera puts the affine colour transform between the tile kernel and the loss
-    (p.exposure, p.exposure_grad), p.exp_partials = camera_exposure(camera), None
-    # a bilateral grid on the camera takes the same place (a camera carrying both is refused, here, before anything is
-    # enqueued)
-    (p.bilagrid, p.bilagrid_grad), p.bg_partials = camera_bilagrid(camera), None
+    # a colour stage on the camera -- (kind, param, grad): an exposure row or a bilateral grid -- puts its transform between
+    # the tile kernel and the loss (a camera carrying both is refused, here, before anything is enqueued)
+    p.colour, p.colour_partials = camera_colour(camera), None
     # an inverse-depth prior on the camera (depth regularisation): the camera is rendered with a fourth channel, the
     # inverse depth, and trained with the L1 term; without one, not one launch differs.  Refused with absgrad, here,
     # before anything is enqueued.
@@ -280,21 +277,14 @@ def camera_forward_finish(gaussians, p, exact=False):
         sm = _sptr(s_mem)
         mask = p.loss_mask
         img = p.out  # what the loss sees
-        if p.exposure is not None:
-            # the camera's exposure transform into a second [H,W,3] buffer, allocated and used on s_mem only (like the
-            # maps); p.out stays: the transform's backward reads it
-            if tuple(p.exposure.shape) != (3, 4) or p.exposure.dtype != F32:
-                raise _lib.ClmgsError(f"camera.exposure must be float32 [3,4], got {p.exposure.dtype} {tuple(p.exposure.shape)}")
+        if p.colour is not None:
+            # the camera's colour stage (exposure transform, or bilateral grid sliced per pixel) into a second buffer of
+            # p.out's shape, allocated and used on s_mem only (like the maps); p.out stays: the stage's backward reads it.
+            # With a depth prior the fourth word of a pixel is not touched.
+            kind, param, _ = p.colour
+            COLOUR[kind].check(param, f"camera.{kind}")
             img = torch.empty_like(p.out)
-            check(L.clmgs_exposure_fwd(sm, H, W, dptr(p.out), sc, sy, sx, dptr(p.exposure, F32), dptr(img), sc, sy, sx))
-        if p.bilagrid is not None:
-            # the camera's bilateral grid, sliced per pixel, into a second buffer of p.out's shape on s_mem only; p.out
-            # stays: the slice's backward reads it.  With a depth prior the fourth word of a pixel is not touched.
-            if p.bilagrid.dim() != 4 or p.bilagrid.shape[3] != 12 or p.bilagrid.dtype != F32 or not p.bilagrid.is_contiguous():
-                raise _lib.ClmgsError(f"camera.bilagrid must be contiguous float32 [L,Hg,Wg,12], got {p.bilagrid.dtype} {tuple(p.bilagrid.shape)}")
-            img = torch.empty_like(p.out)
-            check(L.clmgs_bilagrid_fwd(sm, H, W, dptr(p.out), sc, sy, sx, dptr(p.bilagrid, F32), *p.bilagrid.shape[:3],
-                                       dptr(img), sc, sy, sx))
+            COLOUR[kind].forward(sm, H, W, dptr(p.out), (sc, sy, sx), param, dptr(img), (sc, sy, sx))
         if mask is None:
             check(L.clmgs_l1_ssim_loss_fwd(sm, H, W, dptr(img), sc, sy, sx, dptr(gt, U8), dptr(partials),
                                            dptr(maps[0]), dptr(maps[1]), dptr(maps[2])))
@@ -318,22 +308,13 @@ def camera_forward_finish(gaussians, p, exact=False):
             check(L.clmgs_l1_ssim_loss_masked_bwd(sm, H, W, dptr(img), sc, sy, sx, dptr(gt, U8), dptr(one),
                                                   float(lambda_dssim), dptr(maps[0]), dptr(maps[1]), dptr(maps[2]),
                                                   dptr(p.v_out), dptr(mask, U8)))
-        if p.exposure is not None:
-            # dL/dy -> dL/dx IN PLACE on p.v_out (no third image buffer) + one row of 12 partial sums per workgroup; the
-            # rows wait on the pass: camera_backward adds them to the camera's gradient row once camera_verify has
-            # accepted THIS forward (a forward repeated for capacity replaces them)
-            rows = int(L.clmgs_exposure_partials_rows(H, W))
-            p.exp_partials = torch.empty((rows, 12), dtype=F32, device=dev)
-            check(L.clmgs_exposure_bwd(sm, H, W, dptr(p.out), sc, sy, sx, dptr(p.exposure, F32), dptr(p.v_out), sc, sy, sx,
-                                       dptr(p.v_out), sc, sy, sx, dptr(p.exp_partials)))
-        if p.bilagrid is not None:
-            # dL/dy -> dL/dx IN PLACE on p.v_out + one slab row per workgroup; the slab waits on the pass: camera_backward
-            # adds it to the camera's gradient grid once camera_verify has accepted THIS forward
-            Lz, Hg, Wg = p.bilagrid.shape[:3]
-            rows = int(L.clmgs_bilagrid_partials_rows(H, W, Hg, Wg))
-            p.bg_partials = torch.empty((rows, Lz * 48), dtype=F32, device=dev)
-            check(L.clmgs_bilagrid_bwd(sm, H, W, dptr(p.out), sc, sy, sx, dptr(p.bilagrid, F32), Lz, Hg, Wg, dptr(p.v_out),
-                                       sc, sy, sx, dptr(p.v_out), sc, sy, sx, dptr(p.bg_partials)))
+        if p.colour is not None:
+            # dL/dy -> dL/dx IN PLACE on p.v_out (no third image buffer) + one row of partial sums per workgroup (12 floats for
+            # an exposure row, a slab row for a grid); the rows wait on the pass: camera_backward adds them to the camera's
+            # gradient view once camera_verify has accepted THIS forward (a forward repeated for capacity replaces them)
+            kind, param, _ = p.colour
+            p.colour_partials = COLOUR[kind].backward(sm, H, W, dptr(p.out), (sc, sy, sx), param, dptr(p.v_out), (sc, sy, sx),
+                                                      dptr(p.v_out), (sc, sy, sx), dev)
         if p.invdepth is not None:
             # the depth term, after the loss (and exposure) backward on the same stream, into the same [H,W,4] cotangent:
             # they wrote words 0..2 of every pixel through their strides, this writes word 3.  One partial sum per
@@ -413,19 +394,14 @@ def camera_backward(gaussians, p, g_sh_rows, small_grad=None, update_stats=True,
     dev = gaussians._xyz.device
     camera_verify(gaussians, p)
     s_front, s_mem, s_raster = p.streams
-    if p.exp_partials is not None:
-        # the exposure gradient of the forward camera_verify has just accepted (an overflowed forward was repeated exactly
-        # and left its own rows): added ONCE, on the stream that wrote the rows.  Allocated, written and read on s_mem only.
-        if p.exposure_grad is not None:
-            check(L.clmgs_exposure_grad_finish(_sptr(s_mem), int(p.exp_partials.shape[0]), dptr(p.exp_partials),
-                                               dptr(p.exposure_grad, F32)))
-        p.exp_partials = None
-    if p.bg_partials is not None:  # likewise the bilateral grid's slab: summed per node and added ONCE, on s_mem
-        if p.bilagrid_grad is not None:
-            Lz, Hg, Wg = p.bilagrid.shape[:3]
-            check(L.clmgs_bilagrid_grad_finish(_sptr(s_mem), H, W, Lz, Hg, Wg, dptr(p.bg_partials),
-                                               dptr(p.bilagrid_grad, F32)))
-        p.bg_partials = None
+    if p.colour_partials is not None:
+        # the colour stage's gradient of the forward camera_verify has just accepted (an overflowed forward was repeated exactly
+        # and left its own rows): summed in a fixed order and added ONCE, on the stream that wrote the rows.  Allocated,
+        # written and read on s_mem only.
+        kind, param, grad = p.colour
+        if grad is not None:
+            COLOUR[kind].finish(_sptr(s_mem), H, W, param, p.colour_partials, grad)
+        p.colour_partials = None
     V = p.V
     vm, K, campos = p.cam
     tw, th = math.ceil(W / float(TILE)), math.ceil(H / float(TILE))

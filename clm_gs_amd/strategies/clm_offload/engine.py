@@ -31,7 +31,7 @@ import torch
 
 from ... import _lib, clm_kernels, dp, fast_tsp, mcmc, utils
 from ...cameras import camera_loss_mask
-from ...clm_kernels import (apply_camera_bilagrid, apply_camera_exposure, camera_depth_term, check_depth_prior_args,
+from ...clm_kernels import (apply_camera_colour, camera_depth_term, check_depth_prior_args,
                             send_shs2cpu_grad_buffer_stream, send_shs2gpu_stream, spherical_harmonics_bwd_inplace)
 from ...densification import check_mcmc_args, update_densification_stats_offload_accum_grads
 from ...gsplat import (fully_fused_projection, isect_offset_encode, isect_tiles,
@@ -198,7 +198,7 @@ def _render_and_backward(gaussians, scene, camera, background, pipe_args, this_f
     image, means2D, radiis, colors_detached, dirs, *inv_depth = pipeline_forward_one_step_shs_inplace(
         opa, sca, rot, xyz, shs, camera, scene, gaussians, background, pipe_args,
         render_mode="RGB+ID" if has_prior else "RGB")
-    image = apply_camera_bilagrid(apply_camera_exposure(image, camera), camera)  # the camera's exposure transform or bilateral grid, if it has one
+    image = apply_camera_colour(image, camera)  # the camera's exposure transform or bilateral grid, if it has one
     loss = torch_compiled_loss(image, camera.original_image, *camera_loss_mask(camera))
     if has_prior:
         loss = loss + camera_depth_term(inv_depth[0][0], camera)
@@ -937,5 +937,5 @@ def clm_offload_eval_one_cam(camera, gaussians, background, scene, render_mode="
         res = pipeline_forward_one_step(opa, sca, rot, xyz, shs, camera, scene, gaussians,
                                         background, None, eval=True, render_mode=render_mode,
                                         return_alpha=return_alpha)
-        image = apply_camera_bilagrid(apply_camera_exposure(res[0], camera), camera)  # a training camera is rendered as it was trained
+        image = apply_camera_colour(res[0], camera)  # a training camera is rendered as it was trained
     return image if render_mode == "RGB" else (image,) + tuple(res[3:])

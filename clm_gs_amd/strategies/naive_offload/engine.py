@@ -7,7 +7,7 @@ Same call signatures and return values as the reference."""
 import torch
 
 from ... import utils
-from ...clm_kernels import apply_camera_bilagrid, apply_camera_exposure, check_depth_prior_args
+from ...clm_kernels import apply_camera_colour, check_depth_prior_args
 from ...fused import train_one_camera
 from ..base_engine import calculate_filters, pipeline_forward_one_step
 
@@ -84,7 +84,7 @@ def naive_offload_eval_one_cam(gaussians, scene, camera, background, render_mode
             gaussians.opacity_activation(rep._opacity), gaussians.scaling_activation(rep._scaling),
             gaussians.rotation_activation(rep._rotation), rep._xyz, rep.shs, camera, scene, gaussians,
             background, None, eval=True, render_mode=render_mode, return_alpha=return_alpha)
-        image = apply_camera_bilagrid(apply_camera_exposure(res[0], camera), camera)  # a training camera is rendered as it was trained
+        image = apply_camera_colour(res[0], camera)  # a training camera is rendered as it was trained
     return image if render_mode == "RGB" else (image,) + tuple(res[3:])
 
 
@@ -104,5 +104,5 @@ def render_single_image(gaussians, scene, camera, background=None):
             img, _, _, _ = baseline_accumGrads_micro_step(
                 gaussians.get_xyz, gaussians.get_opacity, gaussians.get_scaling, gaussians.get_rotation,
                 gaussians.get_features, gaussians.active_sh_degree, camera, background, mode="test")
-            img = apply_camera_bilagrid(apply_camera_exposure(img, camera), camera)
+            img = apply_camera_colour(img, camera)
     return torch.clamp(img, 0.0, 1.0)

@@ -7,7 +7,7 @@ import torch
 
 from ... import utils
 from ...cameras import camera_loss_mask
-from ...clm_kernels import apply_camera_bilagrid, apply_camera_exposure, camera_depth_term, check_depth_prior_args
+from ...clm_kernels import apply_camera_colour, camera_depth_term, check_depth_prior_args
 from ...densification import update_densification_stats_baseline_accum_grads
 from ...gsplat import (fully_fused_projection, isect_offset_encode, isect_tiles,
                        rasterize_to_pixels, spherical_harmonics)
@@ -90,7 +90,7 @@ def baseline_accumGrads_impl(gaussians, scene, batched_cameras, background, scal
         rendered_image, means2D, radiis, gaussian_ids, *inv_depth = baseline_accumGrads_micro_step(
             means3D, opacities, scales, rotations, shs, sh_degree, camera, background,
             render_mode="RGB+ID" if has_prior else "RGB")
-        rendered_image = apply_camera_bilagrid(apply_camera_exposure(rendered_image, camera), camera)  # the camera's exposure transform or bilateral grid, if it has one
+        rendered_image = apply_camera_colour(rendered_image, camera)  # the camera's exposure transform or bilateral grid, if it has one
         loss = torch_compiled_loss(rendered_image, camera.original_image, *camera_loss_mask(camera))
         if has_prior:
             loss = loss + camera_depth_term(inv_depth[0][0], camera)

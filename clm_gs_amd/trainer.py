@@ -18,7 +18,7 @@ import torch
 
 from . import dp, mcmc, utils
 from .cameras import camera_loss_mask
-from .clm_kernels import apply_camera_bilagrid, apply_camera_exposure
+from .clm_kernels import apply_camera_colour
 from .densification import check_mcmc_args, gsplat_densification, mcmc_refinement
 from .pose import check_pose_args
 
@@ -335,7 +335,7 @@ def training(gaussians, scene, train_cameras, test_cameras, log_file, iterations
             img, _, _, _ = baseline_accumGrads_micro_step(
                 gaussians.get_xyz, gaussians.get_opacity, gaussians.get_scaling, gaussians.get_rotation,
                 gaussians.get_features, gaussians.active_sh_degree, cam, background, mode="test")
-            return apply_camera_bilagrid(apply_camera_exposure(img, cam), cam)  # a training camera is rendered as it was trained
+            return apply_camera_colour(img, cam)  # a training camera is rendered as it was trained
     spatial = bool(getattr(args, "spatial_row_order", True)) and hasattr(gaussians, "spatial_sort") and not naive
     if spatial:
         gaussians.spatial_sort()  # rows along a Z-order curve: a camera's rows become contiguous runs
@@ -492,12 +492,10 @@ def training(gaussians, scene, train_cameras, test_cameras, log_file, iterations
             log_file.write(memory_line(iteration, gbsz, gaussians))
         if not clm and not naive and not use_mcmc:  # train.py:533-578
             no_offload_optimizer_step(gaussians, args, bsz, visibility)
-        if exposure is not None:
-            exposure.step(iteration)
-            exposure.zero_grad()
-        if bilagrid is not None:
-            bilagrid.step(iteration)
-            bilagrid.zero_grad()
+        for colour in (exposure, bilagrid):
+            if colour is not None:
+                colour.step(iteration)
+                colour.zero_grad()
         if pose is not None:
             pose.step(batch)
         if not defer:

@@ -364,14 +364,14 @@ def test_apply_camera_bilagrid(dev):
     class Cam:
         image_name = "a"
     cam, img = Cam(), torch.rand(3, 6, 10, device=dev)
-    assert K.apply_camera_bilagrid(img, cam) is img
+    assert K.apply_camera_colour(img, cam) is img
     m = BilagridModel(1, dev, grid=(3, 2, 2))
     m.attach([cam])
     with torch.no_grad():
         m.param[0, ..., 3] = 0.25  # A[0][3] at every node: red + 0.25
         m.grad[0] += 1.0
     leaf = img.clone().requires_grad_()
-    y = K.apply_camera_bilagrid(leaf, cam)
+    y = K.apply_camera_colour(leaf, cam)
     assert torch.equal(y.detach()[0], img[0] + 0.25) and torch.equal(y.detach()[1:], img[1:])
     y.sum().backward()
     # the gradient of sum(y) over all nodes: per coefficient 4c + k, sum_p x_k (x_3 = 1), on top of the 1 that was there
@@ -380,11 +380,11 @@ def test_apply_camera_bilagrid(dev):
     assert rel_l2(got, want) < 1e-5 and torch.equal(leaf.grad, torch.ones_like(img))
     with torch.no_grad():  # evaluation: no tape, nothing added
         before = m.grad.clone()
-        y2 = K.apply_camera_bilagrid(img, cam)
+        y2 = K.apply_camera_colour(img, cam)
     assert torch.equal(y2, y.detach()) and torch.equal(m.grad, before)
     cam.exposure = torch.eye(3, 4, device=dev)
     with pytest.raises(ValueError, match="both an exposure row and a bilateral grid"):
-        K.apply_camera_bilagrid(img, cam)
+        K.apply_camera_colour(img, cam)
 
 
 # ------------------------------------------------------------------------------------------- engines

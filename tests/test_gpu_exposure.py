@@ -24,7 +24,7 @@ U = 2.0 ** -24  # unit roundoff of float32
 # 1 pixel; 35 = 8 groups of 4 + a tail of 3; 871 = 4 * 217 + 3; 9100: several forward workgroups (4096 pixels each), a partial last one
 SHAPES = [(1, 1), (5, 7), (13, 67), (70, 130)]
 LAYOUTS = ["hwc", "chw", "hwc_offset"]  # the engine's interleaved buffer (fast path) | planar | interleaved, base moved by one pixel
-# csrc/exposure.hip: EXP_LANE_PIXELS, the DPP steps of wave_sum, EXP_WAVES, EXP_FINISH_SLICES (+ its two-step tree)
+# csrc/exposure.hip: EXP_LANE_PIXELS, the DPP steps of wave_sum, EXP_WAVES, the four slices of rows_finish_kernel<16> (+ its two-step tree)
 LANE_PIXELS, WAVE_STEPS, WAVES, FINISH_SLICES, FINISH_TREE = 64, 6, 4, 4, 2
 
 
@@ -230,14 +230,14 @@ def test_apply_camera_exposure(dev):
     class Cam:
         image_name = "a"
     cam, img = Cam(), torch.rand(3, 6, 10, device=dev)
-    assert K.apply_camera_exposure(img, cam) is img
+    assert K.apply_camera_colour(img, cam) is img
     m = ExposureModel(1, dev)
     m.attach([cam])
     with torch.no_grad():
         m.param[0, 0, 3] = 0.25
         m.grad[0] += 1.0
     leaf = img.clone().requires_grad_()
-    y = K.apply_camera_exposure(leaf, cam)
+    y = K.apply_camera_colour(leaf, cam)
     assert torch.equal(y.detach()[0], img[0] + 0.25) and torch.equal(y.detach()[1:], img[1:])
     y.sum().backward()
     want = torch.ones(3, 4, device=dev)
@@ -246,7 +246,7 @@ def test_apply_camera_exposure(dev):
     assert rel_l2(m.grad[0].cpu(), want.cpu()) < 1e-6 and torch.equal(leaf.grad, torch.ones_like(img))
     with torch.no_grad():  # evaluation: no tape, nothing added
         before = m.grad.clone()
-        y2 = K.apply_camera_exposure(img, cam)
+        y2 = K.apply_camera_colour(img, cam)
     assert torch.equal(y2, y.detach()) and torch.equal(m.grad, before)
 
 
