@@ -15,8 +15,9 @@ Two residency modes for the [N,48] SH rows and their optimizer state (see gaussi
   into pinned staging) and ship 48 MB chunks with hipMemcpyAsync on a side stream, grouped by the camera that uses
   a row first; gradient rows go home as zero-copy stores after the camera that uses a row last.  Two staging forms,
   each its own module of four stage functions: per-camera windows (`host_window.py`, the default; `sh_hbm_budget_gb`
-  keeps a prefix of the rows resident and stepped in HBM) and the union of the batch (`host_batch.py`).  No retention
-  sets, no signal flags, no host Adam thread: the modules' docstrings say what replaced them and why.
+  keeps a prefix of the rows resident and stepped in HBM) and the union of the batch (`host_batch.py`); what the two do
+  identically is in `host_stages.py`.  No retention sets, no signal flags, no host Adam thread: the modules' docstrings
+  say what replaced them and why.
 
 Camera order: both modes process the cameras in the order given (the batch gradient does not depend on it and
 every touched row crosses the host link once per direction whatever the order).  `order_calculation` -- the
@@ -791,75 +792,6 @@ def _train_one_batch_hbm(gaussians, scene, batched_cameras, parameters_grad_buff
 
 
 # ---------------------------------------------------------------------- host-resident
-def _bit_of(bitmap, ids, bit):
-    return ((bitmap[ids].to(torch.int64) >> bit) & 1).to(torch.bool)
-
-
-_HOST_CHUNK_ROWS = 262144  # staging granularity: 48 MB of parameter rows per hipMemcpyAsync
-
-
-def _host_tables(gaussians, dev):
-    """Row-indexed scratch of the host-resident mode (independent of the batch size): row -> slot, two row masks."""
-    N = gaussians._xyz.shape[0]
-    ht = getattr(gaussians, "_host_tabs", None)
-    if ht is None or ht["N"] != N:
-        ht = gaussians._host_tabs = dict(N=N, slot_of=torch.zeros((N,), dtype=torch.int32, device=dev),
-                                         mark=torch.zeros((N,), dtype=torch.bool, device=dev),
-                                         in_spec=torch.zeros((N,), dtype=torch.bool, device=dev))
-    return ht
-
-
-def _host_buffers(gaussians, T, dev):
-    """Per-batch buffers of the host-resident mode, kept between batches (bucketed capacity):
-    pinned row lists + pinned staging rows on the host (one set for the batch's late rows, one for the
-    speculative rows of the next batch), TWO staging parameter tables on the GPU (the batch in flight renders
-    from one while the next batch's speculative rows land in the other) and the gradient staging table.
-    `gen` counts re-allocations: rows staged into an older generation are gone."""
-    from ...gsplat import bucket_size
-    hb = getattr(gaussians, "_host_bufs", None)
-    N = gaussians._xyz.shape[0]
-    if hb is None or hb["cap"] < T or hb["N"] != N:
-        # Two capacities.  DEVICE tables (they count against the GPU peak of the offloading mode): 8 % over the need,
-        # grown when a batch exceeds them.  PINNED host twins: 50 % over the need -- host memory is cheap, and a new
-        # pinned table is a hipHostMalloc of 2 GB at 28 M (300+ ms: ONE such re-allocation inside a 20-batch run was
-        # 21 of the 24 ms of average "host_groups" time rounds 2-3 reported); they are kept when only the device tables
-        # grow.  The union of a batch's filters varies by several percent from batch to batch (shuffled cameras), and
-        # staged-but-unused rows of a hinted batch ride along.
-        cap = bucket_size(max(int(T * 1.08), 1))
-        gen = hb["gen"] + 1 if hb else 0
-        keep_pinned = None
-        if hb is not None:
-            # The staging tables are written by hipMemcpyAsync issued through ctypes on the side streams (speculative
-            # prefetch, feeder): the caching allocator knows nothing of that use, and a dropped speculation is only
-            # JOINED (its last copy may still be in flight).  Growing the tables is rare: drain the device before the
-            # old blocks go back to the allocator, so no late copy can land in a recycled block.
-            torch.cuda.synchronize()
-            if hb["N"] == N and hb["rows_h"].shape[0] >= cap:
-                keep_pinned = (hb["rows_h"], hb["stage_h"], hb["spec_rows_h"], hb["spec_stage_h"])
-            hb.clear()  # the old tables go back to the allocator BEFORE the new ones are requested
-        gaussians._host_bufs = None
-        if keep_pinned is None:
-            cap_h = bucket_size(max(int(T * 1.5), cap))
-            keep_pinned = (pinned_empty((cap_h,), dtype=torch.int32), pinned_empty((cap_h, 48)), None, None)
-        hb = gaussians._host_bufs = dict(
-            cap=cap, N=N, cur=0, gen=gen,
-            rows_h=keep_pinned[0], stage_h=keep_pinned[1], spec_rows_h=keep_pinned[2], spec_stage_h=keep_pinned[3],
-            sh_stage=[torch.empty((cap, 48), device=dev), None],
-            g_stage=torch.empty((cap, 48), device=dev))
-    return hb
-
-
-def _host_spec_buffers(hb, dev):
-    """The second staging table + its pinned twin: allocated when the first hint arrives (a caller that never
-    hints pays nothing for the speculative prefetch)."""
-    if hb["sh_stage"][1] is None:
-        hb["sh_stage"][1] = torch.empty((hb["cap"], 48), device=dev)
-    if hb["spec_rows_h"] is None:
-        cap_h = hb["rows_h"].shape[0]
-        hb["spec_rows_h"] = pinned_empty((cap_h,), dtype=torch.int32)
-        hb["spec_stage_h"] = pinned_empty((cap_h, 48))
-
-
 def hint_next_batch(gaussians, cameras):
     """Host-resident mode: tell the engine which cameras the NEXT call of clm_offload_train_one_batch will get
     (a data loader knows; `trainer.training` and `bench.py` call this).  The engine then selects that batch's rows
@@ -868,10 +800,6 @@ def hint_next_batch(gaussians, cameras):
     against the exact selection when the batch arrives (late rows are staged then, unused ones un-stamped).
     Without a hint, or with a wrong one, the engine behaves as before."""
     gaussians._next_batch_hint = list(cameras) if cameras else None
-
-
-def _drop_speculation(gaussians):
-    gaussians.drop_host_speculation()
 
 
 def _train_one_batch_host(gaussians, scene, batched_cameras, parameters_grad_buffer, background,

@@ -573,7 +573,7 @@ class GaussianModelCLMOffload(BaseGaussianModel):
         """Forget the rows the engine staged for a hinted batch that is not coming (model resized / flushed /
         evaluated / different cameras): they were stamped as expecting that batch's gradient, which will never
         land (clm_offload/engine.py speculative prefetch)."""
-        for attr in ("_host_spec", "_hwin_spec"):  # (batch-wide staging / per-camera windows: engine.py / host_window.py)
+        for attr in ("_host_spec", "_hwin_spec"):  # (batch-wide staging / per-camera windows: host_batch.py / host_window.py)
             sp = getattr(self, attr, None)
             setattr(self, attr, None)
             if sp is None:

@@ -826,6 +826,36 @@ def test_host_staging_tables_grow_under_an_outstanding_speculation(dev, staging)
             assert rel_l2(a.cuda(), b.detach().cuda()) < 2e-6, name
 
 
+@pytest.mark.parametrize("staging", ["host", "host_batch"])
+def test_host_feeder_error_reaches_the_caller_and_leaves_no_thread(dev, staging, monkeypatch):
+    """An exception on a helper thread of the host-resident mode (here: the deferred row optimizer refuses its second
+    chunk) is raised by clm_offload_train_one_batch in the calling thread, and no helper thread is left behind: every
+    event the camera stage or another helper could be blocked on has been released."""
+    import threading
+
+    from clm_gs_amd.strategies.clm_offload import GaussianModelCLMOffload, clm_offload_train_one_batch
+    args, sc, cams = _setup("clm_offload", staging)
+    m = _make("clm_offload", sc, args)
+    real, calls = GaussianModelCLMOffload.host_rows_prepare, []
+
+    def prepare(self, *a, **kw):
+        calls.append(1)
+        if len(calls) == 2:
+            raise RuntimeError("boom")
+        return real(self, *a, **kw)
+
+    monkeypatch.setattr(GaussianModelCLMOffload, "host_rows_prepare", prepare)
+    comm, gen = torch.cuda.Stream(), torch.Generator(device="cuda").manual_seed(1)
+    with pytest.raises(RuntimeError, match="boom"):
+        clm_offload_train_one_batch(m, _Scene, cams, m.parameters_grad_buffer, None, None, comm, gen)
+    monkeypatch.undo()
+    helpers = [t for t in threading.enumerate() if t.name.startswith("clmgs-host")]
+    for t in helpers:
+        t.join(timeout=5.0)
+    assert not [t.name for t in helpers if t.is_alive()]
+    torch.cuda.synchronize()
+
+
 def test_deferred_small_adam_equals_eager(dev):
     """Round 5: xyz / opacity / scaling / rotation stepped per block of 256 rows, only when one of the batch's cameras
     may see the block (GaussianModelCLMOffload.small_deferred, clmgs_adam_small_deferred) == the eager dense Adam of
