@@ -51,68 +51,37 @@ def fused_ssim(img1, img2):
 
 
 class _FusedL1SSIMLoss(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, image, gt_u8, lambda_dssim):
-        L = _lib.lib()
-        assert image.dim() == 3 and image.shape[0] == 3 and image.dtype == F32 and image.is_cuda
-        _, H, W = image.shape
-        gt_u8 = gt_u8.contiguous()
-        assert gt_u8.dtype == U8 and gt_u8.shape == image.shape
-        need = image.requires_grad
-        slots = L.clmgs_loss_slots()
-        partials = torch.zeros((slots, 2), dtype=F32, device=image.device)
-        maps = torch.empty((3, 3, H, W), dtype=F32, device=image.device) if need else None
-        sc, sy, sx = image.stride()
-        check(L.clmgs_l1_ssim_loss_fwd(stream(), H, W, ctypes.c_void_p(image.data_ptr()), sc, sy, sx,
-                                       dptr(gt_u8, U8), dptr(partials),
-                                       dptr(maps[0] if need else None, F32, True),
-                                       dptr(maps[1] if need else None, F32, True),
-                                       dptr(maps[2] if need else None, F32, True)))
-        tot = partials.sum(dim=0) / float(image.numel())
-        ctx.lam = float(lambda_dssim)
-        if need:
-            ctx.save_for_backward(image, gt_u8, maps)
-        return (1.0 - ctx.lam) * tot[0] + ctx.lam * (1.0 - tot[1])
+    """mask None: the unmasked entries; a mask: the _masked_ entries, which take it as their last argument."""
 
-    @staticmethod
-    def backward(ctx, v):
-        L = _lib.lib()
-        image, gt_u8, maps = ctx.saved_tensors
-        _, H, W = image.shape
-        v = v.reshape(1).to(F32).contiguous()
-        v_img = torch.empty_strided(image.shape, image.stride(), dtype=F32, device=image.device)
-        sc, sy, sx = image.stride()
-        check(L.clmgs_l1_ssim_loss_bwd(stream(), H, W, ctypes.c_void_p(image.data_ptr()), sc, sy, sx,
-                                       dptr(gt_u8, U8), dptr(v, F32), ctx.lam, dptr(maps[0]),
-                                       dptr(maps[1]), dptr(maps[2]),
-                                       ctypes.c_void_p(v_img.data_ptr())))
-        return v_img, None, None
-
-
-class _FusedL1SSIMLossMasked(torch.autograd.Function):
     @staticmethod
     def forward(ctx, image, gt_u8, lambda_dssim, mask, mask_count):
         L = _lib.lib()
         assert image.dim() == 3 and image.shape[0] == 3 and image.dtype == F32 and image.is_cuda
         _, H, W = image.shape
-        gt_u8, mask = gt_u8.contiguous(), mask.contiguous()
+        gt_u8 = gt_u8.contiguous()
         assert gt_u8.dtype == U8 and gt_u8.shape == image.shape
-        assert mask.dtype == U8 and tuple(mask.shape) == (H, W) and mask.device == image.device
+        if mask is not None:
+            mask = mask.contiguous()
+            assert mask.dtype == U8 and tuple(mask.shape) == (H, W) and mask.device == image.device
         need = image.requires_grad
         slots = L.clmgs_loss_slots()
         partials = torch.zeros((slots, 2), dtype=F32, device=image.device)
         maps = torch.empty((3, 3, H, W), dtype=F32, device=image.device) if need else None
         sc, sy, sx = image.stride()
-        check(L.clmgs_l1_ssim_loss_masked_fwd(stream(), H, W, ctypes.c_void_p(image.data_ptr()), sc, sy, sx,
-                                              dptr(gt_u8, U8), dptr(partials),
-                                              dptr(maps[0] if need else None, F32, True),
-                                              dptr(maps[1] if need else None, F32, True),
-                                              dptr(maps[2] if need else None, F32, True), dptr(mask, U8)))
-        tot = partials.sum(dim=0)
+        fwd, extra = (L.clmgs_l1_ssim_loss_fwd, ()) if mask is None else (L.clmgs_l1_ssim_loss_masked_fwd, (dptr(mask, U8),))
+        check(fwd(stream(), H, W, ctypes.c_void_p(image.data_ptr()), sc, sy, sx,
+                  dptr(gt_u8, U8), dptr(partials),
+                  dptr(maps[0] if need else None, F32, True),
+                  dptr(maps[1] if need else None, F32, True),
+                  dptr(maps[2] if need else None, F32, True), *extra))
         ctx.lam = float(lambda_dssim)
         if need:
             ctx.save_for_backward(image, gt_u8, maps, mask)
-        return masked_loss_value(tot[0], tot[1], ctx.lam, mask_count, H, W)
+        if mask is not None:
+            tot = partials.sum(dim=0)
+            return masked_loss_value(tot[0], tot[1], ctx.lam, mask_count, H, W)
+        tot = partials.sum(dim=0) / float(image.numel())
+        return (1.0 - ctx.lam) * tot[0] + ctx.lam * (1.0 - tot[1])
 
     @staticmethod
     def backward(ctx, v):
@@ -122,10 +91,11 @@ class _FusedL1SSIMLossMasked(torch.autograd.Function):
         v = v.reshape(1).to(F32).contiguous()
         v_img = torch.empty_strided(image.shape, image.stride(), dtype=F32, device=image.device)
         sc, sy, sx = image.stride()
-        check(L.clmgs_l1_ssim_loss_masked_bwd(stream(), H, W, ctypes.c_void_p(image.data_ptr()), sc, sy, sx,
-                                              dptr(gt_u8, U8), dptr(v, F32), ctx.lam, dptr(maps[0]),
-                                              dptr(maps[1]), dptr(maps[2]),
-                                              ctypes.c_void_p(v_img.data_ptr()), dptr(mask, U8)))
+        bwd, extra = (L.clmgs_l1_ssim_loss_bwd, ()) if mask is None else (L.clmgs_l1_ssim_loss_masked_bwd, (dptr(mask, U8),))
+        check(bwd(stream(), H, W, ctypes.c_void_p(image.data_ptr()), sc, sy, sx,
+                  dptr(gt_u8, U8), dptr(v, F32), ctx.lam, dptr(maps[0]),
+                  dptr(maps[1]), dptr(maps[2]),
+                  ctypes.c_void_p(v_img.data_ptr()), *extra))
         return v_img, None, None, None, None
 
 
@@ -143,11 +113,9 @@ def fused_l1_ssim_loss(image, gt_u8, lambda_dssim=0.2, mask=None, mask_count=Non
     unmasked kernels).  Ignored pixels add nothing to either term; the SSIM statistics are those of the whole images
     and the divisor stays 3 H W ("Masked loss").  mask_count: the number of counted pixels as a
     host integer (Camera.loss_mask_count); counted here, with one read-back, when not given."""
-    if mask is None:
-        return _FusedL1SSIMLoss.apply(image, gt_u8, lambda_dssim)
-    if mask_count is None:
+    if mask is not None and mask_count is None:
         mask_count = int(torch.count_nonzero(mask).item())
-    return _FusedL1SSIMLossMasked.apply(image, gt_u8, lambda_dssim, mask, int(mask_count))
+    return _FusedL1SSIMLoss.apply(image, gt_u8, lambda_dssim, mask, mask_count)
 
 
 # ------------------------------------------------------- depth regularisation

@@ -15,8 +15,7 @@ from . import _lib, utils
 from ._lib import check, dptr
 from .cameras import camera_colour, camera_invdepth, camera_loss_mask, camera_pose_grad
 from .clm_kernels import COLOUR, check_depth_prior_args, masked_loss_value
-from .gsplat import (_record_counts, bucket_size, empty_bucketed, isect2_begin, isect2_counts, isect2_finish, isect3_begin,
-                     isect3_finish)
+from .gsplat import _record_counts, bucket_size, empty_bucketed, isect_begin, isect_counts, isect_finish
 
 F32, I32, U8, U16 = torch.float32, torch.int32, torch.uint8, torch.uint16
 TILE = 16
@@ -209,9 +208,8 @@ def camera_front(gaussians, camera, this_filter, sh_rows, sh_by_filter, backgrou
             p.depths = depths
         # binning route: "tile" (default, csrc/isect3.hip: no global sort) | "sort" (csrc/isect.hip: depth sort + tile sort);
         # identical lists (tests/test_gpu_ops.py)
-        begin = isect3_begin if getattr(args, "binning", "tile") == "tile" else isect2_begin
-        p.isect = begin(means2d, radii, depths, TILE, tw, th, want_slots=True,
-                        packed=packed if getattr(args, "exact_tile_cull", True) else None)
+        p.isect = isect_begin("tile" if getattr(args, "binning", "tile") == "tile" else "sort", means2d, radii, depths, TILE,
+                              tw, th, want_slots=True, packed=packed if getattr(args, "exact_tile_cull", True) else None)
         p.aux = p.aux + (means2d, depths)
         p.means2d = means2d  # [1,V,2] pixel centres (parity checks read them; kept alive through p.aux)
     return p
@@ -235,8 +233,7 @@ def camera_forward_finish(gaussians, p, exact=False):
     cap = None if (exact or V == 0) else _capacity_for(_cap_key(gaussians, W, H), args)
     with torch.cuda.stream(s_front):
         with _lib.host_region("fwd_isect"):
-            finish = isect3_finish if p.isect.route == "tile" else isect2_finish
-            p.fids, p.offsets, _, (p.emit_slot, p.row_cum) = finish(p.isect, capacity=cap)
+            p.fids, p.offsets, _, (p.emit_slot, p.row_cum) = isect_finish(p.isect, capacity=cap)
         if cap is None:
             p.isect, p.n_dev = None, None
             if V:
@@ -368,7 +365,7 @@ def camera_verify(gaussians, p):
     if c is None or p.n_dev is None:
         return
     W, H = int(utils.get_img_width()), int(utils.get_img_height())
-    n, n_ref = isect2_counts(c)
+    n, n_ref = isect_counts(c)
     _observe_count(_cap_key(gaussians, W, H), n)
     if n <= p.fids.numel():
         _record_counts(n, n_ref)

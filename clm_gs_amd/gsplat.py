@@ -38,9 +38,12 @@ def _viewmats_grad(ctx, means, quats, scales, viewmats, Ks, radii, v_means2d, v_
 
 # --------------------------------------------------------------------- projection
 class _Projection(torch.autograd.Function):
+    """clmgs_projection_fwd / _bwd; with calc_compensations the _aa_ entries, whose opacity compensations are a fifth,
+    differentiable output (None otherwise: no buffer, no cotangent)."""
+
     @staticmethod
     def forward(ctx, means, quats, scales, viewmats, Ks, width, height, eps2d, near_plane,
-                far_plane, radius_clip):
+                far_plane, radius_clip, calc_compensations):
         L = _lib.lib()
         means, quats, scales = means.contiguous(), quats.contiguous(), scales.contiguous()
         viewmats, Ks = viewmats.contiguous(), Ks.contiguous()
@@ -50,63 +53,16 @@ class _Projection(torch.autograd.Function):
         means2d = torch.empty((C, N, 2), dtype=F32, device=dev)
         depths = torch.empty((C, N), dtype=F32, device=dev)
         conics = torch.empty((C, N, 3), dtype=F32, device=dev)
-        check(L.clmgs_projection_fwd(
+        comps = torch.empty((C, N), dtype=F32, device=dev) if calc_compensations else None
+        fwd, extra = (L.clmgs_projection_aa_fwd, (dptr(comps),)) if calc_compensations else (L.clmgs_projection_fwd, ())
+        check(fwd(
             stream(), C, N, dptr(means, F32), dptr(quats, F32), dptr(scales, F32),
             dptr(viewmats, F32), dptr(Ks, F32), int(width), int(height), float(eps2d),
             float(near_plane), float(far_plane), float(radius_clip), dptr(radii), dptr(means2d),
-            dptr(depths), dptr(conics)))
+            dptr(depths), dptr(conics), *extra))
         ctx.save_for_backward(means, quats, scales, viewmats, Ks, radii)
         ctx.cfg = (int(width), int(height), float(eps2d))
-        ctx.mark_non_differentiable(radii)
-        return radii, means2d, depths, conics
-
-    @staticmethod
-    def backward(ctx, _v_radii, v_means2d, v_depths, v_conics):
-        L = _lib.lib()
-        means, quats, scales, viewmats, Ks, radii = ctx.saved_tensors
-        width, height, eps2d = ctx.cfg
-        C, N = radii.shape
-        dev = means.device
-        if v_means2d is None:
-            v_means2d = torch.zeros((C, N, 2), dtype=F32, device=dev)
-        if v_conics is None:
-            v_conics = torch.zeros((C, N, 3), dtype=F32, device=dev)
-        v_means2d, v_conics = v_means2d.contiguous(), v_conics.contiguous()
-        v_depths = v_depths.contiguous() if v_depths is not None else None
-        v_means = torch.empty_like(means)
-        v_quats = torch.empty_like(quats)
-        v_scales = torch.empty_like(scales)
-        check(L.clmgs_projection_bwd(
-            stream(), C, N, dptr(means), dptr(quats), dptr(scales), dptr(viewmats), dptr(Ks),
-            width, height, eps2d, dptr(radii), dptr(v_means2d, F32), dptr(v_depths, F32, True),
-            dptr(v_conics, F32), dptr(v_means), dptr(v_quats), dptr(v_scales)))
-        v_viewmats = _viewmats_grad(ctx, means, quats, scales, viewmats, Ks, radii, v_means2d, v_depths, v_conics, None)
-        return v_means, v_quats, v_scales, v_viewmats, None, None, None, None, None, None, None
-
-
-class _ProjectionAA(torch.autograd.Function):
-    """_Projection with the opacity compensations (clmgs_projection_aa_fwd / _aa_bwd) as a fifth, differentiable output."""
-
-    @staticmethod
-    def forward(ctx, means, quats, scales, viewmats, Ks, width, height, eps2d, near_plane,
-                far_plane, radius_clip):
-        L = _lib.lib()
-        means, quats, scales = means.contiguous(), quats.contiguous(), scales.contiguous()
-        viewmats, Ks = viewmats.contiguous(), Ks.contiguous()
-        C, N = viewmats.shape[0], means.shape[0]
-        dev = means.device
-        radii = torch.empty((C, N), dtype=I32, device=dev)
-        means2d = torch.empty((C, N, 2), dtype=F32, device=dev)
-        depths = torch.empty((C, N), dtype=F32, device=dev)
-        conics = torch.empty((C, N, 3), dtype=F32, device=dev)
-        comps = torch.empty((C, N), dtype=F32, device=dev)
-        check(L.clmgs_projection_aa_fwd(
-            stream(), C, N, dptr(means, F32), dptr(quats, F32), dptr(scales, F32),
-            dptr(viewmats, F32), dptr(Ks, F32), int(width), int(height), float(eps2d),
-            float(near_plane), float(far_plane), float(radius_clip), dptr(radii), dptr(means2d),
-            dptr(depths), dptr(conics), dptr(comps)))
-        ctx.save_for_backward(means, quats, scales, viewmats, Ks, radii)
-        ctx.cfg = (int(width), int(height), float(eps2d))
+        ctx.aa = bool(calc_compensations)
         ctx.mark_non_differentiable(radii)
         return radii, means2d, depths, conics, comps
 
@@ -127,12 +83,13 @@ class _ProjectionAA(torch.autograd.Function):
         v_means = torch.empty_like(means)
         v_quats = torch.empty_like(quats)
         v_scales = torch.empty_like(scales)
-        check(L.clmgs_projection_aa_bwd(
+        bwd, extra = (L.clmgs_projection_aa_bwd, (dptr(v_comps, F32, True),)) if ctx.aa else (L.clmgs_projection_bwd, ())
+        check(bwd(
             stream(), C, N, dptr(means), dptr(quats), dptr(scales), dptr(viewmats), dptr(Ks),
             width, height, eps2d, dptr(radii), dptr(v_means2d, F32), dptr(v_depths, F32, True),
-            dptr(v_conics, F32), dptr(v_comps, F32, True), dptr(v_means), dptr(v_quats), dptr(v_scales)))
+            dptr(v_conics, F32), *extra, dptr(v_means), dptr(v_quats), dptr(v_scales)))
         v_viewmats = _viewmats_grad(ctx, means, quats, scales, viewmats, Ks, radii, v_means2d, v_depths, v_conics, v_comps)
-        return v_means, v_quats, v_scales, v_viewmats, None, None, None, None, None, None, None
+        return v_means, v_quats, v_scales, v_viewmats, None, None, None, None, None, None, None, None
 
 
 def fully_fused_projection(means, covars, quats, scales, viewmats, Ks, width, height, eps2d=0.3,
@@ -151,30 +108,15 @@ def fully_fused_projection(means, covars, quats, scales, viewmats, Ks, width, he
     """
     if covars is not None:
         raise NotImplementedError("the CLM-GS engines always pass covars=None")
-    if calc_compensations:
-        if not packed:
-            return _ProjectionAA.apply(means, quats, scales, viewmats, Ks, width, height, eps2d, near_plane,
-                                       far_plane, radius_clip)
-        with torch.no_grad():
-            radii, means2d, depths, conics, comps = _ProjectionAA.apply(
-                means, quats, scales, viewmats, Ks, width, height, eps2d, near_plane, far_plane, radius_clip)
-            camera_ids, gaussian_ids = torch.nonzero(radii > 0, as_tuple=True)
-            return (camera_ids, gaussian_ids, radii[camera_ids, gaussian_ids],
-                    means2d[camera_ids, gaussian_ids], depths[camera_ids, gaussian_ids],
-                    conics[camera_ids, gaussian_ids], comps[camera_ids, gaussian_ids])
+    args = (means, quats, scales, viewmats, Ks, width, height, eps2d, near_plane, far_plane, radius_clip,
+            bool(calc_compensations))
     if not packed:
-        radii, means2d, depths, conics = _Projection.apply(
-            means, quats, scales, viewmats, Ks, width, height, eps2d, near_plane, far_plane,
-            radius_clip)
-        return radii, means2d, depths, conics, None
+        return _Projection.apply(*args)
     with torch.no_grad():
-        radii, means2d, depths, conics = _Projection.apply(
-            means, quats, scales, viewmats, Ks, width, height, eps2d, near_plane, far_plane,
-            radius_clip)
+        radii, *outs = _Projection.apply(*args)
         camera_ids, gaussian_ids = torch.nonzero(radii > 0, as_tuple=True)
         return (camera_ids, gaussian_ids, radii[camera_ids, gaussian_ids],
-                means2d[camera_ids, gaussian_ids], depths[camera_ids, gaussian_ids],
-                conics[camera_ids, gaussian_ids], None)
+                *(t[camera_ids, gaussian_ids] if t is not None else None for t in outs))
 
 
 def visibility_radii(means, quats, scales, viewmats, Ks, width, height, eps2d=0.3,
@@ -366,22 +308,26 @@ def _pinned_totals_slot():
     return _PINNED_TOTALS[_PINNED_NEXT]
 
 
-class _Isect2:
-    """State between isect2_begin and isect2_finish (one camera's binning in flight)."""
+class _Isect:
+    """State between isect_begin and isect_finish (one camera's binning in flight)."""
     __slots__ = ("args", "V", "dev", "depths", "order", "cum", "boxes", "totals", "host", "event",
                  "offsets", "temp", "means2d", "radii", "packed", "row_cum", "route")
 
 
 @torch.no_grad()
-def isect2_begin(means2d, radii, depths, tile_size, tile_width, tile_height, want_isect_ids=False,
-                 want_slots=False, packed=None):
-    """First half of isect_tiles_two_level: depth order + per-row tile counts on the CURRENT stream,
-    then an asynchronous copy of the two totals into pinned memory and an event.  Nothing blocks:
-    the caller can enqueue other work (the next camera's projection) before isect2_finish waits for
-    the event -- unlike a `.tolist()`, which waits for everything enqueued on the stream so far."""
+def isect_begin(route, means2d, radii, depths, tile_size, tile_width, tile_height, want_isect_ids=False,
+                want_slots=False, packed=None):
+    """First half of a camera's binning on the CURRENT stream, then an asynchronous copy of the two totals into pinned
+    memory and an event.  Nothing blocks: the caller can enqueue other work (the next camera's projection) before
+    isect_finish waits for the event -- unlike a `.tolist()`, which waits for everything enqueued on the stream so far.
+    route "sort" (csrc/isect.hip, clmgs_isect2_order_count): depth order + per-row tile counts, for a depth sort of the
+    rows and one stable sort on tile-id bits.  route "tile" (csrc/isect3.hip, clmgs_isect3_front): per-row tile boxes /
+    masks, tile counters and row_cum, for the same lists without a global sort."""
+    if route not in ("tile", "sort"):
+        raise ValueError(f"binning route must be 'tile' or 'sort', got {route!r}")
     L = _lib.lib()
-    c = _Isect2()
-    c.route = "sort"
+    c = _Isect()
+    c.route = route
     c.args = (int(tile_size), int(tile_width), int(tile_height), bool(want_isect_ids), bool(want_slots))
     V = c.V = radii.numel()
     dev = c.dev = radii.device
@@ -389,19 +335,26 @@ def isect2_begin(means2d, radii, depths, tile_size, tile_width, tile_height, wan
     c.packed = packed
     c.offsets = torch.empty((1, tile_height, tile_width), dtype=I32, device=dev)
     c.event = None
+    c.order = c.cum = c.boxes = None
     if V == 0:
         return c
-    c.order = empty_bucketed(V, (), I32, dev)
-    c.cum = empty_bucketed(V, (), I64, dev)
-    c.boxes = empty_bucketed(V, (2,), I64, dev)
+    if route == "sort":
+        c.order = empty_bucketed(V, (), I32, dev)
+        c.cum = empty_bucketed(V, (), I64, dev)
+        c.boxes = empty_bucketed(V, (2,), I64, dev)
     c.totals = torch.empty((2,), dtype=I64, device=dev)
-    c.row_cum = empty_bucketed(V, (), I64, dev) if want_slots else None
-    tb = L.clmgs_isect2_order_temp_bytes(V)
+    c.row_cum = empty_bucketed(V, (), I64, dev) if (want_slots or route == "tile") else None
+    tb = (L.clmgs_isect2_order_temp_bytes(V) if route == "sort"
+          else L.clmgs_isect3_front_temp_bytes(V, int(tile_width) * int(tile_height)))
     c.temp = empty_bucketed(tb, (), torch.uint8, dev)
-    check(L.clmgs_isect2_order_count(stream(), V, dptr(c.means2d, F32), dptr(c.radii, I32), dptr(c.depths, F32),
-                                     c.args[0], c.args[1], c.args[2], dptr(packed, F32, True), dptr(c.order),
-                                     dptr(c.cum), dptr(c.boxes), dptr(c.totals), dptr(c.temp), tb,
-                                     dptr(c.row_cum, I64, True)))
+    if route == "sort":
+        check(L.clmgs_isect2_order_count(stream(), V, dptr(c.means2d, F32), dptr(c.radii, I32), dptr(c.depths, F32),
+                                         c.args[0], c.args[1], c.args[2], dptr(packed, F32, True), dptr(c.order),
+                                         dptr(c.cum), dptr(c.boxes), dptr(c.totals), dptr(c.temp), tb,
+                                         dptr(c.row_cum, I64, True)))
+    else:
+        check(L.clmgs_isect3_front(stream(), V, dptr(c.means2d, F32), dptr(c.radii, I32), c.args[0], c.args[1], c.args[2],
+                                   dptr(packed, F32, True), dptr(c.totals), dptr(c.row_cum), dptr(c.temp), tb))
     c.host = _pinned_totals_slot()
     c.host.copy_(c.totals, non_blocking=True)
     c.event = torch.cuda.Event()
@@ -417,8 +370,8 @@ def _record_counts(n_isects, n_ref):
         del _lib.STATS["n_emitted"][:2048]
 
 
-def isect2_counts(c):
-    """Wait for the totals of isect2_begin (an event on an asynchronous readback) -> (emitted, reference)."""
+def isect_counts(c):
+    """Wait for the totals of isect_begin (an event on an asynchronous readback) -> (emitted, reference)."""
     _t0 = time.perf_counter()
     c.event.synchronize()
     n_isects, n_ref = int(c.host[0]), int(c.host[1])
@@ -427,13 +380,14 @@ def isect2_counts(c):
 
 
 @torch.no_grad()
-def isect2_finish(c, capacity=None):
-    """Second half: emit + tile sort + offsets on the CURRENT stream (the stream isect2_begin ran on, or one
-    ordered after it).
+def isect_finish(c, capacity=None):
+    """Second half on the CURRENT stream (the stream isect_begin ran on, or one ordered after it), by the route
+    isect_begin was given: emit + tile sort + offsets (clmgs_isect2_emit_sort) or tile scan, scatter, per-tile sort
+    (clmgs_isect3_bin).
     capacity None: wait for the totals (the one host wait of the front end) and size everything exactly.
-    capacity = K (device-count form, clmgs_isect2_emit_sort_dev): NOTHING is waited for -- buffers and launches
+    capacity = K (device-count form, the entries' _dev variants): NOTHING is waited for -- buffers and launches
     are sized for K intersections and the kernels read the true count from c.totals on the device; the returned
-    lists have K entries of which the first `count` are valid.  The caller must check isect2_counts(c)[0] <= K
+    lists have K entries of which the first `count` are valid.  The caller must check isect_counts(c)[0] <= K
     later (fused.camera_verify) and redo the camera exactly otherwise."""
     L = _lib.lib()
     tile_size, tile_width, tile_height, want_isect_ids, want_slots = c.args
@@ -444,90 +398,27 @@ def isect2_finish(c, capacity=None):
         res = (e, c.offsets, (torch.empty(0, dtype=I64, device=dev) if want_isect_ids else None))
         return res + ((e, torch.empty(0, dtype=I64, device=dev)),) if want_slots else res
     if capacity is None:
-        n_isects, n_ref = isect2_counts(c)
+        n_isects, n_ref = isect_counts(c)
         _record_counts(n_isects, n_ref)
     else:
         n_isects = int(capacity)
+    sort = c.route == "sort"
     fids = empty_bucketed(n_isects, (), I32, dev)
     ids = empty_bucketed(n_isects, (), I64, dev) if want_isect_ids else None
-    sb = L.clmgs_isect2_sort_temp_bytes(n_isects)
+    sb = (L.clmgs_isect2_sort_temp_bytes(n_isects) if sort
+          else L.clmgs_isect3_bin_temp_bytes(n_isects, tile_width * tile_height))
     temp2 = empty_bucketed(sb, (), torch.uint8, dev)
     emit_slot = empty_bucketed(n_isects, (), I32, dev) if want_slots else None
-    if capacity is None:
-        check(L.clmgs_isect2_emit_sort(stream(), V, n_isects, dptr(c.depths), dptr(c.order), dptr(c.cum),
-                                       dptr(c.boxes), tile_width, tile_height, dptr(fids), dptr(c.offsets),
-                                       dptr(ids, I64, True), dptr(emit_slot, I32, True), dptr(temp2), sb,
-                                       dptr(c.row_cum, I64, True)))
+    count = () if capacity is None else (dptr(c.totals),)  # the _dev entries: the true count, after n_isects
+    if sort:
+        check((L.clmgs_isect2_emit_sort if capacity is None else L.clmgs_isect2_emit_sort_dev)(
+            stream(), V, n_isects, *count, dptr(c.depths), dptr(c.order), dptr(c.cum), dptr(c.boxes), tile_width,
+            tile_height, dptr(fids), dptr(c.offsets), dptr(ids, I64, True), dptr(emit_slot, I32, True), dptr(temp2), sb,
+            dptr(c.row_cum, I64, True)))
     else:
-        check(L.clmgs_isect2_emit_sort_dev(stream(), V, n_isects, dptr(c.totals), dptr(c.depths), dptr(c.order),
-                                           dptr(c.cum), dptr(c.boxes), tile_width, tile_height, dptr(fids),
-                                           dptr(c.offsets), dptr(ids, I64, True), dptr(emit_slot, I32, True),
-                                           dptr(temp2), sb, dptr(c.row_cum, I64, True)))
-    return (fids, c.offsets, ids, (emit_slot, c.row_cum)) if want_slots else (fids, c.offsets, ids)
-
-
-# ---- tile-major binning (csrc/isect3.hip): the same lists without a global sort; same two-phase calling pattern
-@torch.no_grad()
-def isect3_begin(means2d, radii, depths, tile_size, tile_width, tile_height, want_isect_ids=False,
-                 want_slots=False, packed=None):
-    """First half of the tile-major binning (clmgs_isect3_front): per-row tile boxes / masks, tile counters, row_cum and
-    the totals on the CURRENT stream, then the asynchronous readback of the totals -- the calling pattern (and the
-    state object) of isect2_begin; isect2_counts reads the totals of either."""
-    L = _lib.lib()
-    c = _Isect2()
-    c.route = "tile"
-    c.args = (int(tile_size), int(tile_width), int(tile_height), bool(want_isect_ids), bool(want_slots))
-    V = c.V = radii.numel()
-    dev = c.dev = radii.device
-    c.means2d, c.radii, c.depths = means2d.contiguous(), radii.contiguous(), depths.contiguous()
-    c.packed = packed
-    c.offsets = torch.empty((1, tile_height, tile_width), dtype=I32, device=dev)
-    c.event = None
-    c.order = c.cum = c.boxes = None
-    if V == 0:
-        return c
-    c.totals = torch.empty((2,), dtype=I64, device=dev)
-    c.row_cum = empty_bucketed(V, (), I64, dev)
-    tb = L.clmgs_isect3_front_temp_bytes(V, int(tile_width) * int(tile_height))
-    c.temp = empty_bucketed(tb, (), torch.uint8, dev)
-    check(L.clmgs_isect3_front(stream(), V, dptr(c.means2d, F32), dptr(c.radii, I32), c.args[0], c.args[1], c.args[2],
-                               dptr(packed, F32, True), dptr(c.totals), dptr(c.row_cum), dptr(c.temp), tb))
-    c.host = _pinned_totals_slot()
-    c.host.copy_(c.totals, non_blocking=True)
-    c.event = torch.cuda.Event()
-    c.event.record(torch.cuda.current_stream())
-    return c
-
-
-@torch.no_grad()
-def isect3_finish(c, capacity=None):
-    """Second half (clmgs_isect3_bin / _bin_dev): tile scan, scatter, per-tile sort.  Same contract as isect2_finish."""
-    L = _lib.lib()
-    tile_size, tile_width, tile_height, want_isect_ids, want_slots = c.args
-    dev, V = c.dev, c.V
-    if V == 0:
-        c.offsets.zero_()
-        e = torch.empty(0, dtype=I32, device=dev)
-        res = (e, c.offsets, (torch.empty(0, dtype=I64, device=dev) if want_isect_ids else None))
-        return res + ((e, torch.empty(0, dtype=I64, device=dev)),) if want_slots else res
-    if capacity is None:
-        n_isects, n_ref = isect2_counts(c)
-        _record_counts(n_isects, n_ref)
-    else:
-        n_isects = int(capacity)
-    fids = empty_bucketed(n_isects, (), I32, dev)
-    ids = empty_bucketed(n_isects, (), I64, dev) if want_isect_ids else None
-    sb = L.clmgs_isect3_bin_temp_bytes(n_isects, tile_width * tile_height)
-    temp2 = empty_bucketed(sb, (), torch.uint8, dev)
-    emit_slot = empty_bucketed(n_isects, (), I32, dev) if want_slots else None
-    if capacity is None:
-        check(L.clmgs_isect3_bin(stream(), V, n_isects, dptr(c.depths), tile_width, tile_height, dptr(c.row_cum),
-                                 dptr(c.temp), dptr(fids), dptr(c.offsets), dptr(ids, I64, True),
-                                 dptr(emit_slot, I32, True), dptr(temp2), sb))
-    else:
-        check(L.clmgs_isect3_bin_dev(stream(), V, n_isects, dptr(c.totals), dptr(c.depths), tile_width, tile_height,
-                                     dptr(c.row_cum), dptr(c.temp), dptr(fids), dptr(c.offsets), dptr(ids, I64, True),
-                                     dptr(emit_slot, I32, True), dptr(temp2), sb))
+        check((L.clmgs_isect3_bin if capacity is None else L.clmgs_isect3_bin_dev)(
+            stream(), V, n_isects, *count, dptr(c.depths), tile_width, tile_height, dptr(c.row_cum), dptr(c.temp),
+            dptr(fids), dptr(c.offsets), dptr(ids, I64, True), dptr(emit_slot, I32, True), dptr(temp2), sb))
     return (fids, c.offsets, ids, (emit_slot, c.row_cum)) if want_slots else (fids, c.offsets, ids)
 
 
@@ -541,9 +432,9 @@ def isect_tiles_two_level(means2d, radii, depths, tile_size, tile_width, tile_he
     contiguous slot range [row_cum[i-1], row_cum[i]).
     packed: the [V,16] raster records -> EXACT per-tile culling (pairs whose tile cannot reach
     alpha >= 1/255 are not emitted; image and gradients unchanged, the list gets ~29 % shorter).
-    = isect2_begin + isect2_finish back to back."""
-    return isect2_finish(isect2_begin(means2d, radii, depths, tile_size, tile_width, tile_height,
-                                      want_isect_ids, want_slots, packed))
+    = isect_begin("sort", ...) + isect_finish back to back."""
+    return isect_finish(isect_begin("sort", means2d, radii, depths, tile_size, tile_width, tile_height,
+                                    want_isect_ids, want_slots, packed))
 
 
 # ---------------------------------------------------------------------- rasterize

@@ -5,7 +5,8 @@ import math
 import torch
 
 from .. import utils
-from ..clm_kernels import fused_l1_ssim_loss, fused_ssim
+from ..cameras import camera_loss_mask
+from ..clm_kernels import apply_camera_colour, camera_depth_term, fused_l1_ssim_loss, fused_ssim
 from ..gsplat import (fully_fused_projection, isect_offset_encode, isect_tiles,
                       rasterize_to_pixels, spherical_harmonics, visibility_radii)
 
@@ -75,9 +76,7 @@ def torch_compiled_loss(image, image_gt_original, loss_mask=None, loss_mask_coun
     (u8 -> float GT, L1, SSIM, mix) is one fused HIP kernel each way when the GT is uint8.
     loss_mask (uint8 [H,W], 0 = ignored; a camera's `loss_mask`) selects the masked kernels."""
     if image_gt_original.dtype == torch.uint8:
-        if loss_mask is not None:
-            return fused_l1_ssim_loss(image, image_gt_original, LAMBDA_DSSIM, loss_mask, loss_mask_count)
-        return fused_l1_ssim_loss(image, image_gt_original, LAMBDA_DSSIM)
+        return fused_l1_ssim_loss(image, image_gt_original, LAMBDA_DSSIM, loss_mask, loss_mask_count)
     if loss_mask is not None:
         raise ValueError("a loss mask needs the uint8 ground-truth image (the masked loss exists as the fused kernels only)")
     image_gt = torch.clamp(image_gt_original / 255.0, 0.0, 1.0)
@@ -116,8 +115,61 @@ def split_depth(rendered, alphas, render_mode):
     return rendered[..., :3].squeeze(0).permute(2, 0, 1), depth, alpha
 
 
-def _tile_counts(w, h):
-    return math.ceil(w / float(TILE_SIZE)), math.ceil(h / float(TILE_SIZE))
+def fov_camera(camera, device):
+    """-> (viewmat[4,4], K[3,3], centre[1,1,3]) as the two FoV entries make them: K from the field of view as a device
+    tensor, the centre by torch.inverse ON THE DEVICE.  (camera.K / camera.camtoworlds, which
+    pipeline_forward_one_step_shs_inplace reads, come from the host and can differ in the last bit.)"""
+    image_width, image_height = int(utils.get_img_width()), int(utils.get_img_height())
+    fx = image_width / (2 * math.tan(camera.FoVx * 0.5))
+    fy = image_height / (2 * math.tan(camera.FoVy * 0.5))
+    K = torch.tensor([[fx, 0, image_width / 2.0], [0, fy, image_height / 2.0], [0, 0, 1]], device=device)
+    viewmat = camera.world_view_transform.transpose(0, 1)
+    return viewmat, K, torch.inverse(viewmat.unsqueeze(0))[:, None, :3, 3]
+
+
+def camera_forward_ops(means, quats, scales, opacities, coeffs, sh_degree, viewmat, K, centre, backgrounds, render_mode,
+                       train, radius_clip=0.0, sh_masks=False, sh_autograd=True, tile_size=TILE_SIZE):
+    """The op-by-op forward of one camera, which the three reference-named entries share: projection -> SH -> +0.5 clamp
+    -> tile binning -> offsets -> (depth as fourth colour) -> rasterize.  Each entry hands in ITS K, camera centre,
+    coefficient view ([1,V,16,3]) and backgrounds (None, [3] or [1,3]); the knobs are what else differs between them:
+    train (means2D keeps its gradient, and the absgrad one under args.absgrad), radius_clip, sh_masks (SH only where
+    radii > 0), sh_autograd (False: SH under no_grad and the colours re-leafed, for an SH backward that accumulates in
+    place) and tile_size.
+    -> (image[3,H,W] view, means2D[1,V,2], radii[1,V], () | (depth[1,H,W], alpha[1,H,W]) by split_depth,
+        () | (colours leaf[1,V,3], dirs[1,V,3]) without sh_autograd)."""
+    image_width, image_height = int(utils.get_img_width()), int(utils.get_img_height())
+    radiis, means2D, depths, conics, compensations = fully_fused_projection(
+        means=means, covars=None, quats=quats, scales=scales, viewmats=viewmat.unsqueeze(0), Ks=K.unsqueeze(0),
+        width=image_width, height=image_height, radius_clip=radius_clip, packed=False,
+        calc_compensations=utils.antialiased())
+    if train:
+        means2D.retain_grad()
+    dirs = means[None, :, :] - centre
+    sh_leaf = ()
+    with torch.set_grad_enabled(sh_autograd and torch.is_grad_enabled()):
+        colors = spherical_harmonics(degrees_to_use=sh_degree, dirs=dirs, coeffs=coeffs,
+                                     masks=(radiis > 0) if sh_masks else None)
+    if not sh_autograd:
+        colors = colors.detach().requires_grad_()
+        sh_leaf = (colors, dirs)
+    colors = torch.clamp_min(colors + 0.5, 0.0)
+    opacities = opacities.squeeze(1).unsqueeze(0)
+    if compensations is not None:  # rasterize_mode="antialiased"
+        opacities = opacities * compensations
+    tile_width, tile_height = math.ceil(image_width / float(tile_size)), math.ceil(image_height / float(tile_size))
+    _, isect_ids, flatten_ids = isect_tiles(means2d=means2D, radii=radiis, depths=depths, tile_size=tile_size,
+                                            tile_width=tile_width, tile_height=tile_height, packed=False)
+    isect_offsets = isect_offset_encode(isect_ids, 1, tile_width, tile_height)
+    colors, backgrounds = colors_with_depth(colors, depths, backgrounds, render_mode)
+    rendered_image, alphas = rasterize_to_pixels(
+        means2d=means2D, conics=conics, colors=colors, opacities=opacities,
+        image_width=image_width, image_height=image_height, tile_size=tile_size,
+        isect_offsets=isect_offsets, flatten_ids=flatten_ids, backgrounds=backgrounds,
+        absgrad=train and bool(getattr(utils.get_args(), "absgrad", False)))  # -> means2D.absgrad after backward
+    if render_mode != "RGB":
+        rendered_image, depth, alpha = split_depth(rendered_image, alphas, render_mode)
+        return rendered_image, means2D, radiis, (depth, alpha), sh_leaf
+    return rendered_image.squeeze(0).permute(2, 0, 1), means2D, radiis, (), sh_leaf  # [3,H,W] view, no copy
 
 
 def pipeline_forward_one_step(filtered_opacity_gpu, filtered_scaling_gpu, filtered_rotation_gpu,
@@ -126,41 +178,23 @@ def pipeline_forward_one_step(filtered_opacity_gpu, filtered_scaling_gpu, filter
     """One camera over the gathered rows, SH through autograd (base_engine.py:106-207).
     render_mode "RGB+D" / "RGB+ED": a fourth result depth[1,H,W] (see split_depth), and with return_alpha a fifth,
     alpha[1,H,W]."""
-    image_width, image_height = int(utils.get_img_width()), int(utils.get_img_height())
-    fx = image_width / (2 * math.tan(camera.FoVx * 0.5))
-    fy = image_height / (2 * math.tan(camera.FoVy * 0.5))
-    K = torch.tensor([[fx, 0, image_width / 2.0], [0, fy, image_height / 2.0], [0, 0, 1]],
-                     device=filtered_xyz_gpu.device)
-    viewmat = camera.world_view_transform.transpose(0, 1)
-    n_selected = filtered_xyz_gpu.shape[0]
-    radiis, means2D, depths, conics, compensations = fully_fused_projection(
-        means=filtered_xyz_gpu, covars=None, quats=filtered_rotation_gpu,
-        scales=filtered_scaling_gpu, viewmats=viewmat.unsqueeze(0), Ks=K.unsqueeze(0),
-        width=image_width, height=image_height, packed=False, calc_compensations=utils.antialiased())
-    if not eval:
-        means2D.retain_grad()
-    camtoworlds = torch.inverse(viewmat.unsqueeze(0))
-    dirs = filtered_xyz_gpu[None, :, :] - camtoworlds[:, None, :3, 3]
-    colors = spherical_harmonics(degrees_to_use=gaussians.active_sh_degree, dirs=dirs,
-                                 coeffs=filtered_shs.reshape(1, n_selected, 16, 3))
-    colors = torch.clamp_min(colors + 0.5, 0.0)
-    opacities = filtered_opacity_gpu.squeeze(1).unsqueeze(0)
-    if compensations is not None:  # rasterize_mode="antialiased"
-        opacities = opacities * compensations
-    tile_width, tile_height = _tile_counts(image_width, image_height)
-    _, isect_ids, flatten_ids = isect_tiles(means2d=means2D, radii=radiis, depths=depths,
-                                            tile_size=TILE_SIZE, tile_width=tile_width,
-                                            tile_height=tile_height, packed=False)
-    isect_offsets = isect_offset_encode(isect_ids, 1, tile_width, tile_height)
-    backgrounds = background.reshape(1, 3) if background is not None else None
-    colors, backgrounds = colors_with_depth(colors, depths, backgrounds, render_mode)
-    rendered_image, alphas = rasterize_to_pixels(
-        means2d=means2D, conics=conics, colors=colors, opacities=opacities,
-        image_width=image_width, image_height=image_height, tile_size=TILE_SIZE,
-        isect_offsets=isect_offsets, flatten_ids=flatten_ids, backgrounds=backgrounds,
-        absgrad=not eval and bool(getattr(utils.get_args(), "absgrad", False)))  # -> means2D.absgrad after backward
-    if render_mode != "RGB":
-        rendered_image, depth, alpha = split_depth(rendered_image, alphas, render_mode)
-        return (rendered_image, means2D, radiis, depth) + ((alpha,) if return_alpha else ())
-    rendered_image = rendered_image.squeeze(0).permute(2, 0, 1)  # [3,H,W] view, no copy
-    return rendered_image, means2D, radiis
+    viewmat, K, centre = fov_camera(camera, filtered_xyz_gpu.device)
+    image, means2D, radiis, depth_alpha, _ = camera_forward_ops(
+        filtered_xyz_gpu, filtered_rotation_gpu, filtered_scaling_gpu, filtered_opacity_gpu,
+        filtered_shs.reshape(1, filtered_xyz_gpu.shape[0], 16, 3), gaussians.active_sh_degree, viewmat, K, centre,
+        background.reshape(1, 3) if background is not None else None, render_mode, train=not eval)
+    return (image, means2D, radiis) + depth_alpha[:2 if return_alpha else 1]
+
+
+def camera_loss_backward(image, means2D, camera, inv_depth=None):
+    """The op-by-op training tail of one camera, after its forward: the camera's colour stage (exposure transform or
+    bilateral grid, if it has one), the L1+SSIM loss under the camera's loss mask, the depth term when the camera was
+    rendered with its prior's inverse depth (inv_depth[1,H,W]), backward().
+    -> (loss, detached; the means2D gradient the densification statistic is built from: gsplat's absgrad,
+    sum_p |dL_p/dmean2d|, under args.absgrad, else the signed sum)."""
+    image = apply_camera_colour(image, camera)
+    loss = torch_compiled_loss(image, camera.original_image, *camera_loss_mask(camera))
+    if inv_depth is not None:
+        loss = loss + camera_depth_term(inv_depth[0], camera)
+    loss.backward()
+    return loss.detach(), means2D.absgrad if getattr(utils.get_args(), "absgrad", False) else means2D.grad

@@ -25,21 +25,17 @@ reference's TSP order + last-use groups + retention-set sizes (engine.py:135-298
 reference-compatible ordering entry and is what `reference_camera_order=True` runs: the cameras are then
 processed, and `ordered_cams` / `sparsity` reported, in that order, as the reference does.
 """
-import math
 import os
 
 import torch
 
 from ... import _lib, clm_kernels, dp, fast_tsp, mcmc, utils
-from ...cameras import camera_loss_mask
-from ...clm_kernels import (apply_camera_colour, camera_depth_term, check_depth_prior_args,
+from ...clm_kernels import (apply_camera_colour, check_depth_prior_args,
                             send_shs2cpu_grad_buffer_stream, send_shs2gpu_stream, spherical_harmonics_bwd_inplace)
 from ...densification import check_mcmc_args, update_densification_stats_offload_accum_grads
-from ...gsplat import (fully_fused_projection, isect_offset_encode, isect_tiles,
-                       rasterize_to_pixels, spherical_harmonics)
 from ...host import pinned_empty
-from ..base_engine import (select_filters, TILE_SIZE, calculate_filters, colors_with_depth, pipeline_forward_one_step,
-                           split_depth, torch_compiled_loss)
+from ..base_engine import (select_filters, calculate_filters, camera_forward_ops, camera_loss_backward,
+                           pipeline_forward_one_step)
 
 _BITMAP_DTYPE = {4: torch.int8, 8: torch.int8, 16: torch.int16, 32: torch.int32, 64: torch.int64}
 
@@ -51,43 +47,12 @@ def pipeline_forward_one_step_shs_inplace(filtered_opacity_gpu, filtered_scaling
     the SH backward can later accumulate in place (engine.py:30-127).
     Returns (image[3,H,W], means2D[1,V,2], radii[1,V], colors_detached[1,V,3], dirs[1,V,3]); with a depth render mode
     (base_engine.colors_with_depth) a sixth result depth[1,H,W]."""
-    viewmat = camera.world_view_transform.transpose(0, 1)
-    K = camera.K
-    n_selected = filtered_xyz_gpu.shape[0]
-    image_width, image_height = int(utils.get_img_width()), int(utils.get_img_height())
-    radiis, means2D, depths, conics, compensations = fully_fused_projection(
-        means=filtered_xyz_gpu, covars=None, quats=filtered_rotation_gpu,
-        scales=filtered_scaling_gpu, viewmats=viewmat.unsqueeze(0), Ks=K.unsqueeze(0),
-        width=image_width, height=image_height, packed=False, calc_compensations=utils.antialiased())
-    means2D.retain_grad()
-    dirs = filtered_xyz_gpu[None, :, :] - camera.camtoworlds[:, None, :3, 3]
-    filtered_shs = filtered_shs.reshape(1, n_selected, 16, 3)
-    with torch.no_grad():
-        colors_origin = spherical_harmonics(degrees_to_use=gaussians.active_sh_degree, dirs=dirs,
-                                            coeffs=filtered_shs)
-    colors_detached = colors_origin.detach().requires_grad_()
-    colors = torch.clamp_min(colors_detached + 0.5, 0.0)
-    opacities = filtered_opacity_gpu.squeeze(1).unsqueeze(0)
-    if compensations is not None:  # rasterize_mode="antialiased"
-        opacities = opacities * compensations
-    tile_width = math.ceil(image_width / float(TILE_SIZE))
-    tile_height = math.ceil(image_height / float(TILE_SIZE))
-    _, isect_ids, flatten_ids = isect_tiles(means2d=means2D, radii=radiis, depths=depths,
-                                            tile_size=TILE_SIZE, tile_width=tile_width,
-                                            tile_height=tile_height, packed=False)
-    isect_offsets = isect_offset_encode(isect_ids, 1, tile_width, tile_height)
-    backgrounds = background.reshape(1, 3) if background is not None else None
-    colors, backgrounds = colors_with_depth(colors, depths, backgrounds, render_mode)
-    rendered_image, alphas = rasterize_to_pixels(
-        means2d=means2D, conics=conics, colors=colors, opacities=opacities,
-        image_width=image_width, image_height=image_height, tile_size=TILE_SIZE,
-        isect_offsets=isect_offsets, flatten_ids=flatten_ids, backgrounds=backgrounds,
-        absgrad=bool(getattr(utils.get_args(), "absgrad", False)))  # -> means2D.absgrad after backward
-    if render_mode != "RGB":
-        rendered_image, depth, _ = split_depth(rendered_image, alphas, render_mode)
-        return rendered_image, means2D, radiis, colors_detached, dirs, depth
-    rendered_image = rendered_image.squeeze(0).permute(2, 0, 1)  # [3,H,W] view, no copy
-    return rendered_image, means2D, radiis, colors_detached, dirs
+    image, means2D, radiis, depth_alpha, sh_leaf = camera_forward_ops(
+        filtered_xyz_gpu, filtered_rotation_gpu, filtered_scaling_gpu, filtered_opacity_gpu,
+        filtered_shs.reshape(1, filtered_xyz_gpu.shape[0], 16, 3), gaussians.active_sh_degree,
+        camera.world_view_transform.transpose(0, 1), camera.K, camera.camtoworlds[:, None, :3, 3],
+        background.reshape(1, 3) if background is not None else None, render_mode, train=True, sh_autograd=False)
+    return (image, means2D, radiis) + sh_leaf + depth_alpha[:1]
 
 
 # --------------------------------------------------------------------------- ordering
@@ -199,11 +164,7 @@ def _render_and_backward(gaussians, scene, camera, background, pipe_args, this_f
     image, means2D, radiis, colors_detached, dirs, *inv_depth = pipeline_forward_one_step_shs_inplace(
         opa, sca, rot, xyz, shs, camera, scene, gaussians, background, pipe_args,
         render_mode="RGB+ID" if has_prior else "RGB")
-    image = apply_camera_colour(image, camera)  # the camera's exposure transform or bilateral grid, if it has one
-    loss = torch_compiled_loss(image, camera.original_image, *camera_loss_mask(camera))
-    if has_prior:
-        loss = loss + camera_depth_term(inv_depth[0][0], camera)
-    loss.backward()
+    loss, m2_grad = camera_loss_backward(image, means2D, camera, *inv_depth)
     if before_sh_backward is not None:
         before_sh_backward()
     v_dirs = spherical_harmonics_bwd_inplace(
@@ -211,12 +172,10 @@ def _render_and_backward(gaussians, scene, camera, background, pipe_args, this_f
         v_coeffs=shs_grad, v_colors=colors_detached.grad)
     dirs.backward(v_dirs)
     _scatter_small_grads(gaussians, this_filter, xyz, opa_raw, sca_raw, rot_raw)
-    # gsplat's absgrad: the statistic is built from sum_p |dL_p/dmean2d| instead of the signed sum
-    m2_grad = means2D.absgrad if getattr(utils.get_args(), "absgrad", False) else means2D.grad
     update_densification_stats_offload_accum_grads(
         scene, gaussians, int(utils.get_img_height()), int(utils.get_img_width()), this_filter,
         m2_grad.squeeze(0), radiis.squeeze(0))
-    return loss.detach()
+    return loss
 
 
 def _zero_small_grads(gaussians):

@@ -1,17 +1,12 @@
 """no_offload engine (reference: strategies/no_offload/engine.py:15-177): per-camera
 render over all N Gaussians, gradient accumulation over the batch, one backward through the
 activations."""
-import math
-
 import torch
 
 from ... import utils
-from ...cameras import camera_loss_mask
-from ...clm_kernels import apply_camera_colour, camera_depth_term, check_depth_prior_args
+from ...clm_kernels import check_depth_prior_args
 from ...densification import update_densification_stats_baseline_accum_grads
-from ...gsplat import (fully_fused_projection, isect_offset_encode, isect_tiles,
-                       rasterize_to_pixels, spherical_harmonics)
-from ..base_engine import colors_with_depth, split_depth, torch_compiled_loss
+from ..base_engine import camera_forward_ops, camera_loss_backward, fov_camera
 
 
 def baseline_accumGrads_micro_step(means3D, opacities, scales, rotations, shs, sh_degree, camera,
@@ -21,44 +16,11 @@ def baseline_accumGrads_micro_step(means3D, opacities, scales, rotations, shs, s
     rasterize -> [3,H,W].  Returns (image, means2D (grad retained), radii, None); with render_mode "RGB+D" /
     "RGB+ED" / "RGB+ID" a fifth result depth[1,H,W] (accumulated / expected / inverse depth, base_engine.split_depth), and
     with return_alpha a sixth, alpha[1,H,W]."""
-    args = utils.get_args()
-    image_width, image_height = int(utils.get_img_width()), int(utils.get_img_height())
-    fx = image_width / (2 * math.tan(camera.FoVx * 0.5))
-    fy = image_height / (2 * math.tan(camera.FoVy * 0.5))
-    K = torch.tensor([[fx, 0, image_width / 2.0], [0, fy, image_height / 2.0], [0, 0, 1]],
-                     device=means3D.device)
-    viewmat = camera.world_view_transform.transpose(0, 1)
-    radiis, means2D, depths, conics, compensations = fully_fused_projection(
-        means=means3D, covars=None, quats=rotations, scales=scales, viewmats=viewmat.unsqueeze(0),
-        Ks=K.unsqueeze(0), width=image_width, height=image_height, radius_clip=args.radius_clip,
-        packed=False, calc_compensations=utils.antialiased())
-    if mode == "train":
-        means2D.retain_grad()
-    camtoworld = torch.inverse(viewmat.unsqueeze(0))
-    dirs = means3D[None, :, :] - camtoworld[:, None, :3, 3]
-    colors = spherical_harmonics(degrees_to_use=sh_degree, dirs=dirs, coeffs=shs.unsqueeze(0),
-                                 masks=(radiis > 0))
-    colors = torch.clamp_min(colors + 0.5, 0.0)
-    tile_width = math.ceil(image_width / float(tile_size))
-    tile_height = math.ceil(image_height / float(tile_size))
-    _, isect_ids, flatten_ids = isect_tiles(means2d=means2D, radii=radiis, depths=depths,
-                                            tile_size=tile_size, tile_width=tile_width,
-                                            tile_height=tile_height, packed=False)
-    isect_offsets = isect_offset_encode(isect_ids, 1, tile_width, tile_height)
-    colors, background = colors_with_depth(colors, depths, background, render_mode)
-    opacities = opacities.squeeze(1).unsqueeze(0)
-    if compensations is not None:  # rasterize_mode="antialiased"
-        opacities = opacities * compensations
-    rendered_image, alphas = rasterize_to_pixels(
-        means2d=means2D, conics=conics, colors=colors, opacities=opacities,
-        image_width=image_width, image_height=image_height, tile_size=tile_size,
-        isect_offsets=isect_offsets, flatten_ids=flatten_ids, backgrounds=background,
-        absgrad=mode == "train" and bool(getattr(args, "absgrad", False)))  # -> means2D.absgrad after backward
-    if render_mode != "RGB":
-        rendered_image, depth, alpha = split_depth(rendered_image, alphas, render_mode)
-        return (rendered_image, means2D, radiis, None, depth) + ((alpha,) if return_alpha else ())
-    rendered_image = rendered_image.squeeze(0).permute(2, 0, 1)  # [3,H,W] view, no copy
-    return rendered_image, means2D, radiis, None
+    viewmat, K, centre = fov_camera(camera, means3D.device)
+    image, means2D, radiis, depth_alpha, _ = camera_forward_ops(
+        means3D, rotations, scales, opacities, shs.unsqueeze(0), sh_degree, viewmat, K, centre, background, render_mode,
+        train=mode == "train", radius_clip=utils.get_args().radius_clip, sh_masks=True, tile_size=tile_size)
+    return (image, means2D, radiis, None) + depth_alpha[:2 if return_alpha else 1]
 
 
 def baseline_accumGrads_impl(gaussians, scene, batched_cameras, background, scaling_modifier=1.0,
@@ -90,15 +52,9 @@ def baseline_accumGrads_impl(gaussians, scene, batched_cameras, background, scal
         rendered_image, means2D, radiis, gaussian_ids, *inv_depth = baseline_accumGrads_micro_step(
             means3D, opacities, scales, rotations, shs, sh_degree, camera, background,
             render_mode="RGB+ID" if has_prior else "RGB")
-        rendered_image = apply_camera_colour(rendered_image, camera)  # the camera's exposure transform or bilateral grid, if it has one
-        loss = torch_compiled_loss(rendered_image, camera.original_image, *camera_loss_mask(camera))
-        if has_prior:
-            loss = loss + camera_depth_term(inv_depth[0][0], camera)
-        loss.backward()
-        losses.append(loss.detach())
+        loss, m2_grad = camera_loss_backward(rendered_image, means2D, camera, *inv_depth)
+        losses.append(loss)
         with torch.no_grad():
-            # gsplat's absgrad: the statistic is built from sum_p |dL_p/dmean2d| instead of the signed sum
-            m2_grad = means2D.absgrad if getattr(utils.get_args(), "absgrad", False) else means2D.grad
             update_densification_stats_baseline_accum_grads(scene, gaussians, H, W, m2_grad,
                                                             radiis, gaussian_ids)
         if sparse_adam:

@@ -769,7 +769,7 @@ def test_device_count_forms_equal_exact_forms(dev, slack):
                                 dptr(part)))
     # device-count forms
     cap = max(1, int(I * slack))
-    c = G.isect2_begin(m2, radii, d, 16, tw, th, want_slots=True)
+    c = G.isect_begin("sort", m2, radii, d, 16, tw, th, want_slots=True)
     GUARD = 64
     fids2 = torch.full((cap + GUARD,), -12345, dtype=torch.int32, device=dev)
     slot2 = torch.full((cap + GUARD,), -12345, dtype=torch.int32, device=dev)
@@ -799,12 +799,12 @@ def test_device_count_forms_equal_exact_forms(dev, slack):
 
 def _binning_lists(G, m2, radii, d, tw, th, n, pk, cap_slack):
     """Every list the two binning calls produce."""
-    c = G.isect2_begin(m2, radii, d, 16, tw, th, want_isect_ids=True, want_slots=True, packed=pk)
+    c = G.isect_begin("sort", m2, radii, d, 16, tw, th, want_isect_ids=True, want_slots=True, packed=pk)
     torch.cuda.synchronize()
     tot = c.totals.clone()
     res = [c.order[:n].clone(), c.cum[:n].clone(), c.boxes[:n].clone(), tot, c.row_cum[:n].clone()]
     cap = None if cap_slack is None else max(1, int(int(tot[0]) * cap_slack))
-    fids, off, ids, (slot, _) = G.isect2_finish(c, capacity=cap)
+    fids, off, ids, (slot, _) = G.isect_finish(c, capacity=cap)
     torch.cuda.synchronize()
     I = int(tot[0]) if cap is None else min(int(tot[0]), cap)
     return res + [fids[:I].clone(), off.clone(), ids[:I].clone(), slot[:I].clone()]
@@ -1150,11 +1150,11 @@ def test_visibility_candidates_kernel_brackets_its_numpy_restatement(dev):
 
 
 def _tile_major_lists(G, m2, radii, d, tw, th, n, pk, cap_slack):
-    c = G.isect3_begin(m2, radii, d, 16, tw, th, want_isect_ids=True, want_slots=True, packed=pk)
+    c = G.isect_begin("tile", m2, radii, d, 16, tw, th, want_isect_ids=True, want_slots=True, packed=pk)
     torch.cuda.synchronize()
     tot = c.totals.clone()
     cap = None if cap_slack is None else max(1, int(int(tot[0]) * cap_slack))
-    fids, off, ids, (slot, row_cum) = G.isect3_finish(c, capacity=cap)
+    fids, off, ids, (slot, row_cum) = G.isect_finish(c, capacity=cap)
     torch.cuda.synchronize()
     I = int(tot[0])
     return [tot, row_cum[:n].clone(), fids[:I].clone(), off.clone(), ids[:I].clone(), slot[:I].clone()]
@@ -1197,9 +1197,9 @@ def test_tile_major_binning_equals_two_level_sort(dev, n, wh):
             for nm, a, b in zip(names, got, want):
                 assert torch.equal(a, b), (nm, pk is not None, slack)
         # a capacity below the count: memory-safe, every stored id a valid row, offsets monotone and within the capacity
-        c = G.isect3_begin(m2, radii, d, 16, tw, th, want_slots=True, packed=pk)
+        c = G.isect_begin("tile", m2, radii, d, 16, tw, th, want_slots=True, packed=pk)
         cap = int(int(want[0][0]) * 0.6)
-        fids, off, _, (slot, _) = G.isect3_finish(c, capacity=cap)
+        fids, off, _, (slot, _) = G.isect_finish(c, capacity=cap)
         torch.cuda.synchronize()
         assert int(fids.min()) >= 0 and int(fids.max()) < n and int(off.max()) <= cap
         o = off.reshape(-1)
@@ -1286,8 +1286,8 @@ def test_tile_major_binning_with_nothing_on_the_image(dev):
              (torch.full((1, n, 2), -900.0, device=dev), torch.full((1, n), 5, dtype=torch.int32, device=dev))]  # off screen
     for m2, radii in cases:
         for cap in (None, 1):
-            c = G.isect3_begin(m2, radii, depths, 16, tw, th, want_isect_ids=True, want_slots=True)
-            fids, off, ids, (slot, row_cum) = G.isect3_finish(c, capacity=cap)
+            c = G.isect_begin("tile", m2, radii, depths, 16, tw, th, want_isect_ids=True, want_slots=True)
+            fids, off, ids, (slot, row_cum) = G.isect_finish(c, capacity=cap)
             torch.cuda.synchronize()
             assert int(c.totals[0]) == 0
             assert int(off.abs().sum()) == 0 and off.shape == (1, th, tw)
@@ -1295,10 +1295,12 @@ def test_tile_major_binning_with_nothing_on_the_image(dev):
             if cap is None:
                 assert fids.numel() == 0 and slot.numel() == 0
     e = torch.empty((1, 0), device=dev)
-    c = G.isect3_begin(torch.empty((1, 0, 2), device=dev), torch.empty((1, 0), dtype=torch.int32, device=dev), e, 16, tw, th,
-                       want_isect_ids=True, want_slots=True)
-    fids, off, ids, (slot, row_cum) = G.isect3_finish(c)
+    c = G.isect_begin("tile", torch.empty((1, 0, 2), device=dev), torch.empty((1, 0), dtype=torch.int32, device=dev), e, 16,
+                      tw, th, want_isect_ids=True, want_slots=True)
+    fids, off, ids, (slot, row_cum) = G.isect_finish(c)
     assert fids.numel() == 0 and int(off.abs().sum()) == 0 and ids.numel() == 0 and slot.numel() == 0
+    with pytest.raises(ValueError):  # a route the library does not have
+        G.isect_begin("lookback", *cases[0], depths, 16, tw, th)
 
 
 @pytest.mark.gpu
