@@ -524,3 +524,55 @@ def rasterize_to_pixels(means2d, conics, colors, opacities, image_width, image_h
             backgrounds = backgrounds.expand(C, nch)
     return _Rasterize.apply(means2d, conics, colors, opacities, backgrounds, int(image_width),
                             int(image_height), int(tile_size), isect_offsets, flatten_ids, bool(absgrad))
+
+
+# ------------------------------------------------------------------ contributions
+WSUM_UNIT = 2.0 ** -28  # one unit of the fixed-point weight sums (clmgs_rasterize_contrib)
+
+
+def contribution_arrays(n, device):
+    """The three zeroed raw arrays clmgs_rasterize_contrib adds into, n rows: (wsum_q, wmax_bits, pixels).  uint64 /
+    uint32 on the device side, held as int64 / int32 tensors (the sums stay far below 2^63; a non-negative float's bit
+    pattern is a non-negative int32)."""
+    return (torch.zeros((n,), dtype=I64, device=device), torch.zeros((n,), dtype=I32, device=device),
+            torch.zeros((n,), dtype=I64, device=device))
+
+
+def contribution_values(raw):
+    """raw arrays -> (wsum float64, wmax float32, pixels int64)."""
+    wsum_q, wmax_bits, pixels = raw
+    return wsum_q.to(torch.float64) * WSUM_UNIT, wmax_bits.view(F32), pixels
+
+
+@torch.no_grad()
+def rasterize_contributions(means2d, conics, opacities, image_width, image_height, tile_size, isect_offsets, flatten_ids,
+                            rows=None, out=None):
+    """Per-Gaussian blend weights w = alpha * T of C views over the lists rasterize_to_pixels would blend, summed over the
+    in-image pixels at which it accumulates each Gaussian: -> (wsum float64 [R], wmax float32 [R], pixels int64 [R]).
+    R = C*N (row cam * N + g), or len(out) rows when accumulating into `out`, the raw triple of contribution_arrays: the
+    kernel ADDS (integer atomics, bit-reproducible), so one triple can take camera after camera.  rows (int64 [N], one
+    table for all C cameras): Gaussian g of every camera lands in row rows[g] -- a camera's visibility filter scatters
+    straight into model-wide arrays.  Not differentiable: inputs that require grad are detached."""
+    L = _lib.lib()
+    C, N = opacities.shape
+    dev = means2d.device
+    means2d, conics, opacities = (t.detach().contiguous() for t in (means2d, conics, opacities))
+    offsets, fids = isect_offsets.contiguous(), flatten_ids.contiguous()
+    th, tw = offsets.shape[1:]
+    if rows is not None:
+        rows = rows.contiguous()
+        if rows.numel() != N:
+            raise ValueError(f"rows must hold one destination per Gaussian ({N}), got {rows.numel()}")
+    raw = contribution_arrays(C * N, dev) if out is None else tuple(out)
+    n_out = raw[0].numel()
+    if not (raw[1].numel() == n_out and raw[2].numel() == n_out):
+        raise ValueError("out: three arrays of the same length")
+    if n_out == 0:  # no rows: nothing to add to
+        return contribution_values(raw)
+    pb = L.clmgs_rasterize_contrib_pack_bytes(C, N)
+    packed = torch.empty((pb,), dtype=torch.uint8, device=dev)
+    check(L.clmgs_rasterize_contrib(
+        stream(), C, N, fids.numel(), dptr(means2d, F32), dptr(conics, F32), dptr(opacities, F32), int(image_width),
+        int(image_height), int(tile_size), tw, th, dptr(offsets, I32), dptr(fids, I32), dptr(rows, I64, True), n_out,
+        dptr(packed), dptr(raw[0], I64), dptr(raw[1], I32), dptr(raw[2], I64)))
+    return contribution_values(raw)

@@ -19,6 +19,7 @@ import torch
 from . import dp, mcmc, utils
 from .cameras import camera_loss_mask
 from .clm_kernels import apply_camera_colour
+from .contribution import check_contrib_prune_args, contribution_prune, prune_iterations
 from .densification import check_mcmc_args, gsplat_densification, mcmc_refinement
 from .pose import check_pose_args
 
@@ -381,6 +382,8 @@ def training(gaussians, scene, train_cameras, test_cameras, log_file, iterations
     depth_priors = any(getattr(c, "invdepth", None) is not None for c in train_cameras)
     check_depth_flags(args, depth_priors)
     check_mcmc_args(args)
+    check_contrib_prune_args(args)
+    contrib_iters = prune_iterations(args)
     if pose is not None:
         check_pose_args(args, depth_priors, enabled=True)  # a model handed in is refused like the flag
     use_mcmc = mcmc.enabled(args)
@@ -498,6 +501,23 @@ def training(gaussians, scene, train_cameras, test_cameras, log_file, iterations
                 colour.zero_grad()
         if pose is not None:
             pose.step(batch)
+        if contrib_iters and any(iteration <= t < iteration + gbsz for t in contrib_iters):
+            # contribution pruning (contribution.py): after the batch's optimizer step, so no gradient is waiting for rows
+            # that leave; the training cameras are scored at the poses they carry
+            loss_log.flush()
+            if pose is not None:
+                pose.flush()
+            _t = time.perf_counter()
+            contribution_prune(gaussians, train_cameras, getattr(args, "contrib_prune_mode", "sum"),
+                               float(getattr(args, "contrib_prune_ratio", 0.3)),
+                               float(getattr(args, "contrib_prune_threshold", 0.01)),
+                               resort=spatial and bool(getattr(gaussians, "fuse_sort_into_prune", False)),
+                               log_file=log_file, iteration=iteration)
+            if spatial:
+                gaussians.spatial_sort()
+            _acc("contrib_prune", _t)
+            _check_device()
+            log_file.write(memory_line(iteration, gbsz, gaussians, what="contribution_prune"))
         if not defer:
             torch.cuda.synchronize()
         if iter_hook is not None:
@@ -549,6 +569,7 @@ def train_from_colmap(source_path, model_path, strategy="clm_offload", iteration
     check_depth_flags(args, bool(depths))  # raises: before anything is loaded
     check_appearance_flags(args)  # raises: before anything is loaded
     check_pose_args(args, bool(depths))  # raises: before anything is loaded
+    check_contrib_prune_args(args)  # raises: before anything is loaded
     utils.set_args(args)
     if getattr(args, "exposure", False) and dp.world_size() > 1:
         build_exposure([], args.iterations)  # raises: before anything is loaded
@@ -668,6 +689,16 @@ def build_arg_parser():
     ap.add_argument("--mcmc_min_opacity", type=float, default=0.005)
     ap.add_argument("--mcmc_opacity_reg", type=float, default=0.01)
     ap.add_argument("--mcmc_scale_reg", type=float, default=0.01)
+    ap.add_argument("--disable_auto_densification", action="store_true")
+    ap.add_argument("--contrib_prune_iterations", type=int, nargs="*", default=[], metavar="I",
+                    help="contribution pruning: image counters at which the training cameras are scored by blend weight and "
+                         "the model is pruned; each after densify_until_iter unless --disable_auto_densification "
+                         "(no_offload or clm_offload; single GPU; not with --mcmc)")
+    ap.add_argument("--contrib_prune_mode", choices=["sum", "max"], default="sum",
+                    help="sum: prune the lowest --contrib_prune_ratio of rows by summed weight; max: prune rows whose "
+                         "largest weight is below --contrib_prune_threshold")
+    ap.add_argument("--contrib_prune_ratio", type=float, default=0.3)
+    ap.add_argument("--contrib_prune_threshold", type=float, default=0.01)
     return ap
 
 
@@ -692,4 +723,8 @@ if __name__ == "__main__":  # python -m clm_gs_amd.trainer -s <colmap dir> -m <o
                                 mcmc_min_opacity=a.mcmc_min_opacity, mcmc_opacity_reg=a.mcmc_opacity_reg,
                                 mcmc_scale_reg=a.mcmc_scale_reg, pose_opt=a.pose_opt, pose_opt_lr=a.pose_opt_lr,
                                 pose_opt_reg=a.pose_opt_reg, pose_noise=a.pose_noise,
-                                defer_pose_step=not a.immediate_pose_step)
+                                defer_pose_step=not a.immediate_pose_step,
+                                disable_auto_densification=a.disable_auto_densification,
+                                contrib_prune_iterations=tuple(a.contrib_prune_iterations),
+                                contrib_prune_mode=a.contrib_prune_mode, contrib_prune_ratio=a.contrib_prune_ratio,
+                                contrib_prune_threshold=a.contrib_prune_threshold)

@@ -69,6 +69,12 @@ def default_args(**over):
         # run.  pose_noise: a seeded random perturbation of the training poses at the start (experiments).
         # defer_pose_step: the step of batch b is applied once batch b+1 is enqueued (pose.py); refusals: pose.check_pose_args
         pose_opt=False, pose_opt_lr=1e-5, pose_opt_reg=1e-6, pose_noise=0.0, defer_pose_step=True,
+        # this build: contribution pruning (contribution.py) -- at the image counters contrib_prune_iterations the training
+        # cameras are scored by blend weight w = alpha * T (csrc/contrib.hip) and the model is pruned through prune_points:
+        # mode "sum" removes the lowest contrib_prune_ratio of rows by summed weight (Mini-Splatting / LightGaussian), mode
+        # "max" the rows whose largest weight stays below contrib_prune_threshold (RadSplat); refusals:
+        # contribution.check_contrib_prune_args
+        contrib_prune_iterations=(), contrib_prune_mode="sum", contrib_prune_ratio=0.3, contrib_prune_threshold=0.01,
         lr_scale_mode="sqrt", bsz=1, exact_filter=True, log_cpu_adam_trailing_overhead=False,
         # Debug
         stop_update_param=False, drop_initial_3dgs_p=0.0,

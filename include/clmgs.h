@@ -185,6 +185,27 @@ int clmgs_rasterize_bwd(void* stream, int C, int N, int64_t n_isects, const void
                         float* v_conics, float* v_colors, float* v_opacities,
                         const int32_t* emit_slot, const int64_t* row_cum, void* partials);
 
+/* ---- per-Gaussian blend weights (contribution pruning; csrc/contrib.hip)
+ * A forward-only walk of the same lists with the forward's blend rules, no colours.  means2d[C*N,2] conics[C*N,3]
+ * opacities[C*N], offsets / flatten_ids as for clmgs_rasterize_fwd, C >= 1, tile_size 16.  For every (Gaussian, tile)
+ * entry, over the in-image pixels at which clmgs_rasterize_fwd accumulates it, with w = alpha * T:
+ *   wsum_q[r]    += round_to_nearest(2^28 * sum w)    uint64 fixed point, unit 2^-28
+ *   wmax_bits[r]  = max(wmax_bits[r], bits(max w))     uint32: the bit pattern of a non-negative float
+ *   pixels[r]    += number of those pixels             uint64
+ * by integer atomics only: the arrays are bit-reproducible.  The entry ADDS: the caller zeroes the three arrays (n_out
+ * elements each) once and may call camera after camera.  Destination row r of Gaussian g of camera cam: rows[g] with
+ * `rows` (int64[N], one table for all C cameras), cam * N + g with rows == NULL (then n_out >= C*N).  A row outside
+ * [0, n_out) is dropped.  Entries that are culled, never reached or valid at no pixel touch nothing.
+ * `packed`: caller scratch of clmgs_rasterize_contrib_pack_bytes(C,N) bytes (32 B aligned), filled here with one 32 B
+ * record per Gaussian.  Argument errors return CLMGS_EINVAL before anything is written; n_isects == 0 is accepted and
+ * writes nothing. */
+size_t clmgs_rasterize_contrib_pack_bytes(int C, int N);
+int clmgs_rasterize_contrib(void* stream, int C, int N, int64_t n_isects, const float* means2d,
+                            const float* conics, const float* opacities, int width, int height,
+                            int tile_size, int tile_width, int tile_height, const int32_t* offsets,
+                            const int32_t* flatten_ids, const int64_t* rows, int64_t n_out, void* packed,
+                            uint64_t* wsum_q, uint32_t* wmax_bits, uint64_t* pixels);
+
 /* ---- gsplat.rasterize_to_pixels with colors[..., 4]  (what gsplat's rasterization(render_mode="RGB+D" / "RGB+ED")
  * calls: the camera-space depth rides as a fourth colour channel and is blended with the same weights)
  * Same contract as clmgs_rasterize_fwd / _bwd with rows of four: colors[C*N,4], backgrounds[C,4] or NULL ->
