@@ -88,6 +88,11 @@ SIGNATURES = {
     "clmgs_bilagrid_bwd": (_i, [_vp, _i, _i, _vp, _i64, _i64, _i64, _vp, _i, _i, _i, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp]),
     "clmgs_bilagrid_grad_finish": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "clmgs_bilagrid_tv_grad": (_i, [_vp, _vp, _i64, _i, _i, _i, _f, _vp]),
+    # learnable sky: image view, alphas, host viewmat[16] and K[9], the map and its shape; int64 fixed-point accumulator
+    "clmgs_sky_fwd": (_i, [_vp, _i, _i, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i, _i, _vp, _i64, _i64, _i64]),
+    "clmgs_sky_bwd": (_i, [_vp, _i, _i, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "clmgs_sky_acc_add": (_i, [_vp, _i64, _vp, _vp]),
+    "clmgs_sky_grad_convert": (_i, [_vp, _i64, _vp, _vp]),
     # camera pose refinement: the inputs of clmgs_preprocess_bwd -> 16 floats per workgroup; the operator form
     "clmgs_pose_grad_partials_rows": (_i, [_i]),
     "clmgs_pose_grad": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _i, _vp]),

@@ -7,7 +7,10 @@ and loss_mask_count, the per-pixel ignore mask of the training loss.  A training
 `bilagrid` / `bilagrid_grad`, float32 [L,Hg,Wg,12] views of its grids in a bilagrid.BilagridModel -- and `invdepth`
 (uint16 [H,W]) with `invdepth_scale` / `invdepth_offset`, its monocular inverse-depth prior (camera_invdepth below), and
 `pose_grad`, the float32 [15] buffer its pose gradient is added into (camera_pose_grad; pose.PoseModel rewrites
-world_view_transform, camtoworlds and the cached host triple of a camera whose pose it has moved)."""
+world_view_transform, camtoworlds and the cached host triple of a camera whose pose it has moved).  Any camera of a scene
+with a learnable sky carries `sky`, the detached float32 [Hs,Ws,3] equirectangular map of a sky.SkyModel (one table shared
+by all cameras), and `sky_acc`, the model's int64 [Hs,Ws,3] fixed-point gradient accumulator (unit 2^-48) for a camera
+that trains the map, None for one that is only rendered (camera_sky)."""
 import math
 
 import numpy as np
@@ -72,6 +75,39 @@ def camera_pose_grad(camera):
     pose.PoseModel (`camera.pose_grad`) that the kernels of csrc/pose.hip ADD into -- or None: a camera without the
     attribute, or with None, is trained exactly as before (nothing more is launched)."""
     return getattr(camera, "pose_grad", None)
+
+
+def camera_sky(camera):
+    """The sky a camera is rendered in front of: (sky, sky_acc) -- `camera.sky`, the detached float32 [Hs,Ws,3] map of a
+    sky.SkyModel (one table, shared by every camera of the scene), and `camera.sky_acc`, the model's int64 [Hs,Ws,3]
+    fixed-point gradient accumulator, or None for a camera that does not train the map (evaluation, test, trajectory) --
+    or None: a camera without the attribute, or with None, is rendered over the constant background as before (nothing
+    more is launched).  Refused with a pose-gradient buffer, here, before anything is enqueued: the gradient of the
+    lookup with respect to the ray direction is not carried."""
+    sky = getattr(camera, "sky", None)
+    if sky is None:
+        return None
+    if getattr(camera, "pose_grad", None) is not None:
+        raise ValueError("a camera carries both a sky and a pose-gradient buffer: the sky's gradient with respect to the "
+                         "camera is not carried; train with --sky or with --pose_opt")
+    return sky, getattr(camera, "sky_acc", None)
+
+
+def check_sky_background(background):
+    """A camera with a sky is composited over the map, so a constant background has no meaning: a non-zero one is refused
+    (before anything is enqueued; the value is read on the host once per tensor)."""
+    if background is None:
+        return
+    ok = getattr(background, "_clmgs_sky_ok", None)
+    if ok is None:
+        ok = not bool(torch.count_nonzero(background.detach()).item())
+        try:
+            background._clmgs_sky_ok = ok
+        except AttributeError:
+            pass
+    if not ok:
+        raise ValueError("a non-zero background reaches a camera that has a sky: the sky is the background "
+                         "(--white_background and --sky exclude each other)")
 
 
 class Camera:

@@ -281,6 +281,109 @@ def apply_camera_colour(image, camera):
     return _ApplyColour.apply(image, leaf, kind)
 
 
+# ------------------------------------------------------------ learnable sky (csrc/sky.hip)
+I64 = torch.int64
+
+
+def _host_f32(t, n, what):
+    """A camera matrix as the entries take it: a contiguous host float32 array of n values."""
+    import numpy as np
+    a = t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+    a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
+    if a.size != n:
+        raise _lib.ClmgsError(f"{what} must hold {n} values, got {a.size}")
+    return a
+
+
+def check_sky(sky, what="sky"):
+    if not (isinstance(sky, torch.Tensor) and sky.dtype == F32 and sky.dim() == 3 and sky.shape[2] == 3
+            and sky.shape[0] >= 1 and sky.shape[1] >= 1 and sky.is_contiguous()):
+        raise _lib.ClmgsError(f"{what} must be contiguous float32 [Hs,Ws,3], got "
+                              f"{getattr(sky, 'dtype', type(sky))} {tuple(getattr(sky, 'shape', ()))}")
+
+
+def sky_forward(s, H, W, x, xs, alphas, vm, K, sky, y, ys):
+    """clmgs_sky_fwd on raw views: x, y pointers with (sc, sy, sx) strides, vm / K host arrays."""
+    check(_lib.lib().clmgs_sky_fwd(s, H, W, x, *xs, dptr(alphas, F32), vm.ctypes.data_as(ctypes.c_void_p),
+                                   K.ctypes.data_as(ctypes.c_void_p), dptr(sky, F32), int(sky.shape[0]),
+                                   int(sky.shape[1]), y, *ys))
+
+
+def sky_backward(s, H, W, g, gs, alphas, vm, K, sky, v_alphas, acc):
+    """clmgs_sky_bwd on raw views: STORES v_alphas [H,W], ADDS the map gradient into acc int64 [Hs,Ws,3]."""
+    if acc.dtype != I64 or tuple(acc.shape) != tuple(sky.shape):
+        raise _lib.ClmgsError(f"the sky accumulator must be int64 {tuple(sky.shape)}, got {acc.dtype} {tuple(acc.shape)}")
+    check(_lib.lib().clmgs_sky_bwd(s, H, W, g, *gs, dptr(alphas, F32), vm.ctypes.data_as(ctypes.c_void_p),
+                                   K.ctypes.data_as(ctypes.c_void_p), dptr(sky, F32), int(sky.shape[0]),
+                                   int(sky.shape[1]), dptr(v_alphas, F32), dptr(acc, I64)))
+
+
+def sky_acc_add(s, src, dst):
+    assert src.dtype == I64 and dst.dtype == I64 and src.numel() == dst.numel()
+    check(_lib.lib().clmgs_sky_acc_add(s, int(src.numel()), dptr(src, I64), dptr(dst, I64)))
+
+
+def sky_grad_convert(s, acc, grad):
+    """grad += acc * 2^-48, acc = 0 (the one place the fixed-point sums become floats)."""
+    assert acc.dtype == I64 and grad.dtype == F32 and acc.numel() == grad.numel()
+    check(_lib.lib().clmgs_sky_grad_convert(s, int(acc.numel()), dptr(acc, I64), dptr(grad, F32)))
+
+
+class _ApplySky(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, image, alphas, sky, vm, K, acc):
+        assert image.dim() == 3 and image.shape[0] == 3 and image.dtype == F32 and image.is_cuda
+        _, H, W = image.shape
+        assert alphas.dtype == F32 and alphas.device == image.device and alphas.numel() == H * W
+        S = sky.detach()
+        check_sky(S)
+        assert S.device == image.device
+        a = alphas.detach().reshape(H, W).contiguous()
+        out = torch.empty_strided(image.shape, image.stride(), dtype=F32, device=image.device)
+        sky_forward(stream(), H, W, _view_ptr(image), image.stride(), a, vm, K, S, _view_ptr(out), out.stride())
+        ctx.cam, ctx.acc, ctx.alphas_shape = (vm, K), acc, alphas.shape
+        ctx.save_for_backward(a, S)
+        return out
+
+    @staticmethod
+    def backward(ctx, v):
+        a, S = ctx.saved_tensors
+        H, W = a.shape
+        assert v.dtype == F32 and tuple(v.shape) == (3, H, W)
+        v_alphas = torch.empty_like(a)
+        acc = ctx.acc if ctx.acc is not None else torch.zeros(S.shape, dtype=I64, device=S.device)
+        sky_backward(stream(), H, W, _view_ptr(v), v.stride(), a, *ctx.cam, S, v_alphas, acc)
+        v_sky = None
+        if ctx.acc is None and ctx.needs_input_grad[2]:
+            v_sky = torch.zeros_like(S)
+            sky_grad_convert(stream(), acc, v_sky)
+        return v, v_alphas.reshape(ctx.alphas_shape), v_sky, None, None, None
+
+
+def apply_sky(image, alphas, sky, viewmat, K):
+    """The sky map behind a rendered image: image [3,H,W] float32 rendered with NO background (any strides, e.g. the
+    permuted view of the rasterizer's [H,W,3] output), alphas [H,W] or [1,H,W], sky float32 [Hs,Ws,3] (equirectangular,
+    world axes) on the same device, viewmat [4,4] world->camera and K [3,3] of the camera ->
+    y = x + (1 - alpha) * bilinear(sky; ray of the pixel) in the image's layout, unclamped; differentiable in the image
+    (identity), alphas and sky, not in the camera (csrc/sky.hip; DESIGN.md section 3, "Sky")."""
+    return _ApplySky.apply(image, alphas, sky, _host_f32(viewmat, 16, "viewmat"), _host_f32(K, 9, "K"), None)
+
+
+def apply_camera_sky(image, alphas, camera):
+    """The camera's sky (cameras.camera_sky) behind a rendered image and its alpha image; the map's gradient ADDED, in
+    fixed point, into the accumulator the camera carries (a training camera; sky.SkyModel converts it once per step);
+    the image itself for a camera without a sky.  What the op-by-op engines and the evaluation renders call."""
+    from .cameras import camera_sky
+    from .fused import _cam_host
+    sky = camera_sky(camera)
+    if sky is None:
+        return image
+    table, acc = sky
+    vm, K, _ = _cam_host(camera)
+    train = torch.is_grad_enabled() and (image.requires_grad or alphas.requires_grad)
+    return _ApplySky.apply(image, alphas, table.detach(), vm, K, acc if train else None)
+
+
 # ------------------------------------------------------------ MCMC densification
 def _f32_dev(t, shape, what):
     assert t.is_cuda and t.dtype == F32 and t.is_contiguous() and tuple(t.shape) == tuple(shape), \

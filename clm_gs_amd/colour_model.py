@@ -1,6 +1,7 @@
 """What exposure.ExposureModel and bilagrid.BilagridModel share: one learnable table with a row per training camera, a
 gradient table the kernels ADD into, the cameras' views of both (cameras.camera_colour reads them), and a dense Adam step
-at a scheduled learning rate.  The optimizer, the schedule and the file formats belong to the subclass."""
+at a scheduled learning rate.  The optimizer, the schedule and the file formats belong to the subclass.  sky.SkyModel
+builds on the same base with ONE table for the scene (its own attach) and a fixed-point accumulator in front of `grad`."""
 import torch
 
 

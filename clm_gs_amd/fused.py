@@ -13,8 +13,8 @@ import torch
 
 from . import _lib, utils
 from ._lib import check, dptr
-from .cameras import camera_colour, camera_invdepth, camera_loss_mask, camera_pose_grad
-from .clm_kernels import COLOUR, check_depth_prior_args, masked_loss_value
+from .cameras import camera_colour, camera_invdepth, camera_loss_mask, camera_pose_grad, camera_sky, check_sky_background
+from .clm_kernels import COLOUR, check_depth_prior_args, check_sky, masked_loss_value, sky_acc_add, sky_backward, sky_forward
 from .gsplat import _record_counts, bucket_size, empty_bucketed, isect_begin, isect_counts, isect_finish
 
 F32, I32, U8, U16 = torch.float32, torch.int32, torch.uint8, torch.uint16
@@ -63,7 +63,8 @@ class _CameraPass:
                  "bg", "v_out", "maps", "loss", "ev_loss", "streams", "deg", "aux", "loss_partials",
                  "lambda_dssim", "gt_u8", "background", "isect", "sh_index", "means2d", "n_dev", "antialiased",
                  "loss_mask", "mask_count", "colour", "colour_partials",
-                 "invdepth", "depth_weight", "depths", "id_partials", "id_term", "pose_grad")
+                 "invdepth", "depth_weight", "depths", "id_partials", "id_term", "pose_grad",
+                 "sky", "v_alphas", "sky_scratch")
 
 
 def _sptr(torch_stream):
@@ -177,6 +178,13 @@ def camera_front(gaussians, camera, this_filter, sh_rows, sh_by_filter, backgrou
                                   f"{tuple(p.pose_grad.shape)}")
         if sh_index is not None or not sh_rows.is_cuda:
             raise ValueError("pose refinement needs the SH rows in HBM (sh_residency=\"hbm\")")
+    # a sky on the camera -- (map, accumulator or None) -- is composited behind the tile kernel's render, which then runs
+    # with NO background; without one, not one launch differs.  Refused with a pose-gradient buffer (camera_sky) and with
+    # a non-zero background, here, before anything is enqueued.
+    p.sky, p.v_alphas, p.sky_scratch = camera_sky(camera), None, None
+    if p.sky is not None:
+        check_sky(p.sky[0], "camera.sky")
+        check_sky_background(background)
     p.antialiased = utils.antialiased()  # the backward follows the mode its forward ran in
     filt = p.filt = this_filter.contiguous() if this_filter is not None else None  # None: all rows
     if small_packed is not None:
@@ -244,7 +252,7 @@ def camera_forward_finish(gaussians, p, exact=False):
         p.out = torch.empty((H, W, nch), dtype=F32, device=dev)
         p.alphas = torch.empty((H, W), dtype=F32, device=dev)
         p.last_ids = torch.empty((H, W), dtype=I32, device=dev)
-        p.bg = background.reshape(1, 3).to(F32).contiguous() if background is not None else None
+        p.bg = background.reshape(1, 3).to(F32).contiguous() if background is not None and p.sky is None else None
         if nch == 4 and p.bg is not None:  # the inverse depth's background is 0
             p.bg = torch.cat([p.bg, p.bg.new_zeros((1, 1))], dim=1).contiguous()
     if s_raster is not s_front:
@@ -273,6 +281,11 @@ def camera_forward_finish(gaussians, p, exact=False):
         gt = gt_u8.contiguous()
         sm = _sptr(s_mem)
         mask = p.loss_mask
+        if p.sky is not None:
+            # the sky behind the render, IN PLACE on p.out (rendered with no background): the colour stage and the loss
+            # read the composite, and so does the colour stage's backward; the tile backward never reads p.out
+            sky_forward(sm, H, W, dptr(p.out), (sc, sy, sx), p.alphas, p.cam[0], p.cam[1], p.sky[0],
+                        dptr(p.out), (sc, sy, sx))
         img = p.out  # what the loss sees
         if p.colour is not None:
             # the camera's colour stage (exposure transform, or bilateral grid sliced per pixel) into a second buffer of
@@ -312,6 +325,15 @@ def camera_forward_finish(gaussians, p, exact=False):
             kind, param, _ = p.colour
             p.colour_partials = COLOUR[kind].backward(sm, H, W, dptr(p.out), (sc, sy, sx), param, dptr(p.v_out), (sc, sy, sx),
                                                       dptr(p.v_out), (sc, sy, sx), dev)
+        p.v_alphas, p.sky_scratch = None, None
+        if p.sky is not None and p.sky[1] is not None:
+            # p.v_out is dL/d(composite) here: dL/dalpha for the tile backward, and the map's gradient into a zeroed
+            # fixed-point scratch of this pass -- camera_backward adds it to the camera's accumulator once camera_verify
+            # has accepted THIS forward (a forward repeated for capacity replaces it).  Allocated and used on s_mem only.
+            p.v_alphas = torch.empty((H, W), dtype=F32, device=dev)
+            p.sky_scratch = torch.zeros(p.sky[0].shape, dtype=torch.int64, device=dev)
+            sky_backward(sm, H, W, dptr(p.v_out), (sc, sy, sx), p.alphas, p.cam[0], p.cam[1], p.sky[0], p.v_alphas,
+                         p.sky_scratch)
         if p.invdepth is not None:
             # the depth term, after the loss (and exposure) backward on the same stream, into the same [H,W,4] cotangent:
             # they wrote words 0..2 of every pixel through their strides, this writes word 3.  One partial sum per
@@ -399,6 +421,11 @@ def camera_backward(gaussians, p, g_sh_rows, small_grad=None, update_stats=True,
         if grad is not None:
             COLOUR[kind].finish(_sptr(s_mem), H, W, param, p.colour_partials, grad)
         p.colour_partials = None
+    if p.sky_scratch is not None:
+        # the map's gradient of the accepted forward, added ONCE, in integers, on the stream that wrote the scratch
+        with torch.cuda.stream(s_mem):
+            sky_acc_add(_sptr(s_mem), p.sky_scratch, p.sky[1])
+        p.sky_scratch = None
     V = p.V
     vm, K, campos = p.cam
     tw, th = math.ceil(W / float(TILE)), math.ceil(H / float(TILE))
@@ -427,12 +454,12 @@ def camera_backward(gaussians, p, g_sh_rows, small_grad=None, update_stats=True,
     if p.n_dev is None:
         check(raster_bwd(_sptr(s_raster), 1, V, n_isects, dptr(p.packed), dptr(p.bg, F32, True), W, H,
                          TILE, tw, th, dptr(p.offsets), dptr(p.fids), dptr(p.alphas), dptr(p.last_ids),
-                         dptr(p.v_out), None, None, None, None, None, None,
+                         dptr(p.v_out), dptr(p.v_alphas, F32, True), None, None, None, None, None,
                          dptr(p.emit_slot), dptr(p.row_cum), dptr(partials), *((None,) if absgrad else ())))
     else:
         check(raster_bwd_dev(_sptr(s_raster), 1, V, n_isects, dptr(p.n_dev), dptr(p.packed),
                              dptr(p.bg, F32, True), W, H, TILE, tw, th, dptr(p.offsets), dptr(p.fids),
-                             dptr(p.alphas), dptr(p.last_ids), dptr(p.v_out), None,
+                             dptr(p.alphas), dptr(p.last_ids), dptr(p.v_out), dptr(p.v_alphas, F32, True),
                              dptr(p.emit_slot), dptr(p.row_cum), dptr(partials)))
     if s_mem is not s_raster:
         ev = torch.cuda.Event()
@@ -486,8 +513,10 @@ def camera_backward(gaussians, p, g_sh_rows, small_grad=None, update_stats=True,
     if s_mem is not s_raster:
         partials.record_stream(s_mem)
         p.v_out.record_stream(s_raster)
+        if p.v_alphas is not None:
+            p.v_alphas.record_stream(s_raster)
     del partials
-    p.v_out = None
+    p.v_out, p.v_alphas = None, None
     if release:
         # Nothing reads this camera's forward outputs after the two kernels above.  They were allocated on the
         # front stream and used on the tile and memory streams: tell the allocator, then drop them, so the next

@@ -189,6 +189,9 @@ def main(argv=None):
                     help="also write depth_%%05d.npy (float32 expected depth) and depth_%%05d.png (grey) per frame")
     ap.add_argument("--antialiased", action="store_true",
                     help="gsplat's rasterize_mode=\"antialiased\": for a model trained with trainer --antialiased")
+    ap.add_argument("--sky", action="store_true",
+                    help="for a model trained with trainer --sky: composite <model_path>/sky.npz behind every frame "
+                         "(not with --white_background)")
     g = ap.add_mutually_exclusive_group()
     g.add_argument("--clm_offload", action="store_true")
     g.add_argument("--naive_offload", action="store_true")
@@ -196,6 +199,14 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if not (a.clm_offload or a.naive_offload or a.no_offload):
         a.clm_offload = True
+    model_dir = a.model_path if os.path.isdir(a.model_path) else os.path.dirname(a.model_path)
+    if a.sky:  # refusals before anything is loaded
+        if a.white_background:
+            raise SystemExit("--sky and --white_background together are refused: the sky map is the background")
+        from .sky import FILE as SKY_FILE
+        if not os.path.exists(os.path.join(model_dir, SKY_FILE)):
+            raise SystemExit(f"--sky: {os.path.join(model_dir, SKY_FILE)} not found; the model was not trained with "
+                             "trainer --sky (or the map was not copied along with the point cloud)")
     args = utils.default_args(bsz=4, rasterize_mode="antialiased" if a.antialiased else "classic")
     for k in ("clm_offload", "naive_offload", "no_offload", "save_video", "render_depth"):
         setattr(args, k, getattr(a, k))
@@ -218,6 +229,9 @@ def main(argv=None):
     hull = BIGCITY_HULL if not a.hull else tuple(tuple(float(v) for v in p.split(",")) for p in a.hull)
     cams = polyline_trajectory(R_LOOK_DOWN, a.manual_height, a.n_frames, fovx, fovy, a.width, a.height, hull)
     bg = torch.tensor([1.0, 1.0, 1.0], device="cuda") if a.white_background else None
+    if a.sky:
+        from .sky import SkyModel
+        SkyModel.from_file(model_dir, "cuda").attach(cams, train=False)
     with open(os.path.join(out, "render_images.log"), "w") as log:
         log.write(f"Model path: {a.model_path}\nTrajectory type: {a.traj_path}\nNumber of frames: {a.n_frames}\n")
         with torch.no_grad():

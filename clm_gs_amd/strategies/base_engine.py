@@ -5,8 +5,8 @@ import math
 import torch
 
 from .. import utils
-from ..cameras import camera_loss_mask
-from ..clm_kernels import apply_camera_colour, camera_depth_term, fused_l1_ssim_loss, fused_ssim
+from ..cameras import camera_loss_mask, camera_sky, check_sky_background
+from ..clm_kernels import apply_camera_colour, apply_camera_sky, camera_depth_term, fused_l1_ssim_loss, fused_ssim
 from ..gsplat import (fully_fused_projection, isect_offset_encode, isect_tiles,
                       rasterize_to_pixels, spherical_harmonics, visibility_radii)
 
@@ -128,15 +128,22 @@ def fov_camera(camera, device):
 
 
 def camera_forward_ops(means, quats, scales, opacities, coeffs, sh_degree, viewmat, K, centre, backgrounds, render_mode,
-                       train, radius_clip=0.0, sh_masks=False, sh_autograd=True, tile_size=TILE_SIZE):
+                       train, radius_clip=0.0, sh_masks=False, sh_autograd=True, tile_size=TILE_SIZE, sky_camera=None):
     """The op-by-op forward of one camera, which the three reference-named entries share: projection -> SH -> +0.5 clamp
     -> tile binning -> offsets -> (depth as fourth colour) -> rasterize.  Each entry hands in ITS K, camera centre,
     coefficient view ([1,V,16,3]) and backgrounds (None, [3] or [1,3]); the knobs are what else differs between them:
     train (means2D keeps its gradient, and the absgrad one under args.absgrad), radius_clip, sh_masks (SH only where
     radii > 0), sh_autograd (False: SH under no_grad and the colours re-leafed, for an SH backward that accumulates in
-    place) and tile_size.
+    place), tile_size and sky_camera: the camera, handed in when it carries a sky (cameras.camera_sky) -- the rasterizer
+    then runs with NO background (a non-zero one is refused) and the sky is composited behind its two outputs
+    (clm_kernels.apply_camera_sky) before the image is returned; None: unchanged.
     -> (image[3,H,W] view, means2D[1,V,2], radii[1,V], () | (depth[1,H,W], alpha[1,H,W]) by split_depth,
         () | (colours leaf[1,V,3], dirs[1,V,3]) without sh_autograd)."""
+    if sky_camera is not None and camera_sky(sky_camera) is None:
+        sky_camera = None
+    if sky_camera is not None:  # refused before anything is enqueued
+        check_sky_background(backgrounds)
+        backgrounds = None
     image_width, image_height = int(utils.get_img_width()), int(utils.get_img_height())
     radiis, means2D, depths, conics, compensations = fully_fused_projection(
         means=means, covars=None, quats=quats, scales=scales, viewmats=viewmat.unsqueeze(0), Ks=K.unsqueeze(0),
@@ -168,8 +175,13 @@ def camera_forward_ops(means, quats, scales, opacities, coeffs, sh_degree, viewm
         absgrad=train and bool(getattr(utils.get_args(), "absgrad", False)))  # -> means2D.absgrad after backward
     if render_mode != "RGB":
         rendered_image, depth, alpha = split_depth(rendered_image, alphas, render_mode)
+        if sky_camera is not None:
+            rendered_image = apply_camera_sky(rendered_image, alphas[0, ..., 0], sky_camera)
         return rendered_image, means2D, radiis, (depth, alpha), sh_leaf
-    return rendered_image.squeeze(0).permute(2, 0, 1), means2D, radiis, (), sh_leaf  # [3,H,W] view, no copy
+    rendered_image = rendered_image.squeeze(0).permute(2, 0, 1)  # [3,H,W] view, no copy
+    if sky_camera is not None:
+        rendered_image = apply_camera_sky(rendered_image, alphas[0, ..., 0], sky_camera)
+    return rendered_image, means2D, radiis, (), sh_leaf
 
 
 def pipeline_forward_one_step(filtered_opacity_gpu, filtered_scaling_gpu, filtered_rotation_gpu,
@@ -182,7 +194,7 @@ def pipeline_forward_one_step(filtered_opacity_gpu, filtered_scaling_gpu, filter
     image, means2D, radiis, depth_alpha, _ = camera_forward_ops(
         filtered_xyz_gpu, filtered_rotation_gpu, filtered_scaling_gpu, filtered_opacity_gpu,
         filtered_shs.reshape(1, filtered_xyz_gpu.shape[0], 16, 3), gaussians.active_sh_degree, viewmat, K, centre,
-        background.reshape(1, 3) if background is not None else None, render_mode, train=not eval)
+        background.reshape(1, 3) if background is not None else None, render_mode, train=not eval, sky_camera=camera)
     return (image, means2D, radiis) + depth_alpha[:2 if return_alpha else 1]
 
 

@@ -51,7 +51,8 @@ def pipeline_forward_one_step_shs_inplace(filtered_opacity_gpu, filtered_scaling
         filtered_xyz_gpu, filtered_rotation_gpu, filtered_scaling_gpu, filtered_opacity_gpu,
         filtered_shs.reshape(1, filtered_xyz_gpu.shape[0], 16, 3), gaussians.active_sh_degree,
         camera.world_view_transform.transpose(0, 1), camera.K, camera.camtoworlds[:, None, :3, 3],
-        background.reshape(1, 3) if background is not None else None, render_mode, train=True, sh_autograd=False)
+        background.reshape(1, 3) if background is not None else None, render_mode, train=True, sh_autograd=False,
+        sky_camera=camera)
     return (image, means2D, radiis) + sh_leaf + depth_alpha[:1]
 
 

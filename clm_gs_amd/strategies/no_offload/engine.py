@@ -19,7 +19,8 @@ def baseline_accumGrads_micro_step(means3D, opacities, scales, rotations, shs, s
     viewmat, K, centre = fov_camera(camera, means3D.device)
     image, means2D, radiis, depth_alpha, _ = camera_forward_ops(
         means3D, rotations, scales, opacities, shs.unsqueeze(0), sh_degree, viewmat, K, centre, background, render_mode,
-        train=mode == "train", radius_clip=utils.get_args().radius_clip, sh_masks=True, tile_size=tile_size)
+        train=mode == "train", radius_clip=utils.get_args().radius_clip, sh_masks=True, tile_size=tile_size,
+        sky_camera=camera)
     return (image, means2D, radiis, None) + depth_alpha[:2 if return_alpha else 1]
 
 

@@ -261,6 +261,34 @@ def check_appearance_flags(args):
         refuse_bilagrid_under_camera_dp()
 
 
+def check_sky_flags(args):
+    """The refusals of `--sky`, by name, before anything is loaded."""
+    if not getattr(args, "sky", False):
+        return
+    if getattr(args, "white_background", False):
+        raise ValueError("--sky and --white_background together are refused: the sky map is the background")
+    if getattr(args, "pose_opt", False):
+        raise ValueError("--sky and --pose_opt together are refused: the sky's gradient with respect to the camera (the "
+                         "ray direction of the lookup) is not carried")
+    if dp.world_size() > 1:
+        raise ValueError("--sky is not supported with camera-DP (world_size {}): the map's gradient accumulator is not "
+                         "reduced across ranks; train on one GPU or without --sky".format(dp.world_size()))
+
+
+def build_sky(train_cameras, other_cameras, iterations, device="cuda", shape=(256, 512), init=(0.5, 0.5, 0.5),
+              lr_init=0.01, lr_final=0.001):
+    """`--sky`: a sky.SkyModel, one map for the scene.  The training cameras train it; every other camera (test cameras,
+    novel views) is rendered in front of it.  Refused under camera-DP (check_sky_flags)."""
+    if dp.world_size() > 1:
+        raise ValueError("--sky is not supported with camera-DP (world_size {}): the map's gradient accumulator is not "
+                         "reduced across ranks; train on one GPU or without --sky".format(dp.world_size()))
+    from .sky import SkyModel
+    model = SkyModel(tuple(shape), device, init=tuple(init), lr_init=lr_init, lr_final=lr_final, max_steps=int(iterations))
+    model.attach(train_cameras, train=True)
+    model.attach(other_cameras, train=False)
+    return model
+
+
 def build_bilagrid(train_cameras, iterations, device="cuda", grid=(16, 16, 8), lr_init=2e-3, lr_final=2e-5, tv_weight=10.0):
     """`--bilagrid`: a bilagrid.BilagridModel with one grid per TRAINING camera, attached to the cameras (test cameras and
     novel views carry none and are rendered as the model is).  Refused under camera-DP, for the reason of build_exposure."""
@@ -285,8 +313,10 @@ def build_pose(train_cameras, iterations, device="cuda", lr=1e-5, reg=1e-6, nois
 
 def training(gaussians, scene, train_cameras, test_cameras, log_file, iterations=None,
              test_iterations=(), background=None, shuffle_seed=0, phase_times=None, exposure=None, bilagrid=None,
-             pose=None):
+             pose=None, sky=None):
     """Runs `iterations` images of training; returns the End2endTimer.
+    `sky` (optional sky.SkyModel, attached to the cameras): stepped and zeroed next to the exposure step, under the same
+    stream-order reasoning; its step converts the batch's fixed-point sums once.  Refused under camera-DP.
     `exposure` (optional exposure.ExposureModel, attached to the training cameras): stepped at the scheduled learning
     rate and zeroed after every batch, on the current stream -- every engine has joined its camera streams into it by
     the time it returns.  A row's gradient is its camera's alone and is not divided by the batch size.
@@ -312,6 +342,8 @@ def training(gaussians, scene, train_cameras, test_cameras, log_file, iterations
         raise ValueError("an exposure model cannot be trained under camera-DP (see build_exposure)")
     if bilagrid is not None:
         refuse_bilagrid_under_camera_dp()
+    if ws > 1 and sky is not None:
+        raise ValueError("a sky model cannot be trained under camera-DP (see build_sky)")
     if ws > 1:
         assert clm_hbm_only(args), "camera-DP trains clm_offload with sh_residency='hbm'"
         if getattr(gaussians, "split_generator", None) is None:
@@ -495,7 +527,7 @@ def training(gaussians, scene, train_cameras, test_cameras, log_file, iterations
             log_file.write(memory_line(iteration, gbsz, gaussians))
         if not clm and not naive and not use_mcmc:  # train.py:533-578
             no_offload_optimizer_step(gaussians, args, bsz, visibility)
-        for colour in (exposure, bilagrid):
+        for colour in (exposure, bilagrid, sky):
             if colour is not None:
                 colour.step(iteration)
                 colour.zero_grad()
@@ -551,6 +583,8 @@ def train_from_colmap(source_path, model_path, strategy="clm_offload", iteration
     `bilagrid_tv_weight`): bilateral-grid colour correction of the training cameras (build_bilagrid), written to
     `<model_path>/bilagrid.npz`, reachable as `scene.bilagrid`; refused together with `exposure=True`.  `depths` (with `depth_l1_weight_init` / `depth_l1_weight_final`): the directory of the 16-bit
     inverse-depth PNGs of the depth regularisation (colmap_scene.load_colmap_scene); refused with `absgrad=True`.
+    `sky=True` (with `sky_shape`, `sky_init`, `sky_lr_init`, `sky_lr_final`): a learnable sky map for the scene (build_sky),
+    written to `<model_path>/sky.npz`, reachable as `scene.sky`; refusals: check_sky_flags.
     `pose_opt=True` (with `pose_opt_lr`, `pose_opt_reg`, `pose_noise`, `defer_pose_step`): camera pose refinement of the
     training cameras (build_pose), written to `<model_path>/poses.json`, reachable as `scene.pose`; refusals:
     pose.check_pose_args.
@@ -569,6 +603,7 @@ def train_from_colmap(source_path, model_path, strategy="clm_offload", iteration
     check_depth_flags(args, bool(depths))  # raises: before anything is loaded
     check_appearance_flags(args)  # raises: before anything is loaded
     check_pose_args(args, bool(depths))  # raises: before anything is loaded
+    check_sky_flags(args)  # raises: before anything is loaded
     check_contrib_prune_args(args)  # raises: before anything is loaded
     utils.set_args(args)
     if getattr(args, "exposure", False) and dp.world_size() > 1:
@@ -599,13 +634,17 @@ def train_from_colmap(source_path, model_path, strategy="clm_offload", iteration
     if getattr(args, "pose_opt", False):
         scene.pose = build_pose(scene.train_cameras, args.iterations, "cuda", float(args.pose_opt_lr),
                                 float(args.pose_opt_reg), float(args.pose_noise), bool(args.defer_pose_step))
+    scene.sky = None
+    if getattr(args, "sky", False):
+        scene.sky = build_sky(scene.train_cameras, scene.test_cameras, args.iterations, "cuda", tuple(args.sky_shape),
+                              tuple(args.sky_init), float(args.sky_lr_init), float(args.sky_lr_final))
     os.makedirs(model_path, exist_ok=True)
     prev_log = utils.get_log_file()
     try:
         with open(os.path.join(model_path, "python_ws=1_rk=0.log"), "w") as log_file:
             timer = training(gaussians, scene, scene.train_cameras, scene.test_cameras, log_file,
                              iterations=args.iterations, test_iterations=test_iterations, exposure=scene.exposure,
-                             bilagrid=scene.bilagrid, pose=scene.pose)
+                             bilagrid=scene.bilagrid, pose=scene.pose, sky=scene.sky)
     finally:
         utils.set_log_file(prev_log)  # never leave a closed file as the process-wide log
     if save:
@@ -617,6 +656,8 @@ def train_from_colmap(source_path, model_path, strategy="clm_offload", iteration
                 scene.exposure.save_json(os.path.join(model_path, "exposure.json"), scene.train_cameras)
             if scene.bilagrid is not None:  # grids in gsplat's [n,12,L,Hg,Wg] layout + image names
                 scene.bilagrid.save(os.path.join(model_path, "bilagrid.npz"), scene.train_cameras)
+            if scene.sky is not None:  # the map, its shape and the convention string
+                scene.sky.save(model_path)
             if scene.pose is not None:  # {image_name: {"delta": [9], "world_to_camera": 4x4}}
                 scene.pose.save_json(os.path.join(model_path, "poses.json"), scene.train_cameras)
     return gaussians, scene, timer
@@ -662,6 +703,14 @@ def build_arg_parser():
     ap.add_argument("--bilagrid_lr_init", type=float, default=2e-3)
     ap.add_argument("--bilagrid_lr_final", type=float, default=2e-5)
     ap.add_argument("--bilagrid_tv_weight", type=float, default=10.0)
+    ap.add_argument("--sky", action="store_true",
+                    help="learnable sky: one equirectangular environment map composited behind the splats and trained by "
+                         "the same loss, written to <model_path>/sky.npz; render the model with --sky too (single GPU; not "
+                         "with --white_background or --pose_opt)")
+    ap.add_argument("--sky_shape", type=int, nargs=2, default=[256, 512], metavar=("HS", "WS"))
+    ap.add_argument("--sky_init", type=float, nargs=3, default=[0.5, 0.5, 0.5], metavar=("R", "G", "B"))
+    ap.add_argument("--sky_lr_init", type=float, default=0.01)
+    ap.add_argument("--sky_lr_final", type=float, default=0.001)
     ap.add_argument("-d", "--depths", default=None, metavar="DIR",
                     help="depth regularisation: directory (relative to the source path or absolute) of 16-bit inverse-depth "
                          "PNGs NAME.png, scaled by sparse/0/depth_params.json; an L1 term on the rendered inverse depth "
@@ -716,6 +765,8 @@ if __name__ == "__main__":  # python -m clm_gs_amd.trainer -s <colmap dir> -m <o
                                 bilagrid=a.bilagrid, bilagrid_shape=tuple(a.bilagrid_shape),
                                 bilagrid_lr_init=a.bilagrid_lr_init, bilagrid_lr_final=a.bilagrid_lr_final,
                                 bilagrid_tv_weight=a.bilagrid_tv_weight,
+                                sky=a.sky, sky_shape=tuple(a.sky_shape), sky_init=tuple(a.sky_init),
+                                sky_lr_init=a.sky_lr_init, sky_lr_final=a.sky_lr_final,
                                 depths=a.depths, depth_l1_weight_init=a.depth_l1_weight_init,
                                 depth_l1_weight_final=a.depth_l1_weight_final, mcmc=a.mcmc, mcmc_cap_max=a.cap_max,
                                 mcmc_noise_lr=a.mcmc_noise_lr, mcmc_refine_start_iter=a.mcmc_refine_start_iter,

@@ -52,6 +52,9 @@ def default_args(**over):
         # (Wg, Hg, L) lattice of 3x4 affine colour transforms per TRAINING image, sliced by position and luminance, between
         # the rasterizer and the loss; bilagrid_tv_weight x its total variation is added to the objective
         bilagrid=False, bilagrid_shape=(16, 16, 8), bilagrid_lr_init=2e-3, bilagrid_lr_final=2e-5, bilagrid_tv_weight=10.0,
+        # this build: learnable sky (sky.SkyModel): ONE equirectangular map [Hs,Ws,3] per scene, composited behind the splats
+        # between the tile kernels and the colour stage and trained by the same loss; untuned defaults
+        sky=False, sky_shape=(256, 512), sky_init=(0.5, 0.5, 0.5), sky_lr_init=0.01, sky_lr_final=0.001,
         # this build: depth regularisation (the INRIA code base's -d / --depths, --depth_l1_weight_init / _final): an L1 term
         # between the rendered inverse depth and the inverse-depth prior of every training camera that carries one
         # (cameras.camera_invdepth), weighted by depth_l1_weight() below.  depths: the directory of the 16-bit PNGs

@@ -503,6 +503,30 @@ int clmgs_exposure_bwd(void* stream, int H, int W, const float* x, int64_t strid
                        int64_t vstride_x, float* partials);
 int clmgs_exposure_grad_finish(void* stream, int rows, const float* partials, float* grad12);
 
+/* ---- learnable sky (csrc/sky.hip): one equirectangular map sky[Hs,Ws,3] (DEVICE pointer, world axes) composited
+ * behind the splats.  x, y, g are [3,H,W] VIEWS by element strides (c, y, x) like the exposure entries' (with an
+ * [H,W,4] buffer the fourth word of a pixel is neither read nor written); alphas, v_alphas are contiguous [H,W];
+ * viewmat_host[16] (row-major world->camera) and K_host[9] are HOST pointers, as clmgs_preprocess_fwd takes them.  With
+ * R = viewmat[:3,:3], dc = ((px + .5 - cx) / fx, (py + .5 - cy) / fy, 1), d = R^T dc / |dc|,
+ * u = (atan2(d.x, d.z) / 2pi + .5) Ws - .5 (columns wrap), v = (asin(d.y) / pi + .5) Hs - .5 (rows clamp),
+ * s = the bilinear sample of the map at (u, v), weights w_k:
+ *   fwd:  y[c] = x[c] + (1 - alphas) s[c]; y MAY BE x itself (same pointer and strides: in place).
+ *   bwd:  v_alphas = -(g[0] s[0] + g[1] s[1] + g[2] s[2]) is STORED, and round(2^48 (1 - alphas) w_k g[c]) is ADDED
+ *         into acc[Hs,Ws,3], signed 64-bit fixed point with unit 2^-48, by integer atomics only: acc holds the same
+ *         bits whatever the order of pixels, workgroups, calls and cameras.  The caller zeroes acc once and may call
+ *         camera after camera.  CONTRACT: every texel's sum stays below 2^15 in magnitude.
+ *   acc_add:      dst[i] += src[i], i < n (int64).
+ *   grad_convert: grad[i] += float(acc[i] * 2^-48) (through double), then acc[i] = 0.
+ * A null pointer, H < 1, W < 1, Hs < 1, Ws < 1 or a zero focal length returns CLMGS_EINVAL before anything is written. */
+int clmgs_sky_fwd(void* stream, int H, int W, const float* x, int64_t stride_c, int64_t stride_y, int64_t stride_x,
+                  const float* alphas, const float* viewmat_host, const float* K_host, const float* sky, int Hs,
+                  int Ws, float* y, int64_t ystride_c, int64_t ystride_y, int64_t ystride_x);
+int clmgs_sky_bwd(void* stream, int H, int W, const float* g, int64_t gstride_c, int64_t gstride_y, int64_t gstride_x,
+                  const float* alphas, const float* viewmat_host, const float* K_host, const float* sky, int Hs,
+                  int Ws, float* v_alphas, int64_t* acc);
+int clmgs_sky_acc_add(void* stream, int64_t n, const int64_t* src, int64_t* dst);
+int clmgs_sky_grad_convert(void* stream, int64_t n, int64_t* acc, float* grad);
+
 /* ---- depth regularisation (csrc/invdepth.hip; the INRIA 3DGS convention: rendered inverse depth
  * I = sum_i w_i / z_i, the fourth blended channel with 1/z as fourth colour and background 0, against a uint16 prior
  * prior = raw / 65536 * scale + offset)
