@@ -10,7 +10,8 @@ and loss_mask_count, the per-pixel ignore mask of the training loss.  A training
 world_view_transform, camtoworlds and the cached host triple of a camera whose pose it has moved).  Any camera of a scene
 with a learnable sky carries `sky`, the detached float32 [Hs,Ws,3] equirectangular map of a sky.SkyModel (one table shared
 by all cameras), and `sky_acc`, the model's int64 [Hs,Ws,3] fixed-point gradient accumulator (unit 2^-48) for a camera
-that trains the map, None for one that is only rendered (camera_sky)."""
+that trains the map, None for one that is only rendered (camera_sky).  OrthoCamera is the orthographic kind
+(`camera_model = "ortho"`, read through camera_model()): rendered by the eval entries only, refused by the training ones."""
 import math
 
 import numpy as np
@@ -161,3 +162,52 @@ class Camera:
         fy = self.image_height / (2 * math.tan(self.FoVy * 0.5))
         return torch.tensor([[fx, 0, self.image_width / 2.0], [0, fy, self.image_height / 2.0],
                              [0, 0, 1]], dtype=torch.float32, device=device)
+
+
+def camera_model(camera):
+    """The projection a camera is rendered with: "ortho" for an OrthoCamera, "pinhole" for any object without the
+    attribute (every training camera)."""
+    return getattr(camera, "camera_model", "pinhole")
+
+
+def refuse_ortho(camera, where):
+    """Training entries: an orthographic camera is refused by name, before anything is enqueued."""
+    if camera_model(camera) != "pinhole":
+        raise ValueError(f"{where}: camera {getattr(camera, 'image_name', camera)!r} is orthographic "
+                         f"(camera_model={camera_model(camera)!r}); orthographic cameras are rendered through the eval "
+                         "entries only, training on them is not supported")
+
+
+class OrthoCamera:
+    """An orthographic camera (gsplat's camera_model="ortho") for the eval entries: K = [[sx,0,cx],[0,sy,cy],[0,0,1]]
+    with sx, sy in pixels per world unit (`pixels_per_unit`: a scalar or an (sx, sy) pair).  cx, cy default to the image
+    centre and may lie outside the image: that is how one window of a larger map is addressed.  Carries K,
+    world_view_transform, camtoworlds and the host triple like Camera; no image, masks or colour stage."""
+    camera_model = "ortho"
+
+    def __init__(self, uid, world_to_cam, pixels_per_unit, width, height, cx=None, cy=None, image_name=None,
+                 device="cuda"):
+        self.uid = uid
+        try:
+            sx, sy = pixels_per_unit
+        except TypeError:
+            sx = sy = pixels_per_unit
+        self.sx, self.sy = float(sx), float(sy)
+        if not (self.sx > 0 and self.sy > 0 and math.isfinite(self.sx) and math.isfinite(self.sy)):
+            raise ValueError(f"pixels_per_unit must be positive and finite, got {pixels_per_unit}")
+        self.image_width, self.image_height = int(width), int(height)
+        self.cx = self.image_width / 2.0 if cx is None else float(cx)
+        self.cy = self.image_height / 2.0 if cy is None else float(cy)
+        self.image_name = image_name or f"ortho_{uid:05d}"
+        w2c = torch.as_tensor(world_to_cam, dtype=torch.float32)
+        self.world_view_transform = w2c.t().contiguous().to(device)
+        self.original_image = None
+        self.K = self.create_k_on_gpu(device)
+        c2w = torch.inverse(w2c)
+        self.camtoworlds = c2w[None].to(device)
+        self._clmgs_host = (np.ascontiguousarray(w2c.numpy().astype(np.float32).reshape(16)),
+                            np.ascontiguousarray(self.create_k_on_gpu("cpu").numpy().astype(np.float32).reshape(9)),
+                            np.ascontiguousarray(c2w[:3, 3].numpy().astype(np.float32).reshape(3)))
+
+    def create_k_on_gpu(self, device="cuda"):
+        return torch.tensor([[self.sx, 0, self.cx], [0, self.sy, self.cy], [0, 0, 1]], dtype=torch.float32, device=device)

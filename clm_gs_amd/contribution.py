@@ -14,6 +14,7 @@ import torch
 
 from . import dp, utils
 from . import gsplat as G
+from .cameras import refuse_ortho
 
 PRUNE_MODES = ("sum", "max")
 SCORE_CHUNK = 8  # cameras per visibility pass (one host read each)
@@ -125,6 +126,8 @@ def score_cameras(gaussians, cameras):
     bilateral grid, masks and depth priors change no blend weight and are ignored.  `gaussians`: a model, or any object
     with _xyz, _opacity, _scaling, _rotation (stored parameters, device tensors)."""
     args = utils.get_args()
+    for c in cameras:  # the selection kernels are pinhole ones; refused before anything is enqueued
+        refuse_ortho(c, "contribution.score_cameras")
     _flush(gaussians)
     xyz, opa, sca, rot = (getattr(gaussians, a).detach() for a in ("_xyz", "_opacity", "_scaling", "_rotation"))
     if not xyz.is_cuda:

@@ -13,7 +13,8 @@ import torch
 
 from . import _lib, utils
 from ._lib import check, dptr
-from .cameras import camera_colour, camera_invdepth, camera_loss_mask, camera_pose_grad, camera_sky, check_sky_background
+from .cameras import (camera_colour, camera_invdepth, camera_loss_mask, camera_pose_grad, camera_sky, check_sky_background,
+                      refuse_ortho)
 from .clm_kernels import COLOUR, check_depth_prior_args, check_sky, masked_loss_value, sky_acc_add, sky_backward, sky_forward
 from .gsplat import _record_counts, bucket_size, empty_bucketed, isect_begin, isect_counts, isect_finish
 
@@ -34,7 +35,9 @@ _PART_FLOATS = None
 
 
 def _cam_host(camera):
-    """Host copies of viewmat (row-major world->camera), K and the camera centre, cached."""
+    """Host copies of viewmat (row-major world->camera), K and the camera centre, cached.  Every kernel that takes them
+    by value is a pinhole one: an orthographic camera is refused here, before anything is enqueued."""
+    refuse_ortho(camera, "the fused front end (fused.camera_front)")
     h = getattr(camera, "_clmgs_host", None)
     if h is None:
         vm = camera.world_view_transform.detach().t().contiguous().cpu().numpy().astype(np.float32)

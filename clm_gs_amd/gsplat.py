@@ -92,9 +92,70 @@ class _Projection(torch.autograd.Function):
         return v_means, v_quats, v_scales, v_viewmats, None, None, None, None, None, None, None, None
 
 
+CAMERA_MODELS = ("pinhole", "ortho")
+
+
+def _check_camera_model(camera_model):
+    if camera_model not in CAMERA_MODELS:
+        raise ValueError(f"camera_model must be one of {CAMERA_MODELS}, got {camera_model!r}")
+    return camera_model == "ortho"
+
+
+class _ProjectionOrtho(torch.autograd.Function):
+    """clmgs_projection_ortho_fwd / _bwd (gsplat's camera_model="ortho"): _Projection's arguments and results; the
+    compensations buffer and its cotangent are handed over only with calc_compensations.  The view matrices receive no
+    gradient (refused by fully_fused_projection before anything is launched)."""
+
+    @staticmethod
+    def forward(ctx, means, quats, scales, viewmats, Ks, width, height, eps2d, near_plane,
+                far_plane, radius_clip, calc_compensations):
+        L = _lib.lib()
+        means, quats, scales = means.contiguous(), quats.contiguous(), scales.contiguous()
+        viewmats, Ks = viewmats.contiguous(), Ks.contiguous()
+        C, N = viewmats.shape[0], means.shape[0]
+        dev = means.device
+        radii = torch.empty((C, N), dtype=I32, device=dev)
+        means2d = torch.empty((C, N, 2), dtype=F32, device=dev)
+        depths = torch.empty((C, N), dtype=F32, device=dev)
+        conics = torch.empty((C, N, 3), dtype=F32, device=dev)
+        comps = torch.empty((C, N), dtype=F32, device=dev) if calc_compensations else None
+        check(L.clmgs_projection_ortho_fwd(
+            stream(), C, N, dptr(means, F32), dptr(quats, F32), dptr(scales, F32),
+            dptr(viewmats, F32), dptr(Ks, F32), int(width), int(height), float(eps2d),
+            float(near_plane), float(far_plane), float(radius_clip), dptr(radii), dptr(means2d),
+            dptr(depths), dptr(conics), dptr(comps, F32, True)))
+        ctx.save_for_backward(means, quats, scales, viewmats, Ks, radii)
+        ctx.cfg = (int(width), int(height), float(eps2d))
+        ctx.mark_non_differentiable(radii)
+        return radii, means2d, depths, conics, comps
+
+    @staticmethod
+    def backward(ctx, _v_radii, v_means2d, v_depths, v_conics, v_comps):
+        L = _lib.lib()
+        means, quats, scales, viewmats, Ks, radii = ctx.saved_tensors
+        width, height, eps2d = ctx.cfg
+        C, N = radii.shape
+        dev = means.device
+        if v_means2d is None:
+            v_means2d = torch.zeros((C, N, 2), dtype=F32, device=dev)
+        if v_conics is None:
+            v_conics = torch.zeros((C, N, 3), dtype=F32, device=dev)
+        v_means2d, v_conics = v_means2d.contiguous(), v_conics.contiguous()
+        v_depths = v_depths.contiguous() if v_depths is not None else None
+        v_comps = v_comps.contiguous() if v_comps is not None else None
+        v_means = torch.empty_like(means)
+        v_quats = torch.empty_like(quats)
+        v_scales = torch.empty_like(scales)
+        check(L.clmgs_projection_ortho_bwd(
+            stream(), C, N, dptr(means), dptr(quats), dptr(scales), dptr(viewmats), dptr(Ks),
+            width, height, eps2d, dptr(radii), dptr(v_means2d, F32), dptr(v_depths, F32, True),
+            dptr(v_conics, F32), dptr(v_comps, F32, True), dptr(v_means), dptr(v_quats), dptr(v_scales)))
+        return v_means, v_quats, v_scales, None, None, None, None, None, None, None, None, None
+
+
 def fully_fused_projection(means, covars, quats, scales, viewmats, Ks, width, height, eps2d=0.3,
                            near_plane=0.01, far_plane=1e10, radius_clip=0.0, packed=False,
-                           sparse_grad=False, calc_compensations=False):
+                           sparse_grad=False, calc_compensations=False, camera_model="pinhole"):
     """EWA projection of N Gaussians into C cameras.
 
     Unpacked -> (radii[C,N] i32, means2d[C,N,2], depths[C,N], conics[C,N,3], compensations).
@@ -105,25 +166,36 @@ def fully_fused_projection(means, covars, quats, scales, viewmats, Ks, width, he
     otherwise nothing more is launched.
     compensations: None, or with calc_compensations=True (gsplat's; Mip-Splatting) the differentiable opacity
     factors sqrt(max(0, det(cov2d) / det(cov2d + eps2d I))), [C,N] with 0 where culled (packed: [nnz]).
+    camera_model: "pinhole", or "ortho" (gsplat's): Ks = [[sx,0,cx],[0,sy,cy],[0,0,1]] in pixels per world unit, the
+    orthographic kernels of csrc/ortho.hip; same forms and results.  An orthographic view matrix that asks for a
+    gradient raises NotImplementedError before anything is launched; any other string raises ValueError.
     """
+    ortho = _check_camera_model(camera_model)
     if covars is not None:
         raise NotImplementedError("the CLM-GS engines always pass covars=None")
+    if ortho and viewmats.requires_grad:
+        raise NotImplementedError('camera_model="ortho" carries no view-matrix gradient (viewmats.requires_grad)')
+    projection = _ProjectionOrtho if ortho else _Projection
     args = (means, quats, scales, viewmats, Ks, width, height, eps2d, near_plane, far_plane, radius_clip,
             bool(calc_compensations))
     if not packed:
-        return _Projection.apply(*args)
+        return projection.apply(*args)
     with torch.no_grad():
-        radii, *outs = _Projection.apply(*args)
+        radii, *outs = projection.apply(*args)
         camera_ids, gaussian_ids = torch.nonzero(radii > 0, as_tuple=True)
         return (camera_ids, gaussian_ids, radii[camera_ids, gaussian_ids],
                 *(t[camera_ids, gaussian_ids] if t is not None else None for t in outs))
 
 
 def visibility_radii(means, quats, scales, viewmats, Ks, width, height, eps2d=0.3,
-                     near_plane=0.01, far_plane=1e10, radius_clip=0.0, raw=False):
+                     near_plane=0.01, far_plane=1e10, radius_clip=0.0, raw=False, camera_model="pinhole"):
     """radii[C,N] only: the cull of fully_fused_projection without writing the 24 B of
     per-pair outputs (what calculate_filters, strategies/base_engine.py:18-76, needs).
-    raw=True: `quats` un-normalised and `scales` as logs (the stored parameters)."""
+    raw=True: `quats` un-normalised and `scales` as logs (the stored parameters).
+    camera_model="ortho": the cull-only form of clmgs_projection_ortho_fwd; not with raw (nothing calls it)."""
+    ortho = _check_camera_model(camera_model)
+    if ortho and raw:
+        raise NotImplementedError('visibility_radii(raw=True) has no camera_model="ortho" form')
     L = _lib.lib()
     means, quats, scales = means.contiguous(), quats.contiguous(), scales.contiguous()
     viewmats, Ks = viewmats.contiguous(), Ks.contiguous()
@@ -135,10 +207,11 @@ def visibility_radii(means, quats, scales, viewmats, Ks, width, height, eps2d=0.
             dptr(Ks, F32), int(width), int(height), float(eps2d), float(near_plane), float(far_plane),
             float(radius_clip), dptr(radii)))
         return radii
-    check(L.clmgs_projection_fwd(
+    fwd, extra = (L.clmgs_projection_ortho_fwd, (None,)) if ortho else (L.clmgs_projection_fwd, ())
+    check(fwd(
         stream(), C, N, dptr(means, F32), dptr(quats, F32), dptr(scales, F32), dptr(viewmats, F32),
         dptr(Ks, F32), int(width), int(height), float(eps2d), float(near_plane), float(far_plane),
-        float(radius_clip), dptr(radii), None, None, None))
+        float(radius_clip), dptr(radii), None, None, None, *extra))
     return radii
 
 

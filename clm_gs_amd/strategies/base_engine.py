@@ -5,7 +5,7 @@ import math
 import torch
 
 from .. import utils
-from ..cameras import camera_loss_mask, camera_sky, check_sky_background
+from ..cameras import camera_loss_mask, camera_model as camera_model_of, camera_sky, check_sky_background, refuse_ortho
 from ..clm_kernels import apply_camera_colour, apply_camera_sky, camera_depth_term, fused_l1_ssim_loss, fused_ssim
 from ..gsplat import (fully_fused_projection, isect_offset_encode, isect_tiles,
                       rasterize_to_pixels, spherical_harmonics, visibility_radii)
@@ -20,6 +20,8 @@ def select_filters(batched_cameras, xyz_gpu, scaling_raw_gpu, rotation_raw_gpu, 
     plus the union over the batch's cameras."""
     from ..gsplat import visibility_select
     args = utils.get_args()
+    for c in batched_cameras:  # the selection kernels are pinhole ones
+        refuse_ortho(c, "select_filters")
     with torch.no_grad():
         Ks = torch.stack([c.create_k_on_gpu() if getattr(c, "K", None) is None else c.K for c in batched_cameras])
         viewmats = torch.stack([c.world_view_transform.transpose(0, 1) for c in batched_cameras])
@@ -41,14 +43,21 @@ def calculate_filters(batched_cameras, xyz_gpu, opacity_gpu, scaling_gpu, rotati
     nonzero over the flat [C*N] mask (camera boundaries by binary search on the sorted result).
     Returns (filters, camera_ids, gaussian_ids); the id vectors only when return_ids.
     raw=True: scaling_gpu / rotation_gpu are the stored parameters (log-scales, un-normalised
-    quaternions) and the activations happen inside the cull kernel."""
+    quaternions) and the activations happen inside the cull kernel.
+    A call whose cameras are all orthographic (cameras.OrthoCamera) culls with the orthographic form; a mix of the two
+    kinds raises ValueError."""
     args = utils.get_args()
+    models = {camera_model_of(c) for c in batched_cameras}
+    if len(models) > 1:
+        raise ValueError(f"calculate_filters: one call mixes camera models {sorted(models)}; cull each kind on its own")
+    model = models.pop() if models else "pinhole"
     with torch.no_grad():
         Ks = torch.stack([c.create_k_on_gpu() if getattr(c, "K", None) is None else c.K for c in batched_cameras])
         viewmats = torch.stack([c.world_view_transform.transpose(0, 1) for c in batched_cameras])
         radii = visibility_radii(xyz_gpu, rotation_gpu, scaling_gpu, viewmats, Ks,
                                  int(utils.get_img_width()), int(utils.get_img_height()),
-                                 radius_clip=args.radius_clip, raw=raw)
+                                 radius_clip=args.radius_clip, raw=raw,
+                                 **({} if model == "pinhole" else {"camera_model": model}))
         C, N = radii.shape
         flat = torch.nonzero(radii.reshape(-1) > 0).flatten()  # sorted: camera-major, then gaussian
         edges = torch.searchsorted(flat, torch.arange(0, C + 1, device=flat.device) * N)
@@ -118,8 +127,15 @@ def split_depth(rendered, alphas, render_mode):
 def fov_camera(camera, device):
     """-> (viewmat[4,4], K[3,3], centre[1,1,3]) as the two FoV entries make them: K from the field of view as a device
     tensor, the centre by torch.inverse ON THE DEVICE.  (camera.K / camera.camtoworlds, which
-    pipeline_forward_one_step_shs_inplace reads, come from the host and can differ in the last bit.)"""
+    pipeline_forward_one_step_shs_inplace reads, come from the host and can differ in the last bit.)
+    An orthographic camera has no field of view: its own K, and its size must be the global image size."""
     image_width, image_height = int(utils.get_img_width()), int(utils.get_img_height())
+    if camera_model_of(camera) == "ortho":
+        if (camera.image_width, camera.image_height) != (image_width, image_height):
+            raise ValueError(f"orthographic camera {camera.image_name!r} is {camera.image_width}x{camera.image_height}, "
+                             f"the global image size is {image_width}x{image_height} (utils.set_img_size)")
+        viewmat = camera.world_view_transform.transpose(0, 1)
+        return viewmat, camera.K.to(device), torch.inverse(viewmat.unsqueeze(0))[:, None, :3, 3]
     fx = image_width / (2 * math.tan(camera.FoVx * 0.5))
     fy = image_height / (2 * math.tan(camera.FoVy * 0.5))
     K = torch.tensor([[fx, 0, image_width / 2.0], [0, fy, image_height / 2.0], [0, 0, 1]], device=device)
@@ -128,7 +144,8 @@ def fov_camera(camera, device):
 
 
 def camera_forward_ops(means, quats, scales, opacities, coeffs, sh_degree, viewmat, K, centre, backgrounds, render_mode,
-                       train, radius_clip=0.0, sh_masks=False, sh_autograd=True, tile_size=TILE_SIZE, sky_camera=None):
+                       train, radius_clip=0.0, sh_masks=False, sh_autograd=True, tile_size=TILE_SIZE, sky_camera=None,
+                       camera_model="pinhole"):
     """The op-by-op forward of one camera, which the three reference-named entries share: projection -> SH -> +0.5 clamp
     -> tile binning -> offsets -> (depth as fourth colour) -> rasterize.  Each entry hands in ITS K, camera centre,
     coefficient view ([1,V,16,3]) and backgrounds (None, [3] or [1,3]); the knobs are what else differs between them:
@@ -137,10 +154,20 @@ def camera_forward_ops(means, quats, scales, opacities, coeffs, sh_degree, viewm
     place), tile_size and sky_camera: the camera, handed in when it carries a sky (cameras.camera_sky) -- the rasterizer
     then runs with NO background (a non-zero one is refused) and the sky is composited behind its two outputs
     (clm_kernels.apply_camera_sky) before the image is returned; None: unchanged.
+    camera_model "ortho" (K in pixels per world unit): the orthographic projection, and ONE view direction for all rows,
+    the world-space optical axis viewmat[2,:3] -- a parallel projection has one direction, so the image does not depend
+    on how far up its axis the camera sits (gsplat keeps means - campos; DESIGN.md section 3, "Orthographic"); `centre`
+    is not read.  A sky is refused with it: the map lookup is a pinhole ray.
     -> (image[3,H,W] view, means2D[1,V,2], radii[1,V], () | (depth[1,H,W], alpha[1,H,W]) by split_depth,
         () | (colours leaf[1,V,3], dirs[1,V,3]) without sh_autograd)."""
+    if camera_model not in ("pinhole", "ortho"):
+        raise ValueError(f"camera_model must be 'pinhole' or 'ortho', got {camera_model!r}")
+    ortho = camera_model == "ortho"
     if sky_camera is not None and camera_sky(sky_camera) is None:
         sky_camera = None
+    if sky_camera is not None and ortho:
+        raise ValueError(f"camera {getattr(sky_camera, 'image_name', sky_camera)!r} is orthographic and carries a sky: "
+                         "the sky map is looked up along pinhole rays; render it without --sky")
     if sky_camera is not None:  # refused before anything is enqueued
         check_sky_background(backgrounds)
         backgrounds = None
@@ -148,10 +175,13 @@ def camera_forward_ops(means, quats, scales, opacities, coeffs, sh_degree, viewm
     radiis, means2D, depths, conics, compensations = fully_fused_projection(
         means=means, covars=None, quats=quats, scales=scales, viewmats=viewmat.unsqueeze(0), Ks=K.unsqueeze(0),
         width=image_width, height=image_height, radius_clip=radius_clip, packed=False,
-        calc_compensations=utils.antialiased())
+        calc_compensations=utils.antialiased(), **({"camera_model": camera_model} if ortho else {}))
     if train:
         means2D.retain_grad()
-    dirs = means[None, :, :] - centre
+    if ortho:
+        dirs = viewmat[2, :3].reshape(1, 1, 3).expand(1, means.shape[0], 3)
+    else:
+        dirs = means[None, :, :] - centre
     sh_leaf = ()
     with torch.set_grad_enabled(sh_autograd and torch.is_grad_enabled()):
         colors = spherical_harmonics(degrees_to_use=sh_degree, dirs=dirs, coeffs=coeffs,
@@ -194,7 +224,8 @@ def pipeline_forward_one_step(filtered_opacity_gpu, filtered_scaling_gpu, filter
     image, means2D, radiis, depth_alpha, _ = camera_forward_ops(
         filtered_xyz_gpu, filtered_rotation_gpu, filtered_scaling_gpu, filtered_opacity_gpu,
         filtered_shs.reshape(1, filtered_xyz_gpu.shape[0], 16, 3), gaussians.active_sh_degree, viewmat, K, centre,
-        background.reshape(1, 3) if background is not None else None, render_mode, train=not eval, sky_camera=camera)
+        background.reshape(1, 3) if background is not None else None, render_mode, train=not eval, sky_camera=camera,
+        camera_model=camera_model_of(camera))
     return (image, means2D, radiis) + depth_alpha[:2 if return_alpha else 1]
 
 

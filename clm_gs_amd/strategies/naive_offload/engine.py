@@ -7,6 +7,7 @@ Same call signatures and return values as the reference."""
 import torch
 
 from ... import utils
+from ...cameras import refuse_ortho
 from ...clm_kernels import apply_camera_colour, check_depth_prior_args
 from ...fused import train_one_camera
 from ..base_engine import calculate_filters, pipeline_forward_one_step
@@ -38,6 +39,7 @@ def naive_offload_train_one_batch(gaussians, scene, batched_cameras, background,
     args = utils.get_args()
     bsz = len(batched_cameras)
     for camera in batched_cameras:  # absgrad with a depth prior: refused for the whole batch, before any camera runs
+        refuse_ortho(camera, "naive_offload_train_one_batch")
         check_depth_prior_args(camera)
     rep = _DeviceReplica(gaussians)
     with torch.no_grad():

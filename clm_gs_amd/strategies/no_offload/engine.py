@@ -4,6 +4,7 @@ activations."""
 import torch
 
 from ... import utils
+from ...cameras import camera_model
 from ...clm_kernels import check_depth_prior_args
 from ...densification import update_densification_stats_baseline_accum_grads
 from ..base_engine import camera_forward_ops, camera_loss_backward, fov_camera
@@ -20,7 +21,7 @@ def baseline_accumGrads_micro_step(means3D, opacities, scales, rotations, shs, s
     image, means2D, radiis, depth_alpha, _ = camera_forward_ops(
         means3D, rotations, scales, opacities, shs.unsqueeze(0), sh_degree, viewmat, K, centre, background, render_mode,
         train=mode == "train", radius_clip=utils.get_args().radius_clip, sh_masks=True, tile_size=tile_size,
-        sky_camera=camera)
+        sky_camera=camera, camera_model=camera_model(camera))
     return (image, means2D, radiis, None) + depth_alpha[:2 if return_alpha else 1]
 
 

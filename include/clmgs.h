@@ -97,6 +97,26 @@ int clmgs_projection_aa_bwd(void* stream, int C, int N, const float* means, cons
                             const float* v_depths, const float* v_conics, const float* v_compensations,
                             float* v_means, float* v_quats, float* v_scales);
 
+/* ---- gsplat.fully_fused_projection(camera_model="ortho") and rasterization(camera_model="ortho"): the orthographic
+ * projection.  Ks[c] = [[sx,0,cx],[0,sy,cy],[0,0,1]] with sx, sy in pixels per world unit; with p = R m + t,
+ * means2d = (sx p.x + cx, sy p.y + cy), depths = p.z, cov2d = J Sc J^T + eps2d I with the constant
+ * J = [[sx,0,0],[0,sy,0]] (no perspective divide, no frustum clamp); near / far plane, radius, radius_clip, the
+ * off-screen tests and the conic are clmgs_projection_fwd's.  The arguments are clmgs_projection_aa_fwd's; means2d,
+ * depths, conics and compensations are each optional (all NULL: the cull alone, radii only -- visibility_radii).
+ * Culled pairs: radius 0 and zero floats.  N == 0 returns 0 before any pointer check. */
+int clmgs_projection_ortho_fwd(void* stream, int C, int N, const float* means, const float* quats,
+                               const float* scales, const float* viewmats, const float* Ks, int width,
+                               int height, float eps2d, float near_plane, float far_plane,
+                               float radius_clip, int32_t* radii, float* means2d, float* depths,
+                               float* conics, float* compensations);
+/* Its VJP: the arguments of clmgs_projection_aa_bwd; v_depths and v_compensations optional (NULL = zeros), the
+ * compensation's cotangent in gsplat's guarded form.  No view-matrix gradient exists for this model. */
+int clmgs_projection_ortho_bwd(void* stream, int C, int N, const float* means, const float* quats,
+                               const float* scales, const float* viewmats, const float* Ks, int width,
+                               int height, float eps2d, const int32_t* radii, const float* v_means2d,
+                               const float* v_depths, const float* v_conics, const float* v_compensations,
+                               float* v_means, float* v_quats, float* v_scales);
+
 /* ---- gsplat.spherical_harmonics  (base_engine.py:161-163; no_offload/engine.py:67-69;
  *      clm_offload/engine.py:73-76)
  * dirs[n,3] (un-normalised), coeffs[n,16,3], masks[n] u8 or NULL -> colors[n,3]. */
