@@ -12,6 +12,8 @@ A camera takes part by carrying views of its rows (colour_model.ColourModel.atta
 Optimizer: a dense torch.optim.Adam with eps 1e-15 (gsplat's).  The learning rate comes from this project's
 utils.get_expon_lr_func(lr_init, lr_final, lr_delay_steps=1000, lr_delay_mult=0.01) -- a log-linear decay with a sine
 warm-up, NOT gsplat's exact chain of a linear warm-up and an exponential decay -- and is not scaled by sqrt(batch size)."""
+import os
+
 import numpy as np
 import torch
 
@@ -33,6 +35,7 @@ def tv_value(table):
 
 class BilagridModel(ColourModel):
     KIND = "bilagrid"
+    FILE = "bilagrid.npz"  # grids in gsplat's [n,12,L,Hg,Wg] layout + image names
 
     def __init__(self, n_cameras, device, grid=(16, 16, 8), lr_init=2e-3, lr_final=2e-5, max_steps=30000, tv_weight=10.0):
         Wg, Hg, L = (int(v) for v in grid)  # gsplat's order: grid_X, grid_Y, grid_W (the guidance axis)
@@ -74,6 +77,9 @@ class BilagridModel(ColourModel):
         grids = self.param.detach().cpu().permute(0, 4, 1, 2, 3).contiguous().numpy()
         with open(path, "wb") as f:  # a file object: numpy appends no suffix
             np.savez(f, grids=grids, image_names=np.array([str(c.image_name) for c in cameras]))
+
+    def save_to(self, model_dir, cameras):
+        self.save(os.path.join(model_dir, self.FILE), cameras)
 
     def load(self, path, cameras):
         """Grids of the cameras named in the file; a camera the file does not name keeps its grid."""

@@ -41,3 +41,11 @@ class ColourModel:
 
     def zero_grad(self):
         self.grad.zero_()
+
+    # ---- the trainer's calls on every side model, pose.PoseModel too; save_to(model_dir, cameras) writes the subclass's FILE
+    def end_batch(self, iteration, batch_cameras):
+        self.step(iteration)
+        self.zero_grad()
+
+    def flush(self):
+        """Nothing is deferred: a step is enqueued when it is asked for."""

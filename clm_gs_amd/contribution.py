@@ -95,7 +95,7 @@ def check_contrib_prune_args(args):
     if bool(getattr(args, "naive_offload", False)):
         why = "naive_offload: its model keeps the parameters in pinned host tables, the scoring pass reads them in HBM"
     elif dp.world_size() > 1:
-        why = "camera-DP (world_size {}): the scores and the row surgery are not replicated across ranks".format(dp.world_size())
+        why = dp.refusal(dp.world_size(), "the scores and the row surgery are not replicated")
     elif bool(getattr(args, "mcmc", False)):
         why = "mcmc: a fixed Gaussian budget relocates dead rows instead of pruning"
     if why:

@@ -56,7 +56,7 @@ def check_mcmc_args(args):
     elif bool(getattr(args, "naive_offload", False)):
         why = "naive_offload: its model keeps the parameters in pinned host tables"
     elif dp.world_size() > 1:
-        why = "camera-DP (world_size {}): sampling, noise and row surgery are not replicated across ranks".format(dp.world_size())
+        why = dp.refusal(dp.world_size(), "sampling, noise and row surgery are not replicated")
     elif bool(getattr(args, "sparse_adam", False)):
         why = "sparse_adam: the noise and the regularisers step every row, a visibility-masked optimizer does not"
     elif bool(getattr(args, "stop_update_param", False)):

@@ -135,6 +135,11 @@ def world_size():
     return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
 
 
+def refusal(world_size, what_is_not_shared):
+    """The clause every refusal under camera-DP carries: what each rank would keep to itself."""
+    return "camera-DP (world_size {}): {} across ranks".format(world_size, what_is_not_shared)
+
+
 def active():
     """True when the engines must run the exchange: more than one rank, or CLMGS_DP_FORCE=1 with an
     initialised process group (a 1-rank group runs every collective as the identity -- this is how the

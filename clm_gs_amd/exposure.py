@@ -9,6 +9,7 @@ csrc/exposure.hip, reached through fused.camera_forward_finish (the engines) and
 op-by-op path, evaluation), both through the one description clm_kernels.COLOUR["exposure"].  A camera takes part by
 carrying views of its rows (colour_model.ColourModel.attach); cameras.camera_colour reads them."""
 import json
+import os
 
 import torch
 
@@ -18,6 +19,7 @@ from .colour_model import ColourModel
 
 class ExposureModel(ColourModel):
     KIND = "exposure"
+    FILE = "exposure.json"  # {image_name: 3x4}, the INRIA code base's exposure.json
 
     def __init__(self, n_cameras, device, lr_init=0.01, lr_final=0.001, lr_delay_steps=0, lr_delay_mult=0.0,
                  max_steps=30000):
@@ -34,6 +36,9 @@ class ExposureModel(ColourModel):
         rows = self.param.detach().cpu().tolist()
         with open(path, "w") as f:
             json.dump({c.image_name: rows[i] for i, c in enumerate(cameras)}, f, indent=2)
+
+    def save_to(self, model_dir, cameras):
+        self.save_json(os.path.join(model_dir, self.FILE), cameras)
 
     def load_json(self, path, cameras):
         """Rows of the cameras named in the file; a camera the file does not name keeps its row."""

@@ -19,6 +19,7 @@ tail of its earlier gradients.  `defer_pose_step=False` applies the step immedia
 batch): the sequential semantics."""
 import json
 import math
+import os
 
 import numpy as np
 import torch
@@ -64,7 +65,7 @@ def check_pose_args(args, depth_priors=False, enabled=None):
     elif float(getattr(args, "sh_hbm_budget_gb", 0.0) or 0.0) > 0.0:
         why = "sh_hbm_budget_gb > 0: the HBM-resident prefix belongs to the host-resident mode"
     elif dp.world_size() > 1:
-        why = "camera-DP (world_size {}): the pose table is not reduced across ranks".format(dp.world_size())
+        why = dp.refusal(dp.world_size(), "the pose table is not reduced")
     elif depth_priors or bool(getattr(args, "depths", "")):
         why = "--depths / depth render modes: the fourth channel's cotangent reaches the positions outside the " \
               "projection VJP, and the camera gradient would miss it"
@@ -74,6 +75,7 @@ def check_pose_args(args, depth_priors=False, enabled=None):
 
 class PoseModel:
     """gsplat's CameraOptModule + its Adam, on the host in float64."""
+    FILE = "poses.json"  # {image_name: {"delta": [9], "world_to_camera": 4x4}}
 
     def __init__(self, n_cameras, lr=1e-5, reg=1e-6, max_steps=30000, defer=True, device="cuda", lr_final_factor=0.01,
                  betas=(0.9, 0.999), eps=1e-8):
@@ -204,6 +206,9 @@ class PoseModel:
         if prev is not None:
             self._apply_item(prev)
 
+    def end_batch(self, iteration, batch_cameras):
+        self.step(batch_cameras)
+
     def flush(self):
         if self._pending is not None:
             item, self._pending = self._pending, None
@@ -246,6 +251,9 @@ class PoseModel:
         with open(path, "w") as f:
             json.dump({c.image_name: {"delta": self.table[i].tolist(), "world_to_camera": w2c[i].tolist()}
                        for i, c in enumerate(cameras)}, f, indent=2)
+
+    def save_to(self, model_dir, cameras):
+        self.save_json(os.path.join(model_dir, self.FILE), cameras)
 
     def load_json(self, path, cameras):
         """Rows of the cameras named in the file (a camera the file does not name keeps its row), then refresh()."""

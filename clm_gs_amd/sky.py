@@ -27,6 +27,7 @@ FILE = "sky.npz"
 
 class SkyModel(ColourModel):
     KIND = "sky"
+    FILE = FILE  # the map, its shape and the convention string
 
     def __init__(self, shape=(256, 512), device="cuda", init=(0.5, 0.5, 0.5), lr_init=0.01, lr_final=0.001,
                  max_steps=30000):
@@ -71,6 +72,9 @@ class SkyModel(ColourModel):
         np.savez(path, sky=self.param.detach().cpu().numpy(), shape=np.asarray(self.shape, dtype=np.int64),
                  convention=np.asarray(CONVENTION))
         return path
+
+    def save_to(self, model_dir, cameras):
+        self.save(model_dir)
 
     def load(self, model_dir):
         path = os.path.join(model_dir, FILE)

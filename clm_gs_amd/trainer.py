@@ -13,15 +13,19 @@ import gc
 import os
 import random
 import time
+from collections import namedtuple
 
 import torch
 
 from . import dp, mcmc, utils
+from .bilagrid import BilagridModel
 from .cameras import camera_loss_mask
 from .clm_kernels import apply_camera_colour
 from .contribution import check_contrib_prune_args, contribution_prune, prune_iterations
 from .densification import check_mcmc_args, gsplat_densification, mcmc_refinement
-from .pose import check_pose_args
+from .exposure import ExposureModel
+from .pose import PoseModel, check_pose_args
+from .sky import SkyModel
 
 
 class End2endTimer:
@@ -205,14 +209,6 @@ def _warm_structural_ops(device, n=70_000):
     torch.cuda.synchronize()
 
 
-def check_depth_flags(args, depth_priors):
-    """Depth regularisation with absgrad is refused (absgrad blends three channels only, the inverse depth is a fourth):
-    `depth_priors` = a depth directory was asked for, or a training camera carries a prior."""
-    if depth_priors and bool(getattr(args, "absgrad", False)):
-        raise ValueError("--absgrad together with --depths is not supported: absgrad blends three channels only, the depth "
-                         "regularisation renders the inverse depth as a fourth; drop one of the two")
-
-
 def no_offload_optimizer_step(gaussians, args, bsz, visibility=None):
     """The no_offload optimizer epilogue of a batch (train.py:533-578): gradients / bsz, step, zero_grad.  In MCMC mode
     the two regulariser gradients are added before the step and the position noise is injected after it."""
@@ -236,74 +232,36 @@ def build_exposure(train_cameras, iterations, device="cuda", lr_init=0.01, lr_fi
     """`--exposure`: an exposure.ExposureModel with one row per TRAINING camera, attached to the cameras (test cameras and
     novel views carry no exposure and are rendered as the model is).  Refused under camera-DP: every rank would step its
     own copy of the table; the all-reduce of the table's gradient is a later change."""
-    if dp.world_size() > 1:
-        raise ValueError("--exposure is not supported with camera-DP (world_size {}): the exposure table is not reduced "
-                         "across ranks; train on one GPU or without --exposure".format(dp.world_size()))
-    from .exposure import ExposureModel
+    _refuse([camera_dp_rule("exposure")])
     model = ExposureModel(len(train_cameras), device, lr_init=lr_init, lr_final=lr_final, max_steps=int(iterations))
     model.attach(train_cameras)
-    return model
-
-
-def refuse_bilagrid_under_camera_dp():
-    """The one camera-DP refusal of the bilateral grid: every rank would step its own copy of the table."""
-    if dp.world_size() > 1:
-        raise ValueError("--bilagrid is not supported with camera-DP (world_size {}): the grid table is not reduced "
-                         "across ranks; train on one GPU or without --bilagrid".format(dp.world_size()))
-
-
-def check_appearance_flags(args):
-    """The refusals of the two appearance modes, by name, before anything is loaded."""
-    if getattr(args, "exposure", False) and getattr(args, "bilagrid", False):
-        raise ValueError("--exposure and --bilagrid together are refused: the order in which the exposure transform and "
-                         "the bilateral grid compose is not defined; choose one")
-    if getattr(args, "bilagrid", False):
-        refuse_bilagrid_under_camera_dp()
-
-
-def check_sky_flags(args):
-    """The refusals of `--sky`, by name, before anything is loaded."""
-    if not getattr(args, "sky", False):
-        return
-    if getattr(args, "white_background", False):
-        raise ValueError("--sky and --white_background together are refused: the sky map is the background")
-    if getattr(args, "pose_opt", False):
-        raise ValueError("--sky and --pose_opt together are refused: the sky's gradient with respect to the camera (the "
-                         "ray direction of the lookup) is not carried")
-    if dp.world_size() > 1:
-        raise ValueError("--sky is not supported with camera-DP (world_size {}): the map's gradient accumulator is not "
-                         "reduced across ranks; train on one GPU or without --sky".format(dp.world_size()))
-
-
-def build_sky(train_cameras, other_cameras, iterations, device="cuda", shape=(256, 512), init=(0.5, 0.5, 0.5),
-              lr_init=0.01, lr_final=0.001):
-    """`--sky`: a sky.SkyModel, one map for the scene.  The training cameras train it; every other camera (test cameras,
-    novel views) is rendered in front of it.  Refused under camera-DP (check_sky_flags)."""
-    if dp.world_size() > 1:
-        raise ValueError("--sky is not supported with camera-DP (world_size {}): the map's gradient accumulator is not "
-                         "reduced across ranks; train on one GPU or without --sky".format(dp.world_size()))
-    from .sky import SkyModel
-    model = SkyModel(tuple(shape), device, init=tuple(init), lr_init=lr_init, lr_final=lr_final, max_steps=int(iterations))
-    model.attach(train_cameras, train=True)
-    model.attach(other_cameras, train=False)
     return model
 
 
 def build_bilagrid(train_cameras, iterations, device="cuda", grid=(16, 16, 8), lr_init=2e-3, lr_final=2e-5, tv_weight=10.0):
     """`--bilagrid`: a bilagrid.BilagridModel with one grid per TRAINING camera, attached to the cameras (test cameras and
     novel views carry none and are rendered as the model is).  Refused under camera-DP, for the reason of build_exposure."""
-    refuse_bilagrid_under_camera_dp()
-    from .bilagrid import BilagridModel
+    _refuse([camera_dp_rule("bilagrid")])
     model = BilagridModel(len(train_cameras), device, grid=tuple(grid), lr_init=lr_init, lr_final=lr_final,
                           max_steps=int(iterations), tv_weight=tv_weight)
     model.attach(train_cameras)
     return model
 
 
+def build_sky(train_cameras, other_cameras, iterations, device="cuda", shape=(256, 512), init=(0.5, 0.5, 0.5),
+              lr_init=0.01, lr_final=0.001):
+    """`--sky`: a sky.SkyModel, one map for the scene.  The training cameras train it; every other camera (test cameras,
+    novel views) is rendered in front of it.  Refused under camera-DP, for the reason of build_exposure."""
+    _refuse([camera_dp_rule("sky")])
+    model = SkyModel(tuple(shape), device, init=tuple(init), lr_init=lr_init, lr_final=lr_final, max_steps=int(iterations))
+    model.attach(train_cameras, train=True)
+    model.attach(other_cameras, train=False)
+    return model
+
+
 def build_pose(train_cameras, iterations, device="cuda", lr=1e-5, reg=1e-6, noise=0.0, defer=True, seed=0):
     """`--pose_opt`: a pose.PoseModel with one row per TRAINING camera, attached to the cameras (test cameras carry no
     buffer and are evaluated as loaded).  `noise` > 0: gsplat's pose_noise, a seeded perturbation of the training poses."""
-    from .pose import PoseModel
     model = PoseModel(len(train_cameras), lr=lr, reg=reg, max_steps=int(iterations), defer=defer, device=device)
     model.attach(train_cameras)
     if noise:
@@ -311,188 +269,254 @@ def build_pose(train_cameras, iterations, device="cuda", lr=1e-5, reg=1e-6, nois
     return model
 
 
-def training(gaussians, scene, train_cameras, test_cameras, log_file, iterations=None,
-             test_iterations=(), background=None, shuffle_seed=0, phase_times=None, exposure=None, bilagrid=None,
-             pose=None, sky=None):
-    """Runs `iterations` images of training; returns the End2endTimer.
-    `sky` (optional sky.SkyModel, attached to the cameras): stepped and zeroed next to the exposure step, under the same
-    stream-order reasoning; its step converts the batch's fixed-point sums once.  Refused under camera-DP.
-    `exposure` (optional exposure.ExposureModel, attached to the training cameras): stepped at the scheduled learning
-    rate and zeroed after every batch, on the current stream -- every engine has joined its camera streams into it by
-    the time it returns.  A row's gradient is its camera's alone and is not divided by the batch size.
-    `bilagrid` (optional bilagrid.BilagridModel): likewise, next to the exposure step; its step adds the gradient of the
-    total-variation term before Adam.
-    `pose` (optional pose.PoseModel, attached to the training cameras): stepped next to the exposure step with the
-    gradients of the batch's cameras; deferred by one batch unless the model was built with defer=False (pose.py).
-    Training cameras are evaluated at their refined pose, test cameras as loaded.
-    `phase_times` (optional dict): host wall time per phase inside the end-to-end clock is accumulated into it
-    ("engine" = enqueueing the batches, "densify" = gsplat_densification incl. the device work it waits for,
-    "resort" = the Z-order re-sort after a densification, "log" = waiting for loss values, "final_sync"); a callable under
-    "iter_hook" is removed from the dict and called with the image counter after every iteration (diagnosis).
+# The side models of a run, in the order a batch steps them; each has end_batch(iteration, batch_cameras), flush() and
+# save_to(model_dir, cameras).  `name`: the keyword of training() and the attribute of the scene; `flag`: its entry of
+# utils.default_args; `file`: what save_to() writes; `not_shared`: why camera-DP refuses it (None: pose.check_pose_args).
+SideModel = namedtuple("SideModel", "name flag build file not_shared")
+SIDE_MODELS = (
+    SideModel("exposure", "exposure", lambda a, train, other: build_exposure(
+        train, a.iterations, "cuda", float(a.exposure_lr_init), float(a.exposure_lr_final)),
+        ExposureModel.FILE, "the exposure table is not reduced"),
+    SideModel("bilagrid", "bilagrid", lambda a, train, other: build_bilagrid(
+        train, a.iterations, "cuda", tuple(a.bilagrid_shape), float(a.bilagrid_lr_init), float(a.bilagrid_lr_final),
+        float(a.bilagrid_tv_weight)), BilagridModel.FILE, "the grid table is not reduced"),
+    SideModel("sky", "sky", lambda a, train, other: build_sky(
+        train, other, a.iterations, "cuda", tuple(a.sky_shape), tuple(a.sky_init), float(a.sky_lr_init),
+        float(a.sky_lr_final)), SkyModel.FILE, "the map's gradient accumulator is not reduced"),
+    SideModel("pose", "pose_opt", lambda a, train, other: build_pose(
+        train, a.iterations, "cuda", float(a.pose_opt_lr), float(a.pose_opt_reg), float(a.pose_noise),
+        bool(a.defer_pose_step)), PoseModel.FILE, None),
+)
 
-    Camera-DP: when a process group is up every rank runs this same loop over the
-    same shuffled order, takes cameras rank::ranks of each GLOBAL batch (bsz x ranks images), and
-    the image counter strides by the global batch; the engine does the one exchange per batch,
-    densification reduces its statistics (densification.py) and draws identical split samples."""
-    args = utils.get_args()
-    bsz = args.bsz
-    ws, rk = dp.world_size(), dp.rank()
-    gbsz = bsz * ws
-    if ws > 1 and exposure is not None:
-        raise ValueError("an exposure model cannot be trained under camera-DP (see build_exposure)")
-    if bilagrid is not None:
-        refuse_bilagrid_under_camera_dp()
-    if ws > 1 and sky is not None:
-        raise ValueError("a sky model cannot be trained under camera-DP (see build_sky)")
-    if ws > 1:
-        assert clm_hbm_only(args), "camera-DP trains clm_offload with sh_residency='hbm'"
-        if getattr(gaussians, "split_generator", None) is None:
-            dp.seed_split_generator(gaussians)
-    iterations = iterations or args.iterations
-    utils.set_log_file(log_file)
-    clm = bool(getattr(args, "clm_offload", False))
-    naive = bool(getattr(args, "naive_offload", False))
-    if naive:
-        from .strategies.naive_offload import naive_offload_eval_one_cam, naive_offload_train_one_batch
-        render_fn = lambda cam: naive_offload_eval_one_cam(gaussians, scene, cam, background)
-    elif clm:
+
+def camera_dp_rule(flag, on=True):
+    """The (condition, message) rule of a side model whose table every rank would step on its own."""
+    ws = dp.world_size()
+    what = next(r.not_shared for r in SIDE_MODELS if r.flag == flag)
+    return on and ws > 1, "--{0} is not supported with {1}; train on one GPU or without --{0}".format(
+        flag, dp.refusal(ws, what))
+
+
+def _refuse(rules):
+    for refused, message in rules:
+        if refused:
+            raise ValueError(message)
+
+
+def check_training(args, depth_priors=False, models=None):
+    """Every refusal of a run, in one fixed order; train_from_colmap calls it before anything is loaded, training() at its
+    top.  `depth_priors`: a depth directory was asked for, or a training camera carries a prior.  `models`
+    ({SideModel.name: model}): a model handed in counts as its flag being set.  The trainer's own rules first, then the
+    owners of pose refinement, MCMC and contribution pruning."""
+    given = {r.flag for r in SIDE_MODELS if (models or {}).get(r.name) is not None}
+    on = lambda flag: flag in given or bool(getattr(args, flag, False))
+    _refuse([
+        (depth_priors and on("absgrad"), "--absgrad together with --depths is not supported: absgrad blends three channels "
+         "only, the depth regularisation renders the inverse depth as a fourth; drop one of the two"),
+        (on("exposure") and on("bilagrid"), "--exposure and --bilagrid together are refused: the order in which the "
+         "exposure transform and the bilateral grid compose is not defined; choose one"),
+        (on("sky") and on("white_background"),
+         "--sky and --white_background together are refused: the sky map is the background"),
+        (on("sky") and on("pose_opt"), "--sky and --pose_opt together are refused: the sky's gradient with respect to the "
+         "camera (the ray direction of the lookup) is not carried"),
+    ] + [camera_dp_rule(r.flag, on(r.flag)) for r in SIDE_MODELS if r.not_shared])
+    check_pose_args(args, depth_priors, enabled=on("pose_opt"))
+    check_mcmc_args(args)
+    check_contrib_prune_args(args)
+
+
+class _BatchSource:
+    """The shuffled camera order of a run (training()'s docstring), one batch ahead of the engine: the host-resident engine
+    stages the next batch's untouched rows early.  With `locality` (camera-DP, locality exchange, dp.py) a rank draws from
+    the cameras that look mostly at the rows it owns (index ranges of the Z-ordered tables = spatial regions)."""
+
+    def __init__(self, train_cameras, gaussians, bsz, shuffle_seed, locality, log_file):
+        self.cameras, self.gaussians, self.bsz, self.locality, self.log_file = train_cameras, gaussians, bsz, locality, log_file
+        self.ws, self.rk, self.rng = dp.world_size(), dp.rank(), random.Random(shuffle_seed)
+        self.order, self.pool, self.dealt_at, self.ahead = [], None, 0, None
+        if locality:
+            self.deal()
+
+    def deal(self):
+        ranks_of, _ = dp.deal_cameras(self.cameras, self.gaussians, self.ws)
+        self.dealt_at, self.order = self.gaussians.get_xyz.shape[0], []
+        # every rank computes the same deal, so every rank sees the same smallest pool -- no collective needed to agree.
+        # A rank with fewer than bsz cameras could not draw a batch while the others are already inside the batch's
+        # collectives (hang): then ALL ranks fall back to the strided deal of the global shuffled order (the locality
+        # exchange is correct for any camera assignment, it just moves more border rows).
+        smallest = min(sum(1 for q in ranks_of if q == r_) for r_ in range(self.ws))
+        if smallest < self.bsz:
+            self.pool = None
+            self.log_file.write("camera-DP locality deal: smallest pool {} < bsz {} ({} cameras / {} ranks): strided deal\n".format(
+                smallest, self.bsz, len(self.cameras), self.ws))
+        else:
+            self.pool = [i for i, q in enumerate(ranks_of) if q == self.rk]
+
+    def draw(self):
+        if self.locality and self.pool is not None:
+            if len(self.order) < self.bsz:  # new epoch of THIS rank's pool
+                self.order = list(self.pool)
+                self.rng.shuffle(self.order)
+            return [self.cameras[self.order.pop()] for _ in range(self.bsz)]
+        gbsz = self.bsz * self.ws
+        if len(self.order) < gbsz:  # new epoch: shuffle, drop_last (train.py:156-167)
+            self.order = list(range(len(self.cameras)))
+            self.rng.shuffle(self.order)
+        return [self.cameras[self.order.pop()] for _ in range(gbsz)][self.rk::self.ws]
+
+    def next(self, more):
+        """-> (this batch, the batch after it or None when `more` is false)."""
+        batch = self.ahead if self.ahead is not None else self.draw()
+        self.ahead = self.draw() if more else None
+        return batch, self.ahead
+
+    def resorted(self):
+        """After a re-sort of a model that changed size: a new deal once it is 10 % away from the last one."""
+        if self.locality and abs(self.gaussians.get_xyz.shape[0] - self.dealt_at) > 0.1 * self.dealt_at:
+            self.deal()
+            self.ahead = None  # drawn from the old pool
+
+
+def _strategy(args, gaussians, scene, background):
+    """-> (run_batch, render_fn) of the engine the args name.  run_batch(batch) -> (losses, image names in the order of the
+    losses, sparsity or None, visibility or None); render_fn(camera) -> the evaluation image."""
+    if bool(getattr(args, "clm_offload", False)) and not bool(getattr(args, "naive_offload", False)):
         from .strategies.clm_offload import clm_offload_eval_one_cam, clm_offload_train_one_batch
         comm_stream = torch.cuda.Stream()
         perm_generator = torch.Generator(device="cuda")
         perm_generator.manual_seed(1)
-        render_fn = lambda cam: clm_offload_eval_one_cam(cam, gaussians, background, scene)
+
+        def run_batch(batch):
+            losses, ordered_cams, sparsity = clm_offload_train_one_batch(
+                gaussians, scene, batch, gaussians.parameters_grad_buffer, background, None, comm_stream,
+                perm_generator)
+            return losses, [batch[i].image_name for i in ordered_cams], sparsity, None
+        return run_batch, lambda cam: clm_offload_eval_one_cam(cam, gaussians, background, scene)
+    if bool(getattr(args, "naive_offload", False)):
+        from .strategies.naive_offload import naive_offload_eval_one_cam, naive_offload_train_one_batch as one_batch
+        render_fn = lambda cam: naive_offload_eval_one_cam(gaussians, scene, cam, background)
     else:
-        from .strategies.no_offload import baseline_accumGrads_impl, baseline_accumGrads_micro_step
+        from .strategies.no_offload import baseline_accumGrads_impl as one_batch, baseline_accumGrads_micro_step
 
         def render_fn(cam):
             img, _, _, _ = baseline_accumGrads_micro_step(
                 gaussians.get_xyz, gaussians.get_opacity, gaussians.get_scaling, gaussians.get_rotation,
                 gaussians.get_features, gaussians.active_sh_degree, cam, background, mode="test")
             return apply_camera_colour(img, cam)  # a training camera is rendered as it was trained
+
+    def run_batch(batch):
+        losses, visibility = one_batch(gaussians, scene, batch, background, sparse_adam=args.sparse_adam)
+        return losses, [c.image_name for c in batch], None, visibility
+    return run_batch, render_fn
+
+
+def _acc(pt, key, t_start):
+    pt[key] = pt.get(key, 0.0) + time.perf_counter() - t_start
+
+
+def _setup_before_clock(args, gaussians, pt):
+    """What a run pays once, before the end-to-end clock starts (utils/timer.py:87-111 starts it at the first iteration);
+    the wall times go into `pt` as phases "reserve" and "warm_ops"."""
+    # a full cyclic GC pass over torch's ~10^6 long-lived objects stalls the enqueueing thread for
+    # ~100 ms: freeze what exists now, later collections only see what the loop allocates
+    gc.collect()
+    gc.freeze()
+    if clm_hbm_only(args) and getattr(args, "allocator_reservoir", True) and getattr(args, "fused_front_end", True):
+        # allocator warm-up: one block per stream pool instead of dozens of hipMalloc calls spread over the first batches
+        # and every densification (strategies/clm_offload/engine.py reserve_working_set).  SETUP, like the reference's
+        # --prealloc_capacity buffers (train.py:107-115).  (Fresh device memory costs ~0.1 s per GB on some boxes and
+        # nothing on others -- measured 0.002 .. 1.3 s for the same 10 GB.)
+        from .strategies.clm_offload.engine import reserve_working_set
+        _t = time.perf_counter()
+        pt["reserved_bytes"] = float(sum(reserve_working_set(gaussians).values()))
+        torch.cuda.synchronize()
+        _acc(pt, "reserve", _t)
+        if not args.disable_auto_densification and getattr(args, "warm_structural_ops", True):
+            _t = time.perf_counter()
+            _warm_structural_ops(gaussians._xyz.device)
+            _acc(pt, "warm_ops", _t)
+    if torch.cuda.is_available():  # (diagnosis: how many hipMallocs happen INSIDE the end-to-end clock -- bench.py reports it)
+        pt["device_mallocs_before_clock"] = float(torch.cuda.memory_stats().get("num_device_alloc", 0))
+
+
+def training(gaussians, scene, train_cameras, test_cameras, log_file, iterations=None,
+             test_iterations=(), background=None, shuffle_seed=0, phase_times=None, **side_models):
+    """Runs `iterations` images of training; returns the End2endTimer.
+    `side_models`: exposure=, bilagrid=, sky=, pose= (the names of SIDE_MODELS; each optional, attached to its cameras by
+    its build_* function).  All are stepped after every batch in the table's order (end_batch), on the current stream --
+    every engine has joined its camera streams into it by the time it returns -- and flushed before the training cameras
+    are rendered (evaluation, contribution pruning) and at the end.  A model handed in is refused like its flag.
+    `phase_times` (optional dict): host wall time per phase inside the end-to-end clock is accumulated into it
+    ("engine" = enqueueing the batches, "densify" = gsplat_densification incl. the device work it waits for,
+    "resort" = the Z-order re-sort after a densification, "log" = waiting for loss values, "final_sync"); a callable under
+    "iter_hook" is removed from the dict and called with the image counter after every iteration (diagnosis).
+
+    Camera-DP: when a process group is up every rank runs this same loop over the same shuffled order, takes
+    cameras rank::ranks of each GLOBAL batch (bsz x ranks images), and the image counter strides by the global batch; the
+    engine does the one exchange per batch, densification reduces its statistics and draws identical split samples."""
+    args = utils.get_args()
+    if set(side_models) - {r.name for r in SIDE_MODELS}:
+        raise TypeError("training() got unexpected keyword arguments {}".format(sorted(side_models)))
+    models = [side_models[r.name] for r in SIDE_MODELS if side_models.get(r.name) is not None]
+    depth_priors = any(getattr(c, "invdepth", None) is not None for c in train_cameras)
+    check_training(args, depth_priors, side_models)
+    bsz, ws = args.bsz, dp.world_size()
+    gbsz = bsz * ws
+    if ws > 1:
+        assert clm_hbm_only(args), "camera-DP trains clm_offload with sh_residency='hbm'"
+        if getattr(gaussians, "split_generator", None) is None:
+            dp.seed_split_generator(gaussians)
+    iterations = iterations or args.iterations
+    utils.set_log_file(log_file)
+    clm, naive = bool(getattr(args, "clm_offload", False)), bool(getattr(args, "naive_offload", False))
+    no_offload = not clm and not naive
+    run_batch, render_fn = _strategy(args, gaussians, scene, background)
+    host_rows = clm and getattr(args, "sh_residency", "hbm") == "host"
+    if host_rows:
+        from .strategies.clm_offload.engine import hint_next_batch
     spatial = bool(getattr(args, "spatial_row_order", True)) and hasattr(gaussians, "spatial_sort") and not naive
     if spatial:
         gaussians.spatial_sort()  # rows along a Z-order curve: a camera's rows become contiguous runs
         # the prune that ends a densification re-sorts in the same pass over the row tables (clm_offload model, HBM rows)
         gaussians.fuse_sort_into_prune = clm_hbm_only(args)
-    # a full cyclic GC pass over torch's ~10^6 long-lived objects stalls the enqueueing thread for
-    # ~100 ms: freeze what exists now, later collections only see what the loop allocates
-    gc.collect()
-    gc.freeze()
-    rng = random.Random(shuffle_seed)
-    order = []
-    # camera-DP, locality exchange (dp.py): every rank draws its batches from the cameras that look mostly at
-    # the rows it owns (index ranges of the Z-ordered tables = spatial regions); the deal is recomputed when
-    # densification has grown the model by 10 % (rows are re-sorted after every densification)
     locality = ws > 1 and bool(getattr(args, "dp_locality", False))
-    pool, dealt_at = None, 0
-
-    def deal():
-        nonlocal pool, dealt_at, order
-        ranks_of, _ = dp.deal_cameras(train_cameras, gaussians, ws)
-        dealt_at, order = gaussians.get_xyz.shape[0], []
-        # every rank computes the same deal, so every rank sees the same smallest pool -- no collective needed to agree.
-        # A rank with fewer than bsz cameras could not draw a batch while the others are already inside the batch's
-        # collectives (hang): then ALL ranks fall back to the strided deal of the global shuffled order (the locality
-        # exchange is correct for any camera assignment, it just moves more border rows).
-        smallest = min(sum(1 for q in ranks_of if q == r_) for r_ in range(ws))
-        if smallest < bsz:
-            pool = None
-            log_file.write("camera-DP locality deal: smallest pool {} < bsz {} ({} cameras / {} ranks): strided deal\n".format(
-                smallest, bsz, len(train_cameras), ws))
-        else:
-            pool = [i for i, q in enumerate(ranks_of) if q == rk]
-    if locality:
-        assert spatial, "dp_locality needs the Z-ordered row tables (spatial_row_order)"
-        deal()
+    assert spatial or not locality, "dp_locality needs the Z-ordered row tables (spatial_row_order)"
+    batches = _BatchSource(train_cameras, gaussians, bsz, shuffle_seed, locality, log_file)
     from . import _lib
-
-    def _check_device():
-        # the host has just synchronised: an asynchronous device fault / a raised device error word (the deferred
-        # small-attribute Adam) surfaces HERE, not at the end of the run with the model unsaved
-        _lib.check_device_errors()
+    # wherever the host has just synchronised: an asynchronous device fault / a raised device error word (the deferred
+    # small-attribute Adam) surfaces THERE, not at the end of the run with the model unsaved
+    _check_device = _lib.check_device_errors
     defer = bool(getattr(args, "defer_loss_log", True))
-    depth_priors = any(getattr(c, "invdepth", None) is not None for c in train_cameras)
-    check_depth_flags(args, depth_priors)
-    check_mcmc_args(args)
-    check_contrib_prune_args(args)
     contrib_iters = prune_iterations(args)
-    if pose is not None:
-        check_pose_args(args, depth_priors, enabled=True)  # a model handed in is refused like the flag
     use_mcmc = mcmc.enabled(args)
     loss_log = _LossLog(log_file, defer)
     pt = phase_times if phase_times is not None else {}
     iter_hook = pt.pop("iter_hook", None)  # diagnosis only (bench.py --trainer-trace): called after every iteration
-
-    def _acc(key, t_start):
-        pt[key] = pt.get(key, 0.0) + time.perf_counter() - t_start
-    if clm_hbm_only(args) and getattr(args, "allocator_reservoir", True) and getattr(args, "fused_front_end", True):
-        # allocator warm-up: one block per stream pool instead of dozens of hipMalloc calls spread over the first batches
-        # and every densification (strategies/clm_offload/engine.py reserve_working_set).  SETUP, like the reference's
-        # --prealloc_capacity buffers (train.py:107-115): before the end-to-end clock starts (utils/timer.py:87-111 starts
-        # it at the first iteration); its own wall time is reported as phase "reserve".  (Fresh device memory costs
-        # ~0.1 s per GB on some boxes and nothing on others -- measured 0.002 .. 1.3 s for the same 10 GB.)
-        from .strategies.clm_offload.engine import reserve_working_set
-        _t = time.perf_counter()
-        pt["reserved_bytes"] = float(sum(reserve_working_set(gaussians).values()))
-        torch.cuda.synchronize()
-        _acc("reserve", _t)
-        if not args.disable_auto_densification and getattr(args, "warm_structural_ops", True):
-            _t = time.perf_counter()
-            _warm_structural_ops(gaussians._xyz.device)
-            _acc("warm_ops", _t)
-    if torch.cuda.is_available():  # (diagnosis: how many hipMallocs happen INSIDE the end-to-end clock -- bench.py reports it)
-        pt["device_mallocs_before_clock"] = float(torch.cuda.memory_stats().get("num_device_alloc", 0))
+    _setup_before_clock(args, gaussians, pt)
     timer = End2endTimer()
     timer.start()
-    next_batch = None
     for iteration in range(1, iterations + 1, gbsz):
         utils.set_cur_iter(iteration)
         gaussians.update_learning_rate(iteration)
         if utils.check_update_at_this_iter(iteration, gbsz, 1000, 0):
             gaussians.oneupSHdegree()
-        def draw():
-            nonlocal order
-            if locality and pool is not None:
-                if len(order) < bsz:  # new epoch of THIS rank's pool
-                    order = list(pool)
-                    rng.shuffle(order)
-                return [train_cameras[order.pop()] for _ in range(bsz)]
-            if len(order) < gbsz:  # new epoch: shuffle, drop_last (train.py:156-167)
-                order = list(range(len(train_cameras)))
-                rng.shuffle(order)
-            return [train_cameras[order.pop()] for _ in range(gbsz)][rk::ws]
-        # the loader is one batch ahead: the host-resident engine stages the next batch's untouched rows early
-        batch = next_batch if next_batch is not None else draw()
-        next_batch = draw() if iteration + gbsz <= iterations else None
-        if clm and getattr(args, "sh_residency", "hbm") == "host":
-            from .strategies.clm_offload.engine import hint_next_batch
+        batch, next_batch = batches.next(more=iteration + gbsz <= iterations)
+        if host_rows:
             hint_next_batch(gaussians, next_batch)
         _t = time.perf_counter()
-        if naive:
-            losses, visibility = naive_offload_train_one_batch(gaussians, scene, batch, background,
-                                                               sparse_adam=args.sparse_adam)
-            names, sparsity = [c.image_name for c in batch], None
-        elif clm:
-            losses, ordered_cams, sparsity = clm_offload_train_one_batch(
-                gaussians, scene, batch, gaussians.parameters_grad_buffer, background, None, comm_stream,
-                perm_generator)
-            names = [batch[i].image_name for i in ordered_cams]
-        else:
-            losses, visibility = baseline_accumGrads_impl(gaussians, scene, batch, background,
-                                                          sparse_adam=args.sparse_adam)
-            names, sparsity = [c.image_name for c in batch], None
-        _acc("engine", _t)
+        losses, names, sparsity, visibility = run_batch(batch)
+        _acc(pt, "engine", _t)
         _t = time.perf_counter()
         # with depth priors: the depth term's weight of this iteration, next to the losses it is part of
         depth_note = " depth_l1_weight: {:.6f}".format(utils.depth_l1_weight(iteration)) if depth_priors else ""
         loss_log.push("iteration[{},{}) loss: ".format(iteration, iteration + gbsz), losses,
                       depth_note + " image: {}".format(names) + ((" sparsity: " + " ".join("%.4f" % s for s in sparsity) + "\n")
                                                    if sparsity else "\n"))
-        _acc("log", _t)
+        _acc(pt, "log", _t)
         if any(iteration <= t < iteration + gbsz for t in test_iterations):
             loss_log.flush()
-            if pose is not None:
-                pose.flush()  # training cameras are evaluated at their refined pose
+            for model in models:
+                model.flush()  # training cameras are evaluated at their refined pose
             timer.stop()  # evaluation is excluded from the throughput figure
             _check_device()
             if hasattr(gaussians, "flush_lazy_rows"):  # deferred row steps (and, owner-computes DP, the exchange)
@@ -506,39 +530,33 @@ def training(gaussians, scene, train_cameras, test_cameras, log_file, iterations
         if use_mcmc:
             # the batch's optimizer step and noise come first (clm_offload: inside the engine): a refinement moves rows of
             # stepped parameters, and the gradients of a batch belong to the rows as they were rendered
-            if not clm and not naive:
+            if no_offload:
                 no_offload_optimizer_step(gaussians, args, bsz, visibility)
             mcmc_refinement(iteration, scene, gaussians)
         else:
             gsplat_densification(iteration, scene, gaussians, None)
-        _acc("densify", _t)
+        _acc(pt, "densify", _t)
         if gaussians.get_xyz.shape[0] != n_before:
             _check_device()  # (densify_and_prune read its counts back: the device is drained)
         if spatial and gaussians.get_xyz.shape[0] != n_before:
             _t = time.perf_counter()
             gaussians.spatial_sort()  # clones / splits were appended at the end of the tables
-            _acc("resort", _t)
-            if locality and abs(gaussians.get_xyz.shape[0] - dealt_at) > 0.1 * dealt_at:
-                deal()
-                next_batch = None  # drawn from the old pool
+            _acc(pt, "resort", _t)
+            batches.resorted()
         if gaussians.get_xyz.shape[0] != n_before or utils.check_update_at_this_iter(
                 iteration, gbsz, args.mcmc_refine_every if use_mcmc else args.densification_interval, 0):
             loss_log.flush()  # keep the reference's line order: the batch's loss line, then the memory line
             log_file.write(memory_line(iteration, gbsz, gaussians))
-        if not clm and not naive and not use_mcmc:  # train.py:533-578
+        if no_offload and not use_mcmc:  # train.py:533-578
             no_offload_optimizer_step(gaussians, args, bsz, visibility)
-        for colour in (exposure, bilagrid, sky):
-            if colour is not None:
-                colour.step(iteration)
-                colour.zero_grad()
-        if pose is not None:
-            pose.step(batch)
+        for model in models:
+            model.end_batch(iteration, batch)
         if contrib_iters and any(iteration <= t < iteration + gbsz for t in contrib_iters):
             # contribution pruning (contribution.py): after the batch's optimizer step, so no gradient is waiting for rows
             # that leave; the training cameras are scored at the poses they carry
             loss_log.flush()
-            if pose is not None:
-                pose.flush()
+            for model in models:
+                model.flush()
             _t = time.perf_counter()
             contribution_prune(gaussians, train_cameras, getattr(args, "contrib_prune_mode", "sum"),
                                float(getattr(args, "contrib_prune_ratio", 0.3)),
@@ -547,7 +565,7 @@ def training(gaussians, scene, train_cameras, test_cameras, log_file, iterations
                                log_file=log_file, iteration=iteration)
             if spatial:
                 gaussians.spatial_sort()
-            _acc("contrib_prune", _t)
+            _acc(pt, "contrib_prune", _t)
             _check_device()
             log_file.write(memory_line(iteration, gbsz, gaussians, what="contribution_prune"))
         if not defer:
@@ -556,10 +574,10 @@ def training(gaussians, scene, train_cameras, test_cameras, log_file, iterations
             iter_hook(iteration)
     _t = time.perf_counter()
     loss_log.flush()
-    if pose is not None:
-        pose.flush()
+    for model in models:
+        model.flush()
     timer.stop()
-    _acc("final_sync", _t)
+    _acc(pt, "final_sync", _t)
     _check_device()
     n_done = ((iterations - 1) // gbsz + 1) * gbsz + 1
     timer.print_time(log_file, n_done)
@@ -575,19 +593,10 @@ def train_from_colmap(source_path, model_path, strategy="clm_offload", iteration
     split, scene radius, sparse points) -> `create_from_pcd` with `spatial_lr_scale = cameras_extent` ->
     `training_setup` -> `training` (log lines of the reference in `<model_path>/python_ws=1_rk=0.log`) ->
     `point_cloud/iteration_N/point_cloud.ply` (scene/__init__.py:41-143, train.py:60-131 for the order of
-    these steps).  `strategy`: clm_offload | no_offload | naive_offload; `arg_overrides`: any flag of
-    `utils.default_args`.  `masks` / `alpha_mask`: per-pixel ignore masks of the loss (colmap_scene.load_colmap_scene).
-    `exposure=True` (with `exposure_lr_init` / `exposure_lr_final`): per-camera exposure compensation of the training
-    cameras (build_exposure); the table is written to `<model_path>/exposure.json` next to the ply and stays reachable as
-    `scene.exposure`.  `bilagrid=True` (with `bilagrid_shape`, `bilagrid_lr_init`, `bilagrid_lr_final`,
-    `bilagrid_tv_weight`): bilateral-grid colour correction of the training cameras (build_bilagrid), written to
-    `<model_path>/bilagrid.npz`, reachable as `scene.bilagrid`; refused together with `exposure=True`.  `depths` (with `depth_l1_weight_init` / `depth_l1_weight_final`): the directory of the 16-bit
-    inverse-depth PNGs of the depth regularisation (colmap_scene.load_colmap_scene); refused with `absgrad=True`.
-    `sky=True` (with `sky_shape`, `sky_init`, `sky_lr_init`, `sky_lr_final`): a learnable sky map for the scene (build_sky),
-    written to `<model_path>/sky.npz`, reachable as `scene.sky`; refusals: check_sky_flags.
-    `pose_opt=True` (with `pose_opt_lr`, `pose_opt_reg`, `pose_noise`, `defer_pose_step`): camera pose refinement of the
-    training cameras (build_pose), written to `<model_path>/poses.json`, reachable as `scene.pose`; refusals:
-    pose.check_pose_args.
+    these steps).  `strategy`: clm_offload | no_offload | naive_offload; `masks` / `alpha_mask` / `depths`: the arguments of
+    colmap_scene.load_colmap_scene; `arg_overrides`: any flag of `utils.default_args`, described there and, for the ones the
+    command line has, in OPTIONS.  Every refusal is raised by check_training before anything is loaded.  A side model that
+    is asked for (SIDE_MODELS) is written next to the ply and stays reachable as `scene.<name>`, None when off.
     Returns (gaussians, scene, timer)."""
     from .colmap_scene import load_colmap_scene
     from .strategies.clm_offload import GaussianModelCLMOffload
@@ -600,14 +609,8 @@ def train_from_colmap(source_path, model_path, strategy="clm_offload", iteration
     if iterations is not None:
         args.iterations = int(iterations)
     args.depths = depths or ""
-    check_depth_flags(args, bool(depths))  # raises: before anything is loaded
-    check_appearance_flags(args)  # raises: before anything is loaded
-    check_pose_args(args, bool(depths))  # raises: before anything is loaded
-    check_sky_flags(args)  # raises: before anything is loaded
-    check_contrib_prune_args(args)  # raises: before anything is loaded
+    check_training(args, bool(depths))  # raises: before anything is loaded
     utils.set_args(args)
-    if getattr(args, "exposure", False) and dp.world_size() > 1:
-        build_exposure([], args.iterations)  # raises: before anything is loaded
     scene = load_colmap_scene(source_path, images=images, eval=eval, resolution=resolution, device="cuda",
                               masks=masks, alpha_mask=alpha_mask, depths=depths)
     if scene.point_cloud is None:
@@ -621,30 +624,15 @@ def train_from_colmap(source_path, model_path, strategy="clm_offload", iteration
                  "naive_offload": GaussianModelNaiveOffload}[strategy](args.sh_degree)
     gaussians.create_from_pcd(scene.point_cloud, scene.cameras_extent)
     gaussians.training_setup(args)
-    scene.exposure = None
-    if getattr(args, "exposure", False):
-        scene.exposure = build_exposure(scene.train_cameras, args.iterations, "cuda",
-                                        float(args.exposure_lr_init), float(args.exposure_lr_final))
-    scene.bilagrid = None
-    if getattr(args, "bilagrid", False):
-        scene.bilagrid = build_bilagrid(scene.train_cameras, args.iterations, "cuda", tuple(args.bilagrid_shape),
-                                        float(args.bilagrid_lr_init), float(args.bilagrid_lr_final),
-                                        float(args.bilagrid_tv_weight))
-    scene.pose = None
-    if getattr(args, "pose_opt", False):
-        scene.pose = build_pose(scene.train_cameras, args.iterations, "cuda", float(args.pose_opt_lr),
-                                float(args.pose_opt_reg), float(args.pose_noise), bool(args.defer_pose_step))
-    scene.sky = None
-    if getattr(args, "sky", False):
-        scene.sky = build_sky(scene.train_cameras, scene.test_cameras, args.iterations, "cuda", tuple(args.sky_shape),
-                              tuple(args.sky_init), float(args.sky_lr_init), float(args.sky_lr_final))
+    for row in SIDE_MODELS:
+        setattr(scene, row.name, row.build(args, scene.train_cameras, scene.test_cameras) if getattr(args, row.flag) else None)
     os.makedirs(model_path, exist_ok=True)
     prev_log = utils.get_log_file()
     try:
         with open(os.path.join(model_path, "python_ws=1_rk=0.log"), "w") as log_file:
             timer = training(gaussians, scene, scene.train_cameras, scene.test_cameras, log_file,
-                             iterations=args.iterations, test_iterations=test_iterations, exposure=scene.exposure,
-                             bilagrid=scene.bilagrid, pose=scene.pose, sky=scene.sky)
+                             iterations=args.iterations, test_iterations=test_iterations,
+                             **{row.name: getattr(scene, row.name) for row in SIDE_MODELS})
     finally:
         utils.set_log_file(prev_log)  # never leave a closed file as the process-wide log
     if save:
@@ -652,130 +640,105 @@ def train_from_colmap(source_path, model_path, strategy="clm_offload", iteration
             gaussians.flush_lazy_rows()  # ALL ranks (a collective under owner-computes / locality camera-DP) ...
         if dp.rank() == 0:               # ... then rank-0-only I/O (no collective left inside save_ply: nothing is dirty)
             gaussians.save_ply(os.path.join(model_path, "point_cloud", f"iteration_{args.iterations}", "point_cloud.ply"))
-            if scene.exposure is not None:  # {image_name: 3x4}, the INRIA code base's exposure.json
-                scene.exposure.save_json(os.path.join(model_path, "exposure.json"), scene.train_cameras)
-            if scene.bilagrid is not None:  # grids in gsplat's [n,12,L,Hg,Wg] layout + image names
-                scene.bilagrid.save(os.path.join(model_path, "bilagrid.npz"), scene.train_cameras)
-            if scene.sky is not None:  # the map, its shape and the convention string
-                scene.sky.save(model_path)
-            if scene.pose is not None:  # {image_name: {"delta": [9], "world_to_camera": 4x4}}
-                scene.pose.save_json(os.path.join(model_path, "poses.json"), scene.train_cameras)
+            for row in SIDE_MODELS:
+                if getattr(scene, row.name) is not None:
+                    getattr(scene, row.name).save_to(model_path, scene.train_cameras)
     return gaussians, scene, timer
 
 
+def _opt(*names, to=None, conv=None, **kw):
+    """One option -> (argparse's names, its keyword arguments, the attribute of the parsed namespace, the name
+    train_from_colmap / utils.default_args knows the value by, a converter of the parsed value or None).  An option that
+    states no default (and is no switch) takes the one of utils.default_args."""
+    dest = kw.get("dest") or next(n for n in names if n.startswith("--"))[2:]
+    return names, kw, dest, to or dest, conv
+
+
+OPTIONS = (
+    _opt("-s", "--source_path", required=True), _opt("-m", "--model_path", required=True),
+    _opt("-i", "--images", default="images"), _opt("-r", "--resolution", type=float, default=1),
+    _opt("--eval", action="store_true"), _opt("--iterations", type=int), _opt("--bsz", type=int, default=4),
+    _opt("--test_iterations", type=int, nargs="*", default=[7000, 30000], conv=tuple),
+    *(_opt("--" + s, action="store_const", const=s, dest="strategy", default="clm_offload", exclusive=True)
+      for s in ("clm_offload", "no_offload", "naive_offload")),
+    _opt("--sh_residency", choices=["hbm", "host"]),
+    _opt("--sh_hbm_budget_gb", type=float,
+         help="sh_residency=host: HBM that keeps the first rows of the Z-ordered SH table resident (768 B per row)"),
+    _opt("--absgrad", action="store_true",
+         help="densify on sum_p |dL_p/dmean2d| (gsplat's absgrad); gsplat's recipe raises the threshold to 8e-4"),
+    _opt("--antialiased", action="store_true", to="rasterize_mode", conv=lambda on: "antialiased" if on else "classic",
+         help="gsplat's rasterize_mode=\"antialiased\" (Mip-Splatting opacity compensation); render the model with it too"),
+    _opt("--masks", default=None, metavar="DIR", help="directory of per-image loss masks (NAME.EXT.png or NAME.png, 0 = "
+         "pixel ignored by the loss), relative to the source path or absolute"),
+    _opt("--alpha_mask", action="store_true",
+         help="images with an alpha channel and no mask file: the loss ignores pixels with alpha 0"),
+    _opt("--exposure", action="store_true", help="per-camera exposure compensation: a learnable 3x4 affine colour "
+         "transform per training image, written to <model_path>/exposure.json (single GPU)"),
+    _opt("--exposure_lr_init", type=float), _opt("--exposure_lr_final", type=float),
+    _opt("--bilagrid", action="store_true", help="bilateral-grid colour correction (gsplat's use_bilateral_grid): a "
+         "learnable lattice of 3x4 affine colour transforms per training image, sliced by position and luminance, written to "
+         "<model_path>/bilagrid.npz (single GPU; not with --exposure)"),
+    _opt("--bilagrid_shape", type=int, nargs=3, metavar=("WG", "HG", "L"), conv=tuple),
+    _opt("--bilagrid_lr_init", type=float), _opt("--bilagrid_lr_final", type=float), _opt("--bilagrid_tv_weight", type=float),
+    _opt("--sky", action="store_true", help="learnable sky: one equirectangular environment map composited behind the "
+         "splats and trained by the same loss, written to <model_path>/sky.npz; render the model with --sky too (single GPU; "
+         "not with --white_background or --pose_opt)"),
+    _opt("--sky_shape", type=int, nargs=2, metavar=("HS", "WS"), conv=tuple),
+    _opt("--sky_init", type=float, nargs=3, metavar=("R", "G", "B"), conv=tuple),
+    _opt("--sky_lr_init", type=float), _opt("--sky_lr_final", type=float),
+    _opt("-d", "--depths", default=None, metavar="DIR", help="depth regularisation: directory (relative to the source path "
+         "or absolute) of 16-bit inverse-depth PNGs NAME.png, scaled by sparse/0/depth_params.json; an L1 term on the rendered "
+         "inverse depth of every training image with a reliable prior (not with --absgrad)"),
+    _opt("--depth_l1_weight_init", type=float), _opt("--depth_l1_weight_final", type=float),
+    _opt("--pose_opt", action="store_true", help="camera pose refinement (gsplat's pose_opt): a learnable rigid correction "
+         "per training image, written to <model_path>/poses.json (fused front end, SH rows in HBM, single GPU; not with "
+         "--depths)"),
+    _opt("--pose_opt_lr", type=float), _opt("--pose_opt_reg", type=float),
+    _opt("--pose_noise", type=float,
+         help="--pose_opt: seeded random perturbation of the training poses at the start (experiments)"),
+    _opt("--immediate_pose_step", action="store_true", to="defer_pose_step", conv=lambda on: not on,
+         help="--pose_opt: apply a batch's pose step before the next batch is enqueued (the host waits)"),
+    _opt("--mcmc", action="store_true", help="3DGS-MCMC densification (gsplat's MCMCStrategy): a fixed budget of --cap_max "
+         "Gaussians, dead ones relocated instead of pruned, 5 %% growth per refinement, position noise after every step "
+         "(no_offload, or clm_offload with --sh_residency hbm; single GPU)"),
+    _opt("--cap_max", type=int, to="mcmc_cap_max", help="--mcmc: the number of Gaussians the model grows to"),
+    _opt("--mcmc_noise_lr", type=float), _opt("--mcmc_refine_start_iter", type=int),
+    _opt("--mcmc_refine_stop_iter", type=int), _opt("--mcmc_refine_every", type=int),
+    _opt("--mcmc_min_opacity", type=float), _opt("--mcmc_opacity_reg", type=float), _opt("--mcmc_scale_reg", type=float),
+    _opt("--disable_auto_densification", action="store_true"),
+    _opt("--contrib_prune_iterations", type=int, nargs="*", metavar="I", conv=tuple, help="contribution pruning: image "
+         "counters at which the training cameras are scored by blend weight and the model is pruned; each after "
+         "densify_until_iter unless --disable_auto_densification (no_offload or clm_offload; single GPU; not with --mcmc)"),
+    _opt("--contrib_prune_mode", choices=["sum", "max"], help="sum: prune the lowest --contrib_prune_ratio of rows by "
+         "summed weight; max: prune rows whose largest weight is below --contrib_prune_threshold"),
+    _opt("--contrib_prune_ratio", type=float), _opt("--contrib_prune_threshold", type=float),
+)
+
+
 def build_arg_parser():
-    """The command line of `python -m clm_gs_amd.trainer`."""
+    """The command line of `python -m clm_gs_amd.trainer`, from OPTIONS."""
     import argparse
     ap = argparse.ArgumentParser(description="train a 3DGS model from a COLMAP directory (flag names of train.py)")
-    ap.add_argument("-s", "--source_path", required=True)
-    ap.add_argument("-m", "--model_path", required=True)
-    ap.add_argument("-i", "--images", default="images")
-    ap.add_argument("-r", "--resolution", type=float, default=1)
-    ap.add_argument("--eval", action="store_true")
-    ap.add_argument("--iterations", type=int, default=30000)
-    ap.add_argument("--bsz", type=int, default=4)
-    ap.add_argument("--test_iterations", type=int, nargs="*", default=[7000, 30000])
-    grp = ap.add_mutually_exclusive_group()
-    for s_ in ("clm_offload", "no_offload", "naive_offload"):
-        grp.add_argument("--" + s_, action="store_true")
-    ap.add_argument("--sh_residency", choices=["hbm", "host"], default="hbm")
-    ap.add_argument("--sh_hbm_budget_gb", type=float, default=0.0,
-                    help="sh_residency=host: HBM that keeps the first rows of the Z-ordered SH table resident (768 B per row)")
-    ap.add_argument("--absgrad", action="store_true",
-                    help="densify on sum_p |dL_p/dmean2d| (gsplat's absgrad); gsplat's recipe raises the threshold to 8e-4")
-    ap.add_argument("--antialiased", action="store_true",
-                    help="gsplat's rasterize_mode=\"antialiased\" (Mip-Splatting opacity compensation); render the model with it too")
-    ap.add_argument("--masks", default=None, metavar="DIR",
-                    help="directory of per-image loss masks (NAME.EXT.png or NAME.png, 0 = pixel ignored by the loss), "
-                         "relative to the source path or absolute")
-    ap.add_argument("--alpha_mask", action="store_true",
-                    help="images with an alpha channel and no mask file: the loss ignores pixels with alpha 0")
-    ap.add_argument("--exposure", action="store_true",
-                    help="per-camera exposure compensation: a learnable 3x4 affine colour transform per training image, "
-                         "written to <model_path>/exposure.json (single GPU)")
-    ap.add_argument("--exposure_lr_init", type=float, default=0.01)
-    ap.add_argument("--exposure_lr_final", type=float, default=0.001)
-    ap.add_argument("--bilagrid", action="store_true",
-                    help="bilateral-grid colour correction (gsplat's use_bilateral_grid): a learnable lattice of 3x4 affine "
-                         "colour transforms per training image, sliced by position and luminance, written to "
-                         "<model_path>/bilagrid.npz (single GPU; not with --exposure)")
-    ap.add_argument("--bilagrid_shape", type=int, nargs=3, default=[16, 16, 8], metavar=("WG", "HG", "L"))
-    ap.add_argument("--bilagrid_lr_init", type=float, default=2e-3)
-    ap.add_argument("--bilagrid_lr_final", type=float, default=2e-5)
-    ap.add_argument("--bilagrid_tv_weight", type=float, default=10.0)
-    ap.add_argument("--sky", action="store_true",
-                    help="learnable sky: one equirectangular environment map composited behind the splats and trained by "
-                         "the same loss, written to <model_path>/sky.npz; render the model with --sky too (single GPU; not "
-                         "with --white_background or --pose_opt)")
-    ap.add_argument("--sky_shape", type=int, nargs=2, default=[256, 512], metavar=("HS", "WS"))
-    ap.add_argument("--sky_init", type=float, nargs=3, default=[0.5, 0.5, 0.5], metavar=("R", "G", "B"))
-    ap.add_argument("--sky_lr_init", type=float, default=0.01)
-    ap.add_argument("--sky_lr_final", type=float, default=0.001)
-    ap.add_argument("-d", "--depths", default=None, metavar="DIR",
-                    help="depth regularisation: directory (relative to the source path or absolute) of 16-bit inverse-depth "
-                         "PNGs NAME.png, scaled by sparse/0/depth_params.json; an L1 term on the rendered inverse depth "
-                         "of every training image with a reliable prior (not with --absgrad)")
-    ap.add_argument("--depth_l1_weight_init", type=float, default=1.0)
-    ap.add_argument("--depth_l1_weight_final", type=float, default=0.01)
-    ap.add_argument("--pose_opt", action="store_true",
-                    help="camera pose refinement (gsplat's pose_opt): a learnable rigid correction per training image, "
-                         "written to <model_path>/poses.json (fused front end, SH rows in HBM, single GPU; not with --depths)")
-    ap.add_argument("--pose_opt_lr", type=float, default=1e-5)
-    ap.add_argument("--pose_opt_reg", type=float, default=1e-6)
-    ap.add_argument("--pose_noise", type=float, default=0.0,
-                    help="--pose_opt: seeded random perturbation of the training poses at the start (experiments)")
-    ap.add_argument("--immediate_pose_step", action="store_true",
-                    help="--pose_opt: apply a batch's pose step before the next batch is enqueued (the host waits)")
-    ap.add_argument("--mcmc", action="store_true",
-                    help="3DGS-MCMC densification (gsplat's MCMCStrategy): a fixed budget of --cap_max Gaussians, dead ones "
-                         "relocated instead of pruned, 5 %% growth per refinement, position noise after every step "
-                         "(no_offload, or clm_offload with --sh_residency hbm; single GPU)")
-    ap.add_argument("--cap_max", type=int, default=1_000_000, help="--mcmc: the number of Gaussians the model grows to")
-    ap.add_argument("--mcmc_noise_lr", type=float, default=5e5)
-    ap.add_argument("--mcmc_refine_start_iter", type=int, default=500)
-    ap.add_argument("--mcmc_refine_stop_iter", type=int, default=25_000)
-    ap.add_argument("--mcmc_refine_every", type=int, default=100)
-    ap.add_argument("--mcmc_min_opacity", type=float, default=0.005)
-    ap.add_argument("--mcmc_opacity_reg", type=float, default=0.01)
-    ap.add_argument("--mcmc_scale_reg", type=float, default=0.01)
-    ap.add_argument("--disable_auto_densification", action="store_true")
-    ap.add_argument("--contrib_prune_iterations", type=int, nargs="*", default=[], metavar="I",
-                    help="contribution pruning: image counters at which the training cameras are scored by blend weight and "
-                         "the model is pruned; each after densify_until_iter unless --disable_auto_densification "
-                         "(no_offload or clm_offload; single GPU; not with --mcmc)")
-    ap.add_argument("--contrib_prune_mode", choices=["sum", "max"], default="sum",
-                    help="sum: prune the lowest --contrib_prune_ratio of rows by summed weight; max: prune rows whose "
-                         "largest weight is below --contrib_prune_threshold")
-    ap.add_argument("--contrib_prune_ratio", type=float, default=0.3)
-    ap.add_argument("--contrib_prune_threshold", type=float, default=0.01)
+    defaults, exclusive = utils.default_args(), ap.add_mutually_exclusive_group()
+    for names, kw, _, to, _ in OPTIONS:
+        kw = dict(kw)
+        if "default" not in kw and "required" not in kw and kw.get("action") != "store_true":
+            kw["default"] = list(getattr(defaults, to)) if "nargs" in kw else getattr(defaults, to)
+        (exclusive if kw.pop("exclusive", False) else ap).add_argument(*names, **kw)
     return ap
 
 
-if __name__ == "__main__":  # python -m clm_gs_amd.trainer -s <colmap dir> -m <output dir> [--clm_offload] ...
-    # (clm_gs_amd/__init__.py has applied runtime_env.single_gpu_runtime_defaults() before torch was imported: the
-    # hardware-queue default bench.py runs with is the trainer's too)
-    a = build_arg_parser().parse_args()
-    strat = "no_offload" if a.no_offload else ("naive_offload" if a.naive_offload else "clm_offload")
-    _, _, t = train_from_colmap(a.source_path, a.model_path, strategy=strat, iterations=a.iterations, eval=a.eval,
-                                resolution=a.resolution, images=a.images, test_iterations=tuple(a.test_iterations),
-                                bsz=a.bsz, sh_residency=a.sh_residency, sh_hbm_budget_gb=a.sh_hbm_budget_gb,
-                                absgrad=a.absgrad, rasterize_mode="antialiased" if a.antialiased else "classic",
-                                masks=a.masks, alpha_mask=a.alpha_mask, exposure=a.exposure,
-                                exposure_lr_init=a.exposure_lr_init, exposure_lr_final=a.exposure_lr_final,
-                                bilagrid=a.bilagrid, bilagrid_shape=tuple(a.bilagrid_shape),
-                                bilagrid_lr_init=a.bilagrid_lr_init, bilagrid_lr_final=a.bilagrid_lr_final,
-                                bilagrid_tv_weight=a.bilagrid_tv_weight,
-                                sky=a.sky, sky_shape=tuple(a.sky_shape), sky_init=tuple(a.sky_init),
-                                sky_lr_init=a.sky_lr_init, sky_lr_final=a.sky_lr_final,
-                                depths=a.depths, depth_l1_weight_init=a.depth_l1_weight_init,
-                                depth_l1_weight_final=a.depth_l1_weight_final, mcmc=a.mcmc, mcmc_cap_max=a.cap_max,
-                                mcmc_noise_lr=a.mcmc_noise_lr, mcmc_refine_start_iter=a.mcmc_refine_start_iter,
-                                mcmc_refine_stop_iter=a.mcmc_refine_stop_iter, mcmc_refine_every=a.mcmc_refine_every,
-                                mcmc_min_opacity=a.mcmc_min_opacity, mcmc_opacity_reg=a.mcmc_opacity_reg,
-                                mcmc_scale_reg=a.mcmc_scale_reg, pose_opt=a.pose_opt, pose_opt_lr=a.pose_opt_lr,
-                                pose_opt_reg=a.pose_opt_reg, pose_noise=a.pose_noise,
-                                defer_pose_step=not a.immediate_pose_step,
-                                disable_auto_densification=a.disable_auto_densification,
-                                contrib_prune_iterations=tuple(a.contrib_prune_iterations),
-                                contrib_prune_mode=a.contrib_prune_mode, contrib_prune_ratio=a.contrib_prune_ratio,
-                                contrib_prune_threshold=a.contrib_prune_threshold)
+def train_kwargs(namespace):
+    """A namespace of build_arg_parser() -> the keyword arguments of train_from_colmap."""
+    return {to: conv(getattr(namespace, dest)) if conv else getattr(namespace, dest) for _, _, dest, to, conv in OPTIONS}
+
+
+def main(argv=None):
+    """python -m clm_gs_amd.trainer -s <colmap dir> -m <output dir> [--clm_offload] ...  (clm_gs_amd/__init__.py has applied
+    runtime_env.single_gpu_runtime_defaults() before torch was imported: bench.py's hardware-queue default is the trainer's)"""
+    train_from_colmap(**train_kwargs(build_arg_parser().parse_args(argv)))
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

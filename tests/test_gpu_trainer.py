@@ -2,6 +2,7 @@
 SH ramp, engine, densification (clone/split/prune + opacity reset), evaluation, and the exact log
 strings release_scripts/log2csv.py:54-102 parses."""
 import io
+import os
 
 import pytest
 import torch
@@ -89,6 +90,64 @@ def test_training_loop_improves_psnr_and_logs(dev, strategy, residency):
         assert m["pinned_cpu_memory_gb"] > 0
     if budget:
         assert model._hbm_prefix is not None and model._hbm_prefix["K"] == 12000 and not model._hbm_prefix["dirty"]
+
+
+def _reloaded(name, model, path, cameras):
+    """The table of a side model's file, read back through the model's own loader -> (table in the file, table in memory)."""
+    from clm_gs_amd.bilagrid import BilagridModel
+    from clm_gs_amd.exposure import ExposureModel
+    from clm_gs_amd.pose import PoseModel
+    from clm_gs_amd.sky import SkyModel
+    if name == "exposure":
+        fresh = ExposureModel(len(cameras), "cuda")
+        fresh.load_json(str(path), cameras)
+    elif name == "bilagrid":
+        fresh = BilagridModel(len(cameras), "cuda")
+        fresh.load(str(path), cameras)
+    elif name == "sky":
+        fresh = SkyModel.from_file(str(path.parent), "cuda")
+    else:
+        fresh = PoseModel(len(cameras), device=None)
+        fresh.load_json(str(path), cameras)
+        return fresh.table, model.table
+    return fresh.param.detach(), model.param.detach()
+
+
+@pytest.mark.parametrize("flags,names", [
+    (dict(exposure=True, pose_opt=True, defer_pose_step=False), ("exposure", "pose")),
+    (dict(bilagrid=True, sky=True, sky_shape=(8, 16)), ("bilagrid", "sky")),
+], ids=["exposure+pose", "bilagrid+sky"])
+def test_two_side_models_step_in_one_batch_and_are_saved(dev, tmp_path, flags, names):
+    """8 images in two batches of 4 with two side models on: both are stepped through trainer.SIDE_MODELS, both files are
+    written and hold what the scene holds."""
+    from clm_gs_amd import trainer
+    from clm_gs_amd.bilagrid import IDENTITY
+    from tests.test_gpu_exposure import _tiny_scene
+    work = _tiny_scene(tmp_path)
+    out = tmp_path / "out"
+    _, scene, _ = trainer.train_from_colmap(str(work), str(out), strategy="clm_offload", iterations=8, bsz=4,
+                                            disable_auto_densification=True, **flags)
+    rows = {r.name: r for r in trainer.SIDE_MODELS}
+    for row in rows.values():
+        assert (getattr(scene, row.name) is not None) == (row.name in names), row.name
+        assert os.path.exists(out / row.file) == (row.name in names), row.file
+    for name in names:
+        model = getattr(scene, name)
+        in_file, in_memory = _reloaded(name, model, out / rows[name].file, scene.train_cameras)
+        assert torch.equal(in_file, in_memory), name
+    initial = {"exposure": lambda m: torch.eye(3, 4, device="cuda").expand_as(m.param),
+               "bilagrid": lambda m: torch.tensor(IDENTITY, device="cuda").expand_as(m.param),
+               "sky": lambda m: torch.full_like(m.param, 0.5),
+               "pose": lambda m: torch.zeros_like(m.table)}
+    for name in names:
+        model = getattr(scene, name)
+        table = model.table if name == "pose" else model.param.detach()
+        moved = float((table - initial[name](model)).abs().max())
+        print(f"{name}: the table moved by at most {moved:.3e} in two batches")
+        assert moved > 0.0, name
+    log = open(out / "python_ws=1_rk=0.log").read().splitlines()
+    assert [l.split(" loss: ")[0] for l in log if " loss: " in l] == ["iteration[1,5)", "iteration[5,9)"]
+    assert log[-3].startswith("end2end total_time: ") and "iterations: 9," in log[-3]
 
 
 def test_longer_pipelined_run_with_densification_is_stable(dev):
