@@ -107,6 +107,10 @@ SIGNATURES = {
     "clmgs_invdepth_l1_fwd_bwd": (_i, [_vp, _i, _i, _vp, _i64, _i64, _vp, _f, _f, _vp, _f, _vp, _i64, _i64, _vp]),
     "clmgs_invdepth_finish": (_i, [_vp, _i, _vp, _vp]),
     "clmgs_invdepth_rows_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
+    # resolution schedule: exact integer area resampling (u8 planes, one u16 plane, the loss mask + its count)
+    "clmgs_area_resample_u8": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "clmgs_area_resample_u16": (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    "clmgs_area_resample_mask": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
     "clmgs_mcmc_relocation": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "clmgs_mcmc_reg_grad": (_i, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _f, _f]),
     "clmgs_mcmc_noise": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _f, _vp]),

@@ -211,3 +211,121 @@ class OrthoCamera:
 
     def create_k_on_gpu(self, device="cuda"):
         return torch.tensor([[self.sx, 0, self.cx], [0, self.sy, self.cy], [0, 0, 1]], dtype=torch.float32, device=device)
+
+
+# ------------------------------------------------------------------------------------------- resolution schedule
+# ("Resolution schedule").  Level L of a W x H camera is the same pinhole at
+# ceil(W / 2^L) x ceil(H / 2^L): same pose, same FoV, hence its own K (focal lengths and a centred principal point at the
+# level's size).  The image EXTENT is the same at every level, which is what the area filter of csrc/resample.hip keeps.
+
+# what a view shares with its camera -- the same tensors, nothing cloned: the side models step the tables the views read
+_SHARED_BY_VIEWS = ("exposure", "exposure_grad", "bilagrid", "bilagrid_grad", "sky", "sky_acc", "invdepth_scale",
+                    "invdepth_offset")
+
+
+def level_view(camera, level, image=None, loss_mask=None, loss_mask_count=None, invdepth=None):
+    """The Camera that renders `camera` at level `level`: same uid, name, pose and FoV, size (Wo, Ho) =
+    ceil(size / 2^level), its own K, camtoworlds and cached host triple, and every side-model attribute of the camera as
+    the same object.  `image`, `loss_mask` (+ `loss_mask_count`, a host integer) and `invdepth`: the level's ground truth
+    (clm_kernels.area_resample), device tensors taken as they are; a view built without them is a shell (pose and K, no
+    image).  level 0 is the camera itself: nothing is copied, nothing is launched.  An orthographic camera is refused."""
+    level = int(level)
+    if level < 0:
+        raise ValueError(f"level_view: level must be >= 0, got {level}")
+    refuse_ortho(camera, "level_view (the resolution schedule, --num_downscales)")
+    if level == 0:
+        return camera
+    if getattr(camera, "pose_grad", None) is not None:
+        raise ValueError("level_view: the camera carries a pose-gradient buffer (--pose_opt): pose refinement rewrites the "
+                         "camera it is attached to and a level view would go stale; --num_downscales and --pose_opt "
+                         "exclude each other")
+    f = 1 << level
+    W, H = int(camera.image_width), int(camera.image_height)
+    Wo, Ho = (W + f - 1) // f, (H + f - 1) // f
+    view = Camera.__new__(Camera)
+    view.uid, view.image_name = camera.uid, camera.image_name
+    view.FoVx, view.FoVy = float(camera.FoVx), float(camera.FoVy)
+    view.image_width, view.image_height = Wo, Ho
+    view.level, view.full_camera = level, camera
+    view.world_view_transform = camera.world_view_transform
+    view.camtoworlds = camera.camtoworlds
+    device = camera.world_view_transform.device
+    view.K = view.create_k_on_gpu(device)
+    host = getattr(camera, "_clmgs_host", None)
+    if host is None:
+        w2c = camera.world_view_transform.detach().t().contiguous().cpu()
+        host = (np.ascontiguousarray(w2c.numpy().astype(np.float32).reshape(16)), None,
+                np.ascontiguousarray(torch.inverse(w2c)[:3, 3].numpy().astype(np.float32).reshape(3)))
+    view._clmgs_host = (host[0], np.ascontiguousarray(view.create_k_on_gpu("cpu").numpy().astype(np.float32).reshape(9)),
+                        host[2])
+    view.original_image = image
+    view.loss_mask, view.loss_mask_count = loss_mask, (None if loss_mask is None else loss_mask_count)
+    view.invdepth = invdepth
+    view.invdepth_scale = getattr(camera, "invdepth_scale", 1.0)
+    view.invdepth_offset = getattr(camera, "invdepth_offset", 0.0)
+    for name in _SHARED_BY_VIEWS:
+        if hasattr(camera, name):
+            setattr(view, name, getattr(camera, name))
+    return view
+
+
+class LevelCameras:
+    """The training cameras of ONE level L >= 1 of the resolution schedule; the trainer builds one at a level switch and
+    drops the previous one.
+      - the shells (level_view: pose, K, shared side-model attributes) of every camera, once;
+      - the loss masks and inverse-depth priors of the level (small), resampled once; each mask's count is read back
+        here, once per camera and level, with one copy for all of them;
+      - NO cache of images: batch() resamples the ground truth of a batch's cameras into a ring of 2 x bsz preallocated
+        uint8 [3,Ho,Wo] buffers, on the current stream, and hands out the views.  Nothing is allocated per batch.
+    Stream order of the ring: the resample kernels are enqueued on the current stream before the engine is called; every
+    engine orders its side streams behind the current stream at the head of a batch (they read the parameters the
+    optimizer stepped there) and has joined them into it when it returns (DESIGN.md names the lines), and a buffer is
+    rewritten two batches after the batch that read it."""
+
+    def __init__(self, cameras, level, bsz):
+        from .clm_kernels import area_resample, level_size
+        self.level, self.bsz = int(level), int(bsz)
+        if self.level < 1:
+            raise ValueError(f"LevelCameras: level must be >= 1, got {level} (level 0 is the cameras themselves)")
+        sizes = {(int(c.image_height), int(c.image_width)) for c in cameras}
+        if len(sizes) != 1:
+            raise ValueError(f"LevelCameras: all cameras must share one size, got {sorted(sizes)}")
+        (H, W), = sizes
+        self.full_size = (H, W)
+        self.size = level_size(H, W, self.level)  # (Ho, Wo)
+        self.cameras = list(cameras)
+        device = cameras[0].world_view_transform.device
+        for c in cameras:  # planar and contiguous, as Camera keeps it: a strided image is copied once, here, not per batch
+            if c.original_image is not None and not c.original_image.is_contiguous():
+                c.original_image = c.original_image.contiguous()
+        masked = [c for c in cameras if getattr(c, "loss_mask", None) is not None]
+        masks, mask_counts = {}, {}
+        if masked:
+            counts = torch.zeros((len(masked),), dtype=torch.int64, device=device)
+            for k, c in enumerate(masked):
+                masks[id(c)] = area_resample(c.loss_mask, self.level, mask=True, count=counts[k:k + 1])[0]
+            mask_counts = {id(c): int(n) for c, n in zip(masked, counts.cpu().tolist())}  # the one read-back of the level
+        self.views = {}
+        for c in cameras:
+            raw = getattr(c, "invdepth", None)
+            self.views[id(c)] = level_view(
+                c, self.level, loss_mask=masks.get(id(c)), loss_mask_count=mask_counts.get(id(c)),
+                invdepth=None if raw is None else area_resample(raw, self.level))
+        self.ring = [torch.empty((3,) + self.size, dtype=torch.uint8, device=device) for _ in range(2 * self.bsz)]
+        self.turn = 0
+
+    def ring_bytes(self):
+        return sum(t.numel() for t in self.ring)
+
+    def batch(self, cameras):
+        """The level's views of a batch's cameras, their ground truth resampled into the ring's next bsz buffers."""
+        from .clm_kernels import area_resample
+        if len(cameras) > self.bsz:
+            raise ValueError(f"LevelCameras.batch: {len(cameras)} cameras, the ring was built for batches of {self.bsz}")
+        base, self.turn = self.turn * self.bsz, self.turn ^ 1
+        out = []
+        for k, c in enumerate(cameras):
+            view = self.views[id(c)]
+            view.original_image = area_resample(c.original_image, self.level, out=self.ring[base + k])
+            out.append(view)
+        return out

@@ -384,6 +384,56 @@ def apply_camera_sky(image, alphas, camera):
     return _ApplySky.apply(image, alphas, table.detach(), vm, K, acc if train else None)
 
 
+# ------------------------------------------------------------ resolution schedule
+def level_size(H, W, level):
+    """(Ho, Wo) of level `level` of an H x W image: ceil(H / 2^level), ceil(W / 2^level)."""
+    f = 1 << int(level)
+    return (int(H) + f - 1) // f, (int(W) + f - 1) // f
+
+
+@torch.no_grad()
+def area_resample(t, level, out=None, mask=False, count=None):
+    """Exact integer area resampling of a device image to level `level` (csrc/resample.hip; DESIGN.md section 3,
+    "Resolution schedule"): t uint8 [3,H,W] (any number of planes) or [H,W], or uint16 [H,W], contiguous -> the same dtype
+    and rank at level_size(H, W, level), rounded half up.  `out`: a caller-owned contiguous buffer of that shape and dtype
+    (written and returned; nothing is allocated).  mask=True (uint8 [H,W], 0 = ignored): a cell is counted (255) when at
+    least half of its area is; returns (mask, count) with count a device int64 [1] (`count=`: a caller-owned one).
+    level 0 is the input itself: returned as it is (copied into `out` when one is given), no kernel."""
+    level = int(level)
+    if level < 0:
+        raise ValueError(f"area_resample: level must be >= 0, got {level}")
+    if not (t.is_cuda and t.is_contiguous() and t.dim() in (2, 3) and t.dtype in (U8, torch.uint16)):
+        raise _lib.ClmgsError(f"area_resample: contiguous uint8 [P,H,W] / [H,W] or uint16 [H,W] device tensor expected, "
+                              f"got {t.dtype} {tuple(t.shape)}")
+    if t.dtype == torch.uint16 and t.dim() != 2:
+        raise _lib.ClmgsError(f"area_resample: a uint16 input is one plane [H,W], got {tuple(t.shape)}")
+    if mask and (t.dtype != U8 or t.dim() != 2):
+        raise _lib.ClmgsError(f"area_resample: a mask is uint8 [H,W], got {t.dtype} {tuple(t.shape)}")
+    H, W = t.shape[-2:]
+    shape = tuple(t.shape[:-2]) + level_size(H, W, level)
+    if out is not None and not (out.is_cuda and out.is_contiguous() and out.dtype == t.dtype and tuple(out.shape) == shape
+                                and out.device == t.device):
+        raise _lib.ClmgsError(f"area_resample: out must be a contiguous {t.dtype} {shape} tensor on {t.device}, got "
+                              f"{out.dtype} {tuple(out.shape)}")
+    if level == 0:
+        res = t if out is None else out.copy_(t)
+        return (res, torch.count_nonzero(t).reshape(1)) if mask else res
+    if out is None:
+        out = torch.empty(shape, dtype=t.dtype, device=t.device)
+    L = _lib.lib()
+    if mask:
+        if count is None:
+            count = torch.empty((1,), dtype=I64, device=t.device)
+        check(L.clmgs_area_resample_mask(stream(), H, W, level, dptr(t, U8), dptr(out, U8), dptr(count, I64)))
+        return out, count
+    if t.dtype == U8:
+        planes = t.shape[0] if t.dim() == 3 else 1
+        check(L.clmgs_area_resample_u8(stream(), planes, H, W, level, dptr(t, U8), dptr(out, U8)))
+    else:
+        check(L.clmgs_area_resample_u16(stream(), H, W, level, dptr(t, torch.uint16), dptr(out, torch.uint16)))
+    return out
+
+
 # ------------------------------------------------------------ MCMC densification
 def _f32_dev(t, shape, what):
     assert t.is_cuda and t.dtype == F32 and t.is_contiguous() and tuple(t.shape) == tuple(shape), \

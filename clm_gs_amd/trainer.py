@@ -9,6 +9,7 @@ as objects; `train_from_colmap` (and `python -m clm_gs_amd.trainer -s ... -m ...
 directory (colmap_scene.py).  MatrixCity / Blender readers, checkpoint directories and the rest of the
 reference's CLI are out of scope.
 """
+import contextlib
 import gc
 import os
 import random
@@ -19,7 +20,7 @@ import torch
 
 from . import dp, mcmc, utils
 from .bilagrid import BilagridModel
-from .cameras import camera_loss_mask
+from .cameras import LevelCameras, camera_loss_mask
 from .clm_kernels import apply_camera_colour
 from .contribution import check_contrib_prune_args, contribution_prune, prune_iterations
 from .densification import check_mcmc_args, gsplat_densification, mcmc_refinement
@@ -303,11 +304,13 @@ def _refuse(rules):
             raise ValueError(message)
 
 
-def check_training(args, depth_priors=False, models=None):
+def check_training(args, depth_priors=False, models=None, num_downscales=None, resolution_schedule=None, image_size=None):
     """Every refusal of a run, in one fixed order; train_from_colmap calls it before anything is loaded, training() at its
     top.  `depth_priors`: a depth directory was asked for, or a training camera carries a prior.  `models`
-    ({SideModel.name: model}): a model handed in counts as its flag being set.  The trainer's own rules first, then the
-    owners of pose refinement, MCMC and contribution pruning."""
+    ({SideModel.name: model}): a model handed in counts as its flag being set.  `num_downscales`,
+    `resolution_schedule`: the values in force when they are not the args' own (training()'s parameters); `image_size`:
+    (H, W) of the images once it is known (training(); train_from_colmap checks that one rule right after loading).  The trainer's own
+    rules first, then the owners of pose refinement, MCMC and contribution pruning."""
     given = {r.flag for r in SIDE_MODELS if (models or {}).get(r.name) is not None}
     on = lambda flag: flag in given or bool(getattr(args, flag, False))
     _refuse([
@@ -319,10 +322,92 @@ def check_training(args, depth_priors=False, models=None):
          "--sky and --white_background together are refused: the sky map is the background"),
         (on("sky") and on("pose_opt"), "--sky and --pose_opt together are refused: the sky's gradient with respect to the "
          "camera (the ray direction of the lookup) is not carried"),
-    ] + [camera_dp_rule(r.flag, on(r.flag)) for r in SIDE_MODELS if r.not_shared])
+    ] + resolution_rules(args, on("pose_opt"), num_downscales, resolution_schedule, image_size) + [camera_dp_rule(r.flag, on(r.flag)) for r in SIDE_MODELS if r.not_shared])
     check_pose_args(args, depth_priors, enabled=on("pose_opt"))
     check_mcmc_args(args)
     check_contrib_prune_args(args)
+
+
+# ---------------------------------------------------------------------------------------------- resolution schedule
+MIN_LEVEL_SIDE = 16  # the shorter side of the coarsest level: one tile
+
+
+def schedule_level(iteration, first_iteration, num_downscales, resolution_schedule):
+    """The level a batch trains at: L = max(D - (it - it0) // R, 0), `it` the batch's first image counter (the `a` of
+    its `iteration[a,b)` line), `it0` the first batch's.  nerfstudio splatfacto's num_downscales / resolution_schedule."""
+    return max(int(num_downscales) - (int(iteration) - int(first_iteration)) // int(resolution_schedule), 0)
+
+
+def resolution_rules(args, pose_opt=False, num_downscales=None, resolution_schedule=None, image_size=None):
+    """The (condition, message) rules of --num_downscales / --resolution_schedule for check_training."""
+    D = int(getattr(args, "num_downscales", 0) if num_downscales is None else num_downscales)
+    R = int(getattr(args, "resolution_schedule", 3000) if resolution_schedule is None else resolution_schedule)
+    ws = dp.world_size()
+    side = None if image_size is None or D < 0 else -(-min(int(image_size[0]), int(image_size[1])) // (1 << min(D, 30)))
+    return [
+        (D < 0, "--num_downscales must be >= 0, got {}".format(D)),
+        (R <= 0, "--resolution_schedule must be > 0 (images per level), got {}".format(R)),
+        (D > 0 and pose_opt, "--num_downscales and --pose_opt together are refused: pose refinement rewrites the camera "
+         "objects it was attached to, and the level views of the resolution schedule would go stale"),
+        (D > 0 and ws > 1, "--num_downscales is not supported with {}; train on one GPU or without --num_downscales".format(
+            dp.refusal(ws, "the level switch is not agreed"))),
+        (D > 0 and side is not None and side < MIN_LEVEL_SIDE, "--num_downscales {} is too large for {} images: the shorter "
+         "side of the coarsest level would be {} pixels, fewer than {}".format(
+             D, "x".join(str(int(v)) for v in (image_size or (0, 0))[::-1]), side, MIN_LEVEL_SIDE)),
+    ]
+
+
+class _Resolution:
+    """The resolution schedule of a run (D = --num_downscales > 0): which level a batch trains at, the LevelCameras of
+    that level (one at a time; none at level 0), the global image size that goes with it, and full_size(), the one way
+    anything outside the training step renders a full-size camera."""
+
+    def __init__(self, train_cameras, num_downscales, resolution_schedule, bsz, first_iteration, log_file):
+        self.cameras, self.bsz, self.it0, self.log_file = train_cameras, bsz, first_iteration, log_file
+        self.D, self.R = int(num_downscales), int(resolution_schedule)
+        self.full = (int(train_cameras[0].image_height), int(train_cameras[0].image_width))
+        self.level, self.levels = None, None
+
+    def level_at(self, iteration):
+        return schedule_level(iteration, self.it0, self.D, self.R)
+
+    def size(self):
+        return self.levels.size if self.levels is not None else self.full
+
+    def enter(self, iteration):
+        """Called at the head of every batch: switches the level when the schedule says so."""
+        level = self.level_at(iteration)
+        if level == self.level:
+            return
+        self.level, self.levels = level, None  # the previous level's buffers are dropped before the new ones are built
+        if level > 0:
+            self.levels = LevelCameras(self.cameras, level, self.bsz)
+        h, w = self.size()
+        utils.set_img_size(h, w)
+        self.log_file.write("resolution level {}: {}x{} from iteration {}\n".format(level, w, h, iteration))
+
+    def batch(self, batch):
+        return batch if self.levels is None else self.levels.batch(batch)
+
+    def shells(self, iteration, batch):
+        """A coming batch's cameras as that batch will get them (no image yet), or None across a level switch."""
+        if batch is None or self.level_at(iteration) != self.level:
+            return None
+        return batch if self.levels is None else [self.levels.views[id(c)] for c in batch]
+
+    @contextlib.contextmanager
+    def full_size(self):
+        """Inside: the global image size is the full one (evaluation, contribution pruning, anything that renders a camera
+        outside the training step); the level's size is restored afterwards."""
+        utils.set_img_size(*self.full)
+        try:
+            yield
+        finally:
+            utils.set_img_size(*self.size())
+
+    def close(self):
+        self.levels = None
+        utils.set_img_size(*self.full)
 
 
 class _BatchSource:
@@ -440,7 +525,8 @@ def _setup_before_clock(args, gaussians, pt):
 
 
 def training(gaussians, scene, train_cameras, test_cameras, log_file, iterations=None,
-             test_iterations=(), background=None, shuffle_seed=0, phase_times=None, **side_models):
+             test_iterations=(), background=None, shuffle_seed=0, phase_times=None, num_downscales=None,
+             resolution_schedule=None, **side_models):
     """Runs `iterations` images of training; returns the End2endTimer.
     `side_models`: exposure=, bilagrid=, sky=, pose= (the names of SIDE_MODELS; each optional, attached to its cameras by
     its build_* function).  All are stepped after every batch in the table's order (end_batch), on the current stream --
@@ -453,13 +539,34 @@ def training(gaussians, scene, train_cameras, test_cameras, log_file, iterations
 
     Camera-DP: when a process group is up every rank runs this same loop over the same shuffled order, takes
     cameras rank::ranks of each GLOBAL batch (bsz x ranks images), and the image counter strides by the global batch; the
-    engine does the one exchange per batch, densification reduces its statistics and draws identical split samples."""
+    engine does the one exchange per batch, densification reduces its statistics and draws identical split samples.
+
+    Resolution schedule (`num_downscales` D, `resolution_schedule` R; None: the values of the args):
+    with D > 0 a batch whose first image counter is `it` trains at level schedule_level(it, 1, D, R) on the level's views of
+    its cameras (cameras.LevelCameras) with the global image size set to the level's; evaluation and contribution pruning
+    run at full size (_Resolution.full_size).  When training returns or raises, the global image size is the full one."""
+    args = utils.get_args()
+    D = int(getattr(args, "num_downscales", 0) if num_downscales is None else num_downscales)
+    R = int(getattr(args, "resolution_schedule", 3000) if resolution_schedule is None else resolution_schedule)
+    # the schedule: None when off -- no LevelCameras, no new kernel, not one call differs
+    res = _Resolution(train_cameras, D, R, args.bsz, 1, log_file) if D > 0 and R > 0 and train_cameras else None
+    try:
+        return _training(gaussians, scene, train_cameras, test_cameras, log_file, iterations, test_iterations, background,
+                         shuffle_seed, phase_times, side_models, D, R, res)
+    finally:
+        if res is not None:
+            res.close()
+
+
+def _training(gaussians, scene, train_cameras, test_cameras, log_file, iterations, test_iterations, background,
+              shuffle_seed, phase_times, side_models, num_downscales, resolution_schedule, res):
     args = utils.get_args()
     if set(side_models) - {r.name for r in SIDE_MODELS}:
         raise TypeError("training() got unexpected keyword arguments {}".format(sorted(side_models)))
     models = [side_models[r.name] for r in SIDE_MODELS if side_models.get(r.name) is not None]
     depth_priors = any(getattr(c, "invdepth", None) is not None for c in train_cameras)
-    check_training(args, depth_priors, side_models)
+    check_training(args, depth_priors, side_models, num_downscales, resolution_schedule,
+                   (train_cameras[0].image_height, train_cameras[0].image_width) if train_cameras else None)
     bsz, ws = args.bsz, dp.world_size()
     gbsz = bsz * ws
     if ws > 1:
@@ -494,6 +601,7 @@ def training(gaussians, scene, train_cameras, test_cameras, log_file, iterations
     iter_hook = pt.pop("iter_hook", None)  # diagnosis only (bench.py --trainer-trace): called after every iteration
     _setup_before_clock(args, gaussians, pt)
     timer = End2endTimer()
+    full_size = res.full_size if res is not None else contextlib.nullcontext
     timer.start()
     for iteration in range(1, iterations + 1, gbsz):
         utils.set_cur_iter(iteration)
@@ -501,10 +609,14 @@ def training(gaussians, scene, train_cameras, test_cameras, log_file, iterations
         if utils.check_update_at_this_iter(iteration, gbsz, 1000, 0):
             gaussians.oneupSHdegree()
         batch, next_batch = batches.next(more=iteration + gbsz <= iterations)
+        level_batch = batch
+        if res is not None:  # the batch's level: its cameras' views, their ground truth resampled into the ring
+            res.enter(iteration)
+            level_batch, next_batch = res.batch(batch), res.shells(iteration + gbsz, next_batch)
         if host_rows:
             hint_next_batch(gaussians, next_batch)
         _t = time.perf_counter()
-        losses, names, sparsity, visibility = run_batch(batch)
+        losses, names, sparsity, visibility = run_batch(level_batch)
         _acc(pt, "engine", _t)
         _t = time.perf_counter()
         # with depth priors: the depth term's weight of this iteration, next to the losses it is part of
@@ -521,9 +633,10 @@ def training(gaussians, scene, train_cameras, test_cameras, log_file, iterations
             _check_device()
             if hasattr(gaussians, "flush_lazy_rows"):  # deferred row steps (and, owner-computes DP, the exchange)
                 gaussians.flush_lazy_rows()
-            evaluate("train", iteration, train_cameras, render_fn, log_file, max_images=5)
-            if test_cameras:
-                evaluate("test", iteration, test_cameras, render_fn, log_file)
+            with full_size():
+                evaluate("train", iteration, train_cameras, render_fn, log_file, max_images=5)
+                if test_cameras:
+                    evaluate("test", iteration, test_cameras, render_fn, log_file)
             timer.start()
         n_before = gaussians.get_xyz.shape[0]
         _t = time.perf_counter()
@@ -558,11 +671,12 @@ def training(gaussians, scene, train_cameras, test_cameras, log_file, iterations
             for model in models:
                 model.flush()
             _t = time.perf_counter()
-            contribution_prune(gaussians, train_cameras, getattr(args, "contrib_prune_mode", "sum"),
-                               float(getattr(args, "contrib_prune_ratio", 0.3)),
-                               float(getattr(args, "contrib_prune_threshold", 0.01)),
-                               resort=spatial and bool(getattr(gaussians, "fuse_sort_into_prune", False)),
-                               log_file=log_file, iteration=iteration)
+            with full_size():
+                contribution_prune(gaussians, train_cameras, getattr(args, "contrib_prune_mode", "sum"),
+                                   float(getattr(args, "contrib_prune_ratio", 0.3)),
+                                   float(getattr(args, "contrib_prune_threshold", 0.01)),
+                                   resort=spatial and bool(getattr(gaussians, "fuse_sort_into_prune", False)),
+                                   log_file=log_file, iteration=iteration)
             if spatial:
                 gaussians.spatial_sort()
             _acc(pt, "contrib_prune", _t)
@@ -588,13 +702,14 @@ def training(gaussians, scene, train_cameras, test_cameras, log_file, iterations
 
 def train_from_colmap(source_path, model_path, strategy="clm_offload", iterations=None, eval=False, resolution=1,
                       images="images", test_iterations=(), save=True, masks=None, alpha_mask=False, depths=None,
-                      **arg_overrides):
+                      num_downscales=0, resolution_schedule=3000, **arg_overrides):
     """A COLMAP directory -> trained model (row f1): `colmap_scene.load_colmap_scene` (cameras, held-out
     split, scene radius, sparse points) -> `create_from_pcd` with `spatial_lr_scale = cameras_extent` ->
     `training_setup` -> `training` (log lines of the reference in `<model_path>/python_ws=1_rk=0.log`) ->
     `point_cloud/iteration_N/point_cloud.ply` (scene/__init__.py:41-143, train.py:60-131 for the order of
     these steps).  `strategy`: clm_offload | no_offload | naive_offload; `masks` / `alpha_mask` / `depths`: the arguments of
-    colmap_scene.load_colmap_scene; `arg_overrides`: any flag of `utils.default_args`, described there and, for the ones the
+    colmap_scene.load_colmap_scene; `num_downscales` / `resolution_schedule`: the
+    resolution schedule (training()); `arg_overrides`: any flag of `utils.default_args`, described there and, for the ones the
     command line has, in OPTIONS.  Every refusal is raised by check_training before anything is loaded.  A side model that
     is asked for (SIDE_MODELS) is written next to the ply and stays reachable as `scene.<name>`, None when off.
     Returns (gaussians, scene, timer)."""
@@ -603,7 +718,8 @@ def train_from_colmap(source_path, model_path, strategy="clm_offload", iteration
     from .strategies.naive_offload import GaussianModelNaiveOffload
     from .strategies.no_offload import GaussianModelNoOffload
     assert strategy in ("clm_offload", "no_offload", "naive_offload"), strategy
-    args = utils.default_args(**arg_overrides)
+    args = utils.default_args(num_downscales=int(num_downscales), resolution_schedule=int(resolution_schedule),
+                              **arg_overrides)
     setattr(args, strategy, True)
     args.source_path, args.model_path, args.eval = source_path, model_path, bool(eval)
     if iterations is not None:
@@ -618,6 +734,7 @@ def train_from_colmap(source_path, model_path, strategy="clm_offload", iteration
     sizes = {(c.image_height, c.image_width) for c in scene.train_cameras + scene.test_cameras}
     assert len(sizes) == 1, f"all images must share one size (utils.get_img_width/height are global): {sizes}"
     h, w = next(iter(sizes))
+    _refuse(resolution_rules(args, image_size=(h, w)))  # (the one rule that needs the images' size)
     utils.set_img_size(h, w)
     utils.set_cur_iter(1)
     gaussians = {"clm_offload": GaussianModelCLMOffload, "no_offload": GaussianModelNoOffload,
@@ -706,6 +823,10 @@ OPTIONS = (
     _opt("--mcmc_refine_stop_iter", type=int), _opt("--mcmc_refine_every", type=int),
     _opt("--mcmc_min_opacity", type=float), _opt("--mcmc_opacity_reg", type=float), _opt("--mcmc_scale_reg", type=float),
     _opt("--disable_auto_densification", action="store_true"),
+    _opt("--num_downscales", type=int, metavar="D", help="resolution schedule (splatfacto's num_downscales): train at 1/2^D "
+         "of the size first and double it every --resolution_schedule images; ground truth, masks and depth priors are "
+         "area-resampled on the device; evaluation and the final model are full size (single GPU; not with --pose_opt)"),
+    _opt("--resolution_schedule", type=int, metavar="R", help="--num_downscales: images trained at each coarse level"),
     _opt("--contrib_prune_iterations", type=int, nargs="*", metavar="I", conv=tuple, help="contribution pruning: image "
          "counters at which the training cameras are scored by blend weight and the model is pruned; each after "
          "densify_until_iter unless --disable_auto_densification (no_offload or clm_offload; single GPU; not with --mcmc)"),

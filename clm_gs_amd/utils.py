@@ -78,6 +78,11 @@ def default_args(**over):
         # "max" the rows whose largest weight stays below contrib_prune_threshold (RadSplat); refusals:
         # contribution.check_contrib_prune_args
         contrib_prune_iterations=(), contrib_prune_mode="sum", contrib_prune_ratio=0.3, contrib_prune_threshold=0.01,
+        # this build: resolution schedule (nerfstudio splatfacto's num_downscales / resolution_schedule): a batch whose first
+        # image counter is `it` trains at level L = max(num_downscales - (it - 1) // resolution_schedule, 0), i.e. at
+        # ceil(size / 2^L), on ground truth area-resampled on the device (csrc/resample.hip, cameras.LevelCameras);
+        # 0 = off: every image at full size, nothing more is launched.  Refusals: trainer.resolution_rules
+        num_downscales=0, resolution_schedule=3000,
         lr_scale_mode="sqrt", bsz=1, exact_filter=True, log_cpu_adam_trailing_overhead=False,
         # Debug
         stop_update_param=False, drop_initial_3dgs_p=0.0,

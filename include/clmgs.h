@@ -866,6 +866,19 @@ int clmgs_adam_small_deferred(void* stream, int64_t n, float* const* params, flo
  * counterpart; callers check it where they synchronise anyway (evaluation, saving, the end of a benchmark). */
 int clmgs_device_errors(uint32_t* bits, int reset);
 
+/* ---- resolution schedule (csrc/resample.hip): exact integer area resampling to level L >= 1, f = 2^L,
+ * Ho = ceil(H / f), Wo = ceil(W / f); the image extent is kept (pixel pitch W/Wo x H/Ho).  With
+ *   wx(j,x) = max(0, min((x+1) Wo, (j+1) W) - max(x Wo, j W)),  wy(i,y) likewise from H, Ho,
+ *   S(i,j) = sum_y sum_x wy(i,y) wx(j,x) p[y,x]:
+ *   u8 / u16: out = (2 S + W H) / (2 W H) (round half up); u8 takes `planes` contiguous planes [planes,H,W], u16 one.
+ *   mask:     p = [m != 0]; out = 255 where 2 S >= W H (at least half of the cell's area is counted), else 0; *count
+ *             (device int64, 8-byte aligned) is zeroed on the stream and receives the number of 255s.
+ * src and dst are contiguous and do not overlap; H, W <= 32768; 1 <= level <= 8 (level 0 is the input: no kernel).
+ * Integer arithmetic only, the same bits on every run.  Bad arguments return CLMGS_EINVAL before anything is written. */
+int clmgs_area_resample_u8(void* stream, int planes, int H, int W, int level, const uint8_t* src, uint8_t* dst);
+int clmgs_area_resample_u16(void* stream, int H, int W, int level, const uint16_t* src, uint16_t* dst);
+int clmgs_area_resample_mask(void* stream, int H, int W, int level, const uint8_t* src, uint8_t* dst, int64_t* count);
+
 /* ---- pinned host memory  (numba.cuda.pinned_array at clm_offload/gaussian_model.py:34-44) */
 void* clmgs_pinned_alloc(size_t bytes);
 int clmgs_pinned_free(void* p);
