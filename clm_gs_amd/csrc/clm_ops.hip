@@ -651,17 +651,28 @@ struct SmallDeferred {
   int to_step;
 };
 
+//
+// SEL (clmgs_adam_small_deferred_sel; the plain entry runs the <false> form, which is the kernel as it was):
+//  * blk_cams != NULL: one word per block, bit c = "the candidate test admits camera c" for some row of the block (every
+//    camera is then tested: no early exit).  blk_flag[blk] != 0 <=> blk_cams[blk] != 0.
+//  * blk_sel != NULL: the launch takes only the blocks with ((blk_sel[blk] & sel_mask) != 0) == sel_want; a block it
+//    does not take is neither read nor written, and neither are its blk_flag / blk_last / blk_cams entries.  Two launches
+//    with sel_want 0 and 1 do, block for block, what one launch without a selector does: the head of a batch can be split
+//    into the blocks whose inputs are final early and the rest ("Batch head under the last backward").
+template <bool SEL>
 __global__ void __launch_bounds__(SA_ROWS)
 adam_small_deferred_kernel(int64_t n, SmallAdam t, float4* __restrict__ packed_p, const float4* __restrict__ packed_g,
                            const int32_t* __restrict__ g_stamp, int32_t* __restrict__ blk_last, SmallDeferred d,
                            float beta1, float beta2, float ob1, float ob2, float eps, float grad_scale, int C,
                            const float* __restrict__ viewmats, const float* __restrict__ Ks, float W, float H, float eps2d,
                            float near_plane, float far_plane, int flush_all, uint8_t* __restrict__ blk_flag, int n_hist,
-                           uint32_t* __restrict__ dev_err) {
+                           uint32_t* __restrict__ dev_err, unsigned long long* __restrict__ blk_cams,
+                           const unsigned long long* __restrict__ blk_sel, unsigned long long sel_mask, int sel_want) {
   __shared__ __attribute__((aligned(16))) float sg[SA_ROWS * 12];
   __shared__ __attribute__((aligned(16))) float sp[SA_ROWS * 12];
   __shared__ int gstep_s[SA_ROWS];
   __shared__ float cam_s[VB_MAX_CAMS][VB_CAM_F];
+  __shared__ unsigned long long wave_cams[SA_ROWS / 64];  // (SEL) the cameras each wave's rows are candidates of
   const int tid = threadIdx.x;
   if (!flush_all) {
     for (int c = tid; c < C; c += SA_ROWS) vis_store_cam(cam_s[c], viewmats + 16 * c, Ks + 9 * c, W, H);
@@ -670,6 +681,7 @@ adam_small_deferred_kernel(int64_t n, SmallAdam t, float4* __restrict__ packed_p
   const float far_m = far_plane + fabsf(far_plane) * 1e-5f;
   const int64_t n_blocks = (n + SA_ROWS - 1) / SA_ROWS;
   for (int64_t blk = blockIdx.x; blk < n_blocks; blk += gridDim.x) {
+    if (SEL && blk_sel && ((blk_sel[blk] & sel_mask) != 0ull) != (sel_want != 0)) continue;  // (block-uniform)
     const int last = blk_last[blk];
     int k = d.to_step - last;
     if (k <= 0 && (flush_all || !blk_flag)) continue;  // (block-uniform)
@@ -688,6 +700,7 @@ adam_small_deferred_kernel(int64_t n, SmallAdam t, float4* __restrict__ packed_p
       // k steps?  Also handed to the exact visibility pass that follows (blk_flag: it skips the blocks that cannot)
       const int kk = min(max(k, 0), SD_KMAX);
       bool cand = false;
+      unsigned long long row_cams = 0ull;
       if (tid < rows) {
         const float* x = t.p[0] + 3 * (row0 + tid);
         const float* ls = t.p[2] + 3 * (row0 + tid);
@@ -695,11 +708,33 @@ adam_small_deferred_kernel(int64_t n, SmallAdam t, float4* __restrict__ packed_p
         const float sgn = __expf(fmaxf(ls[0], fmaxf(ls[1], ls[2]))) * d.scale_gain[kk];
         const float smax2g = sgn * sgn;
         cand = !(smax2g < 1e30f);  // NaN / overflowing scales: current values decide
-        for (int c = 0; c < C && !cand; ++c)
-          cand = vis_candidate(lds_cam(cam_s[c]), cam_s[c][16], m, smax2g, d.pos_margin[kk], W, H, eps2d, near_m, far_m);
+        if (SEL && blk_cams) {
+          unsigned long long cw = cand ? ~0ull >> (64 - C) : 0ull;  // (1 <= C <= 64)
+          for (int c = 0; c < C && !cand; ++c)
+            if (vis_candidate(lds_cam(cam_s[c]), cam_s[c][16], m, smax2g, d.pos_margin[kk], W, H, eps2d, near_m, far_m))
+              cw |= 1ull << c;
+          cand = cw != 0ull;
+          row_cams = cw;
+        } else {
+          for (int c = 0; c < C && !cand; ++c)
+            cand = vis_candidate(lds_cam(cam_s[c]), cam_s[c][16], m, smax2g, d.pos_margin[kk], W, H, eps2d, near_m, far_m);
+        }
+      }
+      if (SEL && blk_cams) {
+        // OR over the wave (wave-uniform: one ballot per camera), one word per wave to LDS; the barrier inside
+        // __syncthreads_or publishes them, and the next block's words are written after the barrier at its head
+        unsigned long long ww = 0ull;
+        for (int c = 0; c < C; ++c)
+          if (__ballot((row_cams >> c) & 1ull)) ww |= 1ull << c;
+        if ((tid & 63) == 0) wave_cams[tid >> 6] = ww;
       }
       const bool any = __syncthreads_or(cand);
       if (blk_flag && tid == 0) blk_flag[blk] = any ? 1 : 0;
+      if (SEL && blk_cams && tid == 0) {
+        unsigned long long bw = 0ull;
+        for (int w = 0; w < SA_ROWS / 64; ++w) bw |= wave_cams[w];
+        blk_cams[blk] = bw;
+      }
       if (k <= 0 || (!any && k < SD_KMAX)) continue;
     }
     // ---- the block's k waiting steps.  Gradient lines: a row's line belongs to step g_stamp[row]; it is waiting iff
@@ -1137,6 +1172,20 @@ extern "C" int clmgs_small_deferred_kmax(void) { return SD_KMAX; }
 // (it must flush at least every n_hist steps): checked on the host side by construction (a block is never left
 // behind for more than kmax steps: the kernel forces it at k == kmax, and the caller trims its history to kmax entries);
 // the kernel itself raises value 4 of the device error word (clmgs_device_errors) if it ever meets one.
+//
+// _sel: the same with a per-block camera word as a further output and / or a block selector (see the kernel): blk_cams
+// [ceil(n / 256)] (optional; needs blk_flag), blk_sel_bits[ceil(n / 256)] (optional; not with flush_all).  With both NULL
+// it is the plain entry.
+extern "C" int clmgs_adam_small_deferred_sel(void* stream, int64_t n, float* const* params, float* const* exp_avg,
+                                             float* const* exp_avg_sq, void* packed_p, const void* packed_g,
+                                             const int32_t* g_stamp, int32_t* blk_last, int to_step, int n_hist,
+                                             const double* lr4_hist, const int32_t* step_index, const float* pos_margin,
+                                             const float* scale_gain, double beta1, double beta2, double eps,
+                                             float grad_scale, int C, const float* viewmats, const float* Ks, int width,
+                                             int height, float eps2d, float near_plane, float far_plane, int flush_all,
+                                             uint8_t* blk_flag, uint64_t* blk_cams, const uint64_t* blk_sel_bits,
+                                             uint64_t sel_mask, int sel_want);
+
 extern "C" int clmgs_adam_small_deferred(void* stream, int64_t n, float* const* params, float* const* exp_avg,
                                          float* const* exp_avg_sq, void* packed_p, const void* packed_g,
                                          const int32_t* g_stamp, int32_t* blk_last, int to_step, int n_hist,
@@ -1145,11 +1194,30 @@ extern "C" int clmgs_adam_small_deferred(void* stream, int64_t n, float* const* 
                                          float grad_scale, int C, const float* viewmats, const float* Ks, int width,
                                          int height, float eps2d, float near_plane, float far_plane, int flush_all,
                                          uint8_t* blk_flag) {
+  return clmgs_adam_small_deferred_sel(stream, n, params, exp_avg, exp_avg_sq, packed_p, packed_g, g_stamp, blk_last,
+                                       to_step, n_hist, lr4_hist, step_index, pos_margin, scale_gain, beta1, beta2, eps,
+                                       grad_scale, C, viewmats, Ks, width, height, eps2d, near_plane, far_plane,
+                                       flush_all, blk_flag, nullptr, nullptr, 0, 0);
+}
+
+extern "C" int clmgs_adam_small_deferred_sel(void* stream, int64_t n, float* const* params, float* const* exp_avg,
+                                             float* const* exp_avg_sq, void* packed_p, const void* packed_g,
+                                             const int32_t* g_stamp, int32_t* blk_last, int to_step, int n_hist,
+                                             const double* lr4_hist, const int32_t* step_index, const float* pos_margin,
+                                             const float* scale_gain, double beta1, double beta2, double eps,
+                                             float grad_scale, int C, const float* viewmats, const float* Ks, int width,
+                                             int height, float eps2d, float near_plane, float far_plane, int flush_all,
+                                             uint8_t* blk_flag, uint64_t* blk_cams, const uint64_t* blk_sel_bits,
+                                             uint64_t sel_mask, int sel_want) {
   CLMGS_CHECK_ARG(n >= 0 && to_step >= 0 && n_hist >= 0 && n_hist <= SD_KMAX);
   CLMGS_CHECK_ARG(!blk_flag || !flush_all);
+  static_assert(VB_MAX_CAMS <= 64, "one bit per camera in a 64-bit word");
+  CLMGS_CHECK_ARG((!blk_cams || blk_flag) && (!blk_sel_bits || !flush_all) && (sel_want == 0 || sel_want == 1));
   if (n == 0) return 0;
   if (n_hist == 0) {  // nothing recorded yet: nothing waits, and nothing is known about visibility
+    CLMGS_CHECK_ARG(!blk_sel_bits);  // (a selector splits a head that has steps waiting)
     if (blk_flag) CLMGS_HIP(hipMemsetAsync(blk_flag, 1, (size_t)((n + SA_ROWS - 1) / SA_ROWS), (hipStream_t)stream));
+    if (blk_cams) CLMGS_HIP(hipMemsetAsync(blk_cams, 0xff, 8 * (size_t)((n + SA_ROWS - 1) / SA_ROWS), (hipStream_t)stream));
     return 0;
   }
   CLMGS_CHECK_ARG(packed_p && packed_g && g_stamp && blk_last && lr4_hist && step_index && pos_margin && scale_gain &&
@@ -1171,10 +1239,13 @@ extern "C" int clmgs_adam_small_deferred(void* stream, int64_t n, float* const* 
   }
   d.to_step = to_step;
   const float ob1 = (float)(1.0 - beta1), ob2 = (float)(1.0 - beta2);
-  hipLaunchKernelGGL(adam_small_deferred_kernel, dim3(min(ceil_div(n, SA_ROWS), 256 * 16)), dim3(SA_ROWS), 0,
+  const auto kern = (blk_cams || blk_sel_bits) ? adam_small_deferred_kernel<true> : adam_small_deferred_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3(min(ceil_div(n, SA_ROWS), 256 * 16)), dim3(SA_ROWS), 0,
                      (hipStream_t)stream, n, t, (float4*)packed_p, (const float4*)packed_g, g_stamp, blk_last, d,
                      (float)beta1, (float)beta2, ob1, ob2, (float)eps, grad_scale, C, viewmats, Ks, (float)width,
-                     (float)height, eps2d, near_plane, far_plane, flush_all, blk_flag, n_hist, device_error_word());
+                     (float)height, eps2d, near_plane, far_plane, flush_all, blk_flag, n_hist, device_error_word(),
+                     (unsigned long long*)blk_cams, (const unsigned long long*)blk_sel_bits,
+                     (unsigned long long)sel_mask, sel_want);
   CLMGS_LAUNCH_CHECK();
   return 0;
 }

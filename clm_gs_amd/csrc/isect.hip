@@ -654,13 +654,19 @@ __device__ __forceinline__ int vis_classify(const Cam& c, float kc, const float 
   return (mx + Rb <= 0.f || mx - Rb >= W || my + Rb <= 0.f || my - Rb >= H) ? 0 : 2;
 }
 
+// SEL (clmgs_visibility_select_count_blocks_sel; the plain entries run the <false> form, which is the kernel as it was):
+// with blk_sel != NULL the launch takes only the blocks of 256 rows with ((blk_sel[blk] & sel_mask) != 0) == sel_want;
+// a block it does not take is not read and its words are not written, so two launches with sel_want 0 and 1 leave the
+// words of one launch without a selector.
+template <bool SEL>
 __global__ void __launch_bounds__(256)
 visibility_bits_kernel(int C, int N, int W64, const float* __restrict__ means,
                        const float* __restrict__ quats_raw, const float* __restrict__ log_scales,
                        const float* __restrict__ viewmats, const float* __restrict__ Ks, float W, float H,
                        float eps2d, float near_plane, float far_plane, float radius_clip,
                        unsigned long long* __restrict__ bits, int64_t* __restrict__ counts,
-                       const uint8_t* __restrict__ blk_flag) {
+                       const uint8_t* __restrict__ blk_flag, const unsigned long long* __restrict__ blk_sel,
+                       unsigned long long sel_mask, int sel_want) {
   // blk_flag != NULL: one byte per block of 256 rows; 0 = the caller KNOWS that no row of the block passes the cull in any
   // camera (clmgs_adam_small_deferred's candidate test, a superset of this one): the block's words are zeros, its rows
   // are not read
@@ -691,9 +697,12 @@ visibility_bits_kernel(int C, int N, int W64, const float* __restrict__ means,
   // load -> classify -> barrier per block; without the prefetch its time was memory + compute)
   float nm0 = 0.f, nm1 = 0.f, nm2 = 0.f, nl0 = 0.f, nl1 = 0.f, nl2 = 0.f;
   float4 nq = make_float4(0.f, 0.f, 0.f, 0.f);
+  auto taken = [&](int rbn) {  // (block-uniform)
+    return !SEL || !blk_sel || ((blk_sel[rbn] & sel_mask) != 0ull) == (sel_want != 0);
+  };
   auto fetch = [&](int rbn) {
     const int n = rbn * 256 + tid;
-    const bool live_n = rbn < n_rb && (!blk_flag || blk_flag[rbn]);
+    const bool live_n = rbn < n_rb && taken(rbn) && (!blk_flag || blk_flag[rbn]);
     const int nn = (live_n && n < N) ? n : 0;
     nm0 = means[3 * nn]; nm1 = means[3 * nn + 1]; nm2 = means[3 * nn + 2];
     nq = *reinterpret_cast<const float4*>(quats_raw + 4 * nn);
@@ -707,6 +716,7 @@ visibility_bits_kernel(int C, int N, int W64, const float* __restrict__ means,
     const float4 q4 = nq;
     const float s0 = __expf(nl0), s1 = __expf(nl1), s2 = __expf(nl2);
     fetch(rb + gridDim.x);
+    if (!taken(rb)) continue;
     if (blk_flag && !blk_flag[rb]) {  // (block-uniform)
       if (tid < (C + 1) * 4) {
         const int c = tid >> 2, w = rb * 4 + (tid & 3);
@@ -848,6 +858,15 @@ extern "C" int clmgs_visibility_select_count_blocks(void* stream, int C, int N, 
                                                     float radius_clip, void* temp, size_t temp_bytes,
                                                     int64_t* cum_totals, const uint8_t* block_flags);
 
+extern "C" int clmgs_visibility_select_count_blocks_sel(void* stream, int C, int N, const float* means,
+                                                        const float* quats_raw, const float* log_scales,
+                                                        const float* viewmats, const float* Ks, int width, int height,
+                                                        float eps2d, float near_plane, float far_plane,
+                                                        float radius_clip, void* temp, size_t temp_bytes,
+                                                        int64_t* cum_totals, const uint8_t* block_flags,
+                                                        const uint64_t* blk_sel_bits, uint64_t sel_mask, int sel_want,
+                                                        int scan);
+
 extern "C" int clmgs_visibility_select_count(void* stream, int C, int N, const float* means,
                                              const float* quats_raw, const float* log_scales,
                                              const float* viewmats, const float* Ks, int width,
@@ -866,8 +885,25 @@ extern "C" int clmgs_visibility_select_count_blocks(void* stream, int C, int N, 
                                                     float eps2d, float near_plane, float far_plane,
                                                     float radius_clip, void* temp, size_t temp_bytes,
                                                     int64_t* cum_totals, const uint8_t* block_flags) {
+  return clmgs_visibility_select_count_blocks_sel(stream, C, N, means, quats_raw, log_scales, viewmats, Ks, width,
+                                                  height, eps2d, near_plane, far_plane, radius_clip, temp, temp_bytes,
+                                                  cum_totals, block_flags, nullptr, 0, 0, 1);
+}
+
+// blk_sel_bits != NULL (one word per 256 rows): only the blocks with ((blk_sel_bits[blk] & sel_mask) != 0) == sel_want
+// get their words written (see visibility_bits_kernel).  scan == 0: the words only -- a further call on the same `temp`
+// takes the other blocks and, with scan != 0, the scan over all words and cum_totals (not needed when scan == 0).
+extern "C" int clmgs_visibility_select_count_blocks_sel(void* stream, int C, int N, const float* means,
+                                                        const float* quats_raw, const float* log_scales,
+                                                        const float* viewmats, const float* Ks, int width, int height,
+                                                        float eps2d, float near_plane, float far_plane,
+                                                        float radius_clip, void* temp, size_t temp_bytes,
+                                                        int64_t* cum_totals, const uint8_t* block_flags,
+                                                        const uint64_t* blk_sel_bits, uint64_t sel_mask, int sel_want,
+                                                        int scan) {
   CLMGS_CHECK_ARG(C >= 1 && C <= 64 && N >= 1 && width > 0 && height > 0);  // bsz <= 64 (engine.py)
-  CLMGS_CHECK_ARG(means && quats_raw && log_scales && viewmats && Ks && temp && cum_totals);
+  CLMGS_CHECK_ARG(means && quats_raw && log_scales && viewmats && Ks && temp && (cum_totals || !scan));
+  CLMGS_CHECK_ARG((scan || blk_sel_bits) && (sel_want == 0 || sel_want == 1));
   CLMGS_CHECK_ARG(temp_bytes >= clmgs_visibility_select_temp_bytes(C, N));
   hipStream_t s = (hipStream_t)stream;
   const int W64 = (N + 63) / 64;
@@ -876,10 +912,13 @@ extern "C" int clmgs_visibility_select_count_blocks(void* stream, int C, int N, 
   unsigned long long* bits = (unsigned long long*)base; base += align_up(words * 8, 256);
   int64_t* counts = (int64_t*)base; base += align_up(words * 8, 256);
   int64_t* scratch = (int64_t*)base;
-  hipLaunchKernelGGL(visibility_bits_kernel, dim3(min(ceil_div((int64_t)W64 * 64, 256), 256 * 8)),
+  const auto kern = blk_sel_bits ? visibility_bits_kernel<true> : visibility_bits_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3(min(ceil_div((int64_t)W64 * 64, 256), 256 * 8)),
                      dim3(256), 0, s, C, N, W64, means, quats_raw, log_scales, viewmats, Ks,
-                     (float)width, (float)height, eps2d, near_plane, far_plane, radius_clip, bits, counts, block_flags);
+                     (float)width, (float)height, eps2d, near_plane, far_plane, radius_clip, bits, counts, block_flags,
+                     (const unsigned long long*)blk_sel_bits, (unsigned long long)sel_mask, sel_want);
   CLMGS_LAUNCH_CHECK();
+  if (!scan) return 0;
   const int rc = inclusive_scan_i64(s, (int64_t)words, counts, scratch);
   if (rc) return rc;
   // cum_totals[r] = number of set bits in rows 0..r (device array of C+1, read back by the caller)

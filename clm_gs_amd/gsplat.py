@@ -215,25 +215,54 @@ def visibility_radii(means, quats, scales, viewmats, Ks, width, height, eps2d=0.
     return radii
 
 
+def visibility_select_words(means, quats_raw, log_scales, viewmats, Ks, width, height, block_sel, eps2d=0.3,
+                            near_plane=0.01, far_plane=1e10, radius_clip=0.0, block_flags=None):
+    """The first of two launches of visibility_select over disjoint sets of 256-row blocks: the ballot words of the
+    blocks block_sel = (words int64 [ceil(N/256)], mask, want) selects -- ((words[blk] & mask) != 0) == want -- and
+    nothing else; no scan, no host read.  -> temp, to be handed to visibility_select(temp=, block_sel=(words, mask,
+    1 - want)), which takes the other blocks and finishes.  Enqueued, and `temp` allocated, on the current stream."""
+    L = _lib.lib()
+    means, quats_raw, log_scales = means.contiguous(), quats_raw.contiguous(), log_scales.contiguous()
+    viewmats, Ks = viewmats.contiguous(), Ks.contiguous()
+    C, N = viewmats.shape[0], means.shape[0]
+    tb = L.clmgs_visibility_select_temp_bytes(C, N)
+    temp = torch.empty((tb,), dtype=torch.uint8, device=means.device)
+    words, mask, want = block_sel
+    check(L.clmgs_visibility_select_count_blocks_sel(
+        stream(), C, N, dptr(means, F32), dptr(quats_raw, F32), dptr(log_scales, F32), dptr(viewmats, F32),
+        dptr(Ks, F32), int(width), int(height), float(eps2d), float(near_plane), float(far_plane),
+        float(radius_clip), dptr(temp), tb, None, dptr(block_flags, torch.uint8, True), dptr(words, I64),
+        int(mask) & 0xFFFFFFFFFFFFFFFF, int(want), 0))
+    return temp
+
+
 def visibility_select(means, quats_raw, log_scales, viewmats, Ks, width, height, eps2d=0.3,
-                      near_plane=0.01, far_plane=1e10, radius_clip=0.0, block_flags=None):
+                      near_plane=0.01, far_plane=1e10, radius_clip=0.0, block_flags=None, block_sel=None, temp=None):
     """The batch's visibility filters selected on the GPU: same cull as visibility_radii(raw=True)
     but without the radii[C,N] round trip and torch.nonzero -- one ballot word per (camera, 64
     Gaussians), a scan, and an emit pass.  -> (filters: tuple of C int64 index tensors (ascending),
-    touched_rows: int64 indices of the union over the cameras).  One host read (the C+1 totals)."""
+    touched_rows: int64 indices of the union over the cameras).  One host read (the C+1 totals).
+    block_sel + temp: the second of two launches (visibility_select_words made `temp` and the other blocks' words)."""
     L = _lib.lib()
     means, quats_raw, log_scales = means.contiguous(), quats_raw.contiguous(), log_scales.contiguous()
     viewmats, Ks = viewmats.contiguous(), Ks.contiguous()
     C, N = viewmats.shape[0], means.shape[0]
     dev = means.device
     tb = L.clmgs_visibility_select_temp_bytes(C, N)
-    temp = torch.empty((tb,), dtype=torch.uint8, device=dev)
+    assert (block_sel is None) == (temp is None)
+    if temp is None:
+        temp = torch.empty((tb,), dtype=torch.uint8, device=dev)
+    else:
+        assert temp.numel() == tb
+        temp.record_stream(torch.cuda.current_stream())  # (allocated on the first launch's stream)
     cum = torch.empty((C + 1,), dtype=I64, device=dev)
+    words, mask, want = block_sel if block_sel is not None else (None, 0, 0)
     # block_flags (uint8 per 256 rows, 0 = no row of the block can be visible: clmgs_adam_small_deferred's candidate test)
-    check(L.clmgs_visibility_select_count_blocks(
+    check(L.clmgs_visibility_select_count_blocks_sel(
         stream(), C, N, dptr(means, F32), dptr(quats_raw, F32), dptr(log_scales, F32), dptr(viewmats, F32),
         dptr(Ks, F32), int(width), int(height), float(eps2d), float(near_plane), float(far_plane),
-        float(radius_clip), dptr(temp), tb, dptr(cum), dptr(block_flags, torch.uint8, True)))
+        float(radius_clip), dptr(temp), tb, dptr(cum), dptr(block_flags, torch.uint8, True), dptr(words, I64, True),
+        int(mask) & 0xFFFFFFFFFFFFFFFF, int(want), 1))
     _t0 = time.perf_counter()
     ends = cum.tolist()  # the one host sync of the filter stage
     _lib.STATS["host_wait_s"] += time.perf_counter() - _t0

@@ -14,10 +14,25 @@ LAMBDA_DSSIM = 0.2
 TILE_SIZE = 16
 
 
-def select_filters(batched_cameras, xyz_gpu, scaling_raw_gpu, rotation_raw_gpu, block_flags=None):
+def select_filter_words(batched_cameras, xyz_gpu, scaling_raw_gpu, rotation_raw_gpu, cam_mats, block_flags, block_sel):
+    """The first of two launches of select_filters (gsplat.visibility_select_words): the ballot words of the blocks
+    `block_sel` selects, on the current stream, with the camera matrices cam_mats = (viewmats[C,4,4], Ks[C,3,3]) the caller
+    made on that stream -> temp for select_filters(block_sel=the other blocks, temp=temp)."""
+    from ..gsplat import visibility_select_words
+    args = utils.get_args()
+    for c in batched_cameras:
+        refuse_ortho(c, "select_filters")
+    with torch.no_grad():
+        return visibility_select_words(
+            xyz_gpu, rotation_raw_gpu, scaling_raw_gpu, cam_mats[0], cam_mats[1], int(utils.get_img_width()),
+            int(utils.get_img_height()), block_sel, radius_clip=args.radius_clip, block_flags=block_flags)
+
+
+def select_filters(batched_cameras, xyz_gpu, scaling_raw_gpu, rotation_raw_gpu, block_flags=None, block_sel=None,
+                   temp=None):
     """calculate_filters on the stored (raw) parameters, selected entirely on the GPU
     (gsplat.visibility_select) -> (filters, touched_rows): the same index sets as calculate_filters
-    plus the union over the batch's cameras."""
+    plus the union over the batch's cameras.  block_sel + temp: the second of two launches (select_filter_words)."""
     from ..gsplat import visibility_select
     args = utils.get_args()
     for c in batched_cameras:  # the selection kernels are pinhole ones
@@ -27,7 +42,8 @@ def select_filters(batched_cameras, xyz_gpu, scaling_raw_gpu, rotation_raw_gpu, 
         viewmats = torch.stack([c.world_view_transform.transpose(0, 1) for c in batched_cameras])
         filters, touched_rows = visibility_select(
             xyz_gpu, rotation_raw_gpu, scaling_raw_gpu, viewmats, Ks, int(utils.get_img_width()),
-            int(utils.get_img_height()), radius_clip=args.radius_clip, block_flags=block_flags)
+            int(utils.get_img_height()), radius_clip=args.radius_clip, block_flags=block_flags, block_sel=block_sel,
+            temp=temp)
     assert all(f.numel() > 0 for f in filters), (
         "every camera must see at least one gaussian (base_engine.py:64-67)")
     return filters, touched_rows

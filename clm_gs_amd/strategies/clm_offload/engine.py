@@ -34,8 +34,8 @@ from ...clm_kernels import (apply_camera_colour, check_depth_prior_args,
                             send_shs2cpu_grad_buffer_stream, send_shs2gpu_stream, spherical_harmonics_bwd_inplace)
 from ...densification import check_mcmc_args, update_densification_stats_offload_accum_grads
 from ...host import pinned_empty
-from ..base_engine import (select_filters, calculate_filters, camera_forward_ops, camera_loss_backward,
-                           pipeline_forward_one_step)
+from ..base_engine import (select_filters, select_filter_words, calculate_filters, camera_forward_ops,
+                           camera_loss_backward, pipeline_forward_one_step)
 
 _BITMAP_DTYPE = {4: torch.int8, 8: torch.int8, 16: torch.int16, 32: torch.int32, 64: torch.int64}
 
@@ -288,6 +288,35 @@ class _Batch:
     """State of one HBM-resident batch, handed from stage to stage (see _train_one_batch_hbm)."""
 
 
+def _host_camera_mats(cams, device):
+    """(viewmats[C,4,4], Ks[C,3,3]) of the batch from the cameras' HOST constants, uploaded on the current stream from
+    pinned memory: the early head launch (head_overlap) runs on a stream that is not ordered after whatever made the
+    cameras' device tensors.  The values are the device tensors' (cameras.py keeps both)."""
+    import numpy as np
+    C = len(cams)
+    h = torch.from_numpy(np.concatenate([c._clmgs_host[0] for c in cams] + [c._clmgs_host[1] for c in cams])
+                         .astype(np.float32, copy=False)).pin_memory()
+    d = h.to(device, non_blocking=True)
+    return d[:16 * C].view(C, 4, 4), d[16 * C:].view(C, 3, 3)
+
+
+def _head_record(b):
+    """End of a batch on the pipelined single-GPU path with the small attributes deferred: what the NEXT batch's head needs
+    to run part of itself early (head_overlap; taken, checked and used by _stage_visibility) -- the event after the
+    backward of camera bsz-1-head_depth, this head's per-block camera words, the bit mask of the cameras that ran after that
+    event (bit index = a camera's position in the batch as given, before any reordering) and which camera ran last, and
+    what must still hold then: mutation counter, step, row count."""
+    sd = b.gaussians._small_def
+    # (small_defer_record re-makes the block table after a gap in the step numbering: then nothing is left)
+    if b.head_overlap and b.head_words is not None and b.head_event is not None and sd["hist"] \
+            and sd["hist"][-1][0] == b.step and sd["blk_last"] is b.head_blk_last:
+        mask = 0
+        for c in b.ordered_cams[-b.head_depth:]:  # the cameras whose backward had not been enqueued at the event
+            mask |= 1 << int(c)
+        sd["head"] = {"event": b.head_event, "words": b.head_words, "last": int(b.ordered_cams[-1]), "mask": mask,
+                      "mutations": b.gaussians._mutations, "step": b.step, "n": b.N}
+
+
 def _stage_visibility(b):
     """Stage 1: (camera-DP step S) + the batch's visibility filters and the union of touched rows, selected on the GPU."""
     gaussians, args, cams = b.gaussians, b.args, b.cameras
@@ -305,16 +334,48 @@ def _stage_visibility(b):
     b.small_deferred = bool(getattr(gaussians, "small_deferred", False) and b.fused and gaussians.lazy_rows
                             and not args.stop_update_param and getattr(args, "packed_small", True))
     blk_flags = None
+    # head_overlap: what the previous batch left for this head (_head_record) is TAKEN here -- whatever this batch turns
+    # out to be, the record is gone -- and used only if nothing has happened to the model since
+    sd = getattr(gaussians, "_small_def", None)
+    rec = sd.pop("head", None) if sd else None
+    b.head_words = b.head_event = None
+    b.head_overlap = bool(b.small_deferred and getattr(args, "head_overlap", True) and b.bsz >= 2 and not dp.active()
+                          and getattr(args, "overlap_cameras", True) in (True, "pipeline")
+                          and not getattr(args, "pose_opt", False) and sd["hist"]
+                          and all(getattr(c, "_clmgs_host", None) is not None for c in cams))
+    # how many of the batch's last cameras the early part of the NEXT head stays clear of (head_overlap_cameras)
+    b.head_depth = max(1, min(int(getattr(args, "head_overlap_cameras", 2)), b.bsz - 1))
+    sel = temp = None
     if b.small_deferred:
         with torch.no_grad():
-            blk_flags = gaussians.small_catch_up(cams)  # (also: which blocks of 256 rows can hold a visible row at all)
+            if b.head_overlap:
+                b.head_words = gaussians.small_head_words()
+                if (rec is not None and rec["mutations"] == getattr(gaussians, "_mutations", 0)
+                        and rec["step"] == sd["hist"][-1][0] and rec["n"] == N and rec["words"].shape == b.head_words.shape):
+                    # EARLY launch, on the front stream (idle since the last camera's binning), after the recorded
+                    # backward of the previous batch: the blocks none of its later cameras could see (DESIGN.md section
+                    # 3, "Batch head under the last backward"); LATE launch below, on this stream: the other blocks
+                    sel = (rec["words"], rec["mask"])
+                    s_front = _pipeline_streams(gaussians)["mem"][0]
+                    s_front.wait_event(rec["event"])
+                    with torch.cuda.stream(s_front):
+                        mats = _host_camera_mats(cams, gaussians._xyz.device)
+                        flags0 = gaussians.small_catch_up(cams, cam_words=b.head_words, sel=sel + (0,), cam_mats=mats)
+                        temp = select_filter_words(cams, gaussians._xyz.detach(), gaussians._scaling.detach(),
+                                                   gaussians._rotation.detach(), mats, flags0, sel + (0,))
+                    torch.cuda.current_stream().wait_stream(s_front)
+                    _lib.STATS["head_overlap_split"] = _lib.STATS.get("head_overlap_split", 0) + 1
+            # (also: which blocks of 256 rows can hold a visible row at all)
+            blk_flags = gaussians.small_catch_up(cams, cam_words=b.head_words, sel=sel + (1,) if sel else None)
+            b.head_blk_last = sd["blk_last"]
     with torch.no_grad():
         if b.fused:
             # same fast exp as the fused front end -> filter and render agree on every cull;
             # filters AND the union of touched rows are selected on the GPU in one pass
             with _lib.host_region("select_filters"):
                 b.filters, b.touched_rows = select_filters(cams, gaussians._xyz.detach(), gaussians._scaling.detach(),
-                                                           gaussians._rotation.detach(), block_flags=blk_flags)
+                                                           gaussians._rotation.detach(), block_flags=blk_flags,
+                                                           block_sel=sel + (1,) if sel else None, temp=temp)
         else:
             b.filters, _, _ = calculate_filters(cams, gaussians.get_xyz, gaussians.get_opacity,
                                                 gaussians.get_scaling, gaussians.get_rotation)
@@ -532,6 +593,11 @@ def _cameras_pipelined(b):
         with _lib.host_region("camera_backward"):
             camera_backward(gaussians, passes[k], b.grad_buf, b.small_gk, stats_delta=b.stats_d,
                             sh_stamp=b.ft_stamp, cur_step=step, release=True)
+        # head_overlap: the small-attribute gradient lines of every row the last head_depth cameras do not touch are final
+        # once this backward has run -- the event the next batch's early head launch waits for (_stage_visibility)
+        if b.head_overlap and k == bsz - 1 - b.head_depth:
+            b.head_event = torch.cuda.Event()
+            b.head_event.record(s_mem)
         # camera-DP, locality exchange: the gradient lines of the border rows the last camera does not touch are
         # final once camera bsz-2's backward is enqueued -- they travel now, under the last camera's backward
         if b.dp_split and k == bsz - 2:
@@ -680,6 +746,7 @@ def _stage_optimizer(b):
     gaussians, args, N, bsz, step = b.gaussians, b.args, b.N, b.bsz, b.step
     if b.use_packed and b.small_deferred and b.ft_stamp is not None and not dp.active():
         gaussians.small_defer_record(step)  # applied block by block when a camera comes near (small_catch_up)
+        _head_record(b)
     elif b.use_packed:
         if getattr(gaussians, "small_deferred", False):
             gaussians.flush_small()  # (a batch in another mode: nothing may wait across it)

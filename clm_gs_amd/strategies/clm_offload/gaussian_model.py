@@ -407,12 +407,30 @@ class GaussianModelCLMOffload(BaseGaussianModel):
             k = self._small_kmax_v = int(_lib.lib().clmgs_small_deferred_kmax())
         return k
 
-    def small_catch_up(self, cameras=None):
-        """Head of a batch (cameras given) or a flush (None): see small_deferred."""
+    def small_head_words(self):
+        """A [blocks] int64 buffer for the per-block camera words of the head about to run (bit c = the candidate test
+        admits camera c): one of two, alternating, so that the words the previous head left -- the selector of this one
+        (engine.py, head_overlap) -- stay readable while the new ones are written."""
+        sd = self._small_def
+        nb = (self._xyz.shape[0] + 255) // 256
+        bufs = sd.get("cams")
+        if bufs is None or bufs[0].shape[0] != nb:
+            bufs = sd["cams"] = [torch.zeros((nb,), dtype=torch.int64, device=self._xyz.device) for _ in range(2)]
+            sd["cams_i"] = 0
+        sd["cams_i"] ^= 1
+        return bufs[sd["cams_i"]]
+
+    def small_catch_up(self, cameras=None, cam_words=None, sel=None, cam_mats=None):
+        """Head of a batch (cameras given) or a flush (None): see small_deferred.
+        cam_words (small_head_words): also leave the per-block camera words.  sel = (words, mask, want): only the blocks
+        with ((words[blk] & mask) != 0) == want -- two calls with want 0 and 1 are one call without.  cam_mats = (viewmats
+        [C,4,4], Ks[C,3,3]) where the caller has them already (on the stream the call is enqueued on)."""
         import ctypes
         import math
         from ... import _lib
         sd = self._small_def
+        if cameras is None:
+            sd["head"] = None  # (engine.py, head_overlap: nothing recorded at a batch's end survives a flush)
         if not sd["hist"] or (cameras is None and self._small_def_clean()):
             return None
         order = self.optimizer.small_groups()
@@ -437,14 +455,20 @@ class GaussianModelCLMOffload(BaseGaussianModel):
             flags = sd.get("blk_flag")
             if flags is None or flags.shape[0] != blk.shape[0]:
                 flags = sd["blk_flag"] = torch.empty((blk.shape[0],), dtype=torch.uint8, device=blk.device)
-            Ks = torch.stack([c.create_k_on_gpu() if getattr(c, "K", None) is None else c.K for c in cameras]).contiguous()
-            vm = torch.stack([c.world_view_transform.transpose(0, 1) for c in cameras]).contiguous()
-        _lib.check(_lib.lib().clmgs_adam_small_deferred(
+            if cam_mats is not None:
+                vm, Ks = cam_mats
+            else:
+                Ks = torch.stack([c.create_k_on_gpu() if getattr(c, "K", None) is None else c.K for c in cameras]).contiguous()
+                vm = torch.stack([c.world_view_transform.transpose(0, 1) for c in cameras]).contiguous()
+        sel_words, sel_mask, sel_want = sel if sel is not None else (None, 0, 0)
+        _lib.check(_lib.lib().clmgs_adam_small_deferred_sel(
             _lib.stream(), int(self._xyz.shape[0]), ps, ms, vs, _lib.dptr(pk), _lib.dptr(gk),
             _lib.dptr(self._row_g_step, torch.int32), _lib.dptr(blk, torch.int32), int(hist[0][0]), nh, lr, sidx,
             pos_margin, scale_gain, float(b1), float(b2), float(order[0]["eps"]), 1.0 / float(self.args.bsz), C,
             _lib.dptr(vm, None, True), _lib.dptr(Ks, None, True), int(utils.get_img_width()), int(utils.get_img_height()),
-            0.3, 0.01, 1e10, 0 if cameras is not None else 1, _lib.dptr(flags, torch.uint8, True)))
+            0.3, 0.01, 1e10, 0 if cameras is not None else 1, _lib.dptr(flags, torch.uint8, True),
+            _lib.dptr(cam_words, torch.int64, True), _lib.dptr(sel_words, torch.int64, True),
+            int(sel_mask) & 0xFFFFFFFFFFFFFFFF, int(sel_want)))
         if cameras is None:
             self._small_def_dirty = False
         return flags

@@ -109,6 +109,13 @@ def default_args(**over):
         split_catch_up=True,    # camera pipeline: the deferred SH-row steps run camera by camera on a side stream; the first
                                 # camera starts after its own rows' pass instead of the whole batch's
         early_first_catch_up=True,  # ... and the first camera's call is issued before the host work of the camera stage
+        head_overlap=True,      # camera pipeline, deferred small-attribute Adam: the next batch's small-attribute catch-up and
+                                # visibility words of the blocks the LAST camera of a batch cannot see run under that
+                                # camera's backward (engine._stage_visibility); bit-identical results
+        head_overlap_cameras=2,  # ... generalised to the last D cameras: the early part takes the blocks none of them can see
+                                 # and starts after the backward of camera bsz-1-D.  D = 1 starts when the last TILE backward
+                                 # ends (the row backward of camera k runs under the tile backward of camera k+1); D = 2
+                                 # starts a camera earlier and runs under it ("Batch head")
         warm_structural_ops=True,  # trainer: the torch operators of a densification run once on small tensors before the
                                    # end-to-end clock (lazily loaded device code: 110-130 ms inside the first densification)
         defer_loss_log=True,    # trainer: a batch's loss line is written once the NEXT batch is enqueued (no device drain)

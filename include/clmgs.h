@@ -71,6 +71,17 @@ int clmgs_visibility_select_count_blocks(void* stream, int C, int N, const float
                                          int height, float eps2d, float near_plane, float far_plane, float radius_clip,
                                          void* temp, size_t temp_bytes, int64_t* cum_totals,
                                          const uint8_t* block_flags);
+/* The same over a SELECTED set of blocks: with blk_sel_bits[ceil(N/256)] only the blocks with
+ * ((blk_sel_bits[blk] & sel_mask) != 0) == sel_want (0 or 1) are read and get their words written.  scan == 0: the words
+ * only (cum_totals may be NULL); a later call on the same `temp` takes the other blocks and, with scan != 0, runs the
+ * scan over all words and leaves cum_totals.  Two such calls (sel_want 0, then 1 with scan) leave what one call of
+ * clmgs_visibility_select_count_blocks leaves, bit for bit.  blk_sel_bits NULL (then scan must be set): that call. */
+int clmgs_visibility_select_count_blocks_sel(void* stream, int C, int N, const float* means, const float* quats_raw,
+                                             const float* log_scales, const float* viewmats, const float* Ks, int width,
+                                             int height, float eps2d, float near_plane, float far_plane,
+                                             float radius_clip, void* temp, size_t temp_bytes, int64_t* cum_totals,
+                                             const uint8_t* block_flags, const uint64_t* blk_sel_bits,
+                                             uint64_t sel_mask, int sel_want, int scan);
 int clmgs_visibility_select_emit(void* stream, int C, int N, const void* temp, int64_t* out);
 /* VJP of the above.  v_means[N,3], v_quats[N,4], v_scales[N,3] are overwritten
  * with the sum over the C cameras. */
@@ -858,6 +869,21 @@ int clmgs_adam_small_deferred(void* stream, int64_t n, float* const* params, flo
                               int width, int height, float eps2d, float near_plane, float far_plane, int flush_all,
                               uint8_t* blk_flag /* optional [ceil(n/256)] out: 0 = no row of the block can be visible in
                               any of the C cameras; input of clmgs_visibility_select_count_blocks */);
+/* The same with a per-block camera word and / or a block selector.  blk_cams[ceil(n/256)] (optional out, needs blk_flag):
+ * bit c = the candidate test admits camera c for some row of the block (blk_flag[blk] != 0 <=> blk_cams[blk] != 0).
+ * blk_sel_bits[ceil(n/256)] (optional, not with flush_all): the call takes only the blocks with
+ * ((blk_sel_bits[blk] & sel_mask) != 0) == sel_want (0 or 1); a block it does not take is neither read nor written, and
+ * neither are its blk_flag / blk_last / blk_cams entries.  Two calls with sel_want 0 and 1 do what one call without a
+ * selector does, bit for bit, so a caller that knows which blocks' inputs are final early can bring those up to date on
+ * another stream.  Both NULL: clmgs_adam_small_deferred. */
+int clmgs_adam_small_deferred_sel(void* stream, int64_t n, float* const* params, float* const* exp_avg,
+                                  float* const* exp_avg_sq, void* packed_p, const void* packed_g, const int32_t* g_stamp,
+                                  int32_t* blk_last, int to_step, int n_hist, const double* lr4_hist,
+                                  const int32_t* step_index, const float* pos_margin, const float* scale_gain,
+                                  double beta1, double beta2, double eps, float grad_scale, int C, const float* viewmats,
+                                  const float* Ks, int width, int height, float eps2d, float near_plane, float far_plane,
+                                  int flush_all, uint8_t* blk_flag, uint64_t* blk_cams, const uint64_t* blk_sel_bits,
+                                  uint64_t sel_mask, int sel_want);
 
 /* Device error word: kernels that meet a broken invariant of their caller raise a bit in one device word instead of
  * failing silently.  *bits: 4 = clmgs_adam_small_deferred met a block further behind than the step history it was given
