@@ -61,6 +61,7 @@ SIGNATURES = {
     "clmgs_rasterize4_slot_bwd": (_i, [_vp, _i, _i, _i64, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "clmgs_rasterize4_fwd_dev": (_i, [_vp, _i, _i, _i64, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "clmgs_rasterize4_bwd_dev": (_i, [_vp, _i, _i, _i64, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "clmgs_preprocess_grid_cap": (_i, []),
     "clmgs_preprocess_fwd": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "clmgs_preprocess_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i]),
     # gsplat's absgrad: the plain entries' arguments (+ one trailing optional output where the plain entry unpacks)
@@ -188,7 +189,7 @@ class _Namespace:
     pass
 
 
-_NO_STREAM = {"clmgs_version", "clmgs_loss_slots", "clmgs_exposure_partials_rows", "clmgs_bilagrid_partials_rows", "clmgs_invdepth_partials_rows", "clmgs_pose_grad_partials_rows", "clmgs_projection_viewmat_partials_rows", "clmgs_small_deferred_kmax", "clmgs_isect3_front_temp_bytes",
+_NO_STREAM = {"clmgs_version", "clmgs_loss_slots", "clmgs_preprocess_grid_cap","clmgs_exposure_partials_rows", "clmgs_bilagrid_partials_rows", "clmgs_invdepth_partials_rows", "clmgs_pose_grad_partials_rows", "clmgs_projection_viewmat_partials_rows", "clmgs_small_deferred_kmax", "clmgs_isect3_front_temp_bytes",
               "clmgs_isect3_bin_temp_bytes", "clmgs_last_error", "clmgs_isect_count_temp_bytes",
               "clmgs_isect_sort_temp_bytes", "clmgs_host_groups_temp_bytes", "clmgs_isect2_order_temp_bytes", "clmgs_isect2_sort_temp_bytes", "clmgs_visibility_select_temp_bytes", "clmgs_rasterize_pack_bytes", "clmgs_rasterize_contrib_pack_bytes", "clmgs_rasterize_partials_bytes", "clmgs_host_adam_rows", "clmgs_host_pool_start", "clmgs_host_usable_cpus", "clmgs_host_rows_prepare", "clmgs_tsp_tour",
               "clmgs_pinned_alloc", "clmgs_pinned_free", "clmgs_device_errors"}

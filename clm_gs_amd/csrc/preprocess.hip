@@ -22,6 +22,7 @@ namespace clmgs {
 // 0.90 ms), 3 waves/SIMD via launch bounds (spills, 1.02 ms).
 constexpr int PP_ROWS = 64;   // one wavefront owns a chunk of 64 rows; no workgroup barriers
 constexpr int PP_PITCH = 52;  // floats per LDS row (see sh.hip)
+constexpr int PP_GRID_CAP = 256 * 12;  // workgroups of either launch: above PP_ROWS x this a wave takes further chunks
 
 struct PreArgs {
   const int64_t* filter;        // [V] row ids, or NULL (identity)
@@ -571,6 +572,8 @@ static void fill_args(PreArgs& a, const int64_t* filter, const float* xyz, const
   a.eps2d = eps2d; a.near_plane = near_plane; a.far_plane = far_plane; a.radius_clip = radius_clip;
 }
 
+extern "C" int clmgs_preprocess_grid_cap(void) { return PP_GRID_CAP; }
+
 template <bool AA>
 static int preprocess_fwd_impl(void* stream, int V, const int64_t* filter, const float* xyz,
                                     const float* opacity_raw, const float* scaling_raw,
@@ -595,7 +598,7 @@ static int preprocess_fwd_impl(void* stream, int V, const int64_t* filter, const
   CLMGS_CHECK_ARG(!sh_index || sh_by_filter);
   a.sh_index = sh_index;
   const size_t lds = 0;
-  const int grid = min(ceil_div(V, PP_ROWS), 256 * 12);
+  const int grid = min(ceil_div(V, PP_ROWS), PP_GRID_CAP);
 #define CLMGS_PRE_FWD(D, O)                                                                        \
   do {                                                                                             \
     if (a.packed_small)                                                                            \
@@ -680,7 +683,7 @@ static int preprocess_bwd_impl(bool abs, float* v_means2d_abs_out, void* stream,
              pg ? 1 : 0, ps ? 1 : 0, v_means2d_out, stats_only_visible, (const float4*)partials, row_cum,
              sh_stamp, cur_step};
   const size_t lds = 0;
-  const int grid = min(ceil_div(V, PP_ROWS), 256 * 12);
+  const int grid = min(ceil_div(V, PP_ROWS), PP_GRID_CAP);
   PreGradsOf<false> o0;
   PreGradsOf<true> o1;
   static_cast<PreGrads&>(o0) = o; static_cast<PreGrads&>(o1) = o; o1.v_means2d_abs_out = v_means2d_abs_out;

@@ -396,7 +396,12 @@ int clmgs_rasterize_abs_bwd_dev(void* stream, int C, int N, int64_t capacity, co
  * STORED (its previous content was consumed -- clmgs_adam_catch_up(keep_grad = 1) does not clear it) and
  * stamped cur_step, later cameras of the same step accumulate.  sh_stamp doubles as the deferred
  * optimizer's g_step table.  The reference clears the whole gradient buffer every batch
- * (clm_offload/engine.py:870-882) and accumulates (send_shs2cpu_grad_buffer_stream, accum = True). */
+ * (clm_offload/engine.py:870-882) and accumulates (send_shs2cpu_grad_buffer_stream, accum = True).
+ * At degree d < 3 both policies touch only the row's first ceil(3 (d+1)^2 / 4) float4s; the rest of the 48 floats
+ * is neither read nor written ("Gradient rows are stored on first touch": why nothing stale waits there).
+ * Both launches run min(ceil(V / 64), clmgs_preprocess_grid_cap()) one-wave workgroups of 64 rows; above 64 x the cap
+ * a wave takes further chunks, grid-stride. */
+int clmgs_preprocess_grid_cap(void);
 int clmgs_preprocess_fwd(void* stream, int V, const int64_t* filter, const float* xyz,
                          const float* opacity_raw, const float* scaling_raw,
                          const float* rotation_raw, const float* sh_rows, int sh_by_filter,

@@ -26,8 +26,10 @@ class GuardedSqrt(torch.autograd.Function):
 
 
 def projection(means, quats, scales, viewmats, Ks, width, height, eps2d=0.3, near_plane=0.01, far_plane=1e10,
-               radius_clip=0.0, guarded=True):
-    """-> radii[C,N] i32, means2d[C,N,2], depths[C,N], conics[C,N,3], compensations[C,N] (0 where culled)."""
+               radius_clip=0.0, guarded=True, details=None):
+    """-> radii[C,N] i32, means2d[C,N,2], depths[C,N], conics[C,N,3], compensations[C,N] (0 where culled).
+    `details`: a dict that receives the values the culls compare (detached): z, the real-valued radius 3 sqrt(v1), its
+    ceiling, the pixel mean and the four partial verdicts -- for tests that keep a scene clear of these decisions."""
     C, N = viewmats.shape[0], means.shape[0]
     dt = means.dtype
     Rv, tv = viewmats[:, :3, :3], viewmats[:, :3, 3]
@@ -68,6 +70,10 @@ def projection(means, quats, scales, viewmats, Ks, width, height, eps2d=0.3, nea
     ok_r = radius > radius_clip
     ok_img = ~((mu_x + radius <= 0) | (mu_x - radius >= width) | (mu_y + radius <= 0) | (mu_y - radius >= height))
     valid = ok_z & ok_det & ok_r & ok_img
+    if details is not None:
+        details.update(z=z_raw.detach(), radius_real=(3.0 * torch.sqrt(v1)).detach(), radius=radius, mu_x=mu_x.detach(),
+                       mu_y=mu_y.detach(), ok_z=ok_z, ok_det=ok_det, ok_r=ok_r, ok_img=ok_img, tx_over_z=(x * rz).detach(),
+                       lim_x=(lim_x_neg, lim_x_pos))
     ratio = torch.clamp(det_orig / det_s, min=0.0)
     ratio = torch.where(valid, ratio, torch.ones_like(ratio))  # culled pairs: no 0/0 in the square root's derivative
     comp = (GuardedSqrt.apply(ratio) if guarded else torch.sqrt(ratio)) * valid

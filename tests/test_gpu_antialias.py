@@ -108,19 +108,10 @@ def _pre_case(V, with_filter):
 
 def _reference(raw, filt, vm, K, pg, deg):
     """Float64 composition over the filter's rows: reference projection, the oracle's SH, clamp, opacity * compensation;
-    gradients of the raw parameters from the gradient lines  x y ca cb | cc r g b | o."""
-    P = {k: v.double().clone().requires_grad_() for k, v in raw.items()}
-    rows = filt if filt is not None else torch.arange(raw["xyz"].shape[0])
-    xyz = P["xyz"][rows]
-    radii, m2, d, cn, comp = R.projection(xyz, P["rotation"][rows], torch.exp(P["scaling"][rows]), vm.double()[None],
-                                          K.double()[None], W0, H0)
-    dirs = xyz[None] - torch.inverse(vm.double())[:3, 3]
-    col = torch.clamp_min(O.spherical_harmonics(deg, dirs, P["shs"][rows].reshape(1, -1, 16, 3), masks=radii > 0) + 0.5, 0.0)
-    op = torch.sigmoid(P["opacity"][rows])[None] * comp
-    g = pg.double()
-    ((m2[0] * g[:, 0:2]).sum() + (cn[0] * g[:, 2:5]).sum() + (col[0] * g[:, 5:8]).sum() + (op[0] * g[:, 8]).sum()).backward()
-    grads = {k: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in P.items()}
-    return dict(radii=radii[0], comp=comp[0].detach(), op=op[0].detach(), col=col[0].detach(), grads=grads)
+    gradients of the raw parameters from the gradient lines  x y ca cb | cc r g b | o  (tests/front_end_reference.py, which
+    tests/test_front_end_cpu.py holds to the composition that stood here)."""
+    from tests import front_end_reference as FR
+    return FR.reference(raw, filt, dict(viewmat=vm, K=K, width=W0, height=H0), deg, True, lines=pg)
 
 
 def _run_pre(dev, raw, filt, vm, K, pg, N, V, deg, pk, fwd_name, bwd_name):
