@@ -114,6 +114,9 @@ SIGNATURES = {
     "clmgs_area_resample_u8": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "clmgs_area_resample_u16": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "clmgs_area_resample_mask": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
+    # lens distortion: sizes, the host lens record [10 doubles], the fisheye flag, fxo, fyo, src, (src_mask), dst, (valid, count)
+    "clmgs_undistort_u8": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _d, _d, _vp, _vp, _vp, _vp, _vp]),
+    "clmgs_undistort_u16": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _d, _d, _vp, _vp]),
     "clmgs_mcmc_relocation": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "clmgs_mcmc_reg_grad": (_i, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _f, _f]),
     "clmgs_mcmc_noise": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _f, _vp]),

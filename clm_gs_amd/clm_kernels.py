@@ -434,6 +434,139 @@ def area_resample(t, level, out=None, mask=False, count=None):
     return out
 
 
+# ------------------------------------------------------------ lens distortion
+# COLMAP camera model -> where its parameters go in the lens record (fx, fy, cx, cy, k1, k2, k3, k4, p1, p2); a model
+# with one focal length fills fx and fy with it
+_LENS_MODELS = {
+    "SIMPLE_PINHOLE": ("f", "cx", "cy"),
+    "PINHOLE": ("fx", "fy", "cx", "cy"),
+    "SIMPLE_RADIAL": ("f", "cx", "cy", "k1"),
+    "RADIAL": ("f", "cx", "cy", "k1", "k2"),
+    "OPENCV": ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2"),
+    "OPENCV_FISHEYE": ("fx", "fy", "cx", "cy", "k1", "k2", "k3", "k4"),
+}
+_LENS_FIELDS = ("fx", "fy", "cx", "cy", "k1", "k2", "k3", "k4", "p1", "p2")
+
+
+class Lens:
+    """The lens of a COLMAP camera as csrc/undistort.hip takes it ("Lens distortion"): a host object.
+    `model_name`, `params`: COLMAP's model and its parameter list; `width`, `height`: the image size the intrinsics are
+    in pixels of (COLMAP's convention: the centre of the top-left pixel is at (0.5, 0.5)).  Accepted: SIMPLE_PINHOLE,
+    PINHOLE, SIMPLE_RADIAL, RADIAL, OPENCV, OPENCV_FISHEYE; every other model is refused by name."""
+
+    def __init__(self, model_name, params, width, height):
+        if model_name not in _LENS_MODELS:
+            raise ValueError(f"COLMAP camera model {model_name} cannot be undistorted here: the lens record holds "
+                             f"{' / '.join(_LENS_MODELS)} only; undistort the dataset with COLMAP's image_undistorter")
+        names = _LENS_MODELS[model_name]
+        params = [float(p) for p in params]
+        if len(params) != len(names):
+            raise ValueError(f"COLMAP camera model {model_name} takes {len(names)} parameters ({', '.join(names)}), "
+                             f"got {len(params)}")
+        given = dict(zip(names, params))
+        if "f" in given:
+            given["fx"] = given["fy"] = given.pop("f")
+        self.model, self.params = model_name, tuple(params)
+        self.width, self.height = int(width), int(height)
+        self.fisheye = model_name == "OPENCV_FISHEYE"
+        for name in _LENS_FIELDS:
+            setattr(self, name, given.get(name, 0.0))
+        if self.width < 1 or self.height < 1 or not all(map(_finite, self.record())) or self.fx <= 0 or self.fy <= 0:
+            raise ValueError(f"COLMAP camera {model_name} {self.width}x{self.height} {list(params)}: the size and the focal "
+                             "lengths must be positive and every parameter finite")
+
+    def record(self):
+        """The ten doubles fx, fy, cx, cy, k1, k2, k3, k4, p1, p2."""
+        return tuple(getattr(self, name) for name in _LENS_FIELDS)
+
+    def at(self, width, height):
+        """The same lens for the image decoded at width x height (`-r`, or files of another size than the model's): focal
+        lengths and principal point scale with the size, the distortion terms act on normalised coordinates and stay."""
+        width, height = int(width), int(height)
+        if (width, height) == (self.width, self.height):
+            return self
+        out = Lens.__new__(Lens)
+        out.__dict__.update(self.__dict__)
+        sx, sy = width / self.width, height / self.height
+        out.fx, out.cx, out.fy, out.cy = self.fx * sx, self.cx * sx, self.fy * sy, self.cy * sy
+        out.width, out.height = width, height
+        return out
+
+    def is_identity(self, out_size=None, zoom=1.0):
+        """True when undistorting an image of this lens' size to `out_size` (Ho, Wo; None: the same size) changes nothing:
+        a perspective model, every k and p zero, zoom 1, the same size and the principal point exactly at the centre.  A
+        caller then launches nothing."""
+        same = out_size is None or (int(out_size[0]), int(out_size[1])) == (self.height, self.width)
+        return (not self.fisheye and same and float(zoom) == 1.0 and not any(self.record()[4:])
+                and self.cx == self.width / 2.0 and self.cy == self.height / 2.0)
+
+    def __repr__(self):
+        return f"Lens({self.model}, {list(self.params)}, {self.width}x{self.height})"
+
+
+def _finite(v):
+    return v == v and v not in (float("inf"), float("-inf"))
+
+
+def check_undistort_zoom(zoom):
+    """The zoom as a float; anything but a positive finite number is refused (the operator, the loader and
+    trainer.check_training share the message)."""
+    zoom = float(zoom)
+    if not (_finite(zoom) and zoom > 0):
+        raise ValueError(f"--undistort_zoom must be positive and finite, got {zoom}")
+    return zoom
+
+
+@torch.no_grad()
+def undistort(src, lens, out_size=None, zoom=1.0, src_mask=None, want_valid=False, out=None):
+    """Remaps a distorted device image onto the ideal centred pinhole (csrc/undistort.hip; DESIGN.md section 3, "Lens
+    distortion"): src uint8 [3,H,W] (any number of planes) / [H,W] or uint16 [H,W], contiguous; `lens` a Lens (taken at
+    the size of `src`: Lens.at); out_size (Ho, Wo), None = the size of `src`; the pinhole's focal lengths are
+    fx * zoom, fy * zoom (zoom < 1 widens it to keep more of a barrel or fisheye frame).  `src_mask` (uint8 [H,W], uint8
+    input only): a pixel is valid only if all four source pixels it blends are non-zero there.  Returns the image (same
+    dtype and rank; `out`: a caller-owned buffer, written and returned); with want_valid (uint8 input only)
+    (image, valid, count): valid uint8 [Ho,Wo] 255 / 0 and a device int64 [1], the number of valid pixels.  The kernel
+    is launched for any lens: a caller that wants to launch nothing for an identity lens asks Lens.is_identity first."""
+    zoom = check_undistort_zoom(zoom)
+    if not (isinstance(src, torch.Tensor) and src.is_cuda and src.is_contiguous() and src.dim() in (2, 3)
+            and src.dtype in (U8, torch.uint16)):
+        raise _lib.ClmgsError("undistort: contiguous uint8 [P,H,W] / [H,W] or uint16 [H,W] device tensor expected, got "
+                              f"{getattr(src, 'dtype', type(src))} {tuple(getattr(src, 'shape', ()))}")
+    u16 = src.dtype == torch.uint16
+    if u16 and (src.dim() != 2 or src_mask is not None or want_valid):
+        raise _lib.ClmgsError("undistort: a uint16 input is one plane [H,W] and takes no mask and gives no valid map")
+    H, W = (int(v) for v in src.shape[-2:])
+    lens = lens.at(W, H)
+    Ho, Wo = (H, W) if out_size is None else (int(out_size[0]), int(out_size[1]))
+    if Ho < 1 or Wo < 1:
+        raise ValueError(f"undistort: out_size must be positive, got {out_size}")
+    shape = tuple(src.shape[:-2]) + (Ho, Wo)
+    if out is not None and not (out.is_cuda and out.is_contiguous() and out.dtype == src.dtype and tuple(out.shape) == shape
+                                and out.device == src.device):
+        raise _lib.ClmgsError(f"undistort: out must be a contiguous {src.dtype} {shape} tensor on {src.device}, got "
+                              f"{out.dtype} {tuple(out.shape)}")
+    if src_mask is not None and not (src_mask.is_cuda and src_mask.is_contiguous() and src_mask.dtype == U8
+                                     and tuple(src_mask.shape) == (H, W) and src_mask.device == src.device):
+        raise _lib.ClmgsError(f"undistort: src_mask must be a contiguous uint8 [{H}, {W}] tensor on {src.device}, got "
+                              f"{src_mask.dtype} {tuple(src_mask.shape)}")
+    if out is None:
+        out = torch.empty(shape, dtype=src.dtype, device=src.device)
+    rec = (ctypes.c_double * 10)(*lens.record())
+    fxo, fyo = lens.fx * zoom, lens.fy * zoom
+    L = _lib.lib()
+    if u16:
+        check(L.clmgs_undistort_u16(stream(), H, W, Ho, Wo, rec, int(lens.fisheye), fxo, fyo, dptr(src, torch.uint16),
+                                    dptr(out, torch.uint16)))
+        return out
+    valid = torch.empty((Ho, Wo), dtype=U8, device=src.device) if want_valid else None
+    count = torch.empty((1,), dtype=I64, device=src.device) if want_valid else None
+    planes = src.shape[0] if src.dim() == 3 else 1
+    check(L.clmgs_undistort_u8(stream(), planes, H, W, Ho, Wo, rec, int(lens.fisheye), fxo, fyo, dptr(src, U8),
+                               dptr(src_mask, U8, allow_none=True), dptr(out, U8), dptr(valid, U8, allow_none=True),
+                               dptr(count, I64, allow_none=True)))
+    return (out, valid, count) if want_valid else out
+
+
 # ------------------------------------------------------------ MCMC densification
 def _f32_dev(t, shape, what):
     assert t.is_cuda and t.dtype == F32 and t.is_contiguous() and tuple(t.shape) == tuple(shape), \

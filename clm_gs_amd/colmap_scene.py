@@ -8,6 +8,8 @@ SIMPLE_PINHOLE / PINHOLE / OPENCV (distortion ignored, as there), images sorted 
 centre from their mean (getNerfppNorm).  The file formats are COLMAP's published model formats
 (https://colmap.github.io/format.html); the parsing below is written against that description with
 numpy record reads.  Images are decoded with PIL to uint8 [3,H,W] (what the engines' fused loss reads).
+With `undistort=True` the distorted models SIMPLE_RADIAL / RADIAL / OPENCV / OPENCV_FISHEYE and off-centre principal
+points are remapped onto centred pinholes on the device at load (clm_kernels.undistort; load_colmap_scene's docstring).
 """
 import math
 import os
@@ -270,8 +272,69 @@ def read_model(sparse_dir):
     return cams, imgs, (xyz, rgb)
 
 
+class _Undistorter:
+    """The remap of load_colmap_scene(undistort=True): one reused device staging buffer per kind (image, mask, prior) that
+    a distorted file is uploaded into, one kernel (clm_kernels.undistort) into the tensor the camera keeps -- the distorted
+    copy of an image never stays next to the undistorted one -- and, per COLMAP camera id, the number of pixels that have
+    no source (taken once, from the first image of that camera)."""
+
+    def __init__(self, device, zoom):
+        self.device, self.zoom, self.staging, self.sourced = device, zoom, {}, {}
+
+    def _stage(self, kind, host):
+        buf = self.staging.get(kind)
+        if buf is None or buf.shape != host.shape or buf.dtype != host.dtype:
+            buf = self.staging[kind] = torch.empty(host.shape, dtype=host.dtype, device=self.device)
+        return buf.copy_(host)
+
+    def image(self, cam_id, lens, img, mask):
+        """(image, loss mask or None, count or None) on the device: the mask is `valid AND file mask` (a pixel blended from
+        an ignored pixel is ignored), None when every pixel is counted."""
+        from .clm_kernels import undistort
+        h, w = int(img.shape[1]), int(img.shape[2])
+        lens = lens.at(w, h)
+        if lens.is_identity((h, w), self.zoom):  # nothing to remap: nothing is launched
+            self.sourced.setdefault(cam_id, (h * w, h * w))
+            return img, mask, None
+        if torch.device(self.device).type != "cuda":
+            raise ValueError(f"undistort=True with images needs a GPU device, got device={self.device!r}: the remap of "
+                             f"{lens!r} is a device kernel (load_images=False builds the geometry only)")
+        src_mask = None if mask is None else self._stage("mask", mask)
+        out, valid, count = undistort(self._stage("image", img), lens, zoom=self.zoom, src_mask=src_mask, want_valid=True)
+        count = int(count.item())  # the one read-back of the camera
+        if cam_id not in self.sourced:
+            n = count if src_mask is None else int(undistort(src_mask, lens, zoom=self.zoom, want_valid=True)[2].item())
+            self.sourced[cam_id] = (n, h * w)
+        if count == h * w:
+            return out, None, None
+        return out, valid, count
+
+    def prior(self, lens, raw):
+        from .clm_kernels import undistort
+        lens = lens.at(int(raw.shape[1]), int(raw.shape[0]))
+        if lens.is_identity(tuple(raw.shape), self.zoom):
+            return raw
+        return undistort(self._stage("prior", raw), lens, zoom=self.zoom)
+
+    def log_lines(self, lenses):
+        """One line per COLMAP camera id: the model, its parameters and the share of pixels without a source."""
+        out = []
+        for cam_id, lens in sorted(lenses.items()):
+            line = "undistort: camera {} {} [{}] {}x{} zoom {:g}".format(
+                cam_id, lens.model, ", ".join("%.6g" % p for p in lens.params), lens.width, lens.height, self.zoom)
+            if cam_id in self.sourced:
+                n, total = self.sourced[cam_id]
+                lost = 1.0 - n / float(total)
+                line += ": {:.2%} of the pixels have no source".format(lost)
+                if lens.fisheye and lost > 0.25:
+                    line += (" (more than a quarter is lost to the fisheye: a lower --undistort_zoom keeps more of its frame, "
+                             "a higher one crops the pinhole to the pixels that have a source)")
+            out.append(line)
+        return out
+
+
 def load_colmap_scene(source_path, images="images", eval=False, llffhold=10, resolution=1, device="cuda",
-                      load_images=True, masks=None, alpha_mask=False, depths=None):
+                      load_images=True, masks=None, alpha_mask=False, depths=None, undistort=False, undistort_zoom=1.0):
     """-> namespace(train_cameras, test_cameras, point_cloud(points, colors in [0,1]) or None,
     cameras_extent, nerf_normalization).  `cameras_extent` is what the trainer passes as
     `spatial_lr_scale` and what densification compares scales with (train.py:118-131).
@@ -285,13 +348,27 @@ def load_colmap_scene(source_path, images="images", eval=False, llffhold=10, res
     `sparse/0/depth_params.json` = {NAME: {"scale": s, "offset": o}} (prior = raw / 65536 * scale + offset); a map of
     another size than the training image is resampled to it (bilinear on float32, rounded back to uint16).  An image gets
     no prior when its PNG or its json entry is missing, its scale is <= 0, or its scale lies outside [0.2, 5] x the median
-    scale (reliable_depth_params)."""
+    scale (reliable_depth_params).
+    Lens distortion (`undistort`, `undistort_zoom`; DESIGN.md section 3, "Lens distortion").  False: SIMPLE_RADIAL, RADIAL
+    and OPENCV_FISHEYE cameras are refused, the distortion terms of an OPENCV camera and every principal point are
+    ignored.  True: cameras of the models SIMPLE_PINHOLE, PINHOLE, SIMPLE_RADIAL, RADIAL, OPENCV and OPENCV_FISHEYE
+    (clm_kernels.Lens; any other is refused by name) become the CENTRED pinhole of the decoded size with
+    FoV = 2 atan(size / (2 f zoom)), and the image, its mask file or alpha mask and its inverse-depth prior are remapped
+    onto it on the device at load (clm_kernels.undistort).  The loss mask becomes `valid AND file mask`; a camera whose
+    every pixel has a source and that has no mask file carries none.  `load_images=False` builds the geometry only; images
+    on a CPU `device` with a lens that is not the identity are refused.  The scene carries `undistort_log`, one line per
+    COLMAP camera id (also printed)."""
+    from .clm_kernels import Lens, check_undistort_zoom
     cams, imgs, (xyz, rgb) = read_model(os.path.join(source_path, "sparse", "0"))
     folder = os.path.join(source_path, images or "images")
+    zoom = check_undistort_zoom(undistort_zoom) if undistort else 1.0
+    used = sorted({im.camera_id for im in imgs.values()})
+    lenses = {cid: Lens(cams[cid].model, cams[cid].params, cams[cid].width, cams[cid].height) for cid in used} if undistort else {}
+    remap = _Undistorter(device, zoom) if undistort and load_images else None
     recs = []
     for im in imgs.values():
         intr = cams[im.camera_id]
-        fovx, fovy = _intrinsics_to_fov(intr)
+        fovx, fovy = (None, None) if undistort else _intrinsics_to_fov(intr)  # (with a lens: from the decoded size, in build)
         w2c = np.eye(4)
         w2c[:3, :3] = quat_to_rotation(im.qvec)
         w2c[:3, 3] = im.tvec
@@ -349,8 +426,20 @@ def load_colmap_scene(source_path, images="images", eval=False, llffhold=10, res
             dpath = os.path.join(depth_dir, r.name + ".png")
             if so is not None and os.path.exists(dpath):
                 prior = dict(invdepth=_decode_invdepth(dpath, (w, h)), invdepth_scale=so[0], invdepth_offset=so[1])
-        return Camera(r.uid, torch.from_numpy(r.w2c).float(), r.fovx, r.fovy, w, h, image_u8=img,
-                      image_name=r.name, device=device, loss_mask=mask, **prior)
+        if not undistort:
+            return Camera(r.uid, torch.from_numpy(r.w2c).float(), r.fovx, r.fovy, w, h, image_u8=img,
+                          image_name=r.name, device=device, loss_mask=mask, **prior)
+        lens = lenses[r.uid].at(w, h)
+        count = None
+        if remap is not None:
+            img, mask, count = remap.image(r.uid, lens, img, mask)
+            if "invdepth" in prior:
+                prior["invdepth"] = remap.prior(lens, prior["invdepth"])
+        cam = Camera(r.uid, torch.from_numpy(r.w2c).float(), focal_to_fov(lens.fx * zoom, w), focal_to_fov(lens.fy * zoom, h),
+                     w, h, image_u8=img, image_name=r.name, device=device, loss_mask=mask if count is None else None, **prior)
+        if count is not None:  # the kernel's valid map, already on the device, and the kernel's count
+            cam.loss_mask, cam.loss_mask_count = mask, count
+        return cam
 
     pcd = None
     if xyz is not None and len(xyz):
@@ -364,6 +453,11 @@ def load_colmap_scene(source_path, images="images", eval=False, llffhold=10, res
         if n_prior == 0:
             raise ValueError(f"depths={depths!r}: no training camera received an inverse-depth prior (no PNG matches, or "
                              "every scale of depth_params.json is unreliable)")
-    return SimpleNamespace(train_cameras=train_cameras, test_cameras=[build(r, False) for r in test],
+    test_cameras = [build(r, False) for r in test]
+    undistort_log = []
+    if undistort:
+        undistort_log = (remap or _Undistorter(device, zoom)).log_lines(lenses)
+        print("\n".join(undistort_log))
+    return SimpleNamespace(train_cameras=train_cameras, test_cameras=test_cameras,
                            point_cloud=pcd, cameras_extent=radius,
-                           nerf_normalization={"translate": translate, "radius": radius})
+                           nerf_normalization={"translate": translate, "radius": radius}, undistort_log=undistort_log)

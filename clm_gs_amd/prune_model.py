@@ -1,7 +1,7 @@
 """Contribution pruning of a finished model:
 
     python -m clm_gs_amd.prune_model -m <model dir | .ply> -s <colmap dir> [--mode sum|max --ratio R --threshold T
-                                     --antialiased] -o <out.ply>
+                                     --antialiased --undistort --undistort_zoom Z] -o <out.ply>
 
 scores the model over the scene's training cameras (contribution.score_cameras: blend weights w = alpha * T by
 csrc/contrib.hip) and writes the kept rows, in their order, as a .ply (io_ply).  The scoring pass reads positions,
@@ -18,14 +18,16 @@ from .render_trajectory import _find_ply
 
 
 def prune_ply(ply_path, source_path, out_path, mode="sum", ratio=0.3, threshold=0.01, antialiased=False, images="images",
-              resolution=1, eval=False, log=None):
-    """-> (rows before, rows after).  `eval`: the scene's held-out split is left out of the scoring, as in training."""
+              resolution=1, eval=False, log=None, undistort=False, undistort_zoom=1.0):
+    """-> (rows before, rows after).  `eval`: the scene's held-out split is left out of the scoring, as in training;
+    `undistort`, `undistort_zoom`: as the model was trained (trainer --undistort), so that it is scored on the same cameras."""
     from .colmap_scene import load_colmap_scene
     if mode not in contribution.PRUNE_MODES:
         raise ValueError(f"--mode must be one of {contribution.PRUNE_MODES}, got {mode!r}")
     args = utils.default_args(rasterize_mode="antialiased" if antialiased else "classic")
     utils.set_args(args)
-    scene = load_colmap_scene(source_path, images=images, eval=eval, resolution=resolution, device="cuda")
+    scene = load_colmap_scene(source_path, images=images, eval=eval, resolution=resolution, device="cuda",
+                              undistort=undistort, undistort_zoom=undistort_zoom)
     cams = scene.train_cameras
     sizes = {(c.image_height, c.image_width) for c in cams}
     assert len(sizes) == 1, f"all images must share one size: {sizes}"
@@ -58,11 +60,13 @@ def main(argv=None):
     ap.add_argument("--ratio", type=float, default=0.3, help="--mode sum: the fraction of rows pruned, lowest summed weight first")
     ap.add_argument("--threshold", type=float, default=0.01, help="--mode max: rows whose largest weight is below it are pruned")
     ap.add_argument("--antialiased", action="store_true", help="for a model trained with trainer --antialiased")
+    ap.add_argument("--undistort", action="store_true", help="for a model trained with trainer --undistort")
+    ap.add_argument("--undistort_zoom", type=float, default=1.0, help="--undistort: the trainer's --undistort_zoom")
     ap.add_argument("-o", "--output", required=True, help="the pruned .ply")
     a = ap.parse_args(argv)
     with torch.no_grad():
         prune_ply(_find_ply(a.model_path, a.iteration), a.source_path, a.output, a.mode, a.ratio, a.threshold,
-                  a.antialiased, a.images, a.resolution, a.eval)
+                  a.antialiased, a.images, a.resolution, a.eval, undistort=a.undistort, undistort_zoom=a.undistort_zoom)
     return 0
 
 

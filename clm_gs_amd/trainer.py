@@ -21,7 +21,7 @@ import torch
 from . import dp, mcmc, utils
 from .bilagrid import BilagridModel
 from .cameras import LevelCameras, camera_loss_mask
-from .clm_kernels import apply_camera_colour
+from .clm_kernels import apply_camera_colour, check_undistort_zoom
 from .contribution import check_contrib_prune_args, contribution_prune, prune_iterations
 from .densification import check_mcmc_args, gsplat_densification, mcmc_refinement
 from .exposure import ExposureModel
@@ -322,10 +322,19 @@ def check_training(args, depth_priors=False, models=None, num_downscales=None, r
          "--sky and --white_background together are refused: the sky map is the background"),
         (on("sky") and on("pose_opt"), "--sky and --pose_opt together are refused: the sky's gradient with respect to the "
          "camera (the ray direction of the lookup) is not carried"),
-    ] + resolution_rules(args, on("pose_opt"), num_downscales, resolution_schedule, image_size) + [camera_dp_rule(r.flag, on(r.flag)) for r in SIDE_MODELS if r.not_shared])
+    ] + undistort_rules(args) + resolution_rules(args, on("pose_opt"), num_downscales, resolution_schedule, image_size) + [camera_dp_rule(r.flag, on(r.flag)) for r in SIDE_MODELS if r.not_shared])
     check_pose_args(args, depth_priors, enabled=on("pose_opt"))
     check_mcmc_args(args)
     check_contrib_prune_args(args)
+
+
+def undistort_rules(args):
+    """The (condition, message) rule of --undistort_zoom for check_training (the message is clm_kernels')."""
+    try:
+        check_undistort_zoom(getattr(args, "undistort_zoom", 1.0))
+    except ValueError as e:
+        return [(bool(getattr(args, "undistort", False)), str(e))]
+    return []
 
 
 # ---------------------------------------------------------------------------------------------- resolution schedule
@@ -702,14 +711,16 @@ def _training(gaussians, scene, train_cameras, test_cameras, log_file, iteration
 
 def train_from_colmap(source_path, model_path, strategy="clm_offload", iterations=None, eval=False, resolution=1,
                       images="images", test_iterations=(), save=True, masks=None, alpha_mask=False, depths=None,
-                      num_downscales=0, resolution_schedule=3000, **arg_overrides):
+                      num_downscales=0, resolution_schedule=3000, undistort=False, undistort_zoom=1.0, **arg_overrides):
     """A COLMAP directory -> trained model (row f1): `colmap_scene.load_colmap_scene` (cameras, held-out
     split, scene radius, sparse points) -> `create_from_pcd` with `spatial_lr_scale = cameras_extent` ->
     `training_setup` -> `training` (log lines of the reference in `<model_path>/python_ws=1_rk=0.log`) ->
     `point_cloud/iteration_N/point_cloud.ply` (scene/__init__.py:41-143, train.py:60-131 for the order of
     these steps).  `strategy`: clm_offload | no_offload | naive_offload; `masks` / `alpha_mask` / `depths`: the arguments of
     colmap_scene.load_colmap_scene; `num_downscales` / `resolution_schedule`: the
-    resolution schedule (training()); `arg_overrides`: any flag of `utils.default_args`, described there and, for the ones the
+    resolution schedule (training()); `undistort` / `undistort_zoom`: distorted COLMAP cameras and off-centre principal
+    points are remapped onto centred pinholes on the device at load (load_colmap_scene; its per-camera lines head the
+    log); `arg_overrides`: any flag of `utils.default_args`, described there and, for the ones the
     command line has, in OPTIONS.  Every refusal is raised by check_training before anything is loaded.  A side model that
     is asked for (SIDE_MODELS) is written next to the ply and stays reachable as `scene.<name>`, None when off.
     Returns (gaussians, scene, timer)."""
@@ -719,7 +730,7 @@ def train_from_colmap(source_path, model_path, strategy="clm_offload", iteration
     from .strategies.no_offload import GaussianModelNoOffload
     assert strategy in ("clm_offload", "no_offload", "naive_offload"), strategy
     args = utils.default_args(num_downscales=int(num_downscales), resolution_schedule=int(resolution_schedule),
-                              **arg_overrides)
+                              undistort=bool(undistort), undistort_zoom=float(undistort_zoom), **arg_overrides)
     setattr(args, strategy, True)
     args.source_path, args.model_path, args.eval = source_path, model_path, bool(eval)
     if iterations is not None:
@@ -728,7 +739,8 @@ def train_from_colmap(source_path, model_path, strategy="clm_offload", iteration
     check_training(args, bool(depths))  # raises: before anything is loaded
     utils.set_args(args)
     scene = load_colmap_scene(source_path, images=images, eval=eval, resolution=resolution, device="cuda",
-                              masks=masks, alpha_mask=alpha_mask, depths=depths)
+                              masks=masks, alpha_mask=alpha_mask, depths=depths, undistort=args.undistort,
+                              undistort_zoom=args.undistort_zoom)
     if scene.point_cloud is None:
         raise ValueError(f"{source_path}/sparse/0 holds no points3D.bin / points3D.txt to initialise from")
     sizes = {(c.image_height, c.image_width) for c in scene.train_cameras + scene.test_cameras}
@@ -747,6 +759,8 @@ def train_from_colmap(source_path, model_path, strategy="clm_offload", iteration
     prev_log = utils.get_log_file()
     try:
         with open(os.path.join(model_path, "python_ws=1_rk=0.log"), "w") as log_file:
+            for line in scene.undistort_log:
+                log_file.write(line + "\n")
             timer = training(gaussians, scene, scene.train_cameras, scene.test_cameras, log_file,
                              iterations=args.iterations, test_iterations=test_iterations,
                              **{row.name: getattr(scene, row.name) for row in SIDE_MODELS})
@@ -827,6 +841,11 @@ OPTIONS = (
          "of the size first and double it every --resolution_schedule images; ground truth, masks and depth priors are "
          "area-resampled on the device; evaluation and the final model are full size (single GPU; not with --pose_opt)"),
     _opt("--resolution_schedule", type=int, metavar="R", help="--num_downscales: images trained at each coarse level"),
+    _opt("--undistort", action="store_true", help="lens distortion: SIMPLE_RADIAL / RADIAL / OPENCV / OPENCV_FISHEYE cameras "
+         "and off-centre principal points are remapped onto centred pinholes on the device at load (images, masks, depth "
+         "priors); pixels without a source are ignored by the loss"),
+    _opt("--undistort_zoom", type=float, metavar="Z", help="--undistort: the pinhole's focal length is Z x the lens'; Z < 1 "
+         "widens it to keep more of a barrel or fisheye frame"),
     _opt("--contrib_prune_iterations", type=int, nargs="*", metavar="I", conv=tuple, help="contribution pruning: image "
          "counters at which the training cameras are scored by blend weight and the model is pruned; each after "
          "densify_until_iter unless --disable_auto_densification (no_offload or clm_offload; single GPU; not with --mcmc)"),

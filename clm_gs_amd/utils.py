@@ -83,6 +83,11 @@ def default_args(**over):
         # ceil(size / 2^L), on ground truth area-resampled on the device (csrc/resample.hip, cameras.LevelCameras);
         # 0 = off: every image at full size, nothing more is launched.  Refusals: trainer.resolution_rules
         num_downscales=0, resolution_schedule=3000,
+        # this build: lens distortion (colmap_scene.load_colmap_scene(undistort=True); csrc/undistort.hip): the images, masks
+        # and depth priors of SIMPLE_RADIAL / RADIAL / OPENCV / OPENCV_FISHEYE cameras, and of any camera with an off-centre
+        # principal point, are remapped onto centred pinholes with focal lengths f * undistort_zoom on the device at load;
+        # False = the loader as it was (distortion terms and principal points ignored, the three models refused)
+        undistort=False, undistort_zoom=1.0,
         lr_scale_mode="sqrt", bsz=1, exact_filter=True, log_cpu_adam_trailing_overhead=False,
         # Debug
         stop_update_param=False, drop_initial_3dgs_p=0.0,

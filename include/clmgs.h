@@ -910,6 +910,39 @@ int clmgs_area_resample_u8(void* stream, int planes, int H, int W, int level, co
 int clmgs_area_resample_u16(void* stream, int H, int W, int level, const uint16_t* src, uint16_t* dst);
 int clmgs_area_resample_mask(void* stream, int H, int W, int level, const uint8_t* src, uint8_t* dst, int64_t* count);
 
+/* ---- lens distortion (csrc/undistort.hip, csrc/lens_math.h): inverse-map bilinear remap of a distorted source image
+ * [planes,Hs,Ws] onto the ideal centred pinhole [planes,Ho,Wo] with focal lengths fxo, fyo and principal point
+ * (Wo/2, Ho/2).  lens: HOST array of ten doubles fx, fy, cx, cy, k1, k2, k3, k4, p1, p2 -- intrinsics in pixels of the
+ * source image, COLMAP's convention (the centre of the top-left pixel is at (0.5, 0.5)); `fisheye`: 0 or 1.  For output
+ * pixel (i, j), all in float64, every product and sum rounded on its own in the order written:
+ *   x = (j + 0.5 - Wo/2) / fxo,   y = (i + 0.5 - Ho/2) / fyo,   r2 = x*x + y*y
+ *   perspective:  rad  = 1 + r2*(k1 + r2*k2)
+ *                 mono = 1 + r2*(3*k1 + r2*5*k2)
+ *                 xd = x*rad + 2*p1*x*y + p2*(r2 + 2*x*x)
+ *                 yd = y*rad + p1*(r2 + 2*y*y) + 2*p2*x*y
+ *   fisheye:      r = sqrt(r2),  th = atan(r),  t2 = th*th
+ *                 rad  = 1 + t2*(k1 + t2*(k2 + t2*(k3 + t2*k4)))
+ *                 mono = 1 + t2*(3*k1 + t2*(5*k2 + t2*(7*k3 + t2*9*k4)))
+ *                 s = th*rad/r  (s = 1 where r < 1e-12),  xd = x*s,  yd = y*s
+ *   u = fx*xd + cx - 0.5,   v = fy*yd + cy - 0.5        (the source sample position, in pixel indices)
+ * valid, with tau = 2^-20:  mono > 0  (the derivative of the distorted radius: where it is not positive a strongly
+ *   negative k1 has folded the radial profile back and (u, v) is a second image of a ray that is not there),
+ *   -tau <= u <= Ws-1+tau  and  -tau <= v <= Hs-1+tau;  with src_mask (uint8 [Hs,Ws]) also all four taps non-zero there.
+ * sampling: u, v clamped into [0, Ws-1] x [0, Hs-1];  x0 = min(floor(u), max(Ws-2, 0)),  x1 = min(x0+1, Ws-1),
+ *   a = u - x0;  y0, y1, b likewise from v;
+ *   val = (1-b)*((1-a)*p[y0,x0] + a*p[y0,x1]) + b*((1-a)*p[y1,x0] + a*p[y1,x1]);  out = floor(val + 0.5) where valid, else 0.
+ * u8: `planes` contiguous planes, one map for all of them; optional outputs `valid` (uint8 [Ho,Wo], 255 / 0) and `count`
+ * (device int64, 8-byte aligned: zeroed on the stream, receives the number of valid pixels by integer atomics); optional
+ * input src_mask.  u16: one plane, same map, same rounding, no mask.  What is written overlaps nothing that is read;
+ * every side <= 32768.  The same inputs give the same bits on every run.  A size or `planes` below 1, a null src / dst /
+ * lens, a non-finite or non-positive focal length or a non-finite lens term return CLMGS_EINVAL before anything is
+ * written. */
+int clmgs_undistort_u8(void* stream, int planes, int Hs, int Ws, int Ho, int Wo, const double* lens, int fisheye,
+                       double fxo, double fyo, const uint8_t* src, const uint8_t* src_mask, uint8_t* dst, uint8_t* valid,
+                       int64_t* count);
+int clmgs_undistort_u16(void* stream, int Hs, int Ws, int Ho, int Wo, const double* lens, int fisheye, double fxo,
+                        double fyo, const uint16_t* src, uint16_t* dst);
+
 /* ---- pinned host memory  (numba.cuda.pinned_array at clm_offload/gaussian_model.py:34-44) */
 void* clmgs_pinned_alloc(size_t bytes);
 int clmgs_pinned_free(void* p);
