@@ -117,6 +117,11 @@ SIGNATURES = {
     # lens distortion: sizes, the host lens record [10 doubles], the fisheye flag, fxo, fyo, src, (src_mask), dst, (valid, count)
     "clmgs_undistort_u8": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _d, _d, _vp, _vp, _vp, _vp, _vp]),
     "clmgs_undistort_u16": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _d, _d, _vp, _vp]),
+    # compressed models: n, K, rows, codebook, idx, (dist), temp | rows, idx, scale, acc, counts | acc, counts, scale, codebook
+    "clmgs_vq_assign_temp_bytes": (_sz, [_i]),
+    "clmgs_vq_assign": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _vp, _vp, _sz]),
+    "clmgs_vq_accumulate": (_i, [_vp, _i64, _i, _vp, _vp, _d, _vp, _vp]),
+    "clmgs_vq_finish": (_i, [_vp, _i, _vp, _vp, _d, _vp]),
     "clmgs_mcmc_relocation": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "clmgs_mcmc_reg_grad": (_i, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _f, _f]),
     "clmgs_mcmc_noise": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _f, _vp]),
@@ -195,7 +200,7 @@ class _Namespace:
 _NO_STREAM = {"clmgs_version", "clmgs_loss_slots", "clmgs_preprocess_grid_cap","clmgs_exposure_partials_rows", "clmgs_bilagrid_partials_rows", "clmgs_invdepth_partials_rows", "clmgs_pose_grad_partials_rows", "clmgs_projection_viewmat_partials_rows", "clmgs_small_deferred_kmax", "clmgs_isect3_front_temp_bytes",
               "clmgs_isect3_bin_temp_bytes", "clmgs_last_error", "clmgs_isect_count_temp_bytes",
               "clmgs_isect_sort_temp_bytes", "clmgs_host_groups_temp_bytes", "clmgs_isect2_order_temp_bytes", "clmgs_isect2_sort_temp_bytes", "clmgs_visibility_select_temp_bytes", "clmgs_rasterize_pack_bytes", "clmgs_rasterize_contrib_pack_bytes", "clmgs_rasterize_partials_bytes", "clmgs_host_adam_rows", "clmgs_host_pool_start", "clmgs_host_usable_cpus", "clmgs_host_rows_prepare", "clmgs_tsp_tour",
-              "clmgs_pinned_alloc", "clmgs_pinned_free", "clmgs_device_errors"}
+              "clmgs_pinned_alloc", "clmgs_pinned_free", "clmgs_device_errors", "clmgs_vq_assign_temp_bytes"}
 
 
 def timing_summary():

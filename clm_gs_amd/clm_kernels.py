@@ -567,6 +567,90 @@ def undistort(src, lens, out_size=None, zoom=1.0, src_mask=None, want_valid=Fals
     return (out, valid, count) if want_valid else out
 
 
+# ------------------------------------------------------------ compressed models
+VQ_MAX_K = 65536
+
+
+def _vq_rows(t, what, n=None):
+    """A [n,48] float32 contiguous device table (`n`: the number of rows it must have); anything else is refused."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise _lib.ClmgsError(f"{what} must be a tensor on the device (no CPU fallback in clm_gs_amd)")
+    if not t.is_contiguous():
+        raise _lib.ClmgsError(f"{what} must be contiguous")
+    if t.dtype != F32 or t.dim() != 2 or t.shape[1] != 48 or (n is not None and t.shape[0] != n):
+        raise _lib.ClmgsError(f"{what}: float32 [{'N' if n is None else n}, 48] expected, got {t.dtype} {tuple(t.shape)}")
+    return t
+
+
+def _vq_sizes(rows, codebook):
+    _vq_rows(rows, "vq: rows")
+    _vq_rows(codebook, "vq: codebook")
+    n, k = int(rows.shape[0]), int(codebook.shape[0])
+    if not 1 <= k <= VQ_MAX_K:
+        raise _lib.ClmgsError(f"vq: K must be in [1, {VQ_MAX_K}], got {k}")
+    if n >= 1 << 31:
+        raise _lib.ClmgsError(f"vq: N must be below 2^31, got {n}")
+    if n < 1:
+        raise _lib.ClmgsError("vq: at least one row expected")
+    if rows.device != codebook.device:
+        raise _lib.ClmgsError(f"vq: rows are on {rows.device}, the codebook on {codebook.device}")
+    return n, k
+
+
+@torch.no_grad()
+def vq_assign(rows, codebook, want_dist=False):
+    """Nearest centroid of every SH row over its 45 higher-order coefficients (csrc/vq.hip; DESIGN.md section 3,
+    "Compressed models"): rows float32 [N,48], codebook float32 [K,48], both contiguous on the device, columns 0..2 (the
+    DC) ignored on both sides -> idx int32 [N] = argmin_k sum_{j=3..47} (x_j - c_kj)^2, the lowest k on an exact tie;
+    with want_dist (idx, dist), dist float32 [N] that squared distance.  1 <= K <= 65536, N < 2^31."""
+    n, k = _vq_sizes(rows, codebook)
+    L = _lib.lib()
+    idx = torch.empty((n,), dtype=I32, device=rows.device)
+    dist = torch.empty((n,), dtype=F32, device=rows.device) if want_dist else None
+    nbytes = int(L.clmgs_vq_assign_temp_bytes(k))
+    temp = torch.empty((nbytes,), dtype=U8, device=rows.device)
+    check(L.clmgs_vq_assign(stream(), n, k, dptr(rows, F32), dptr(codebook, F32), dptr(idx, I32),
+                            dptr(dist, F32, allow_none=True), dptr(temp), nbytes))
+    return (idx, dist) if want_dist else idx
+
+
+def vq_scale(n, max_abs):
+    """The power of two the Lloyd update multiplies a coefficient by before it rounds it to an integer: 2^(61 - e) with
+    e the binary exponent of n * max_abs (n * max_abs < 2^e), so that n * (max_abs * scale + 1/2) < 2^62 and a sum of n
+    rounded values fits an int64; an all-zero table takes 1."""
+    import math
+    prod = float(n) * float(max_abs)
+    if not math.isfinite(prod):
+        raise ValueError(f"vq: the rows must be finite, got max |x| = {max_abs}")
+    if prod <= 0.0:
+        return 1.0
+    return math.ldexp(1.0, max(-900, min(900, 61 - math.frexp(prod)[1])))
+
+
+@torch.no_grad()
+def vq_update(rows, idx, codebook, scale=None):
+    """One Lloyd update (csrc/vq.hip): every centroid becomes the mean of the rows assigned to it, summed in fixed point
+    (rint(x * scale) as int64 by integer atomics: the same bits whatever the order of the rows) -> (codebook, counts):
+    a NEW float32 [K,48] codebook (columns 0..2 zero; a centroid without rows keeps its previous columns 3..47) and
+    counts int64 [K].  idx int32 [N] as vq_assign returns it.  `scale`: None = vq_scale(N, max |x|)."""
+    n, k = _vq_sizes(rows, codebook)
+    if not (isinstance(idx, torch.Tensor) and idx.is_cuda and idx.is_contiguous() and idx.dtype == I32
+            and tuple(idx.shape) == (n,) and idx.device == rows.device):
+        raise _lib.ClmgsError(f"vq_update: idx must be a contiguous int32 [{n}] tensor on {rows.device}, got "
+                              f"{getattr(idx, 'dtype', type(idx))} {tuple(getattr(idx, 'shape', ()))}")
+    if scale is None:
+        lo, hi = torch.aminmax(rows)
+        scale = vq_scale(n, max(-float(lo), float(hi)))
+    L = _lib.lib()
+    acc = torch.zeros((k, 45), dtype=I64, device=rows.device)
+    counts = torch.zeros((k,), dtype=I64, device=rows.device)
+    out = codebook.clone()
+    check(L.clmgs_vq_accumulate(stream(), n, k, dptr(rows, F32), dptr(idx, I32), float(scale), dptr(acc, I64),
+                                dptr(counts, I64)))
+    check(L.clmgs_vq_finish(stream(), k, dptr(acc, I64), dptr(counts, I64), float(scale), dptr(out, F32)))
+    return out, counts
+
+
 # ------------------------------------------------------------ MCMC densification
 def _f32_dev(t, shape, what):
     assert t.is_cuda and t.dtype == F32 and t.is_contiguous() and tuple(t.shape) == tuple(shape), \

@@ -68,3 +68,15 @@ def load_ply(path):
     return dict(xyz=t(get(["x", "y", "z"])), shs48=t(sh.reshape(n, 48)), opacity=t(get(["opacity"])),
                 scaling=t(get(["scale_0", "scale_1", "scale_2"])),
                 rotation=t(get(["rot_0", "rot_1", "rot_2", "rot_3"])))
+
+
+def load_model(path):
+    """A finished model by its extension: .ply -> load_ply, .npz (a compressed model, clm_gs_amd/compress.py) ->
+    compress.load_compressed; both return load_ply's dict."""
+    p = str(path).lower()
+    if p.endswith(".ply"):
+        return load_ply(path)
+    if p.endswith(".npz"):
+        from .compress import load_compressed
+        return load_compressed(path)
+    raise ValueError(f"{path}: a model file is a .ply or a compressed .npz")

@@ -33,7 +33,7 @@ def prune_ply(ply_path, source_path, out_path, mode="sum", ratio=0.3, threshold=
     assert len(sizes) == 1, f"all images must share one size: {sizes}"
     h, w = next(iter(sizes))
     utils.set_img_size(h, w)
-    rows = io_ply.load_ply(ply_path)
+    rows = io_ply.load_model(ply_path)
     model = contribution.tensors_model(rows["xyz"], rows["opacity"], rows["scaling"], rows["rotation"])
     t0 = time.perf_counter()
     stats = contribution.score_cameras(model, cams)

@@ -162,7 +162,7 @@ def render_trajectory(gaussians, cameras, args, output_dir, background=None, log
 
 
 def _find_ply(model_path, iteration):
-    if model_path.endswith(".ply"):
+    if model_path.endswith((".ply", ".npz")):  # a model file: a .ply or a compressed model (io_ply.load_model)
         return model_path
     pc = os.path.join(model_path, "point_cloud")
     if iteration < 0:  # searchForMaxIteration (utils/system_utils.py)
@@ -173,7 +173,7 @@ def _find_ply(model_path, iteration):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description="Trajectory rendering")
-    ap.add_argument("-m", "--model_path", required=True, help="model directory (point_cloud/iteration_*/point_cloud.ply) or a .ply")
+    ap.add_argument("-m", "--model_path", required=True, help="model directory (point_cloud/iteration_*/point_cloud.ply), a .ply or a compressed .npz")
     ap.add_argument("--iteration", type=int, default=-1)
     ap.add_argument("--traj_path", default="original")
     ap.add_argument("--manual_height", type=float, default=30.0)

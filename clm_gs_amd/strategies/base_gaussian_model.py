@@ -486,8 +486,8 @@ class BaseGaussianModel(ABC):
         self.active_sh_degree = self.max_sh_degree
 
     def load_ply(self, path, spatial_lr_scale=1.0):
-        from ..io_ply import load_ply
-        d = load_ply(path)
+        from ..io_ply import load_model  # a .ply, or a compressed .npz (clm_gs_amd/compress.py)
+        d = load_model(path)
         self.create_from_tensors(d["xyz"], d["shs48"], d["scaling"], d["rotation"], d["opacity"],
                                  spatial_lr_scale)
         self.active_sh_degree = self.max_sh_degree

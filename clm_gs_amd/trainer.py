@@ -322,10 +322,32 @@ def check_training(args, depth_priors=False, models=None, num_downscales=None, r
          "--sky and --white_background together are refused: the sky map is the background"),
         (on("sky") and on("pose_opt"), "--sky and --pose_opt together are refused: the sky's gradient with respect to the "
          "camera (the ray direction of the lookup) is not carried"),
-    ] + undistort_rules(args) + resolution_rules(args, on("pose_opt"), num_downscales, resolution_schedule, image_size) + [camera_dp_rule(r.flag, on(r.flag)) for r in SIDE_MODELS if r.not_shared])
+    ] + undistort_rules(args) + compress_rules(args) + resolution_rules(args, on("pose_opt"), num_downscales, resolution_schedule, image_size) + [camera_dp_rule(r.flag, on(r.flag)) for r in SIDE_MODELS if r.not_shared])
     check_pose_args(args, depth_priors, enabled=on("pose_opt"))
     check_mcmc_args(args)
     check_contrib_prune_args(args)
+
+
+def compress_bits(args):
+    """The bit widths of --compress as compress.check_bits takes them (raises on one outside [1, 16])."""
+    from .compress import BITS, check_bits
+    return check_bits({b: getattr(args, "compress_" + b, v) for b, v in BITS.items()})
+
+
+def compress_rules(args):
+    """The (condition, message) rules of --compress for check_training: the knobs are checked before anything is loaded."""
+    if not getattr(args, "compress", False):
+        return []
+    rules = [(not 1 <= int(getattr(args, "compress_codebook", 65536)) <= 65536,
+              f"--compress_codebook must be in [1, 65536], got {getattr(args, 'compress_codebook', None)}"),
+             (int(getattr(args, "compress_iters", 10)) < 0 or int(getattr(args, "compress_sample", 1)) < 1,
+              "--compress_iters must be >= 0 and --compress_sample >= 1"),
+             (int(getattr(args, "sh_degree", 3)) != 3, "--compress: SH degrees other than 3 are not supported")]
+    try:
+        compress_bits(args)
+    except ValueError as e:
+        rules.append((True, str(e)))
+    return rules
 
 
 def undistort_rules(args):
@@ -770,7 +792,13 @@ def train_from_colmap(source_path, model_path, strategy="clm_offload", iteration
         if hasattr(gaussians, "flush_lazy_rows"):
             gaussians.flush_lazy_rows()  # ALL ranks (a collective under owner-computes / locality camera-DP) ...
         if dp.rank() == 0:               # ... then rank-0-only I/O (no collective left inside save_ply: nothing is dirty)
-            gaussians.save_ply(os.path.join(model_path, "point_cloud", f"iteration_{args.iterations}", "point_cloud.ply"))
+            ply = os.path.join(model_path, "point_cloud", f"iteration_{args.iterations}", "point_cloud.ply")
+            gaussians.save_ply(ply)
+            if args.compress:
+                from .compress_model import compress_file
+                with open(os.path.join(model_path, "python_ws=1_rk=0.log"), "a") as log_file:
+                    compress_file(ply, ply[:-4] + ".vq.npz", args.compress_codebook, args.compress_iters, args.compress_sample,
+                                  compress_bits(args), log=log_file)
             for row in SIDE_MODELS:
                 if getattr(scene, row.name) is not None:
                     getattr(scene, row.name).save_to(model_path, scene.train_cameras)
@@ -852,6 +880,11 @@ OPTIONS = (
     _opt("--contrib_prune_mode", choices=["sum", "max"], help="sum: prune the lowest --contrib_prune_ratio of rows by "
          "summed weight; max: prune rows whose largest weight is below --contrib_prune_threshold"),
     _opt("--contrib_prune_ratio", type=float), _opt("--contrib_prune_threshold", type=float),
+    _opt("--compress", action="store_true", help="compressed export: after the final .ply also write point_cloud.vq.npz next "
+         "to it (SH vector quantisation + quantised attributes, clm_gs_amd.compress_model) and log its size line"),
+    _opt("--compress_codebook", type=int, metavar="K", help="--compress: number of SH centroids (<= 65536)"),
+    _opt("--compress_iters", type=int), _opt("--compress_sample", type=int),
+    *(_opt("--compress_" + b, type=int) for b in ("pos_bits", "scale_bits", "opacity_bits", "rot_bits", "dc_bits")),
 )
 
 

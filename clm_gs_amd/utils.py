@@ -88,6 +88,11 @@ def default_args(**over):
         # principal point, are remapped onto centred pinholes with focal lengths f * undistort_zoom on the device at load;
         # False = the loader as it was (distortion terms and principal points ignored, the three models refused)
         undistort=False, undistort_zoom=1.0,
+        # this build: compressed export (compress.py; csrc/vq.hip): after the final .ply, point_cloud.vq.npz next to it --
+        # the SH rest as indices into a compress_codebook-entry k-means codebook (compress_iters Lloyd iterations on
+        # compress_sample rows), the other attributes at compress_*_bits per value; False = nothing more is called
+        compress=False, compress_codebook=65536, compress_iters=10, compress_sample=1 << 22, compress_pos_bits=16,
+        compress_scale_bits=8, compress_opacity_bits=8, compress_rot_bits=8, compress_dc_bits=8,
         lr_scale_mode="sqrt", bsz=1, exact_filter=True, log_cpu_adam_trailing_overhead=False,
         # Debug
         stop_update_param=False, drop_initial_3dgs_p=0.0,

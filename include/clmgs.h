@@ -943,6 +943,30 @@ int clmgs_undistort_u8(void* stream, int planes, int Hs, int Ws, int Ho, int Wo,
 int clmgs_undistort_u16(void* stream, int Hs, int Ws, int Ho, int Wo, const double* lens, int fisheye, double fxo,
                         double fyo, const uint16_t* src, uint16_t* dst);
 
+/* ---- compressed models (csrc/vq.hip; clm_gs_amd/compress.py): vector quantisation of the 45 higher-order SH
+ * coefficients.  rows [n,48] and codebook [K,48] are float32 in the in-memory SH row layout (coefficient-major, DC in
+ * columns 0..2), contiguous and 16-byte aligned; columns 0..2 of both are read and IGNORED (taken as zeros).
+ * 1 <= n < 2^31, 1 <= K <= 65536; nothing is allocated.
+ *  - clmgs_vq_assign: idx[n] (int32) = argmin_k sum_{j=3..47} (x_j - c_kj)^2, scored as |c_k|^2 - 2 x.c_k with x.c_k a
+ *    column-ordered float32 fmaf chain (the exact f32 MFMA) and |c_k|^2 a column-ordered fmaf sum; the lowest k wins an
+ *    exact tie of the scores.  dist (optional, float32 [n]) = sum_{j=3..47} (x_j - c_kj)^2 for the k chosen, summed
+ *    directly from the winning centroid (exactly 0 for a row equal to its centroid), not as |x|^2 + score.  temp:
+ *    clmgs_vq_assign_temp_bytes(K) bytes, 16-byte aligned (the |c_k|^2 of a pre-pass).  Rows and centroids outside
+ *    [0,n) x [0,K) are neither read nor written.
+ *  - clmgs_vq_accumulate: for every row, counts[idx[row]] += 1 and acc[idx[row], j-3] += rint(double(x_j) * scale) for
+ *    j = 3..47, by 64-bit integer atomics only: acc int64 [K,45] and counts int64 [K] are the CALLER's and are added to
+ *    (zero them before the first call; several calls sum several chunks of rows).  scale is a power of two with
+ *    n_total * max|x| * scale < 2^62.  A row whose idx is outside [0,K) adds nothing.  The sums do not depend on the
+ *    order of the rows: the same bits on every run.
+ *  - clmgs_vq_finish: codebook[k, j] = float32(double(acc[k, j-3]) / double(counts[k]) / scale) for j = 3..47 where
+ *    counts[k] > 0; a centroid with counts[k] == 0 keeps those columns; columns 0..2 of every centroid are written as 0. */
+size_t clmgs_vq_assign_temp_bytes(int K);
+int clmgs_vq_assign(void* stream, int64_t n, int K, const float* rows, const float* codebook, int32_t* idx, float* dist,
+                    void* temp, size_t temp_bytes);
+int clmgs_vq_accumulate(void* stream, int64_t n, int K, const float* rows, const int32_t* idx, double scale, int64_t* acc,
+                        int64_t* counts);
+int clmgs_vq_finish(void* stream, int K, const int64_t* acc, const int64_t* counts, double scale, float* codebook);
+
 /* ---- pinned host memory  (numba.cuda.pinned_array at clm_offload/gaussian_model.py:34-44) */
 void* clmgs_pinned_alloc(size_t bytes);
 int clmgs_pinned_free(void* p);
