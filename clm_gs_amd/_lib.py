@@ -122,6 +122,13 @@ SIGNATURES = {
     "clmgs_vq_assign": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _vp, _vp, _sz]),
     "clmgs_vq_accumulate": (_i, [_vp, _i64, _i, _vp, _vp, _d, _vp, _vp]),
     "clmgs_vq_finish": (_i, [_vp, _i, _vp, _vp, _d, _vp]),
+    # mesh export: grid dims, grid, B, H, W, depth, alpha, rgb, host cams[B,16], near, depth_max, alpha_min, trunc, inv_trunc,
+    # cull | grid, min_weight, cell_count | grid, cell_scan, V, host grid_to_world[12], verts, colours | ... quad_count | faces
+    "clmgs_tsdf_integrate": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _i]),
+    "clmgs_tsdf_cells": (_i, [_vp, _i, _i, _i, _vp, _f, _vp]),
+    "clmgs_tsdf_vertices": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    "clmgs_tsdf_quad_count": (_i, [_vp, _i, _i, _i, _vp, _f, _vp, _vp]),
+    "clmgs_tsdf_quads": (_i, [_vp, _i, _i, _i, _vp, _f, _vp, _vp, _i, _i, _vp]),
     "clmgs_mcmc_relocation": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "clmgs_mcmc_reg_grad": (_i, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _f, _f]),
     "clmgs_mcmc_noise": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _f, _vp]),

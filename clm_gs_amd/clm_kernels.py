@@ -651,6 +651,99 @@ def vq_update(rows, idx, codebook, scale=None):
     return out, counts
 
 
+# ------------------------------------------------------------------ mesh export
+TSDF_MAX_B = 16
+
+
+def _tsdf_grid(grid):
+    if not (isinstance(grid, torch.Tensor) and grid.is_cuda and grid.is_contiguous() and grid.dtype == F32
+            and grid.dim() == 4 and grid.shape[0] == 6):
+        raise _lib.ClmgsError("tsdf: the volume is a contiguous float32 [6, nz, ny, nx] device tensor, got "
+                              f"{getattr(grid, 'dtype', type(grid))} {tuple(getattr(grid, 'shape', ()))}")
+    nz, ny, nx = (int(v) for v in grid.shape[1:])
+    if min(nx, ny, nz) < 2 or nx * ny * nz >= 1 << 31:
+        raise _lib.ClmgsError(f"tsdf: every side of the volume must be >= 2 and nx ny nz < 2^31, got {nx} x {ny} x {nz}")
+    return nx, ny, nz
+
+
+@torch.no_grad()
+def tsdf_integrate(grid, depth, alpha, rgb, cams, near=0.01, depth_max=float("inf"), alpha_min=0.5, trunc=1.0, cull=True):
+    """Fuses cameras into a TSDF volume in place (csrc/tsdf.hip; DESIGN.md section 3, "Mesh export"): grid float32
+    [6,nz,ny,nx] (tsum, wsum, cr, cg, cb, cw); depth [B,H,W] (expected depth), alpha [B,H,W], rgb [B,3,H,W], float32 on the
+    device; cams float64 [B,16] on the HOST (numpy or tensor): per camera the 3x4 matrix from grid coordinates (voxel
+    (i,j,k) at (i+0.5, j+0.5, k+0.5)) to camera space, then fx, fy, cx, cy; trunc in camera-space units.  More than 16
+    cameras go in launches of 16, in order: the result does not depend on how they are split.  `cull`: the brick-level
+    frustum test (the same bits with and without).  Returns grid."""
+    import numpy as np
+    nx, ny, nz = _tsdf_grid(grid)
+    cams = np.ascontiguousarray(cams.numpy() if isinstance(cams, torch.Tensor) else cams, dtype=np.float64)
+    if not (isinstance(depth, torch.Tensor) and depth.dim() == 3 and cams.shape == (depth.shape[0], 16) and depth.shape[0] >= 1):
+        raise _lib.ClmgsError(f"tsdf_integrate: depth [B,H,W] and cams [B,16] expected, got {tuple(getattr(depth, 'shape', ()))} "
+                              f"and {cams.shape}")
+    B, H, W = (int(v) for v in depth.shape)
+    for t, shape, what in ((depth, (B, H, W), "depth"), (alpha, (B, H, W), "alpha"), (rgb, (B, 3, H, W), "rgb")):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.dtype == F32 and tuple(t.shape) == shape
+                and t.device == grid.device):
+            raise _lib.ClmgsError(f"tsdf_integrate: {what} must be a contiguous float32 {shape} tensor on {grid.device}, got "
+                                  f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+    trunc32 = float(torch.tensor(float(trunc), dtype=F32))
+    if not (_finite(trunc32) and trunc32 > 0):
+        raise ValueError(f"tsdf_integrate: trunc must be positive and finite, got {trunc}")
+    inv_trunc = float(torch.tensor(1.0, dtype=F32) / torch.tensor(trunc32, dtype=F32))  # the float32 quotient
+    L = _lib.lib()
+    for b0 in range(0, B, TSDF_MAX_B):
+        b1 = min(B, b0 + TSDF_MAX_B)
+        rec = (ctypes.c_double * (16 * (b1 - b0)))(*cams[b0:b1].reshape(-1))
+        check(L.clmgs_tsdf_integrate(stream(), nx, ny, nz, dptr(grid, F32), b1 - b0, H, W, dptr(depth[b0:b1], F32),
+                                     dptr(alpha[b0:b1], F32), dptr(rgb[b0:b1], F32), rec, float(near), float(depth_max),
+                                     float(alpha_min), trunc32, inv_trunc, 1 if cull else 0))
+    return grid
+
+
+@torch.no_grad()
+def tsdf_extract(grid, min_weight, grid_to_world):
+    """Naive Surface Nets on a TSDF volume (csrc/tsdf.hip): a voxel is valid iff wsum >= min_weight and inside iff
+    tsum < 0; every cell of eight valid voxels whose flags differ gets one vertex, every sign-changing grid edge whose four
+    cells are active one quad (two triangles).  grid_to_world: float64 [3,4] on the host, from grid coordinates to the
+    frame the vertices are wanted in.  -> (verts float32 [V,3], colours uint8 [V,3], faces int32 [F,3]) on the device,
+    vertices in cell order, faces in (owner voxel, axis) order; V = F = 0 for a volume without a surface."""
+    import numpy as np
+    nx, ny, nz = _tsdf_grid(grid)
+    g2w = np.ascontiguousarray(grid_to_world.numpy() if isinstance(grid_to_world, torch.Tensor) else grid_to_world,
+                               dtype=np.float64)
+    if g2w.shape != (3, 4) or not np.isfinite(g2w).all():
+        raise ValueError(f"tsdf_extract: grid_to_world must be a finite 3x4 matrix, got shape {g2w.shape}")
+    mw = float(torch.tensor(float(min_weight), dtype=F32))
+    if not (_finite(mw) and mw > 0):
+        raise ValueError(f"tsdf_extract: min_weight must be positive and finite, got {min_weight}")
+    L, dev, n = _lib.lib(), grid.device, nx * ny * nz
+    empty = (torch.empty((0, 3), dtype=F32, device=dev), torch.empty((0, 3), dtype=U8, device=dev),
+             torch.empty((0, 3), dtype=I32, device=dev))
+    count = torch.empty((n,), dtype=I32, device=dev)
+    check(L.clmgs_tsdf_cells(stream(), nx, ny, nz, dptr(grid, F32), mw, dptr(count, I32)))
+    cell_scan = torch.cumsum(count, 0, dtype=I32)
+    V = int(cell_scan[-1])
+    if V == 0:
+        return empty
+    verts = torch.empty((V, 3), dtype=F32, device=dev)
+    colours = torch.empty((V, 3), dtype=U8, device=dev)
+    rec = (ctypes.c_double * 12)(*g2w.reshape(-1))
+    check(L.clmgs_tsdf_vertices(stream(), nx, ny, nz, dptr(grid, F32), dptr(cell_scan, I32), V, rec, dptr(verts, F32),
+                                dptr(colours, U8)))
+    check(L.clmgs_tsdf_quad_count(stream(), nx, ny, nz, dptr(grid, F32), mw, dptr(cell_scan, I32), dptr(count, I32)))
+    Q = int(count.sum(dtype=I64))
+    if Q >= 1 << 30:
+        raise _lib.ClmgsError(f"tsdf_extract: {Q} quads, 2^30 at the most: extract with a larger voxel or a smaller box")
+    if Q == 0:
+        return verts, colours, empty[2]
+    quad_scan = torch.cumsum(count, 0, dtype=I32)
+    del count
+    faces = torch.empty((2 * Q, 3), dtype=I32, device=dev)
+    check(L.clmgs_tsdf_quads(stream(), nx, ny, nz, dptr(grid, F32), mw, dptr(cell_scan, I32), dptr(quad_scan, I32), V, Q,
+                             dptr(faces, I32)))
+    return verts, colours, faces
+
+
 # ------------------------------------------------------------ MCMC densification
 def _f32_dev(t, shape, what):
     assert t.is_cuda and t.dtype == F32 and t.is_contiguous() and tuple(t.shape) == tuple(shape), \

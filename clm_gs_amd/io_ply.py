@@ -80,3 +80,66 @@ def load_model(path):
         from .compress import load_compressed
         return load_compressed(path)
     raise ValueError(f"{path}: a model file is a .ply or a compressed .npz")
+
+
+_MESH_VERTEX = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+_MESH_FACE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])
+
+
+def _host(a, dtype):
+    return np.ascontiguousarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=dtype)
+
+
+def save_mesh_ply(path, verts, colours, faces):
+    """A triangle mesh (clm_gs_amd/tsdf.py) as a binary little-endian .ply: vertex properties x y z (float) and red green
+    blue (uchar), faces as `property list uchar int vertex_indices`.  verts [V,3], colours [V,3] in 0..255, faces [F,3]
+    (tensors or arrays); V = F = 0 is a valid, empty mesh."""
+    verts, colours, faces = _host(verts, np.float32), _host(colours, np.uint8), _host(faces, np.int32)
+    verts, colours, faces = verts.reshape(-1, 3), colours.reshape(-1, 3), faces.reshape(-1, 3)
+    if len(colours) != len(verts):
+        raise ValueError(f"save_mesh_ply: {len(verts)} vertices and {len(colours)} colours")
+    if len(faces) and (int(faces.min()) < 0 or int(faces.max()) >= len(verts)):
+        raise ValueError(f"save_mesh_ply: a face index lies outside [0, {len(verts)})")
+    v = np.empty(len(verts), dtype=_MESH_VERTEX)
+    for k, name in enumerate(("x", "y", "z")):
+        v[name] = verts[:, k]
+    for k, name in enumerate(("red", "green", "blue")):
+        v[name] = colours[:, k]
+    f = np.empty(len(faces), dtype=_MESH_FACE)
+    f["n"], f["v"] = 3, faces
+    header = "ply\nformat binary_little_endian 1.0\nelement vertex %d\n" % len(v)
+    header += "property float x\nproperty float y\nproperty float z\n"
+    header += "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+    header += "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % len(f)
+    with open(path, "wb") as out:
+        out.write(header.encode("ascii"))
+        out.write(v.tobytes())
+        out.write(f.tobytes())
+
+
+def load_mesh_ply(path):
+    """Inverse of save_mesh_ply -> (verts float32 [V,3], colours uint8 [V,3], faces int32 [F,3]) numpy arrays.  Reads
+    the layout save_mesh_ply writes (triangles only); anything else is refused by name."""
+    with open(path, "rb") as f:
+        if f.readline().strip() != b"ply" or f.readline().decode().split()[1:2] != ["binary_little_endian"]:
+            raise ValueError(f"{path}: a binary little-endian .ply expected")
+        counts, props, element = {}, {}, None
+        while True:
+            tok = f.readline().decode().split()
+            if tok[:1] == ["end_header"]:
+                break
+            if tok[:1] == ["element"]:
+                element = tok[1]
+                counts[element], props[element] = int(tok[2]), []
+            elif tok[:1] == ["property"]:
+                props[element].append(" ".join(tok[1:]))
+        if props.get("vertex") != ["float x", "float y", "float z", "uchar red", "uchar green", "uchar blue"] or \
+                props.get("face") != ["list uchar int vertex_indices"]:
+            raise ValueError(f"{path}: not a mesh written by save_mesh_ply (properties {props})")
+        v = np.frombuffer(f.read(counts["vertex"] * _MESH_VERTEX.itemsize), dtype=_MESH_VERTEX)
+        fc = np.frombuffer(f.read(counts["face"] * _MESH_FACE.itemsize), dtype=_MESH_FACE)
+    if len(v) != counts["vertex"] or len(fc) != counts["face"] or (len(fc) and not (fc["n"] == 3).all()):
+        raise ValueError(f"{path}: truncated, or a face that is no triangle")
+    verts = np.stack([v["x"], v["y"], v["z"]], axis=1).astype(np.float32).reshape(-1, 3)
+    colours = np.stack([v["red"], v["green"], v["blue"]], axis=1).astype(np.uint8).reshape(-1, 3)
+    return verts, colours, np.ascontiguousarray(fc["v"], dtype=np.int32).reshape(-1, 3)

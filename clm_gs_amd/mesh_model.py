@@ -1,0 +1,176 @@
+"""Mesh export of a finished model ("Mesh export"):
+
+    python -m clm_gs_amd.mesh_model -m <model dir | .ply | .vq.npz> -s <colmap dir> -o <mesh.ply> --voxel V
+        [--trunc_voxels 4] [--bounds emin nmin umin emax nmax umax] [--up X Y Z] [--east X Y Z] [--every K] [-r R]
+        [--alpha_min 0.5] [--depth_max D] [--min_weight 2] [--grid_gb 16] [--antialiased] [--undistort --undistort_zoom Z]
+        [--eval] [--clm_offload | --naive_offload | --no_offload]
+
+renders every selected training camera of the scene through the strategy's own eval entry (render_mode "RGB+ED":
+expected depth and alpha), fuses the depth maps into a dense TSDF volume in the map frame of render_ortho (tsdf.TsdfVolume,
+csrc/tsdf.hip), extracts the surface by naive Surface Nets and writes the coloured triangle mesh (io_ply.save_mesh_ply)
+and, next to it, <mesh>.json: frame, bounds, voxel, truncation, grid, counts and the cameras used.  --bounds default: the
+1st to 99th percentile box of the rows in the map frame.  A non-positive --voxel, inverted --bounds and a grid above
+--grid_gb or 2^31 voxels are refused by name (with the voxel size that fits) before anything is loaded or written.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import torch
+
+from . import io_ply, tsdf, utils
+from .render_ortho import map_frame, percentile_sorted
+from .render_trajectory import _find_ply, eval_one_cam
+
+
+def percentile_box(means, frame, lo=1.0, hi=99.0):
+    """(emin, nmin, umin, emax, nmax, umax): the lo-th to hi-th percentile of the rows along the three axes of the frame."""
+    if means.shape[0] == 0:
+        raise ValueError("percentile bounds of an empty model")
+    los, his = [], []
+    for axis in frame:
+        coord = torch.sort(means.detach().float() @ torch.as_tensor(axis, dtype=torch.float32, device=means.device)).values
+        los.append(percentile_sorted(coord, lo))
+        his.append(percentile_sorted(coord, hi))
+    return tuple(los + his)
+
+
+def json_path(mesh_path):
+    return os.path.splitext(mesh_path)[0] + ".json"
+
+
+@torch.no_grad()
+def build_mesh(gaussians, cameras, args, out_path, voxel, frame=None, bounds=None, trunc_voxels=4.0, every=1, alpha_min=0.5,
+               depth_max=None, min_weight=2.0, grid_gb=16.0, near=0.01, background=None, log=None):
+    """Renders cameras[::every] from `gaussians` through the eval entry of the strategy `args` names, fuses them, extracts
+    and writes out_path and its .json.  -> the dict written to the .json.  The global image size (utils.set_img_size)
+    must be the cameras' size."""
+    log = log or sys.stdout
+    frame = frame if frame is not None else map_frame()
+    if bounds is None:
+        bounds = percentile_box(gaussians.get_xyz.detach().to("cuda"), frame)
+    volume = tsdf.TsdfVolume(frame, bounds, voxel, trunc_voxels, device="cuda", grid_gb=grid_gb)
+    cams = list(cameras)[::max(1, int(every))]
+    if not cams:
+        raise ValueError("mesh export: no camera selected")
+    depth_max = float("inf") if depth_max is None else float(depth_max)
+    t_render = t_fuse = 0.0
+    for cam in cams:
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        image, depth, alpha = eval_one_cam(cam, gaussians, background, args, None, render_mode="RGB+ED")
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        volume.add(cam, image, depth, alpha, near=near, depth_max=depth_max, alpha_min=alpha_min)
+        torch.cuda.synchronize()
+        t_render, t_fuse = t_render + (t1 - t0), t_fuse + (time.perf_counter() - t1)
+    t1 = time.perf_counter()
+    volume.flush()
+    torch.cuda.synchronize()
+    t_fuse += time.perf_counter() - t1
+    t0 = time.perf_counter()
+    verts, colours, faces = volume.extract(min_weight)
+    torch.cuda.synchronize()
+    t_extract = time.perf_counter() - t0
+    d = os.path.dirname(out_path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    io_ply.save_mesh_ply(out_path, verts, colours, faces)
+    e, n, u = volume.frame
+    meta = dict(east=[float(v) for v in e], north=[float(v) for v in n], up=[float(v) for v in u],
+                bounds=[float(v) for v in volume.bounds], voxel=volume.voxel, trunc=volume.trunc,
+                grid=[volume.nx, volume.ny, volume.nz], min_weight=float(min_weight), alpha_min=float(alpha_min),
+                depth_max=None if depth_max == float("inf") else depth_max, vertices=int(verts.shape[0]),
+                faces=int(faces.shape[0]), cameras=len(cams), camera_names=[str(c.image_name) for c in cams])
+    with open(json_path(out_path), "w") as f:
+        json.dump(meta, f, indent=1)
+    log.write("mesh export: grid {} x {} x {} voxel {:g} cameras {} render {:.1f} cameras/s integration {:.1f} cameras/s "
+              "extraction {:.3f} s vertices {} faces {} -> {}\n".format(
+                  volume.nx, volume.ny, volume.nz, volume.voxel, len(cams), len(cams) / max(t_render, 1e-9),
+                  len(cams) / max(t_fuse, 1e-9), t_extract, meta["vertices"], meta["faces"], out_path))
+    return meta
+
+
+def check_options(voxel, bounds=None, grid_gb=16.0, trunc_voxels=4.0, min_weight=2.0, every=1):
+    """The refusals that need nothing loaded (ValueError by name)."""
+    tsdf.grid_shape((0, 0, 0, 1, 1, 1), voxel)  # (--voxel alone)
+    if not trunc_voxels > 0:
+        raise ValueError(f"--trunc_voxels must be positive, got {trunc_voxels}")
+    if not min_weight > 0:
+        raise ValueError(f"--min_weight must be positive, got {min_weight}")
+    if int(every) < 1:
+        raise ValueError(f"--every must be >= 1, got {every}")
+    if not grid_gb > 0:
+        raise ValueError(f"--grid_gb must be positive, got {grid_gb}")
+    if bounds is not None:
+        tsdf.check_grid(bounds, voxel, grid_gb)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description="triangle mesh of a trained model: TSDF fusion of its rendered depth maps")
+    ap.add_argument("-m", "--model_path", required=True, help="model directory (point_cloud/iteration_*/point_cloud.ply), a .ply or a compressed .npz")
+    ap.add_argument("--iteration", type=int, default=-1)
+    ap.add_argument("-s", "--source_path", required=True, help="the COLMAP directory whose training cameras are rendered")
+    ap.add_argument("-i", "--images", default="images")
+    ap.add_argument("-r", "--resolution", type=float, default=1)
+    ap.add_argument("-o", "--output", required=True, help="the mesh (.ply); <output without .ply>.json is written next to it")
+    ap.add_argument("--voxel", type=float, required=True, help="voxel size in world units")
+    ap.add_argument("--trunc_voxels", type=float, default=4.0, help="truncation distance in voxels")
+    ap.add_argument("--bounds", type=float, nargs=6, default=None, metavar=("EMIN", "NMIN", "UMIN", "EMAX", "NMAX", "UMAX"),
+                    help="map coordinates; default: 1st to 99th percentile box of the rows")
+    ap.add_argument("--up", type=float, nargs=3, default=(0.0, 0.0, 1.0), metavar=("X", "Y", "Z"))
+    ap.add_argument("--east", type=float, nargs=3, default=(1.0, 0.0, 0.0), metavar=("X", "Y", "Z"))
+    ap.add_argument("--every", type=int, default=1, metavar="K", help="use every K-th training camera")
+    ap.add_argument("--alpha_min", type=float, default=0.5, help="pixels below this opacity are not fused")
+    ap.add_argument("--depth_max", type=float, default=None, help="pixels deeper than this are not fused")
+    ap.add_argument("--min_weight", type=float, default=2.0, help="a voxel counts when at least this many cameras observed it")
+    ap.add_argument("--grid_gb", type=float, default=16.0, help="the largest grid allocated (24 B per voxel)")
+    ap.add_argument("--antialiased", action="store_true", help="for a model trained with trainer --antialiased")
+    ap.add_argument("--undistort", action="store_true", help="for a model trained with trainer --undistort")
+    ap.add_argument("--undistort_zoom", type=float, default=1.0, help="--undistort: the trainer's --undistort_zoom")
+    ap.add_argument("--eval", action="store_true", help="leave the held-out test split out, as in training")
+    g = ap.add_mutually_exclusive_group()
+    g.add_argument("--clm_offload", action="store_true")
+    g.add_argument("--naive_offload", action="store_true")
+    g.add_argument("--no_offload", action="store_true")
+    a = ap.parse_args(argv)
+    try:  # refusals before anything is loaded or written
+        check_options(a.voxel, a.bounds, a.grid_gb, a.trunc_voxels, a.min_weight, a.every)
+        frame = map_frame(a.up, a.east)
+    except ValueError as e:
+        raise SystemExit(str(e))
+    if not (a.clm_offload or a.naive_offload or a.no_offload):
+        a.clm_offload = True
+    from .colmap_scene import load_colmap_scene
+    args = utils.default_args(bsz=4, rasterize_mode="antialiased" if a.antialiased else "classic")
+    for k in ("clm_offload", "naive_offload", "no_offload"):
+        setattr(args, k, getattr(a, k))
+    utils.set_args(args)
+    scene = load_colmap_scene(a.source_path, images=a.images, eval=a.eval, resolution=a.resolution, device="cuda",
+                              load_images=False, undistort=a.undistort, undistort_zoom=a.undistort_zoom)
+    cams = scene.train_cameras
+    sizes = {(c.image_height, c.image_width) for c in cams}
+    if len(sizes) != 1:
+        raise SystemExit(f"all images must share one size: {sizes}")
+    utils.set_img_size(*next(iter(sizes)))
+    if a.clm_offload:
+        from .strategies.clm_offload import GaussianModelCLMOffload as M
+    elif a.naive_offload:
+        from .strategies.naive_offload import GaussianModelNaiveOffload as M
+    else:
+        from .strategies.no_offload import GaussianModelNoOffload as M
+    gaussians = M(3, only_for_rendering=True)
+    gaussians.load_ply(_find_ply(a.model_path, a.iteration))
+    gaussians.active_sh_degree = gaussians.max_sh_degree
+    try:
+        build_mesh(gaussians, cams, args, a.output, a.voxel, frame, a.bounds, a.trunc_voxels, a.every, a.alpha_min,
+                   a.depth_max, a.min_weight, a.grid_gb)
+    except ValueError as e:  # (the size of a grid whose bounds come from the model)
+        raise SystemExit(str(e))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -322,10 +322,27 @@ def check_training(args, depth_priors=False, models=None, num_downscales=None, r
          "--sky and --white_background together are refused: the sky map is the background"),
         (on("sky") and on("pose_opt"), "--sky and --pose_opt together are refused: the sky's gradient with respect to the "
          "camera (the ray direction of the lookup) is not carried"),
-    ] + undistort_rules(args) + compress_rules(args) + resolution_rules(args, on("pose_opt"), num_downscales, resolution_schedule, image_size) + [camera_dp_rule(r.flag, on(r.flag)) for r in SIDE_MODELS if r.not_shared])
+    ] + undistort_rules(args) + compress_rules(args) + mesh_rules(args) + resolution_rules(args, on("pose_opt"), num_downscales, resolution_schedule, image_size) + [camera_dp_rule(r.flag, on(r.flag)) for r in SIDE_MODELS if r.not_shared])
     check_pose_args(args, depth_priors, enabled=on("pose_opt"))
     check_mcmc_args(args)
     check_contrib_prune_args(args)
+
+
+def mesh_rules(args):
+    """The (condition, message) rules of --mesh_voxel for check_training: checked before anything is loaded."""
+    voxel = getattr(args, "mesh_voxel", 0.0)
+    if not voxel:
+        return []
+    from .mesh_model import check_options
+    try:
+        check_options(voxel, None, getattr(args, "mesh_grid_gb", 16.0), getattr(args, "mesh_trunc_voxels", 4.0),
+                      getattr(args, "mesh_min_weight", 2.0), getattr(args, "mesh_every", 1))
+    except ValueError as e:
+        return [(True, str(e).replace("--voxel", "--mesh_voxel").replace("--trunc_voxels", "--mesh_trunc_voxels")
+                 .replace("--min_weight", "--mesh_min_weight").replace("--every", "--mesh_every").replace("--grid_gb", "--mesh_grid_gb"))]
+    ws = dp.world_size()
+    return [(ws > 1, "--mesh_voxel is not supported with {}; train on one GPU, or mesh the saved model with "
+             "clm_gs_amd.mesh_model".format(dp.refusal(ws, "the eval entry renders every training camera on one rank")))]
 
 
 def compress_bits(args):
@@ -799,6 +816,12 @@ def train_from_colmap(source_path, model_path, strategy="clm_offload", iteration
                 with open(os.path.join(model_path, "python_ws=1_rk=0.log"), "a") as log_file:
                     compress_file(ply, ply[:-4] + ".vq.npz", args.compress_codebook, args.compress_iters, args.compress_sample,
                                   compress_bits(args), log=log_file)
+            if args.mesh_voxel:
+                from .mesh_model import build_mesh
+                with open(os.path.join(model_path, "python_ws=1_rk=0.log"), "a") as log_file:
+                    build_mesh(gaussians, scene.train_cameras, args, os.path.join(model_path, "mesh.ply"), args.mesh_voxel,
+                               trunc_voxels=args.mesh_trunc_voxels, every=args.mesh_every, min_weight=args.mesh_min_weight,
+                               grid_gb=args.mesh_grid_gb, log=log_file)
             for row in SIDE_MODELS:
                 if getattr(scene, row.name) is not None:
                     getattr(scene, row.name).save_to(model_path, scene.train_cameras)
@@ -885,6 +908,11 @@ OPTIONS = (
     _opt("--compress_codebook", type=int, metavar="K", help="--compress: number of SH centroids (<= 65536)"),
     _opt("--compress_iters", type=int), _opt("--compress_sample", type=int),
     *(_opt("--compress_" + b, type=int) for b in ("pos_bits", "scale_bits", "opacity_bits", "rot_bits", "dc_bits")),
+    _opt("--mesh_voxel", type=float, metavar="V", help="mesh export: after the final .ply also write <model_path>/mesh.ply, "
+         "the training cameras' depth maps fused into a TSDF volume of V world units per voxel and its surface "
+         "(clm_gs_amd.mesh_model; single GPU); 0 = off"),
+    _opt("--mesh_trunc_voxels", type=float), _opt("--mesh_min_weight", type=float), _opt("--mesh_every", type=int),
+    _opt("--mesh_grid_gb", type=float),
 )
 
 

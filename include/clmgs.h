@@ -967,6 +967,51 @@ int clmgs_vq_accumulate(void* stream, int64_t n, int K, const float* rows, const
                         int64_t* counts);
 int clmgs_vq_finish(void* stream, int K, const int64_t* acc, const int64_t* counts, double scale, float* codebook);
 
+/* ---- mesh export (csrc/tsdf.hip, csrc/tsdf_math.h; clm_gs_amd/tsdf.py): TSDF fusion of depth maps into a dense grid and
+ * naive Surface Nets.  The volume: nx x ny x nz voxels, x fastest, as ONE contiguous float32 tensor [6, nz, ny, nx] with the
+ * planes tsum, wsum, cr, cg, cb, cw; every side >= 2 and nx ny nz < 2^31.  The kernels know nothing of the world frame.
+ *  - clmgs_tsdf_integrate fuses B (1..16) cameras of one size H x W (each <= 32768): depth [B,H,W] (expected depth), alpha
+ *    [B,H,W], rgb [B,3,H,W], float32 on the device; cams: HOST array [B,16] of doubles, per camera the 12 entries of the
+ *    3x4 row-major matrix M that takes the grid point (i + 0.5, j + 0.5, k + 0.5, 1) of voxel (i, j, k) to camera space,
+ *    then fx, fy, cx, cy.  Per voxel, for the cameras in the order given (float64, every operation rounded on its own):
+ *      x, y, z = M p (each row ((m0 px + m1 py) + m2 pz) + m3);  skip unless z > near
+ *      u = fx x / z + cx,  v = fy y / z + cy;  column floor(u), row floor(v) (pixel j covers [j, j + 1)); skip outside
+ *      d, a = depth, alpha of that pixel;  skip unless a >= alpha_min and 0 < d <= depth_max
+ *      sdf = d - (float) z  (float32);  skip if sdf < -trunc
+ *      tsum += fminf(sdf * inv_trunc, 1.0f);  wsum += 1.0f
+ *      if sdf <= trunc:  cr, cg, cb += the pixel's colour clamped to [0, 1];  cw += 1.0f
+ *    A voxel that no camera of the call observed is neither read nor written.  The sums are sequential in camera order and
+ *    a voxel has one owner (no atomics): splitting the cameras into calls differently gives the same bits.  cull: 1 = a
+ *    workgroup first tests the box of its 64 x 4 x 8 voxels against every camera's frustum with a margin and skips the
+ *    cameras that cannot observe it; 0 = no test; the result is the same, bit for bit.
+ *  - extraction, with two inclusive int32 prefix sums taken by the caller in between.  A voxel is valid iff
+ *    wsum >= min_weight (> 0) and inside iff tsum < 0; the cell at voxel (i, j, k) is that voxel and its +1 neighbours, and
+ *    is active iff all eight are valid and their inside flags differ.  All arrays below have one entry per VOXEL:
+ *      clmgs_tsdf_cells:      cell_count[v] = 1 if the cell at voxel v is active, else 0
+ *      clmgs_tsdf_vertices:   cell_scan = inclusive prefix sum of cell_count, V = its last entry; vertex cell_scan[v] - 1 of
+ *                             every active cell: the mean (float64) of the zero crossings of its sign-changing edges,
+ *                             interpolated linearly on tsum / wsum, in grid coordinates, through grid_to_world (HOST, 12
+ *                             doubles, 3x4 row-major) rounded to float32 -> verts [V,3]; the same mean of the corner colours
+ *                             c / cw (0.5 where cw == 0) as floor(255 c + 0.5) -> colours uint8 [V,3]
+ *      clmgs_tsdf_quad_count: quad_count[v] = how many of voxel v's +x, +y, +z grid edges carry a quad: both voxels valid,
+ *                             different inside flags, and the four cells around the edge active
+ *      clmgs_tsdf_quads:      quad_scan = inclusive prefix sum of quad_count, Q = its last entry (< 2^30); faces int32 [2Q,3]:
+ *                             per quad, in (voxel, axis) order, the four cells around the edge right-handed about the axis
+ *                             when the owner is inside, reversed otherwise, as two triangles along the diagonal q0 - q2.
+ * Every entry returns CLMGS_EINVAL, before anything is launched, for a null or misaligned pointer, outputs that overlap
+ * an input or each other, B outside 1..16, a non-finite or non-positive trunc, inv_trunc, fx, fy or min_weight, a
+ * non-finite camera or grid_to_world entry, and sizes beyond the limits above. */
+int clmgs_tsdf_integrate(void* stream, int nx, int ny, int nz, float* grid, int B, int H, int W, const float* depth,
+                         const float* alpha, const float* rgb, const double* cams, float near, float depth_max,
+                         float alpha_min, float trunc, float inv_trunc, int cull);
+int clmgs_tsdf_cells(void* stream, int nx, int ny, int nz, const float* grid, float min_weight, int32_t* cell_count);
+int clmgs_tsdf_vertices(void* stream, int nx, int ny, int nz, const float* grid, const int32_t* cell_scan, int V,
+                        const double* grid_to_world, float* verts, uint8_t* colours);
+int clmgs_tsdf_quad_count(void* stream, int nx, int ny, int nz, const float* grid, float min_weight,
+                          const int32_t* cell_scan, int32_t* quad_count);
+int clmgs_tsdf_quads(void* stream, int nx, int ny, int nz, const float* grid, float min_weight, const int32_t* cell_scan,
+                     const int32_t* quad_scan, int V, int Q, int32_t* faces);
+
 /* ---- pinned host memory  (numba.cuda.pinned_array at clm_offload/gaussian_model.py:34-44) */
 void* clmgs_pinned_alloc(size_t bytes);
 int clmgs_pinned_free(void* p);
