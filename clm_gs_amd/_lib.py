@@ -55,6 +55,9 @@ SIGNATURES = {
     # per-Gaussian blend weights (contribution pruning): integer atomics into three caller-owned arrays
     "clmgs_rasterize_contrib_pack_bytes": (_sz, [_i, _i]),
     "clmgs_rasterize_contrib": (_i, [_vp, _i, _i, _i64, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    # median depth: per pixel the depth and row of the entry at which T falls through one half
+    "clmgs_rasterize_median_pack_bytes": (_sz, [_i, _i]),
+    "clmgs_rasterize_median": (_i, [_vp, _i, _i, _i64, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "clmgs_rasterize4_fwd": (_i, [_vp, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "clmgs_rasterize4_bwd": (_i, [_vp, _i, _i, _i64, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     # four channels on the slot route and in the device-count forms: the argument lists of the 3-channel entries
@@ -206,7 +209,7 @@ class _Namespace:
 
 _NO_STREAM = {"clmgs_version", "clmgs_loss_slots", "clmgs_preprocess_grid_cap","clmgs_exposure_partials_rows", "clmgs_bilagrid_partials_rows", "clmgs_invdepth_partials_rows", "clmgs_pose_grad_partials_rows", "clmgs_projection_viewmat_partials_rows", "clmgs_small_deferred_kmax", "clmgs_isect3_front_temp_bytes",
               "clmgs_isect3_bin_temp_bytes", "clmgs_last_error", "clmgs_isect_count_temp_bytes",
-              "clmgs_isect_sort_temp_bytes", "clmgs_host_groups_temp_bytes", "clmgs_isect2_order_temp_bytes", "clmgs_isect2_sort_temp_bytes", "clmgs_visibility_select_temp_bytes", "clmgs_rasterize_pack_bytes", "clmgs_rasterize_contrib_pack_bytes", "clmgs_rasterize_partials_bytes", "clmgs_host_adam_rows", "clmgs_host_pool_start", "clmgs_host_usable_cpus", "clmgs_host_rows_prepare", "clmgs_tsp_tour",
+              "clmgs_isect_sort_temp_bytes", "clmgs_host_groups_temp_bytes", "clmgs_isect2_order_temp_bytes", "clmgs_isect2_sort_temp_bytes", "clmgs_visibility_select_temp_bytes", "clmgs_rasterize_pack_bytes", "clmgs_rasterize_contrib_pack_bytes", "clmgs_rasterize_median_pack_bytes", "clmgs_rasterize_partials_bytes", "clmgs_host_adam_rows", "clmgs_host_pool_start", "clmgs_host_usable_cpus", "clmgs_host_rows_prepare", "clmgs_tsp_tour",
               "clmgs_pinned_alloc", "clmgs_pinned_free", "clmgs_device_errors", "clmgs_vq_assign_temp_bytes"}
 
 

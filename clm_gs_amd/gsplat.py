@@ -678,3 +678,31 @@ def rasterize_contributions(means2d, conics, opacities, image_width, image_heigh
         int(image_height), int(tile_size), tw, th, dptr(offsets, I32), dptr(fids, I32), dptr(rows, I64, True), n_out,
         dptr(packed), dptr(raw[0], I64), dptr(raw[1], I32), dptr(raw[2], I64)))
     return contribution_values(raw)
+
+
+# ------------------------------------------------------------------ median depth
+@torch.no_grad()
+def rasterize_median_depth(means2d, conics, opacities, depths, image_width, image_height, tile_size, isect_offsets,
+                           flatten_ids):
+    """The median depth of C views over the lists rasterize_to_pixels would blend: per pixel, the entry at which the
+    transmittance falls through one half -- the last accumulated entry whose T before blending is > 0.5, so the pixel's
+    last contributor where the final T stays above one half (csrc/median.hip; DESIGN.md section 3, "Median depth").
+    means2d [C,N,2], conics [C,N,3], opacities [C,N], depths [C,N] (camera-space)
+    -> (median_depth float32 [C,H,W]: depths[] of that entry, copied; median_ids int32 [C,H,W]: its row within its camera);
+    0.0 and -1 where a pixel accumulates nothing.  Not differentiable: inputs that require grad are detached."""
+    L = _lib.lib()
+    C, N = opacities.shape
+    dev = means2d.device
+    means2d, conics, opacities, depths = (t.detach().contiguous() for t in (means2d, conics, opacities, depths))
+    offsets, fids = isect_offsets.contiguous(), flatten_ids.contiguous()
+    th, tw = offsets.shape[1:]
+    H, W = int(image_height), int(image_width)
+    median_depth = torch.empty((C, H, W), dtype=F32, device=dev)
+    median_ids = torch.empty((C, H, W), dtype=I32, device=dev)
+    pb = L.clmgs_rasterize_median_pack_bytes(C, N)
+    packed = torch.empty((pb,), dtype=torch.uint8, device=dev)
+    check(L.clmgs_rasterize_median(
+        stream(), C, N, fids.numel(), dptr(means2d, F32), dptr(conics, F32), dptr(opacities, F32), dptr(depths, F32), W, H,
+        int(tile_size), tw, th, dptr(offsets, I32), dptr(fids, I32), dptr(packed), dptr(median_depth, F32),
+        dptr(median_ids, I32)))
+    return median_depth, median_ids

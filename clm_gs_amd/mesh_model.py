@@ -3,7 +3,7 @@
     python -m clm_gs_amd.mesh_model -m <model dir | .ply | .vq.npz> -s <colmap dir> -o <mesh.ply> --voxel V
         [--trunc_voxels 4] [--bounds emin nmin umin emax nmax umax] [--up X Y Z] [--east X Y Z] [--every K] [-r R]
         [--alpha_min 0.5] [--depth_max D] [--min_weight 2] [--grid_gb 16] [--antialiased] [--undistort --undistort_zoom Z]
-        [--eval] [--clm_offload | --naive_offload | --no_offload]
+        [--depth_mode expected|median] [--eval] [--clm_offload | --naive_offload | --no_offload]
 
 renders every selected training camera of the scene through the strategy's own eval entry (render_mode "RGB+ED":
 expected depth and alpha), fuses the depth maps into a dense TSDF volume in the map frame of render_ortho (tsdf.TsdfVolume,
@@ -11,6 +11,9 @@ csrc/tsdf.hip), extracts the surface by naive Surface Nets and writes the colour
 and, next to it, <mesh>.json: frame, bounds, voxel, truncation, grid, counts and the cameras used.  --bounds default: the
 1st to 99th percentile box of the rows in the map frame.  A non-positive --voxel, inverted --bounds and a grid above
 --grid_gb or 2^31 voxels are refused by name (with the voxel size that fits) before anything is loaded or written.
+--depth_mode median fuses the median depth (render_mode "RGB+MD": the depth of the Gaussian at which the transmittance
+falls through one half; DESIGN.md section 3, "Median depth") instead of the expected depth, which a translucent layer in
+front of a surface pulls forward; the .json then carries "depth_mode": "median".  An unknown mode is refused by name.
 """
 import argparse
 import json
@@ -22,7 +25,7 @@ import torch
 
 from . import io_ply, tsdf, utils
 from .render_ortho import map_frame, percentile_sorted
-from .render_trajectory import _find_ply, eval_one_cam
+from .render_trajectory import _find_ply, depth_render_mode, eval_one_cam
 
 
 def percentile_box(means, frame, lo=1.0, hi=99.0):
@@ -43,10 +46,12 @@ def json_path(mesh_path):
 
 @torch.no_grad()
 def build_mesh(gaussians, cameras, args, out_path, voxel, frame=None, bounds=None, trunc_voxels=4.0, every=1, alpha_min=0.5,
-               depth_max=None, min_weight=2.0, grid_gb=16.0, near=0.01, background=None, log=None):
+               depth_max=None, min_weight=2.0, grid_gb=16.0, near=0.01, background=None, log=None, depth_mode="expected"):
     """Renders cameras[::every] from `gaussians` through the eval entry of the strategy `args` names, fuses them, extracts
     and writes out_path and its .json.  -> the dict written to the .json.  The global image size (utils.set_img_size)
-    must be the cameras' size."""
+    must be the cameras' size.  depth_mode "expected" fuses the "RGB+ED" depth, "median" the "RGB+MD" one (the .json gains
+    "depth_mode" only then)."""
+    render_mode = depth_render_mode(depth_mode)
     log = log or sys.stdout
     frame = frame if frame is not None else map_frame()
     if bounds is None:
@@ -60,7 +65,7 @@ def build_mesh(gaussians, cameras, args, out_path, voxel, frame=None, bounds=Non
     for cam in cams:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        image, depth, alpha = eval_one_cam(cam, gaussians, background, args, None, render_mode="RGB+ED")
+        image, depth, alpha = eval_one_cam(cam, gaussians, background, args, None, render_mode=render_mode)
         torch.cuda.synchronize()
         t1 = time.perf_counter()
         volume.add(cam, image, depth, alpha, near=near, depth_max=depth_max, alpha_min=alpha_min)
@@ -84,6 +89,8 @@ def build_mesh(gaussians, cameras, args, out_path, voxel, frame=None, bounds=Non
                 grid=[volume.nx, volume.ny, volume.nz], min_weight=float(min_weight), alpha_min=float(alpha_min),
                 depth_max=None if depth_max == float("inf") else depth_max, vertices=int(verts.shape[0]),
                 faces=int(faces.shape[0]), cameras=len(cams), camera_names=[str(c.image_name) for c in cams])
+    if depth_mode == "median":
+        meta["depth_mode"] = "median"
     with open(json_path(out_path), "w") as f:
         json.dump(meta, f, indent=1)
     log.write("mesh export: grid {} x {} x {} voxel {:g} cameras {} render {:.1f} cameras/s integration {:.1f} cameras/s "
@@ -93,9 +100,10 @@ def build_mesh(gaussians, cameras, args, out_path, voxel, frame=None, bounds=Non
     return meta
 
 
-def check_options(voxel, bounds=None, grid_gb=16.0, trunc_voxels=4.0, min_weight=2.0, every=1):
+def check_options(voxel, bounds=None, grid_gb=16.0, trunc_voxels=4.0, min_weight=2.0, every=1, depth_mode="expected"):
     """The refusals that need nothing loaded (ValueError by name)."""
     tsdf.grid_shape((0, 0, 0, 1, 1, 1), voxel)  # (--voxel alone)
+    depth_render_mode(depth_mode)
     if not trunc_voxels > 0:
         raise ValueError(f"--trunc_voxels must be positive, got {trunc_voxels}")
     if not min_weight > 0:
@@ -127,6 +135,9 @@ def main(argv=None):
     ap.add_argument("--depth_max", type=float, default=None, help="pixels deeper than this are not fused")
     ap.add_argument("--min_weight", type=float, default=2.0, help="a voxel counts when at least this many cameras observed it")
     ap.add_argument("--grid_gb", type=float, default=16.0, help="the largest grid allocated (24 B per voxel)")
+    ap.add_argument("--depth_mode", default="expected", metavar="expected|median",
+                    help="the depth map fused: the expected depth D / alpha, or the median depth (the Gaussian at which "
+                         "the transmittance falls through one half)")
     ap.add_argument("--antialiased", action="store_true", help="for a model trained with trainer --antialiased")
     ap.add_argument("--undistort", action="store_true", help="for a model trained with trainer --undistort")
     ap.add_argument("--undistort_zoom", type=float, default=1.0, help="--undistort: the trainer's --undistort_zoom")
@@ -137,7 +148,7 @@ def main(argv=None):
     g.add_argument("--no_offload", action="store_true")
     a = ap.parse_args(argv)
     try:  # refusals before anything is loaded or written
-        check_options(a.voxel, a.bounds, a.grid_gb, a.trunc_voxels, a.min_weight, a.every)
+        check_options(a.voxel, a.bounds, a.grid_gb, a.trunc_voxels, a.min_weight, a.every, a.depth_mode)
         frame = map_frame(a.up, a.east)
     except ValueError as e:
         raise SystemExit(str(e))
@@ -166,7 +177,7 @@ def main(argv=None):
     gaussians.active_sh_degree = gaussians.max_sh_degree
     try:
         build_mesh(gaussians, cams, args, a.output, a.voxel, frame, a.bounds, a.trunc_voxels, a.every, a.alpha_min,
-                   a.depth_max, a.min_weight, a.grid_gb)
+                   a.depth_max, a.min_weight, a.grid_gb, depth_mode=a.depth_mode)
     except ValueError as e:  # (the size of a grid whose bounds come from the model)
         raise SystemExit(str(e))
     return 0

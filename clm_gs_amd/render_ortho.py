@@ -4,6 +4,7 @@ perspective lean -- with the matching elevation raster.
 
     python -m clm_gs_amd.render_ortho -m <model dir | .ply> --clm_offload --gsd 0.05 [--bounds emin nmin emax nmax]
         [--up X Y Z] [--east X Y Z] [--camera_height H] [--tile 4096] [--output_dir DIR] [--antialiased] [--white_background]
+        [--depth_mode expected|median]
 
 Map frame: u = --up (default 0 0 1), e = --east projected onto the plane perpendicular to u (default 1 0 0; 0 1 0 if that
 is parallel to u), n = u x e.  The camera's rows are x = e, y = -n, z = -u: it looks straight down and image row 0 is
@@ -15,7 +16,9 @@ raster tiles as in a one-shot render, so seams differ by the rounding of sx * x 
 
 Outputs in --output_dir: ortho.png (8-bit RGB), ortho_height.npy (float32 [H,W]: camera_height - expected depth, NaN
 where alpha < 0.5), ortho_alpha.npy (float32 [H,W]) and ortho.json (origin, east, north, up, gsd, width, height,
-camera_height)."""
+camera_height).  --depth_mode median: the height map is camera_height - median depth (render_mode "RGB+MD": the depth of
+the Gaussian at which the transmittance falls through one half, which a translucent layer above the ground does not pull
+up) under the same alpha < 0.5 -> NaN rule, and ortho.json gains "depth_mode": "median"."""
 import argparse
 import json
 import math
@@ -27,7 +30,7 @@ import torch
 
 from . import utils
 from .cameras import OrthoCamera
-from .render_trajectory import _find_ply, eval_one_cam, write_png
+from .render_trajectory import _find_ply, depth_render_mode, eval_one_cam, write_png
 
 RASTER_TILE = 16
 JSON_FIELDS = ("origin", "east", "north", "up", "gsd", "width", "height", "camera_height")
@@ -184,25 +187,26 @@ def window_sees_anything(camera, gaussians):
     return bool((radii > 0).any())
 
 
-def render_window(camera, gaussians, background, args):
+def render_window(camera, gaussians, background, args, depth_mode="expected"):
     """One OrthoCamera (the global image size must be its size) -> (image[3,h,w], expected depth[h,w], alpha[h,w]) on the
-    GPU; a window that sees no Gaussian is background, depth 0 and alpha 0."""
+    GPU (depth_mode "median": the median depth); a window that sees no Gaussian is background, depth 0 and alpha 0."""
     h, w = camera.image_height, camera.image_width
     if not window_sees_anything(camera, gaussians):
         bg = background if background is not None else torch.zeros(3, device="cuda")
         return (bg.reshape(3, 1, 1).expand(3, h, w).float(), torch.zeros((h, w), device="cuda"),
                 torch.zeros((h, w), device="cuda"))
-    img, depth, alpha = eval_one_cam(camera, gaussians, background, args, None, render_mode="RGB+ED")
+    img, depth, alpha = eval_one_cam(camera, gaussians, background, args, None, render_mode=depth_render_mode(depth_mode))
     return img, depth[0], alpha[0]
 
 
-def render_mosaic(gaussians, geometry, args, tile=4096, background=None, quantise=False, log=None):
-    """The whole map, window by window, assembled on the host.
+def render_mosaic(gaussians, geometry, args, tile=4096, background=None, quantise=False, log=None, depth_mode="expected"):
+    """The whole map, window by window, assembled on the host (depth_mode "median": heights from the median depth).
     -> (rgb [H,W,3]: float32 as rendered, or uint8 (clamped, x255) with quantise -- a 20 000^2 map is 1.2 GB of uint8 --,
         height float32 [H,W]: camera_height - expected depth, NaN where alpha < 0.5, alpha float32 [H,W]).
     Windows are min(tile, size rounded up to 16) pixels on a side; the last row and column are rendered whole and
     cropped.  Sets the global image size (utils.set_img_size) to the window."""
     tile = check_tile(tile)
+    depth_render_mode(depth_mode)
     W, H = geometry.width, geometry.height
     tw, th = min(tile, _round_up(W, RASTER_TILE)), min(tile, _round_up(H, RASTER_TILE))
     rgb = np.empty((H, W, 3), dtype=np.uint8 if quantise else np.float32)
@@ -213,7 +217,7 @@ def render_mosaic(gaussians, geometry, args, tile=4096, background=None, quantis
         for y0 in range(0, H, th):
             for x0 in range(0, W, tw):
                 cam = geometry.camera(x0, y0, tw, th, uid=(y0 // th) * ((W + tw - 1) // tw) + x0 // tw)
-                img, depth, al = render_window(cam, gaussians, background, args)
+                img, depth, al = render_window(cam, gaussians, background, args, depth_mode)
                 h, w = min(th, H - y0), min(tw, W - x0)
                 img = img[:, :h, :w].permute(1, 2, 0)
                 if quantise:
@@ -228,13 +232,14 @@ def render_mosaic(gaussians, geometry, args, tile=4096, background=None, quantis
     return rgb, height, alpha
 
 
-def write_outputs(output_dir, geometry, rgb_u8, height, alpha):
+def write_outputs(output_dir, geometry, rgb_u8, height, alpha, depth_mode="expected"):
+    """(ortho.json carries "depth_mode" only when it is "median")"""
     os.makedirs(output_dir, exist_ok=True)
     write_png(os.path.join(output_dir, "ortho.png"), rgb_u8)
     np.save(os.path.join(output_dir, "ortho_height.npy"), height.astype(np.float32))
     np.save(os.path.join(output_dir, "ortho_alpha.npy"), alpha.astype(np.float32))
     with open(os.path.join(output_dir, "ortho.json"), "w") as f:
-        json.dump(geometry.to_json(), f, indent=1)
+        json.dump(dict(geometry.to_json(), **({"depth_mode": "median"} if depth_mode == "median" else {})), f, indent=1)
 
 
 def main(argv=None):
@@ -253,6 +258,9 @@ def main(argv=None):
     ap.add_argument("--white_background", action="store_true")
     ap.add_argument("--antialiased", action="store_true",
                     help="gsplat's rasterize_mode=\"antialiased\": for a model trained with trainer --antialiased")
+    ap.add_argument("--depth_mode", default="expected", metavar="expected|median",
+                    help="the depth behind the height map: the expected depth D / alpha, or the median depth (the Gaussian "
+                         "at which the transmittance falls through one half)")
     g = ap.add_mutually_exclusive_group()
     g.add_argument("--clm_offload", action="store_true")
     g.add_argument("--naive_offload", action="store_true")
@@ -260,6 +268,7 @@ def main(argv=None):
     a = ap.parse_args(argv)
     try:  # refusals before anything is loaded
         tile = check_tile(a.tile)
+        depth_render_mode(a.depth_mode)
     except ValueError as e:
         raise SystemExit(str(e))
     if (a.gsd is None) == (a.width is None):
@@ -294,8 +303,9 @@ def main(argv=None):
     bg = torch.tensor([1.0, 1.0, 1.0], device="cuda") if a.white_background else None
     with open(os.path.join(out, "render_ortho.log"), "w") as log:
         log.write(f"Model path: {a.model_path}\nMap: {geometry.width}x{geometry.height} px, gsd {geometry.gsd}\n")
-        rgb, height, alpha = render_mosaic(gaussians, geometry, args, tile=tile, background=bg, quantise=True, log=log)
-    write_outputs(out, geometry, rgb, height, alpha)
+        rgb, height, alpha = render_mosaic(gaussians, geometry, args, tile=tile, background=bg, quantise=True, log=log,
+                                           depth_mode=a.depth_mode)
+    write_outputs(out, geometry, rgb, height, alpha, a.depth_mode)
     print(f"Orthophoto saved to: {out} ({geometry.width}x{geometry.height} px, gsd {geometry.gsd:g})")
     return 0
 

@@ -7,9 +7,13 @@ training) and is written as an 8-bit PNG.
 
     python -m clm_gs_amd.render_trajectory -m <model dir | .ply> --clm_offload --n_frames 120 \
         --manual_height 30 --width 1920 --height 1080 [--output_dir DIR] [--hull x,y x,y ...] [--render_depth]
+        [--depth_mode expected|median]
 
 --render_depth: next to each frame_%05d.png, depth_%05d.npy (float32 [H,W], expected depth D / alpha) and
 depth_%05d.png (the same map in grey, normalised to its min / max over the pixels with alpha > 0.5).
+--depth_mode median (only with --render_depth; refused by name without it): the two files hold the median depth, the depth
+of the Gaussian at which the transmittance falls through one half (render mode "RGB+MD"; DESIGN.md section 3, "Median
+depth"), 0.0 where nothing is accumulated.
 
 `render_single_image` keeps the reference's signature and return value ([H,W,3] in [0,1] on the GPU).
 No imageio / PIL in this image: PNGs are written with zlib (8-bit RGB, no interlace).
@@ -95,6 +99,26 @@ def read_png(path):
     return raw[:, 1:].reshape(h, w, 3).copy()
 
 
+# --depth_mode of the command lines that render depth maps -> the render mode their eval entry is asked for
+DEPTH_MODES = {"expected": "RGB+ED", "median": "RGB+MD"}
+
+
+def depth_render_mode(depth_mode, flag="--depth_mode"):
+    """"expected" (None: the default) -> "RGB+ED", "median" -> "RGB+MD"; anything else: ValueError naming the flag."""
+    if depth_mode is None:
+        return DEPTH_MODES["expected"]
+    if depth_mode not in DEPTH_MODES:
+        raise ValueError(f"{flag} must be one of {sorted(DEPTH_MODES)}, got {depth_mode!r}")
+    return DEPTH_MODES[depth_mode]
+
+
+def check_depth_options(render_depth, depth_mode):
+    """render_trajectory's refusals that need nothing loaded (ValueError by name)."""
+    depth_render_mode(depth_mode)
+    if depth_mode is not None and not render_depth:
+        raise ValueError(f"--depth_mode {depth_mode} has effect only with --render_depth: give both, or neither")
+
+
 def eval_one_cam(camera, gaussians, background, args, scene=None, render_mode="RGB"):
     """The strategy's single-camera eval entry -> image[3,H,W], or (image, depth[1,H,W], alpha[1,H,W]) with a depth
     mode."""
@@ -129,9 +153,11 @@ def render_single_image(camera, gaussians, background, save_path, args, scene=No
     """One frame through the strategy's eval entry, clamped to [0,1], saved to `save_path` unless
     args.save_video (render_bigcity_images.py:638-722).  -> colors [H,W,3] on the GPU.
     depth_path: the same render also blends the depth channel ("RGB+ED"); the expected depth goes to
-    depth_path + ".npy" (float32 [H,W]) and, in grey over the range of the pixels with alpha > 0.5, depth_path + ".png"."""
+    depth_path + ".npy" (float32 [H,W]) and, in grey over the range of the pixels with alpha > 0.5, depth_path + ".png".
+    args.depth_mode "median": the median depth ("RGB+MD") instead."""
     if depth_path:
-        img, depth, alpha = eval_one_cam(camera, gaussians, background, args, scene, render_mode="RGB+ED")
+        img, depth, alpha = eval_one_cam(camera, gaussians, background, args, scene,
+                                         render_mode=depth_render_mode(getattr(args, "depth_mode", None)))
     else:
         img = eval_one_cam(camera, gaussians, background, args, scene)
     colors = torch.clamp(img, 0.0, 1.0)
@@ -187,6 +213,9 @@ def main(argv=None):
     ap.add_argument("--save_video", action="store_true", help="skip the per-frame PNGs (no video writer in this image)")
     ap.add_argument("--render_depth", action="store_true",
                     help="also write depth_%%05d.npy (float32 expected depth) and depth_%%05d.png (grey) per frame")
+    ap.add_argument("--depth_mode", default=None, metavar="expected|median",
+                    help="with --render_depth: the expected depth D / alpha (default) or the median depth, the depth of the "
+                         "Gaussian at which the transmittance falls through one half")
     ap.add_argument("--antialiased", action="store_true",
                     help="gsplat's rasterize_mode=\"antialiased\": for a model trained with trainer --antialiased")
     ap.add_argument("--sky", action="store_true",
@@ -200,6 +229,10 @@ def main(argv=None):
     if not (a.clm_offload or a.naive_offload or a.no_offload):
         a.clm_offload = True
     model_dir = a.model_path if os.path.isdir(a.model_path) else os.path.dirname(a.model_path)
+    try:  # refusals before anything is loaded
+        check_depth_options(a.render_depth, a.depth_mode)
+    except ValueError as e:
+        raise SystemExit(str(e))
     if a.sky:  # refusals before anything is loaded
         if a.white_background:
             raise SystemExit("--sky and --white_background together are refused: the sky map is the background")
@@ -208,7 +241,7 @@ def main(argv=None):
             raise SystemExit(f"--sky: {os.path.join(model_dir, SKY_FILE)} not found; the model was not trained with "
                              "trainer --sky (or the map was not copied along with the point cloud)")
     args = utils.default_args(bsz=4, rasterize_mode="antialiased" if a.antialiased else "classic")
-    for k in ("clm_offload", "naive_offload", "no_offload", "save_video", "render_depth"):
+    for k in ("clm_offload", "naive_offload", "no_offload", "save_video", "render_depth", "depth_mode"):
         setattr(args, k, getattr(a, k))
     utils.set_args(args)
     utils.set_img_size(a.height, a.width)

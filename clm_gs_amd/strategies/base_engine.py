@@ -8,7 +8,7 @@ from .. import utils
 from ..cameras import camera_loss_mask, camera_model as camera_model_of, camera_sky, check_sky_background, refuse_ortho
 from ..clm_kernels import apply_camera_colour, apply_camera_sky, camera_depth_term, fused_l1_ssim_loss, fused_ssim
 from ..gsplat import (fully_fused_projection, isect_offset_encode, isect_tiles,
-                      rasterize_to_pixels, spherical_harmonics, visibility_radii)
+                      rasterize_median_depth, rasterize_to_pixels, spherical_harmonics, visibility_radii)
 
 LAMBDA_DSSIM = 0.2
 TILE_SIZE = 16
@@ -109,7 +109,15 @@ def torch_compiled_loss(image, image_gt_original, loss_mask=None, loss_mask_coun
     return loss_combined(image, image_gt, ssim_loss)
 
 
-RENDER_MODES = ("RGB", "RGB+D", "RGB+ED", "RGB+ID")
+RENDER_MODES = ("RGB", "RGB+D", "RGB+ED", "RGB+ID", "RGB+MD")
+MEDIAN_DEPTH = "RGB+MD"  # no fourth colour: the 3-channel forward, then a pass of its own (gsplat.rasterize_median_depth)
+
+
+def refuse_median_training(render_mode, where):
+    """The median depth has no gradient: the training entries refuse the mode by name."""
+    if render_mode == MEDIAN_DEPTH:
+        raise ValueError(f'{where}: render_mode "RGB+MD" (median depth) is not differentiable and cannot be trained on; '
+                         'render it through an eval entry, or train with "RGB+ED" / "RGB+ID"')
 
 
 def colors_with_depth(colors, depths, backgrounds, render_mode):
@@ -119,7 +127,7 @@ def colors_with_depth(colors, depths, backgrounds, render_mode):
     the camera plane (they reach no tile list)."""
     if render_mode not in RENDER_MODES:
         raise ValueError(f"render_mode must be one of {RENDER_MODES}, got {render_mode!r}")
-    if render_mode == "RGB":
+    if render_mode in ("RGB", MEDIAN_DEPTH):  # the median depth is not blended: three channels, backgrounds as they are
         return colors, backgrounds
     if render_mode == "RGB+ID":
         front = depths > 0
@@ -174,8 +182,16 @@ def camera_forward_ops(means, quats, scales, opacities, coeffs, sh_degree, viewm
     the world-space optical axis viewmat[2,:3] -- a parallel projection has one direction, so the image does not depend
     on how far up its axis the camera sits (gsplat keeps means - campos; DESIGN.md section 3, "Orthographic"); `centre`
     is not read.  A sky is refused with it: the map lookup is a pinhole ray.
+    render_mode "RGB+MD" (eval only; train=True is refused by name): the forward runs exactly as for "RGB", then
+    gsplat.rasterize_median_depth walks the same lists with the same means2D, conics, depths and the opacities the forward
+    got (x compensation under rasterize_mode="antialiased"); depth is the median depth, 0.0 where nothing is accumulated,
+    alpha the forward's.  A sky is composited behind the splats and changes neither.
     -> (image[3,H,W] view, means2D[1,V,2], radii[1,V], () | (depth[1,H,W], alpha[1,H,W]) by split_depth,
         () | (colours leaf[1,V,3], dirs[1,V,3]) without sh_autograd)."""
+    if render_mode not in RENDER_MODES:
+        raise ValueError(f"render_mode must be one of {RENDER_MODES}, got {render_mode!r}")
+    if train:
+        refuse_median_training(render_mode, "camera_forward_ops(train=True)")
     if camera_model not in ("pinhole", "ortho"):
         raise ValueError(f"camera_model must be 'pinhole' or 'ortho', got {camera_model!r}")
     ortho = camera_model == "ortho"
@@ -219,6 +235,13 @@ def camera_forward_ops(means, quats, scales, opacities, coeffs, sh_degree, viewm
         image_width=image_width, image_height=image_height, tile_size=tile_size,
         isect_offsets=isect_offsets, flatten_ids=flatten_ids, backgrounds=backgrounds,
         absgrad=train and bool(getattr(utils.get_args(), "absgrad", False)))  # -> means2D.absgrad after backward
+    if render_mode == MEDIAN_DEPTH:
+        depth, _ = rasterize_median_depth(means2D, conics, opacities, depths, image_width, image_height, tile_size,
+                                          isect_offsets, flatten_ids)
+        rendered_image = rendered_image.squeeze(0).permute(2, 0, 1)
+        if sky_camera is not None:
+            rendered_image = apply_camera_sky(rendered_image, alphas[0, ..., 0], sky_camera)
+        return rendered_image, means2D, radiis, (depth, alphas[..., 0]), sh_leaf
     if render_mode != "RGB":
         rendered_image, depth, alpha = split_depth(rendered_image, alphas, render_mode)
         if sky_camera is not None:

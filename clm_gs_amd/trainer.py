@@ -331,14 +331,17 @@ def check_training(args, depth_priors=False, models=None, num_downscales=None, r
 def mesh_rules(args):
     """The (condition, message) rules of --mesh_voxel for check_training: checked before anything is loaded."""
     voxel = getattr(args, "mesh_voxel", 0.0)
+    depth_mode = getattr(args, "mesh_depth_mode", None)
     if not voxel:
-        return []
+        return [] if depth_mode is None else [(True, f"--mesh_depth_mode {depth_mode} has effect only with --mesh_voxel: "
+                                                      "give both, or neither")]
     from .mesh_model import check_options
     try:
         check_options(voxel, None, getattr(args, "mesh_grid_gb", 16.0), getattr(args, "mesh_trunc_voxels", 4.0),
-                      getattr(args, "mesh_min_weight", 2.0), getattr(args, "mesh_every", 1))
+                      getattr(args, "mesh_min_weight", 2.0), getattr(args, "mesh_every", 1), depth_mode or "expected")
     except ValueError as e:
         return [(True, str(e).replace("--voxel", "--mesh_voxel").replace("--trunc_voxels", "--mesh_trunc_voxels")
+                 .replace("--depth_mode", "--mesh_depth_mode")
                  .replace("--min_weight", "--mesh_min_weight").replace("--every", "--mesh_every").replace("--grid_gb", "--mesh_grid_gb"))]
     ws = dp.world_size()
     return [(ws > 1, "--mesh_voxel is not supported with {}; train on one GPU, or mesh the saved model with "
@@ -821,7 +824,8 @@ def train_from_colmap(source_path, model_path, strategy="clm_offload", iteration
                 with open(os.path.join(model_path, "python_ws=1_rk=0.log"), "a") as log_file:
                     build_mesh(gaussians, scene.train_cameras, args, os.path.join(model_path, "mesh.ply"), args.mesh_voxel,
                                trunc_voxels=args.mesh_trunc_voxels, every=args.mesh_every, min_weight=args.mesh_min_weight,
-                               grid_gb=args.mesh_grid_gb, log=log_file)
+                               grid_gb=args.mesh_grid_gb, log=log_file,
+                               depth_mode=getattr(args, "mesh_depth_mode", None) or "expected")
             for row in SIDE_MODELS:
                 if getattr(scene, row.name) is not None:
                     getattr(scene, row.name).save_to(model_path, scene.train_cameras)
@@ -913,6 +917,8 @@ OPTIONS = (
          "(clm_gs_amd.mesh_model; single GPU); 0 = off"),
     _opt("--mesh_trunc_voxels", type=float), _opt("--mesh_min_weight", type=float), _opt("--mesh_every", type=int),
     _opt("--mesh_grid_gb", type=float),
+    _opt("--mesh_depth_mode", metavar="expected|median", help="--mesh_voxel: fuse the expected depth (default) or the "
+         "median depth, the depth of the Gaussian at which the transmittance falls through one half"),
 )
 
 

@@ -237,6 +237,25 @@ int clmgs_rasterize_contrib(void* stream, int C, int N, int64_t n_isects, const 
                             const int32_t* flatten_ids, const int64_t* rows, int64_t n_out, void* packed,
                             uint64_t* wsum_q, uint32_t* wmax_bits, uint64_t* pixels);
 
+/* ---- median depth (surface depth for mesh export; csrc/median.hip)
+ * A forward-only walk of the same lists with the forward's blend rules, no colours, which stops where the transmittance
+ * has fallen to one half.  means2d[C*N,2] conics[C*N,3] opacities[C*N] depths[C*N] (camera-space depth), offsets /
+ * flatten_ids as for clmgs_rasterize_fwd, C >= 1, tile_size 16.  The median entry of a pixel is the last entry that
+ * clmgs_rasterize_fwd accumulates there while the transmittance before it is > 0.5: the entry at which T crosses one
+ * half, or the pixel's last contributor where the final T stays above it.
+ *   median_depth[C,H,W]  depths[] of that entry, copied; 0.0 where nothing is accumulated
+ *   median_id[C,H,W]     its row within its camera, flatten_id - cam * N; -1 where nothing is accumulated
+ * Every pixel is written exactly once, nothing else is; no atomics: the maps are bit-reproducible.  A list entry whose
+ * id is not a row of its camera reads and writes nothing.  Not differentiable.
+ * `packed`: caller scratch of clmgs_rasterize_median_pack_bytes(C,N) bytes (32 B aligned), filled here with one 32 B
+ * record per Gaussian.  Argument errors return CLMGS_EINVAL before anything is written; n_isects == 0 or N == 0 is
+ * accepted and writes 0.0 / -1 to every pixel. */
+size_t clmgs_rasterize_median_pack_bytes(int C, int N);
+int clmgs_rasterize_median(void* stream, int C, int N, int64_t n_isects, const float* means2d,
+                           const float* conics, const float* opacities, const float* depths, int width, int height,
+                           int tile_size, int tile_width, int tile_height, const int32_t* offsets,
+                           const int32_t* flatten_ids, void* packed, float* median_depth, int32_t* median_id);
+
 /* ---- gsplat.rasterize_to_pixels with colors[..., 4]  (what gsplat's rasterization(render_mode="RGB+D" / "RGB+ED")
  * calls: the camera-space depth rides as a fourth colour channel and is blended with the same weights)
  * Same contract as clmgs_rasterize_fwd / _bwd with rows of four: colors[C*N,4], backgrounds[C,4] or NULL ->
