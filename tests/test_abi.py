@@ -69,10 +69,16 @@ def test_tsp_and_host_adam_run_on_cpu():
     O.adam_rows(*ref, rows, col_lr.double(), 0.9 ** 4, 0.999 ** 4, 5e-16, step=3, scale=0.25, zero_grad=True)
     sig = torch.ones(1, dtype=torch.int32)
     P = lambda t: ctypes.c_void_p(t.data_ptr())
+    from tests import adam_cases as C
+    p_old = p.clone()
+    want = C.one_step(p.numpy(), m.numpy(), v.numpy(), gr.numpy(), col_lr.numpy(), 0.9 ** 4, 0.999 ** 4, 5e-16, 3, True, 0.25)
     _lib.check(_lib.lib().clmgs_host_adam_rows(P(p), P(gr), P(m), P(v), P(rows), rows.numel(), cols, P(col_lr),
                                                0.9 ** 4, 0.999 ** 4, 5e-16, 3, 1, 0.25, 1, P(sig), 2))
     for a, b in zip((p, gr, m, v), ref):
         assert ((a.double() - b).norm() / (b.norm() + 1e-30)) < 1e-6
+    # the step itself, element by element: p_new - p_old, m and v within the error budget of tests/adam_reference.py
+    C.report("host_adam_rows, 2500 listed rows", torch.zeros(N, dtype=torch.int64).numpy(), p_old.numpy(),
+             [p.numpy(), m.numpy(), v.numpy()], want, rows=rows.long().numpy())
 
 
 @pytest.mark.parametrize("sparse", [0, 1])
@@ -108,11 +114,18 @@ def test_deferred_host_row_optimizer_equals_step_by_step_adam(sparse):
         O.adam_rows(rp, gg, rm, rv, rows, col_lr.double(), b1, b2, eps, step=s, scale=0.25)
     rows = torch.randperm(N, generator=g0).to(torch.int32).contiguous()
     stage = torch.empty(N, cols)
+    from tests import adam_reference as R
+    from tests import adam_cases as C
+    want = R.replay64(p.numpy(), m.numpy(), v.numpy(), g.numpy(), last.numpy(), gstep.numpy(), to_step, col_lr.numpy(), b1,
+                      b2, eps, True, 0.25, 256, lazy=False, sparse=bool(sparse))
     assert L.clmgs_host_pool_start(3) == 3
     _lib.check(L.clmgs_host_rows_prepare(P(p), P(g), P(m), P(v), P(last), P(gstep), P(rows), N, cols, P(col_lr),
                                          b1, b2, eps, to_step, to_step + 1, 1, 0.25, 256, P(stage), sparse))
     rl = lambda a, b: ((a.double() - b).norm() / (b.norm() + 1e-30)).item()
     assert rl(p, rp) < 1e-6 and rl(m, rm) < 1e-6 and rl(v, rv) < 1e-6
+    # every element's displacement p_new - p_old, m and v within the error budget of tests/adam_reference.py
+    C.report(f"host_rows_prepare sparse={sparse}", torch.zeros(N, dtype=torch.int64).numpy(), p0.numpy(),
+             [p.numpy(), m.numpy(), v.numpy()], want[:6])
     assert torch.equal(stage, p[rows.long()])
     assert int(last.min()) == to_step == int(last.max()) and int(gstep.min()) == to_step + 1
     untouched = (~pend)[:100]  # all-zero moments, no gradient: bit-identical

@@ -331,6 +331,13 @@ def test_adam_rows_and_selective(dev):
     K.adam_rows(*d, rows.to(dev), col_lr.to(dev), 0.9 ** 4, 0.999 ** 4, 1e-15 / 2, 7, True, 0.25, True)
     for a, b in zip(d, ref):
         assert rel_l2(a.cpu(), b) < 1e-6
+    # the step itself, element by element: p_new - p_old, m and v within the error budget of tests/adam_reference.py
+    from tests import adam_cases as C
+    cls = torch.zeros(N, dtype=torch.int64).numpy()
+    want = C.one_step(p.numpy(), m.numpy(), v.numpy(), gr.numpy(), col_lr.numpy(), 0.9 ** 4, 0.999 ** 4, 1e-15 / 2, 7,
+                      True, 0.25)
+    C.report("adam_rows, 900 listed rows", cls, p.numpy(), [d[i].cpu().numpy() for i in (0, 2, 3)], want,
+             rows=rows.long().numpy())
     # selective (masked, no bias correction) on a [N,3] tensor
     p3, g3 = torch.randn(N, 3, generator=g), torch.randn(N, 3, generator=g)
     m3, v3 = torch.zeros(N, 3), torch.zeros(N, 3)
@@ -341,6 +348,10 @@ def test_adam_rows_and_selective(dev):
     K.selective_adam_update(*d, vis.to(dev), 1e-3, 0.9, 0.999, 1e-15, N, 3)
     for a, b in zip(d, ref):
         assert rel_l2(a.cpu(), b) < 1e-6
+    want = C.one_step(p3.numpy(), m3.numpy(), v3.numpy(), g3.numpy(), torch.tensor(1e-3).numpy(), 0.9, 0.999, 1e-15, 1,
+                      False, 1.0)
+    C.report("selective_adam_update", cls, p3.numpy(), [d[i].cpu().numpy() for i in (0, 2, 3)], want,
+             rows=torch.nonzero(vis).flatten().numpy())
 
 
 def test_densify_stats(dev):
