@@ -132,6 +132,10 @@ SIGNATURES = {
     "clmgs_tsdf_vertices": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "clmgs_tsdf_quad_count": (_i, [_vp, _i, _i, _i, _vp, _f, _vp, _vp]),
     "clmgs_tsdf_quads": (_i, [_vp, _i, _i, _i, _vp, _f, _vp, _vp, _i, _i, _vp]),
+    # mesh cleanup: V, F, faces, parent, flag | V, parent, flag | V, F, faces, labels, count
+    "clmgs_mesh_hook": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
+    "clmgs_mesh_shortcut": (_i, [_vp, _i, _vp, _vp]),
+    "clmgs_mesh_component_faces": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
     "clmgs_mcmc_relocation": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "clmgs_mcmc_reg_grad": (_i, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _f, _f]),
     "clmgs_mcmc_noise": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _f, _vp]),

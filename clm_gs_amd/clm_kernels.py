@@ -744,6 +744,76 @@ def tsdf_extract(grid, min_weight, grid_to_world):
     return verts, colours, faces
 
 
+# ------------------------------------------------------------------ mesh cleanup
+MESH_MAX_ROUNDS = 64
+
+
+def _mesh_faces(faces, V, what):
+    """faces: a contiguous int32 [F,3] device tensor whose indices lie in [0, V) (checked on the device, before any
+    launch) -> F; anything else is refused by name."""
+    if not (isinstance(faces, torch.Tensor) and faces.is_cuda):
+        raise _lib.ClmgsError(f"{what}: faces must be a tensor on the device (no CPU fallback in clm_gs_amd), got "
+                              f"{getattr(faces, 'device', type(faces))}")
+    if faces.dtype != I32 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise _lib.ClmgsError(f"{what}: faces must be int32 [F,3], got {faces.dtype} {tuple(faces.shape)}")
+    if not faces.is_contiguous():
+        raise _lib.ClmgsError(f"{what}: faces must be contiguous")
+    if isinstance(V, bool) or int(V) != V:
+        raise ValueError(f"{what}: V must be an integer, got {V!r}")
+    if V < 0 or V >= 1 << 31:
+        raise ValueError(f"{what}: V must be in [0, 2^31), got {V}")
+    F = int(faces.shape[0])
+    if F >= 1 << 31:
+        raise _lib.ClmgsError(f"{what}: F must be below 2^31, got {F}")
+    if F:
+        lo, hi = (int(v) for v in torch.aminmax(faces))
+        if lo < 0 or hi >= V:
+            raise _lib.ClmgsError(f"{what}: a face index lies outside [0, {int(V)}): the indices span [{lo}, {hi}]")
+    return F
+
+
+@torch.no_grad()
+def mesh_components(faces, V):
+    """Connected components of a triangle list (csrc/mesh.hip; DESIGN.md section 3, "Mesh cleanup"): faces int32 [F,3] on
+    the device over V vertices; two vertices are connected when a face names both -> (labels int32 [V], rounds):
+    labels[v] = the smallest vertex index of v's component (v for a vertex no face names), rounds = how many hook and
+    shortcut rounds ran, the last of which changed nothing.  More than MESH_MAX_ROUNDS rounds raise ClmgsError.  F == 0
+    or V == 0 launches nothing."""
+    F = _mesh_faces(faces, V, "mesh_components")
+    V = int(V)
+    parent = torch.arange(V, dtype=I32, device=faces.device)
+    if F == 0 or V == 0:
+        return parent, 0
+    L = _lib.lib()
+    flags = torch.zeros((MESH_MAX_ROUNDS,), dtype=I32, device=faces.device)
+    for r in range(MESH_MAX_ROUNDS):
+        check(L.clmgs_mesh_hook(stream(), V, F, dptr(faces, I32), dptr(parent, I32), dptr(flags[r:], I32)))
+        check(L.clmgs_mesh_shortcut(stream(), V, dptr(parent, I32), dptr(flags[r:], I32)))
+        if int(flags[r]) == 0:
+            return parent, r + 1
+    raise _lib.ClmgsError(f"mesh_components: no fixed point after {MESH_MAX_ROUNDS} rounds (V {V}, F {F})")
+
+
+@torch.no_grad()
+def mesh_component_faces(faces, labels):
+    """The face count of every component (csrc/mesh.hip): labels int32 [V] as mesh_components returns it -> int32 [V],
+    count[l] = the number of faces whose first vertex has label l: zero except at labels.  An integer sum: the same bits
+    whatever the order."""
+    if not (isinstance(labels, torch.Tensor) and labels.is_cuda and labels.is_contiguous() and labels.dtype == I32
+            and labels.dim() == 1):
+        raise _lib.ClmgsError("mesh_component_faces: labels must be a contiguous int32 [V] device tensor, got "
+                              f"{getattr(labels, 'dtype', type(labels))} {tuple(getattr(labels, 'shape', ()))}")
+    V = int(labels.shape[0])
+    F = _mesh_faces(faces, V, "mesh_component_faces")
+    if faces.device != labels.device:
+        raise _lib.ClmgsError(f"mesh_component_faces: faces are on {faces.device}, labels on {labels.device}")
+    count = torch.zeros((V,), dtype=I32, device=labels.device)
+    if F == 0 or V == 0:
+        return count
+    check(_lib.lib().clmgs_mesh_component_faces(stream(), V, F, dptr(faces, I32), dptr(labels, I32), dptr(count, I32)))
+    return count
+
+
 # ------------------------------------------------------------ MCMC densification
 def _f32_dev(t, shape, what):
     assert t.is_cuda and t.dtype == F32 and t.is_contiguous() and tuple(t.shape) == tuple(shape), \

@@ -3,7 +3,8 @@
     python -m clm_gs_amd.mesh_model -m <model dir | .ply | .vq.npz> -s <colmap dir> -o <mesh.ply> --voxel V
         [--trunc_voxels 4] [--bounds emin nmin umin emax nmax umax] [--up X Y Z] [--east X Y Z] [--every K] [-r R]
         [--alpha_min 0.5] [--depth_max D] [--min_weight 2] [--grid_gb 16] [--antialiased] [--undistort --undistort_zoom Z]
-        [--depth_mode expected|median] [--eval] [--clm_offload | --naive_offload | --no_offload]
+        [--depth_mode expected|median] [--min_component_faces N] [--keep_components K] [--eval]
+        [--clm_offload | --naive_offload | --no_offload]
 
 renders every selected training camera of the scene through the strategy's own eval entry (render_mode "RGB+ED":
 expected depth and alpha), fuses the depth maps into a dense TSDF volume in the map frame of render_ortho (tsdf.TsdfVolume,
@@ -14,6 +15,10 @@ and, next to it, <mesh>.json: frame, bounds, voxel, truncation, grid, counts and
 --depth_mode median fuses the median depth (render_mode "RGB+MD": the depth of the Gaussian at which the transmittance
 falls through one half; DESIGN.md section 3, "Median depth") instead of the expected depth, which a translucent layer in
 front of a surface pulls forward; the .json then carries "depth_mode": "median".  An unknown mode is refused by name.
+--min_component_faces N and --keep_components K drop the small connected components of the extracted mesh on the device
+before it is written (mesh_clean.clean; DESIGN.md section 3, "Mesh cleanup"): those with fewer than N faces, and all but
+the K with the most faces; the .json then carries "cleanup" (the options and the report) and the log line the component
+counts.  Negative values are refused by name.  Without either flag nothing changes.
 """
 import argparse
 import json
@@ -23,7 +28,7 @@ import time
 
 import torch
 
-from . import io_ply, tsdf, utils
+from . import io_ply, mesh_clean, tsdf, utils
 from .render_ortho import map_frame, percentile_sorted
 from .render_trajectory import _find_ply, depth_render_mode, eval_one_cam
 
@@ -46,11 +51,15 @@ def json_path(mesh_path):
 
 @torch.no_grad()
 def build_mesh(gaussians, cameras, args, out_path, voxel, frame=None, bounds=None, trunc_voxels=4.0, every=1, alpha_min=0.5,
-               depth_max=None, min_weight=2.0, grid_gb=16.0, near=0.01, background=None, log=None, depth_mode="expected"):
+               depth_max=None, min_weight=2.0, grid_gb=16.0, near=0.01, background=None, log=None, depth_mode="expected",
+               min_component_faces=0, keep_components=0):
     """Renders cameras[::every] from `gaussians` through the eval entry of the strategy `args` names, fuses them, extracts
     and writes out_path and its .json.  -> the dict written to the .json.  The global image size (utils.set_img_size)
     must be the cameras' size.  depth_mode "expected" fuses the "RGB+ED" depth, "median" the "RGB+MD" one (the .json gains
-    "depth_mode" only then)."""
+    "depth_mode" only then).  min_component_faces / keep_components: mesh_clean.clean between the extraction and the file
+    (the .json gains "cleanup" and the log line its component counts only when one of them is on)."""
+    min_component_faces, keep_components = mesh_clean.check_options(min_component_faces, keep_components,
+                                                                    ("--min_component_faces", "--keep_components"))
     render_mode = depth_render_mode(depth_mode)
     log = log or sys.stdout
     frame = frame if frame is not None else map_frame()
@@ -79,6 +88,7 @@ def build_mesh(gaussians, cameras, args, out_path, voxel, frame=None, bounds=Non
     verts, colours, faces = volume.extract(min_weight)
     torch.cuda.synchronize()
     t_extract = time.perf_counter() - t0
+    verts, colours, faces, report = mesh_clean.clean(verts, colours, faces, min_component_faces, keep_components)
     d = os.path.dirname(out_path)
     if d:
         os.makedirs(d, exist_ok=True)
@@ -91,17 +101,23 @@ def build_mesh(gaussians, cameras, args, out_path, voxel, frame=None, bounds=Non
                 faces=int(faces.shape[0]), cameras=len(cams), camera_names=[str(c.image_name) for c in cams])
     if depth_mode == "median":
         meta["depth_mode"] = "median"
+    if report is not None:
+        meta = mesh_clean.json_record(meta, min_component_faces, keep_components, report, verts.shape[0], faces.shape[0])
     with open(json_path(out_path), "w") as f:
         json.dump(meta, f, indent=1)
     log.write("mesh export: grid {} x {} x {} voxel {:g} cameras {} render {:.1f} cameras/s integration {:.1f} cameras/s "
-              "extraction {:.3f} s vertices {} faces {} -> {}\n".format(
+              "extraction {:.3f} s vertices {} faces {}{} -> {}\n".format(
                   volume.nx, volume.ny, volume.nz, volume.voxel, len(cams), len(cams) / max(t_render, 1e-9),
-                  len(cams) / max(t_fuse, 1e-9), t_extract, meta["vertices"], meta["faces"], out_path))
+                  len(cams) / max(t_fuse, 1e-9), t_extract, meta["vertices"], meta["faces"],
+                  "" if report is None else " components {} kept {}".format(report["components"], report["components_kept"]),
+                  out_path))
     return meta
 
 
-def check_options(voxel, bounds=None, grid_gb=16.0, trunc_voxels=4.0, min_weight=2.0, every=1, depth_mode="expected"):
+def check_options(voxel, bounds=None, grid_gb=16.0, trunc_voxels=4.0, min_weight=2.0, every=1, depth_mode="expected",
+                  min_component_faces=0, keep_components=0):
     """The refusals that need nothing loaded (ValueError by name)."""
+    mesh_clean.check_options(min_component_faces, keep_components, ("--min_component_faces", "--keep_components"))
     tsdf.grid_shape((0, 0, 0, 1, 1, 1), voxel)  # (--voxel alone)
     depth_render_mode(depth_mode)
     if not trunc_voxels > 0:
@@ -138,6 +154,10 @@ def main(argv=None):
     ap.add_argument("--depth_mode", default="expected", metavar="expected|median",
                     help="the depth map fused: the expected depth D / alpha, or the median depth (the Gaussian at which "
                          "the transmittance falls through one half)")
+    ap.add_argument("--min_component_faces", type=int, default=0, metavar="N",
+                    help="drop the connected components of the mesh with fewer than N faces")
+    ap.add_argument("--keep_components", type=int, default=0, metavar="K",
+                    help="keep only the K connected components with the most faces")
     ap.add_argument("--antialiased", action="store_true", help="for a model trained with trainer --antialiased")
     ap.add_argument("--undistort", action="store_true", help="for a model trained with trainer --undistort")
     ap.add_argument("--undistort_zoom", type=float, default=1.0, help="--undistort: the trainer's --undistort_zoom")
@@ -148,7 +168,8 @@ def main(argv=None):
     g.add_argument("--no_offload", action="store_true")
     a = ap.parse_args(argv)
     try:  # refusals before anything is loaded or written
-        check_options(a.voxel, a.bounds, a.grid_gb, a.trunc_voxels, a.min_weight, a.every, a.depth_mode)
+        check_options(a.voxel, a.bounds, a.grid_gb, a.trunc_voxels, a.min_weight, a.every, a.depth_mode,
+                      a.min_component_faces, a.keep_components)
         frame = map_frame(a.up, a.east)
     except ValueError as e:
         raise SystemExit(str(e))
@@ -177,7 +198,8 @@ def main(argv=None):
     gaussians.active_sh_degree = gaussians.max_sh_degree
     try:
         build_mesh(gaussians, cams, args, a.output, a.voxel, frame, a.bounds, a.trunc_voxels, a.every, a.alpha_min,
-                   a.depth_max, a.min_weight, a.grid_gb, depth_mode=a.depth_mode)
+                   a.depth_max, a.min_weight, a.grid_gb, depth_mode=a.depth_mode,
+                   min_component_faces=a.min_component_faces, keep_components=a.keep_components)
     except ValueError as e:  # (the size of a grid whose bounds come from the model)
         raise SystemExit(str(e))
     return 0

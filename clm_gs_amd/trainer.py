@@ -332,6 +332,12 @@ def mesh_rules(args):
     """The (condition, message) rules of --mesh_voxel for check_training: checked before anything is loaded."""
     voxel = getattr(args, "mesh_voxel", 0.0)
     depth_mode = getattr(args, "mesh_depth_mode", None)
+    components = (getattr(args, "mesh_min_component_faces", 0), getattr(args, "mesh_keep_components", 0))
+    try:  # (refused with and without --mesh_voxel)
+        from .mesh_clean import check_options as check_components
+        check_components(*components, names=("--mesh_min_component_faces", "--mesh_keep_components"))
+    except ValueError as e:
+        return [(True, str(e))]
     if not voxel:
         return [] if depth_mode is None else [(True, f"--mesh_depth_mode {depth_mode} has effect only with --mesh_voxel: "
                                                       "give both, or neither")]
@@ -825,7 +831,9 @@ def train_from_colmap(source_path, model_path, strategy="clm_offload", iteration
                     build_mesh(gaussians, scene.train_cameras, args, os.path.join(model_path, "mesh.ply"), args.mesh_voxel,
                                trunc_voxels=args.mesh_trunc_voxels, every=args.mesh_every, min_weight=args.mesh_min_weight,
                                grid_gb=args.mesh_grid_gb, log=log_file,
-                               depth_mode=getattr(args, "mesh_depth_mode", None) or "expected")
+                               depth_mode=getattr(args, "mesh_depth_mode", None) or "expected",
+                               min_component_faces=getattr(args, "mesh_min_component_faces", 0),
+                               keep_components=getattr(args, "mesh_keep_components", 0))
             for row in SIDE_MODELS:
                 if getattr(scene, row.name) is not None:
                     getattr(scene, row.name).save_to(model_path, scene.train_cameras)
@@ -919,6 +927,10 @@ OPTIONS = (
     _opt("--mesh_grid_gb", type=float),
     _opt("--mesh_depth_mode", metavar="expected|median", help="--mesh_voxel: fuse the expected depth (default) or the "
          "median depth, the depth of the Gaussian at which the transmittance falls through one half"),
+    _opt("--mesh_min_component_faces", type=int, metavar="N", help="--mesh_voxel: drop the connected components of the mesh "
+         "with fewer than N faces (clm_gs_amd.mesh_clean); 0 = off"),
+    _opt("--mesh_keep_components", type=int, metavar="K", help="--mesh_voxel: keep only the K connected components with the "
+         "most faces; 0 = off"),
 )
 
 

@@ -1031,6 +1031,24 @@ int clmgs_tsdf_quad_count(void* stream, int nx, int ny, int nz, const float* gri
 int clmgs_tsdf_quads(void* stream, int nx, int ny, int nz, const float* grid, float min_weight, const int32_t* cell_scan,
                      const int32_t* quad_scan, int V, int Q, int32_t* faces);
 
+/* ---- mesh cleanup (csrc/mesh.hip; clm_gs_amd/mesh_clean.py): the connected components of a triangle list and their face
+ * counts.  faces int32 [F,3] on the device, any triangle list over V vertices, 1 <= V < 2^31, 1 <= F < 2^31; two vertices
+ * are connected when a face names both.  A face with an index outside [0, V) is skipped by every kernel.
+ *  - clmgs_mesh_hook and clmgs_mesh_shortcut are the two halves of one labelling round over parent int32 [V], which the
+ *    caller starts as 0, 1, .., V - 1: hook lowers, per face, the parents and grandparents of its three vertices to the
+ *    smallest grandparent (integer atomic min); shortcut sets parent[v] = parent[parent[v]].  Either stores 1 to *flag
+ *    (device int32) when it lowered an entry and leaves it alone otherwise.  The caller alternates them, each round with
+ *    a zeroed flag, until a round leaves the flag zero: then parent[v] is the smallest vertex index of v's component (v
+ *    itself for a vertex no face names), the same bits whatever the order of the faces.  Neither kernel waits for
+ *    another workgroup; the number of rounds grows with the logarithm of a component's diameter.
+ *  - clmgs_mesh_component_faces adds 1 to count[labels[faces[f,0]]] for every face (integer atomics, aggregated per run
+ *    of equal labels inside a wave); count int32 [V] is zeroed by the caller.
+ * Every entry returns CLMGS_EINVAL, before anything is launched, for V < 1 or F < 1, a null or misaligned pointer, and
+ * outputs that overlap an input or each other. */
+int clmgs_mesh_hook(void* stream, int V, int F, const int32_t* faces, int32_t* parent, int32_t* flag);
+int clmgs_mesh_shortcut(void* stream, int V, int32_t* parent, int32_t* flag);
+int clmgs_mesh_component_faces(void* stream, int V, int F, const int32_t* faces, const int32_t* labels, int32_t* count);
+
 /* ---- pinned host memory  (numba.cuda.pinned_array at clm_offload/gaussian_model.py:34-44) */
 void* clmgs_pinned_alloc(size_t bytes);
 int clmgs_pinned_free(void* p);
