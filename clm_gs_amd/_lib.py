@@ -133,6 +133,10 @@ SIGNATURES = {
     "clmgs_tsdf_quad_count": (_i, [_vp, _i, _i, _i, _vp, _f, _vp, _vp]),
     "clmgs_tsdf_quads": (_i, [_vp, _i, _i, _i, _vp, _f, _vp, _vp, _i, _i, _vp]),
     # mesh cleanup: V, F, faces, parent, flag | V, parent, flag | V, F, faces, labels, count
+    "clmgs_tsdf_mark": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _f, _f, _f, _f, _d]),
+    "clmgs_tsdf_sparse_integrate": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _i]),
+    "clmgs_tsdf_sparse_extract": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp,
+                                       _vp, _vp]),
     "clmgs_mesh_hook": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
     "clmgs_mesh_shortcut": (_i, [_vp, _i, _vp, _vp]),
     "clmgs_mesh_component_faces": (_i, [_vp, _i, _i, _vp, _vp, _vp]),

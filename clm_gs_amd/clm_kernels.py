@@ -744,6 +744,187 @@ def tsdf_extract(grid, min_weight, grid_to_world):
     return verts, colours, faces
 
 
+# ------------------------------------------------------------------ mesh export, sparse volume
+TSDF_BRICK = 8
+TSDF_MAX_BRICK_GRID = 1 << 30
+
+
+def tsdf_brick_grid(nx, ny, nz):
+    """(nbx, nby, nbz) of a grid of nx x ny x nz voxels in bricks of 8 x 8 x 8; sides below 2 and a brick grid above 2^30 are
+    refused by name."""
+    nx, ny, nz = int(nx), int(ny), int(nz)
+    if min(nx, ny, nz) < 2 or max(nx, ny, nz) >= 1 << 31:
+        raise _lib.ClmgsError(f"tsdf: every side of the volume must be >= 2 and below 2^31, got {nx} x {ny} x {nz}")
+    nb = tuple(-(-v // TSDF_BRICK) for v in (nx, ny, nz))
+    if nb[0] * nb[1] * nb[2] > TSDF_MAX_BRICK_GRID:
+        raise _lib.ClmgsError(f"tsdf: the brick grid {nb[0]} x {nb[1]} x {nb[2]} of {nx} x {ny} x {nz} voxels is above 2^30 bricks")
+    return nb
+
+
+def _tsdf_images(what, dev, cams, depth, alpha, rgb=None):
+    """The checks tsdf_integrate makes of its images and records -> (cams float64 [B,16], B, H, W)."""
+    import numpy as np
+    cams = np.ascontiguousarray(cams.numpy() if isinstance(cams, torch.Tensor) else cams, dtype=np.float64)
+    if not (isinstance(depth, torch.Tensor) and depth.dim() == 3 and cams.shape == (depth.shape[0], 16) and depth.shape[0] >= 1):
+        raise _lib.ClmgsError(f"{what}: depth [B,H,W] and cams [B,16] expected, got {tuple(getattr(depth, 'shape', ()))} "
+                              f"and {cams.shape}")
+    B, H, W = (int(v) for v in depth.shape)
+    for t, shape, name in ((depth, (B, H, W), "depth"), (alpha, (B, H, W), "alpha"), (rgb, (B, 3, H, W), "rgb")):
+        if name == "rgb" and rgb is None:
+            continue
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.dtype == F32 and tuple(t.shape) == shape
+                and t.device == dev):
+            raise _lib.ClmgsError(f"{what}: {name} must be a contiguous float32 {shape} tensor on {dev}, got "
+                                  f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+    return cams, B, H, W
+
+
+def _tsdf_trunc(what, trunc):
+    trunc32 = float(torch.tensor(float(trunc), dtype=F32))
+    if not (_finite(trunc32) and trunc32 > 0):
+        raise ValueError(f"{what}: trunc must be positive and finite, got {trunc}")
+    return trunc32
+
+
+@torch.no_grad()
+def tsdf_mark(marks, shape, depth, alpha, cams_inv, near=0.01, depth_max=float("inf"), alpha_min=0.5, trunc=1.0, voxel_cam=1.0):
+    """Marks, in place, the bricks of a sparse TSDF volume that the cameras can put a surface into (csrc/tsdf_sparse.hip;
+    DESIGN.md section 3, "Sparse volume"): marks uint8 [nbz,nby,nbx] on the device for the grid shape = (nx, ny, nz);
+    depth, alpha float32 [B,H,W] on the device; cams_inv float64 [B,16] on the HOST: per camera the 3x4 matrix from
+    camera space to grid coordinates (the inverse of tsdf_integrate's), then fx, fy, cx, cy; trunc and voxel_cam (the
+    length of a voxel) in camera units.  The marked set is a superset of every voxel within 1 voxel of a voxel some
+    camera observes with -trunc <= sdf < 0, and a pure function of the set of cameras: more than 16 go in launches of 16,
+    and neither their order nor their split changes a byte.  Returns marks."""
+    nx, ny, nz = (int(v) for v in shape)
+    nbx, nby, nbz = tsdf_brick_grid(nx, ny, nz)
+    if not (isinstance(marks, torch.Tensor) and marks.is_cuda and marks.is_contiguous() and marks.dtype == U8
+            and tuple(marks.shape) == (nbz, nby, nbx)):
+        raise _lib.ClmgsError(f"tsdf_mark: marks must be a contiguous uint8 {(nbz, nby, nbx)} device tensor, got "
+                              f"{getattr(marks, 'dtype', type(marks))} {tuple(getattr(marks, 'shape', ()))}")
+    cams, B, H, W = _tsdf_images("tsdf_mark", marks.device, cams_inv, depth, alpha)
+    trunc32 = _tsdf_trunc("tsdf_mark", trunc)
+    if not (_finite(float(voxel_cam)) and voxel_cam > 0 and trunc32 / float(voxel_cam) <= 4096):
+        raise ValueError(f"tsdf_mark: voxel_cam must be positive and finite and trunc at most 4096 voxels, got {voxel_cam}, "
+                         f"trunc {trunc}")
+    L = _lib.lib()
+    for b0 in range(0, B, TSDF_MAX_B):
+        b1 = min(B, b0 + TSDF_MAX_B)
+        rec = (ctypes.c_double * (16 * (b1 - b0)))(*cams[b0:b1].reshape(-1))
+        check(L.clmgs_tsdf_mark(stream(), nx, ny, nz, dptr(marks), b1 - b0, H, W, dptr(depth[b0:b1], F32),
+                                dptr(alpha[b0:b1], F32), rec, float(near), float(depth_max), float(alpha_min), trunc32,
+                                float(voxel_cam)))
+    return marks
+
+
+def _tsdf_sparse(what, shape, bricks, table, pool):
+    """The checks of a sparse volume's three tensors against the grid shape -> (nx, ny, nz, S)."""
+    nx, ny, nz = (int(v) for v in shape)
+    nbx, nby, nbz = tsdf_brick_grid(nx, ny, nz)
+    ok = lambda t, dt: isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.dtype == dt
+    if not (ok(pool, F32) and pool.dim() == 5 and tuple(pool.shape[1:]) == (6, 8, 8, 8) and pool.shape[0] >= 1):
+        raise _lib.ClmgsError(f"{what}: the pool is a contiguous float32 [S, 6, 8, 8, 8] device tensor with S >= 1, got "
+                              f"{getattr(pool, 'dtype', type(pool))} {tuple(getattr(pool, 'shape', ()))}")
+    S = int(pool.shape[0])
+    if S * 512 >= 1 << 31:
+        raise _lib.ClmgsError(f"{what}: {S} bricks, S * 512 must stay below 2^31")
+    if not (ok(bricks, I32) and tuple(bricks.shape) == (S,) and bricks.device == pool.device):
+        raise _lib.ClmgsError(f"{what}: bricks must be a contiguous int32 [{S}] tensor on {pool.device}, got "
+                              f"{getattr(bricks, 'dtype', type(bricks))} {tuple(getattr(bricks, 'shape', ()))}")
+    if table is not None:
+        if not (ok(table, I32) and tuple(table.shape) == (nbz, nby, nbx) and table.device == pool.device):
+            raise _lib.ClmgsError(f"{what}: table must be a contiguous int32 {(nbz, nby, nbx)} tensor on {pool.device}, got "
+                                  f"{getattr(table, 'dtype', type(table))} {tuple(getattr(table, 'shape', ()))}")
+        slots = table.reshape(-1)[bricks.long().clamp_(0, table.numel() - 1)]
+        if int(table.max()) != S - 1 or int((table >= 0).sum()) != S or not torch.equal(
+                slots, torch.arange(S, dtype=I32, device=pool.device)):
+            raise _lib.ClmgsError(f"{what}: the table does not belong to a pool of {S} bricks (its slots must be 0 .. {S - 1}, "
+                                  "each once, at the bricks the list names)")
+    else:
+        lo, hi = (int(v) for v in torch.aminmax(bricks))
+        if lo < 0 or hi >= nbx * nby * nbz or (S > 1 and not bool((bricks[1:] > bricks[:-1]).all())):
+            raise _lib.ClmgsError(f"{what}: bricks must be ascending indices into the {nbx} x {nby} x {nbz} brick grid")
+    return nx, ny, nz, S
+
+
+@torch.no_grad()
+def tsdf_sparse_integrate(pool, bricks, shape, depth, alpha, rgb, cams, near=0.01, depth_max=float("inf"), alpha_min=0.5,
+                          trunc=1.0, cull=True):
+    """tsdf_integrate on a brick-allocated volume (csrc/tsdf_sparse.hip): pool float32 [S,6,8,8,8], bricks int32 [S] (the
+    ascending linear brick indices of the slots) for the grid shape = (nx, ny, nz); the other arguments as tsdf_integrate.
+    A stored voxel gets exactly the sums the dense volume gives it.  Returns pool."""
+    nx, ny, nz, S = _tsdf_sparse("tsdf_sparse_integrate", shape, bricks, None, pool)
+    cams, B, H, W = _tsdf_images("tsdf_sparse_integrate", pool.device, cams, depth, alpha, rgb)
+    trunc32 = _tsdf_trunc("tsdf_sparse_integrate", trunc)
+    inv_trunc = float(torch.tensor(1.0, dtype=F32) / torch.tensor(trunc32, dtype=F32))  # the float32 quotient
+    L = _lib.lib()
+    for b0 in range(0, B, TSDF_MAX_B):
+        b1 = min(B, b0 + TSDF_MAX_B)
+        rec = (ctypes.c_double * (16 * (b1 - b0)))(*cams[b0:b1].reshape(-1))
+        check(L.clmgs_tsdf_sparse_integrate(stream(), nx, ny, nz, S, dptr(bricks, I32), dptr(pool, F32), b1 - b0, H, W,
+                                            dptr(depth[b0:b1], F32), dptr(alpha[b0:b1], F32), dptr(rgb[b0:b1], F32), rec,
+                                            float(near), float(depth_max), float(alpha_min), trunc32, inv_trunc,
+                                            1 if cull else 0))
+    return pool
+
+
+@torch.no_grad()
+def tsdf_sparse_extract(pool, bricks, table, shape, min_weight, grid_to_world, want_keys=False):
+    """tsdf_extract on a brick-allocated volume (csrc/tsdf_sparse.hip): the four passes over the S * 512 stored voxels, then
+    the vertices sorted by the dense linear index of their cell and the quads by (owner voxel, axis), on the device
+    (torch.sort), so that the output is in tsdf_extract's order.  -> (verts, colours, faces), with want_keys also the
+    sorted int64 keys of the vertices (cell index) and the quads (3 * voxel index + axis)."""
+    import numpy as np
+    nx, ny, nz, S = _tsdf_sparse("tsdf_sparse_extract", shape, bricks, table, pool)
+    g2w = np.ascontiguousarray(grid_to_world.numpy() if isinstance(grid_to_world, torch.Tensor) else grid_to_world,
+                               dtype=np.float64)
+    if g2w.shape != (3, 4) or not np.isfinite(g2w).all():
+        raise ValueError(f"tsdf_sparse_extract: grid_to_world must be a finite 3x4 matrix, got shape {g2w.shape}")
+    mw = float(torch.tensor(float(min_weight), dtype=F32))
+    if not (_finite(mw) and mw > 0):
+        raise ValueError(f"tsdf_sparse_extract: min_weight must be positive and finite, got {min_weight}")
+    L, dev, n = _lib.lib(), pool.device, S * 512
+    rec = (ctypes.c_double * 12)(*g2w.reshape(-1))
+
+    def run(ps, count=None, cell_scan=None, quad_scan=None, V=0, Q=0, verts=None, colours=None, vkeys=None, faces=None,
+            qkeys=None):
+        o = lambda t, dt=None: dptr(t, dt, allow_none=True)
+        check(L.clmgs_tsdf_sparse_extract(stream(), ps, nx, ny, nz, S, dptr(bricks, I32), dptr(table, I32), dptr(pool, F32), mw,
+                                          o(count, I32), o(cell_scan, I32), o(quad_scan, I32), V, Q, rec, o(verts, F32),
+                                          o(colours, U8), o(vkeys, I64), o(faces, I32), o(qkeys, I64)))
+
+    e64 = torch.empty((0,), dtype=I64, device=dev)
+    empty = (torch.empty((0, 3), dtype=F32, device=dev), torch.empty((0, 3), dtype=U8, device=dev),
+             torch.empty((0, 3), dtype=I32, device=dev))
+    count = torch.empty((n,), dtype=I32, device=dev)
+    run(0, count=count)
+    cell_scan = torch.cumsum(count, 0, dtype=I32)
+    V = int(cell_scan[-1])
+    if V == 0:
+        return empty + (e64, e64) if want_keys else empty
+    verts = torch.empty((V, 3), dtype=F32, device=dev)
+    colours = torch.empty((V, 3), dtype=U8, device=dev)
+    vkeys = torch.empty((V,), dtype=I64, device=dev)
+    run(1, cell_scan=cell_scan, V=V, verts=verts, colours=colours, vkeys=vkeys)
+    vkeys, order = torch.sort(vkeys)
+    verts, colours = verts[order], colours[order]
+    run(2, count=count, cell_scan=cell_scan)
+    Q = int(count.sum(dtype=I64))
+    if Q >= 1 << 30:
+        raise _lib.ClmgsError(f"tsdf_sparse_extract: {Q} quads, 2^30 at the most: extract with a larger voxel or a smaller box")
+    if Q == 0:
+        return (verts, colours, empty[2], vkeys, e64) if want_keys else (verts, colours, empty[2])
+    quad_scan = torch.cumsum(count, 0, dtype=I32)
+    del count
+    faces = torch.empty((2 * Q, 3), dtype=I32, device=dev)
+    qkeys = torch.empty((Q,), dtype=I64, device=dev)
+    run(3, cell_scan=cell_scan, quad_scan=quad_scan, V=V, Q=Q, faces=faces, qkeys=qkeys)
+    new_id = torch.empty((V,), dtype=I32, device=dev)  # the inverse permutation: the rank of every vertex in the dense order
+    new_id[order] = torch.arange(V, dtype=I32, device=dev)
+    qkeys, qorder = torch.sort(qkeys)
+    faces = new_id[faces.long()].reshape(Q, 6)[qorder].reshape(2 * Q, 3).contiguous()
+    return (verts, colours, faces, vkeys, qkeys) if want_keys else (verts, colours, faces)
+
+
 # ------------------------------------------------------------------ mesh cleanup
 MESH_MAX_ROUNDS = 64
 

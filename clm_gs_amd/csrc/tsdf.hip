@@ -25,6 +25,7 @@
 // voxel: its +x, +y, +z edges) and quads (two triangles per quad at the voxel's rank).  The output order is fixed by the
 // ranks: vertices by cell index, faces by (owner voxel index, axis).
 #include "common.h"
+#include "tsdf_fuse.h"
 #include "tsdf_math.h"
 
 namespace clmgs {
@@ -34,17 +35,8 @@ constexpr int TS_THREADS = TS_BX * TS_BY;
 constexpr int TS_MAX_SIDE = 32768;      // of an image
 constexpr int TS_EX_THREADS = 256;
 constexpr int TS_EX_MAX_BLOCKS = 8192;  // the extraction passes stride over the voxels
-constexpr double TS_CULL_EPS = 1.0 / 1099511627776.0;  // 2^-40
 
-struct TsdfCams {
-  double c[TSDF_MAX_B][TSDF_CAM_DOUBLES];
-};
-
-// |r0| X + |r1| Y + |r2| Z + |r3|: a bound of the magnitude of every term of tsdf_row over the box [0,X] x [0,Y] x [0,Z]
-__device__ __forceinline__ double row_mag(const double* r, double X, double Y, double Z) {
-  return fabs(r[0]) * X + fabs(r[1]) * Y + fabs(r[2]) * Z + fabs(r[3]);
-}
-
+// The cull and the per-voxel camera loop are csrc/tsdf_fuse.h, shared with the brick-allocated volume.
 __global__ void __launch_bounds__(TS_THREADS)
 tsdf_integrate_kernel(float* __restrict__ grid, int nx, int ny, int nz, int nbx, int nby, const TsdfCams cams, int B, int H,
                       int W, const float* __restrict__ depth, const float* __restrict__ alpha,
@@ -57,42 +49,10 @@ tsdf_integrate_kernel(float* __restrict__ grid, int nx, int ny, int nz, int nbx,
   const int i0 = bi * TS_BX, j0 = bj * TS_BY, k0 = bk * TS_BZ;
   const double near = (double)near_f;
   unsigned seen = (1u << B) - 1u;  // B <= 16
-  if (cull) {                      // (uniform)
-    const int t = threadIdx.x;
-    if (t < 8 * TSDF_MAX_B) {  // waves 0 and 1, whole: lanes 8 b .. 8 b + 7 are the corners of camera b
-      const int b = t >> 3, c = t & 7;
-      bool out[5] = {false, false, false, false, false};
-      if (b < B) {
-        const double* m = cams.c[b];
-        const double xl = (double)i0 + 0.5, xh = (double)min(i0 + TS_BX - 1, nx - 1) + 0.5;
-        const double yl = (double)j0 + 0.5, yh = (double)min(j0 + TS_BY - 1, ny - 1) + 0.5;
-        const double zl = (double)k0 + 0.5, zh = (double)min(k0 + TS_BZ - 1, nz - 1) + 0.5;
-        const double px = (c & 1) ? xh : xl, py = (c & 2) ? yh : yl, pz = (c & 4) ? zh : zl;
-        const double x = tsdf_row(m, px, py, pz), y = tsdf_row(m + 4, px, py, pz), z = tsdf_row(m + 8, px, py, pz);
-        const double sx = row_mag(m, xh, yh, zh), sy = row_mag(m + 4, xh, yh, zh), sz = row_mag(m + 8, xh, yh, zh);
-        const double fx = m[12], fy = m[13], cx = m[14], cy = m[15];
-        out[0] = z + TS_CULL_EPS * (sz + fabs(near)) < near;
-        if (near >= 0.0) {
-          const double l = cx + 1.0, r = cx - (double)W - 1.0, u = cy + 1.0, d = cy - (double)H - 1.0;
-          out[1] = fx * x + l * z + TS_CULL_EPS * (fx * sx + fabs(l) * sz) < 0.0;
-          out[2] = fx * x + r * z - TS_CULL_EPS * (fx * sx + fabs(r) * sz) > 0.0;
-          out[3] = fy * y + u * z + TS_CULL_EPS * (fy * sy + fabs(u) * sz) < 0.0;
-          out[4] = fy * y + d * z - TS_CULL_EPS * (fy * sy + fabs(d) * sz) > 0.0;
-        }
-      }
-      bool culled = false;
-#pragma unroll
-      for (int p = 0; p < 5; ++p) {  // the eight corners of a camera are eight neighbouring lanes of one wave
-        const unsigned long long all = __ballot(out[p]);
-        culled = culled || ((all >> (t & 56)) & 0xffull) == 0xffull;
-      }
-      if (c == 0) seen_lds[b] = (b < B && !culled) ? 1 : 0;
-    }
-    __syncthreads();
-    seen = 0u;
-#pragma unroll
-    for (int b = 0; b < TSDF_MAX_B; ++b) seen |= seen_lds[b] ? (1u << b) : 0u;
-  }
+  if (cull)  // (uniform)
+    seen = ts_cull_seen(cams, B, H, W, near, (double)i0 + 0.5, (double)min(i0 + TS_BX - 1, nx - 1) + 0.5, (double)j0 + 0.5,
+                        (double)min(j0 + TS_BY - 1, ny - 1) + 0.5, (double)k0 + 0.5, (double)min(k0 + TS_BZ - 1, nz - 1) + 0.5,
+                        seen_lds);
   seen = __builtin_amdgcn_readfirstlane(seen);
   if (seen == 0u) return;
   const int i = i0 + (threadIdx.x & (TS_BX - 1)), j = j0 + (threadIdx.x >> 6);
@@ -102,49 +62,8 @@ tsdf_integrate_kernel(float* __restrict__ grid, int nx, int ny, int nz, int nbx,
   const int kend = min(k0 + TS_BZ, nz);
   for (int k = k0; k < kend; ++k) {
     const double pz = (double)k + 0.5;
-    float* g = grid + ((int64_t)k * ny + j) * nx + i;
-    float tsum = 0.f, wsum = 0.f, cr = 0.f, cg = 0.f, cb = 0.f, cw = 0.f;
-    bool touched = false, coloured = false;
-    for (int b = 0; b < B; ++b) {
-      if (!((seen >> b) & 1u)) continue;
-      int col, row;
-      double z;
-      if (!tsdf_pixel(cams.c[b], px, py, pz, near, H, W, col, row, z)) continue;
-      const int64_t pix = (int64_t)b * hw + (int64_t)row * W + col;
-      float sdf;
-      if (!tsdf_sdf(depth[pix], alpha[pix], z, depth_max, alpha_min, trunc, sdf)) continue;
-      if (!touched) {
-        tsum = g[0];
-        wsum = g[n];
-        touched = true;
-      }
-      tsum = tsum + tsdf_term(sdf, inv_trunc);
-      wsum = wsum + 1.0f;
-      if (sdf <= trunc) {
-        if (!coloured) {
-          cr = g[2 * n];
-          cg = g[3 * n];
-          cb = g[4 * n];
-          cw = g[5 * n];
-          coloured = true;
-        }
-        const float* c3 = rgb + ((int64_t)b * 3) * hw + (int64_t)row * W + col;
-        cr = cr + tsdf_clamp01(c3[0]);
-        cg = cg + tsdf_clamp01(c3[hw]);
-        cb = cb + tsdf_clamp01(c3[2 * hw]);
-        cw = cw + 1.0f;
-      }
-    }
-    if (touched) {  // a voxel no camera of the batch observed is not stored back
-      g[0] = tsum;
-      g[n] = wsum;
-    }
-    if (coloured) {
-      g[2 * n] = cr;
-      g[3 * n] = cg;
-      g[4 * n] = cb;
-      g[5 * n] = cw;
-    }
+    ts_fuse_voxel(grid + ((int64_t)k * ny + j) * nx + i, n, cams, B, seen, px, py, pz, near, H, W, hw, depth, alpha, rgb,
+                  depth_max, alpha_min, trunc, inv_trunc);
   }
 }
 
@@ -296,19 +215,9 @@ static bool ts_dims(int nx, int ny, int nz, TsdfDims& D) {
   return true;
 }
 
-static bool ts_aligned(const void* p, size_t a) { return p != nullptr && ((uintptr_t)p % a) == 0; }
-
-// [a, a + na) and [b, b + nb) do not overlap
-static bool ts_apart(const void* a, uint64_t na, const void* b, uint64_t nb) {
-  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-  return a0 + na <= b0 || b0 + nb <= a0;
-}
-
 static dim3 ts_ex_grid(const TsdfDims& D) {
   return dim3((unsigned)min((int64_t)TS_EX_MAX_BLOCKS, (D.n + TS_EX_THREADS - 1) / TS_EX_THREADS));
 }
-
-static bool ts_weight(float w) { return isfinite(w) && w > 0.0f; }
 
 }  // namespace clmgs
 

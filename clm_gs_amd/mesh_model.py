@@ -3,7 +3,7 @@
     python -m clm_gs_amd.mesh_model -m <model dir | .ply | .vq.npz> -s <colmap dir> -o <mesh.ply> --voxel V
         [--trunc_voxels 4] [--bounds emin nmin umin emax nmax umax] [--up X Y Z] [--east X Y Z] [--every K] [-r R]
         [--alpha_min 0.5] [--depth_max D] [--min_weight 2] [--grid_gb 16] [--antialiased] [--undistort --undistort_zoom Z]
-        [--depth_mode expected|median] [--min_component_faces N] [--keep_components K] [--eval]
+        [--depth_mode expected|median] [--min_component_faces N] [--keep_components K] [--sparse] [--eval]
         [--clm_offload | --naive_offload | --no_offload]
 
 renders every selected training camera of the scene through the strategy's own eval entry (render_mode "RGB+ED":
@@ -19,6 +19,12 @@ front of a surface pulls forward; the .json then carries "depth_mode": "median".
 before it is written (mesh_clean.clean; DESIGN.md section 3, "Mesh cleanup"): those with fewer than N faces, and all but
 the K with the most faces; the .json then carries "cleanup" (the options and the report) and the log line the component
 counts.  Negative values are refused by name.  Without either flag nothing changes.
+--sparse stores the volume in bricks of 8 x 8 x 8 voxels allocated only where some camera's depth map can put a surface
+(tsdf.SparseTsdfVolume, csrc/tsdf_sparse.hip; DESIGN.md section 3, "Sparse volume"): the cameras are rendered twice, once to
+mark the bricks and once to fuse, and mesh.ply is byte for byte the file the dense volume writes wherever that fits; the
+dense limits (2^31 voxels, 24 B per voxel under --grid_gb) give way to a brick grid of at most 2^30 bricks, 2^31 STORED
+voxels and marks + table + pool under --grid_gb.  The .json gains "sparse" and the log line the brick counts, the pool's GB
+and the marking rate.  Without the flag every file is what it was.
 """
 import argparse
 import json
@@ -52,12 +58,14 @@ def json_path(mesh_path):
 @torch.no_grad()
 def build_mesh(gaussians, cameras, args, out_path, voxel, frame=None, bounds=None, trunc_voxels=4.0, every=1, alpha_min=0.5,
                depth_max=None, min_weight=2.0, grid_gb=16.0, near=0.01, background=None, log=None, depth_mode="expected",
-               min_component_faces=0, keep_components=0):
+               min_component_faces=0, keep_components=0, sparse=False):
     """Renders cameras[::every] from `gaussians` through the eval entry of the strategy `args` names, fuses them, extracts
     and writes out_path and its .json.  -> the dict written to the .json.  The global image size (utils.set_img_size)
     must be the cameras' size.  depth_mode "expected" fuses the "RGB+ED" depth, "median" the "RGB+MD" one (the .json gains
     "depth_mode" only then).  min_component_faces / keep_components: mesh_clean.clean between the extraction and the file
-    (the .json gains "cleanup" and the log line its component counts only when one of them is on)."""
+    (the .json gains "cleanup" and the log line its component counts only when one of them is on).  sparse: the
+    brick-allocated volume; every camera is rendered twice, to mark and to fuse (the eval forward is deterministic: see
+    DESIGN.md section 3, "Sparse volume"), and the .json gains "sparse"."""
     min_component_faces, keep_components = mesh_clean.check_options(min_component_faces, keep_components,
                                                                     ("--min_component_faces", "--keep_components"))
     render_mode = depth_render_mode(depth_mode)
@@ -65,12 +73,23 @@ def build_mesh(gaussians, cameras, args, out_path, voxel, frame=None, bounds=Non
     frame = frame if frame is not None else map_frame()
     if bounds is None:
         bounds = percentile_box(gaussians.get_xyz.detach().to("cuda"), frame)
-    volume = tsdf.TsdfVolume(frame, bounds, voxel, trunc_voxels, device="cuda", grid_gb=grid_gb)
     cams = list(cameras)[::max(1, int(every))]
     if not cams:
         raise ValueError("mesh export: no camera selected")
     depth_max = float("inf") if depth_max is None else float(depth_max)
-    t_render = t_fuse = 0.0
+    t_render = t_fuse = t_mark = 0.0
+    if sparse:  # pass 1: the union of the bricks every camera can put a surface into, before any sum is formed
+        volume = tsdf.SparseTsdfVolume(frame, bounds, voxel, trunc_voxels, device="cuda", grid_gb=grid_gb)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for cam in cams:
+            _, depth, alpha = eval_one_cam(cam, gaussians, background, args, None, render_mode=render_mode)
+            volume.mark(cam, depth, alpha, near=near, depth_max=depth_max, alpha_min=alpha_min)
+        volume.allocate()
+        torch.cuda.synchronize()
+        t_mark = time.perf_counter() - t0
+    else:
+        volume = tsdf.TsdfVolume(frame, bounds, voxel, trunc_voxels, device="cuda", grid_gb=grid_gb)
     for cam in cams:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -101,22 +120,27 @@ def build_mesh(gaussians, cameras, args, out_path, voxel, frame=None, bounds=Non
                 faces=int(faces.shape[0]), cameras=len(cams), camera_names=[str(c.image_name) for c in cams])
     if depth_mode == "median":
         meta["depth_mode"] = "median"
+    if sparse:
+        meta["sparse"] = dict(bricks=volume.S, bricks_total=volume.bricks_total, pool_gb=volume.S * tsdf.BYTES_PER_BRICK / 1e9)
     if report is not None:
         meta = mesh_clean.json_record(meta, min_component_faces, keep_components, report, verts.shape[0], faces.shape[0])
     with open(json_path(out_path), "w") as f:
         json.dump(meta, f, indent=1)
     log.write("mesh export: grid {} x {} x {} voxel {:g} cameras {} render {:.1f} cameras/s integration {:.1f} cameras/s "
-              "extraction {:.3f} s vertices {} faces {}{} -> {}\n".format(
+              "extraction {:.3f} s vertices {} faces {}{}{} -> {}\n".format(
                   volume.nx, volume.ny, volume.nz, volume.voxel, len(cams), len(cams) / max(t_render, 1e-9),
                   len(cams) / max(t_fuse, 1e-9), t_extract, meta["vertices"], meta["faces"],
                   "" if report is None else " components {} kept {}".format(report["components"], report["components_kept"]),
+                  "" if not sparse else " sparse bricks {} of {} pool {:.3f} GB marking {:.1f} cameras/s".format(
+                      volume.S, volume.bricks_total, meta["sparse"]["pool_gb"], len(cams) / max(t_mark, 1e-9)),
                   out_path))
     return meta
 
 
 def check_options(voxel, bounds=None, grid_gb=16.0, trunc_voxels=4.0, min_weight=2.0, every=1, depth_mode="expected",
-                  min_component_faces=0, keep_components=0):
-    """The refusals that need nothing loaded (ValueError by name)."""
+                  min_component_faces=0, keep_components=0, sparse=False):
+    """The refusals that need nothing loaded (ValueError by name); with sparse the brick-grid limits take the place of the
+    dense ones."""
     mesh_clean.check_options(min_component_faces, keep_components, ("--min_component_faces", "--keep_components"))
     tsdf.grid_shape((0, 0, 0, 1, 1, 1), voxel)  # (--voxel alone)
     depth_render_mode(depth_mode)
@@ -129,7 +153,7 @@ def check_options(voxel, bounds=None, grid_gb=16.0, trunc_voxels=4.0, min_weight
     if not grid_gb > 0:
         raise ValueError(f"--grid_gb must be positive, got {grid_gb}")
     if bounds is not None:
-        tsdf.check_grid(bounds, voxel, grid_gb)
+        (tsdf.check_brick_grid if sparse else tsdf.check_grid)(bounds, voxel, grid_gb)
 
 
 def main(argv=None):
@@ -158,6 +182,8 @@ def main(argv=None):
                     help="drop the connected components of the mesh with fewer than N faces")
     ap.add_argument("--keep_components", type=int, default=0, metavar="K",
                     help="keep only the K connected components with the most faces")
+    ap.add_argument("--sparse", action="store_true",
+                    help="a brick-allocated volume: the same mesh.ply, on boxes far beyond 2^31 voxels (renders every camera twice)")
     ap.add_argument("--antialiased", action="store_true", help="for a model trained with trainer --antialiased")
     ap.add_argument("--undistort", action="store_true", help="for a model trained with trainer --undistort")
     ap.add_argument("--undistort_zoom", type=float, default=1.0, help="--undistort: the trainer's --undistort_zoom")
@@ -169,7 +195,7 @@ def main(argv=None):
     a = ap.parse_args(argv)
     try:  # refusals before anything is loaded or written
         check_options(a.voxel, a.bounds, a.grid_gb, a.trunc_voxels, a.min_weight, a.every, a.depth_mode,
-                      a.min_component_faces, a.keep_components)
+                      a.min_component_faces, a.keep_components, a.sparse)
         frame = map_frame(a.up, a.east)
     except ValueError as e:
         raise SystemExit(str(e))
@@ -199,7 +225,7 @@ def main(argv=None):
     try:
         build_mesh(gaussians, cams, args, a.output, a.voxel, frame, a.bounds, a.trunc_voxels, a.every, a.alpha_min,
                    a.depth_max, a.min_weight, a.grid_gb, depth_mode=a.depth_mode,
-                   min_component_faces=a.min_component_faces, keep_components=a.keep_components)
+                   min_component_faces=a.min_component_faces, keep_components=a.keep_components, sparse=a.sparse)
     except ValueError as e:  # (the size of a grid whose bounds come from the model)
         raise SystemExit(str(e))
     return 0

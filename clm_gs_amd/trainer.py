@@ -339,12 +339,15 @@ def mesh_rules(args):
     except ValueError as e:
         return [(True, str(e))]
     if not voxel:
-        return [] if depth_mode is None else [(True, f"--mesh_depth_mode {depth_mode} has effect only with --mesh_voxel: "
-                                                      "give both, or neither")]
+        return ([] if depth_mode is None else [(True, f"--mesh_depth_mode {depth_mode} has effect only with --mesh_voxel: "
+                                                       "give both, or neither")]) + \
+            ([(True, "--mesh_sparse has effect only with --mesh_voxel: give both, or neither")]
+             if getattr(args, "mesh_sparse", False) else [])
     from .mesh_model import check_options
     try:
         check_options(voxel, None, getattr(args, "mesh_grid_gb", 16.0), getattr(args, "mesh_trunc_voxels", 4.0),
-                      getattr(args, "mesh_min_weight", 2.0), getattr(args, "mesh_every", 1), depth_mode or "expected")
+                      getattr(args, "mesh_min_weight", 2.0), getattr(args, "mesh_every", 1), depth_mode or "expected",
+                      sparse=bool(getattr(args, "mesh_sparse", False)))
     except ValueError as e:
         return [(True, str(e).replace("--voxel", "--mesh_voxel").replace("--trunc_voxels", "--mesh_trunc_voxels")
                  .replace("--depth_mode", "--mesh_depth_mode")
@@ -833,7 +836,8 @@ def train_from_colmap(source_path, model_path, strategy="clm_offload", iteration
                                grid_gb=args.mesh_grid_gb, log=log_file,
                                depth_mode=getattr(args, "mesh_depth_mode", None) or "expected",
                                min_component_faces=getattr(args, "mesh_min_component_faces", 0),
-                               keep_components=getattr(args, "mesh_keep_components", 0))
+                               keep_components=getattr(args, "mesh_keep_components", 0),
+                               sparse=bool(getattr(args, "mesh_sparse", False)))
             for row in SIDE_MODELS:
                 if getattr(scene, row.name) is not None:
                     getattr(scene, row.name).save_to(model_path, scene.train_cameras)
@@ -931,6 +935,8 @@ OPTIONS = (
          "with fewer than N faces (clm_gs_amd.mesh_clean); 0 = off"),
     _opt("--mesh_keep_components", type=int, metavar="K", help="--mesh_voxel: keep only the K connected components with the "
          "most faces; 0 = off"),
+    _opt("--mesh_sparse", action="store_true", help="--mesh_voxel: the brick-allocated volume (mesh_model --sparse): the same "
+         "mesh.ply, on boxes beyond the dense volume's 2^31 voxels; renders every camera twice"),
 )
 
 

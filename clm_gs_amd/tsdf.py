@@ -1,4 +1,4 @@
-"""Mesh export ("Mesh export"): a dense TSDF volume in a map frame, fused from rendered depth maps
+"""Mesh export ("Mesh export" and "Sparse volume"): a dense TSDF volume in a map frame, fused from rendered depth maps
 (csrc/tsdf.hip through clm_kernels.tsdf_integrate) and turned into a triangle mesh by naive Surface Nets
 (clm_kernels.tsdf_extract).
 
@@ -6,7 +6,11 @@ The box: frame (e, n, u) as render_ortho.map_frame gives it, bounds (emin, nmin,
 `voxel` world units per voxel.  Grid axis x runs along e, y along n, z along u; voxel (i, j, k) sits at the grid point
 (i + 0.5, j + 0.5, k + 0.5), i.e. at the world point  e (emin + (i + 0.5) voxel) + n (nmin + ...) + u (umin + ...).  The
 kernels see grid coordinates only: the host composes, in float64, grid_to_world (3x4) for the vertices and one matrix
-M = world_to_camera . grid_to_world per camera."""
+M = world_to_camera . grid_to_world per camera.
+
+SparseTsdfVolume is the same volume stored in bricks of 8 x 8 x 8 voxels, allocated only where some camera's depth map can put
+a surface (csrc/tsdf_sparse.hip): two passes over the cameras, mark then fuse, and the mesh of the dense volume bit for bit
+on a box far beyond what the dense volume can hold."""
 import math
 
 import numpy as np
@@ -103,11 +107,18 @@ class TsdfVolume:
         """Two slots of stacked batch inputs, allocated once per image size: a slot is filled while the launch that reads
         the other one may still be running."""
         if self._ring is None or self._ring[0][0].shape[1:] != (H, W):
-            dev = self.grid.device
+            dev = self._device()
             self._ring = [(torch.empty((BATCH, H, W), dtype=torch.float32, device=dev),
                            torch.empty((BATCH, H, W), dtype=torch.float32, device=dev),
                            torch.empty((BATCH, 3, H, W), dtype=torch.float32, device=dev)) for _ in range(2)]
         return self._ring[self._slot]
+
+    def _device(self):
+        return self.grid.device
+
+    def _fuse(self, depth, alpha, rgb, records, near, depth_max, alpha_min):
+        clm_kernels.tsdf_integrate(self.grid, depth, alpha, rgb, records, near=near, depth_max=depth_max, alpha_min=alpha_min,
+                                   trunc=self.trunc)
 
     def add(self, camera, image, depth, alpha, near=0.01, depth_max=float("inf"), alpha_min=0.5):
         """Stages one camera's render (image [3,H,W], expected depth and alpha [H,W] or [1,H,W]) and launches the fusion
@@ -131,8 +142,7 @@ class TsdfVolume:
             return
         d, a, c = self._ring[self._slot]
         near, depth_max, alpha_min = self._gates
-        clm_kernels.tsdf_integrate(self.grid, d[:self._fill], a[:self._fill], c[:self._fill], np.stack(self._records),
-                                   near=near, depth_max=depth_max, alpha_min=alpha_min, trunc=self.trunc)
+        self._fuse(d[:self._fill], a[:self._fill], c[:self._fill], np.stack(self._records), near, depth_max, alpha_min)
         self.cameras_used += self._fill
         self._slot, self._fill, self._records = 1 - self._slot, 0, []
 
@@ -153,3 +163,191 @@ class TsdfVolume:
         result is V = F = 0, not an error."""
         self.flush()
         return clm_kernels.tsdf_extract(self.grid, min_weight, self.grid_to_world)
+
+
+# ---------------------------------------------------------------------------------------------- sparse volume
+BRICK = clm_kernels.TSDF_BRICK
+BYTES_PER_BRICK = BYTES_PER_VOXEL * BRICK ** 3   # 12 288: six float32 planes of 512 voxels
+BYTES_PER_TABLE_ENTRY = 5                        # marks uint8 + table int32, per brick of the box
+MAX_BRICK_GRID = clm_kernels.TSDF_MAX_BRICK_GRID  # inclusive
+MAX_SPARSE_VOXELS = 1 << 31                      # S * 512, exclusive
+
+
+def check_brick_grid(bounds, voxel, grid_gb=16.0):
+    """grid_shape and the brick grid (nbx, nby, nbz) = ceil(n / 8) of the sparse volume, refused by name when a side reaches
+    2^31 voxels, the brick grid holds more than 2^30 bricks, or marks + table alone (5 B per brick) exceed grid_gb: what can be
+    refused from the bounds before anything is loaded.  -> ((nx, ny, nz), (nbx, nby, nbz))"""
+    shape = grid_shape(bounds, voxel)
+    if not (isinstance(grid_gb, (int, float)) and math.isfinite(grid_gb) and grid_gb > 0):
+        raise ValueError(f"--grid_gb must be positive and finite, got {grid_gb}")
+    if max(shape) >= 1 << 31:
+        raise ValueError(f"--sparse: --voxel {voxel:g} gives a grid of {shape[0]} x {shape[1]} x {shape[2]} voxels, a side of "
+                         "2^31 voxels or more; use a larger --voxel (or shrink --bounds)")
+    nb = tuple(-(-v // BRICK) for v in shape)
+    total = nb[0] * nb[1] * nb[2]
+    if total > MAX_BRICK_GRID:
+        fit = float(voxel) * (total / MAX_BRICK_GRID) ** (1.0 / 3.0)
+        raise ValueError(f"--sparse: --voxel {voxel:g} gives a brick grid of {nb[0]} x {nb[1]} x {nb[2]} = {total} bricks, above "
+                         f"2^30 bricks; about --voxel {fit:.3g} fits (an estimate; or shrink --bounds)")
+    if total * BYTES_PER_TABLE_ENTRY > float(grid_gb) * 1e9:
+        raise ValueError(f"--sparse: the brick table of {nb[0]} x {nb[1]} x {nb[2]} = {total} bricks takes "
+                         f"{total * BYTES_PER_TABLE_ENTRY / 1e9:.2f} GB before any brick is allocated, above --grid_gb {grid_gb:g}")
+    return shape, nb
+
+
+def check_sparse_size(S, bricks_total, voxel, grid_gb=16.0):
+    """The sizes of an allocation of S bricks out of bricks_total, refused by name: S * 512 < 2^31 and marks + table + pool
+    <= grid_gb.  The message gives the brick count, the GB and an ESTIMATE of the voxel size that fits: a surface is
+    two-dimensional, so the bytes go with voxel^-2 and the estimate is voxel sqrt(bytes / cap).  -> bytes"""
+    S, bricks_total = int(S), int(bricks_total)
+    nbytes = bricks_total * BYTES_PER_TABLE_ENTRY + S * BYTES_PER_BRICK
+    cap_bytes = float(grid_gb) * 1e9
+    cap_slots = (MAX_SPARSE_VOXELS - 1) // BRICK ** 3
+    if S > cap_slots:
+        fit = float(voxel) * math.sqrt(S / cap_slots)
+        raise ValueError(f"--sparse: {S} of {bricks_total} bricks are marked ({nbytes / 1e9:.2f} GB), above 2^31 stored voxels "
+                         f"({cap_slots} bricks); about --voxel {fit:.3g} fits (an estimate; or shrink --bounds)")
+    if nbytes > cap_bytes:
+        fit = float(voxel) * math.sqrt(nbytes / cap_bytes)
+        raise ValueError(f"--sparse: {S} of {bricks_total} bricks are marked, marks + table + pool take {nbytes / 1e9:.2f} GB, "
+                         f"above --grid_gb {grid_gb:g}; about --voxel {fit:.3g} fits (an estimate; or shrink --bounds)")
+    return nbytes
+
+
+def camera_mark_record(camera, g2w):
+    """The 16 doubles clm_kernels.tsdf_mark takes: the inverse of camera_record's M (camera space -> grid coordinates, 3x4,
+    float64), then fx, fy, cx, cy."""
+    rec = camera_record(camera, g2w)
+    inv = np.linalg.inv(np.vstack([rec[:12].reshape(3, 4), [0.0, 0.0, 0.0, 1.0]]))
+    return np.concatenate([inv[:3].reshape(12), rec[12:]])
+
+
+class SparseTsdfVolume(TsdfVolume):
+    """TsdfVolume in bricks of 8 x 8 x 8 voxels, allocated where a surface can be.  First mark() every camera, then allocate(),
+    then add() / integrate() the SAME cameras and depth maps, then extract(): the mesh is the dense volume's, bit for bit
+    ("Sparse volume").  The dense limits do not apply; grid_gb bounds marks + table + pool."""
+
+    def __init__(self, frame, bounds, voxel, trunc_voxels=4.0, device="cuda", grid_gb=16.0):
+        self.frame = tuple(np.asarray(v, dtype=np.float64) for v in frame)
+        self.bounds = tuple(float(v) for v in bounds)
+        (self.nx, self.ny, self.nz), (self.nbx, self.nby, self.nbz) = check_brick_grid(self.bounds, voxel, grid_gb)
+        self.voxel, self.grid_gb = float(voxel), float(grid_gb)
+        if not (math.isfinite(trunc_voxels) and trunc_voxels > 0):
+            raise ValueError(f"--trunc_voxels must be positive and finite, got {trunc_voxels}")
+        self.trunc = float(trunc_voxels) * self.voxel
+        self.grid_to_world = grid_to_world(self.frame, self.bounds, self.voxel)
+        self.marks = torch.zeros((self.nbz, self.nby, self.nbx), dtype=torch.uint8, device=device)
+        self.table = self.bricks = self.pool = None
+        self.cameras_used = self.cameras_marked = 0
+        self._ring, self._slot, self._fill, self._records = None, 0, 0, []
+        self._gates = None
+        self._mring, self._mslot, self._mfill, self._mrecords, self._mgates = None, 0, 0, [], None
+
+    @property
+    def shape(self):
+        return self.nx, self.ny, self.nz
+
+    @property
+    def bricks_total(self):
+        return self.nbx * self.nby * self.nbz
+
+    @property
+    def S(self):
+        if self.pool is None:
+            raise ValueError("SparseTsdfVolume: allocate() has not been called")
+        return int(self.pool.shape[0])
+
+    @property
+    def nbytes(self):
+        return self.bricks_total * BYTES_PER_TABLE_ENTRY + self.S * BYTES_PER_BRICK
+
+    def _device(self):
+        return self.marks.device
+
+    # ------------------------------------------------------------------------------------------ pass 1: marking
+    def mark(self, camera, depth, alpha, near=0.01, depth_max=float("inf"), alpha_min=0.5):
+        """Stages one camera's depth and alpha ([H,W] or [1,H,W]) and launches the marking when 16 are staged, as add()
+        does for the fusion; allocate() launches what is left."""
+        if self.pool is not None:
+            raise ValueError("SparseTsdfVolume: mark() after allocate(): a brick allocated late would lack the earlier "
+                             "cameras' observations; mark every camera first")
+        gates = (float(near), float(depth_max), float(alpha_min))
+        H, W = (int(v) for v in depth.shape[-2:])
+        if self._mfill and (self._mgates != gates or self._mring[0][0].shape[1:] != (H, W)):
+            self._flush_marks()
+        self._mgates = gates
+        if self._mring is None or self._mring[0][0].shape[1:] != (H, W):
+            dev = self._device()
+            self._mring = [tuple(torch.empty((BATCH, H, W), dtype=torch.float32, device=dev) for _ in range(2)) for _ in range(2)]
+        d, a = self._mring[self._mslot]
+        d[self._mfill].copy_(depth.reshape(H, W))
+        a[self._mfill].copy_(alpha.reshape(H, W))
+        self._mrecords.append(camera_mark_record(camera, self.grid_to_world))
+        self._mfill += 1
+        if self._mfill == BATCH:
+            self._flush_marks()
+
+    def _flush_marks(self):
+        if not self._mfill:
+            return
+        d, a = self._mring[self._mslot]
+        near, depth_max, alpha_min = self._mgates
+        clm_kernels.tsdf_mark(self.marks, self.shape, d[:self._mfill], a[:self._mfill], np.stack(self._mrecords), near=near,
+                              depth_max=depth_max, alpha_min=alpha_min, trunc=self.trunc, voxel_cam=self.voxel)
+        self.cameras_marked += self._mfill
+        self._mslot, self._mfill, self._mrecords = 1 - self._mslot, 0, []
+
+    def allocate(self):
+        """Builds table, bricks and the zeroed pool from the marks; refuses by name S * 512 >= 2^31 and marks + table + pool
+        above grid_gb.  -> S.  No marked brick is a result (S = 0), not an error."""
+        if self.pool is not None:
+            raise ValueError("SparseTsdfVolume: allocate() has been called already")
+        self._flush_marks()
+        self._mring = None
+        flat = self.marks.reshape(-1) != 0
+        S = int(flat.sum())
+        check_sparse_size(S, self.bricks_total, self.voxel, self.grid_gb)
+        scan = torch.cumsum(flat, 0, dtype=torch.int32)
+        self.table = torch.where(flat, scan - 1, torch.full_like(scan, -1)).reshape(self.nbz, self.nby, self.nbx).contiguous()
+        del scan
+        self.bricks = torch.nonzero(flat).reshape(-1).to(torch.int32)
+        self.pool = torch.zeros((S, 6, BRICK, BRICK, BRICK), dtype=torch.float32, device=self._device())
+        return S
+
+    # ------------------------------------------------------------------------------------------ pass 2: fusion
+    def add(self, camera, image, depth, alpha, near=0.01, depth_max=float("inf"), alpha_min=0.5):
+        if self.pool is None:
+            raise ValueError("SparseTsdfVolume: add() before allocate(): mark() every camera, then allocate(), then add() them")
+        if self.S:
+            super().add(camera, image, depth, alpha, near, depth_max, alpha_min)
+        else:
+            camera_record(camera, self.grid_to_world)  # (an orthographic camera is refused all the same)
+            self.cameras_used += 1
+
+    def _fuse(self, depth, alpha, rgb, records, near, depth_max, alpha_min):
+        clm_kernels.tsdf_sparse_integrate(self.pool, self.bricks, self.shape, depth, alpha, rgb, records, near=near,
+                                          depth_max=depth_max, alpha_min=alpha_min, trunc=self.trunc)
+
+    # ------------------------------------------------------------------------------------------ surface
+    def extract(self, min_weight=2.0):
+        """As TsdfVolume.extract, in the same order: vertices by cell index, faces by (owner voxel, axis)."""
+        self.flush()
+        if self.S == 0:
+            dev = self._device()
+            return (torch.empty((0, 3), dtype=torch.float32, device=dev), torch.empty((0, 3), dtype=torch.uint8, device=dev),
+                    torch.empty((0, 3), dtype=torch.int32, device=dev))
+        return clm_kernels.tsdf_sparse_extract(self.pool, self.bricks, self.table, self.shape, min_weight, self.grid_to_world)
+
+    def to_dense(self):
+        """float32 [6, nz, ny, nx] with zeros where nothing is stored: for tests and for boxes that fit."""
+        self.flush()
+        S = self.S
+        n = self.nx * self.ny * self.nz
+        if n >= MAX_VOXELS:
+            raise ValueError(f"SparseTsdfVolume.to_dense: {self.nx} x {self.ny} x {self.nz} = {n} voxels, 2^31 or more")
+        full = torch.zeros((self.bricks_total, 6, BRICK, BRICK, BRICK), dtype=torch.float32, device=self._device())
+        if S:
+            full[self.bricks.long()] = self.pool
+        full = full.reshape(self.nbz, self.nby, self.nbx, 6, BRICK, BRICK, BRICK).permute(3, 0, 4, 1, 5, 2, 6)
+        full = full.reshape(6, self.nbz * BRICK, self.nby * BRICK, self.nbx * BRICK)
+        return full[:, :self.nz, :self.ny, :self.nx].contiguous()

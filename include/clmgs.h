@@ -1031,6 +1031,40 @@ int clmgs_tsdf_quad_count(void* stream, int nx, int ny, int nz, const float* gri
 int clmgs_tsdf_quads(void* stream, int nx, int ny, int nz, const float* grid, float min_weight, const int32_t* cell_scan,
                      const int32_t* quad_scan, int V, int Q, int32_t* faces);
 
+/* ---- mesh export, sparse volume (csrc/tsdf_sparse.hip, csrc/tsdf_fuse.h; clm_gs_amd/tsdf.py SparseTsdfVolume): the same
+ * fusion and extraction on a brick-allocated volume; DESIGN.md section 3, "Sparse volume".  Bricks are 8 x 8 x 8 voxels
+ * aligned to the grid origin; the brick grid is nbx x nby x nbz = ceil(n / 8) per axis, at most 2^30 bricks.  marks uint8
+ * [nbz, nby, nbx]; table int32 [nbz, nby, nbx]: the slot of a brick or -1; bricks int32 [S]: the linear brick index of every
+ * slot, ascending; pool float32 [S, 6, 8, 8, 8] (the six planes of a brick, z, y, x with x fastest); 1 <= S, S * 512 < 2^31.
+ *  - clmgs_tsdf_mark stores 1 into marks[] for every brick that can hold a voxel some pixel of the B (1..16) cameras
+ *    observes with -trunc <= sdf < 0, or a voxel within 1 voxel of one (a superset: the frustum piece of the pixel square
+ *    between the depths max(d, near) (1 - 2^-20) and (d + trunc) (1 + 2^-20), cut into sub-slabs of at most 4 voxels, each
+ *    as the bounding box of its eight corners widened by 1 + 2^-16 voxels).  cams: HOST array [B,16] of doubles, per camera
+ *    the 12 entries of the 3x4 row-major matrix from camera space to grid coordinates (the inverse of clmgs_tsdf_integrate's
+ *    M), then fx, fy, cx, cy, every entry finite and at most 1e30 in magnitude; voxel_cam: the length of a voxel in camera
+ *    units, trunc / voxel_cam <= 4096.  Same-value byte stores: the result is a set, independent of the order and the
+ *    split of the cameras.  marks is never cleared.
+ *  - clmgs_tsdf_sparse_integrate: clmgs_tsdf_integrate on the voxels of the S bricks (one workgroup per brick, the same
+ *    cull and camera loop); voxels of a border brick beyond the grid are not touched.
+ *  - clmgs_tsdf_sparse_extract: the four extraction passes over the S * 512 slot voxels sv = slot * 512 + (z * 64 + y * 8 + x);
+ *    count, cell_scan and quad_scan are int32 [S * 512] in that order.  pass 0: count = cells; pass 1: verts, colours and
+ *    vert_keys int64 [V] (the dense linear index (k ny + j) nx + i of the vertex's cell); pass 2: count = quad counts (needs
+ *    cell_scan); pass 3: faces int32 [2Q,3] and quad_keys int64 [Q] (3 * the owner's dense linear index + axis), face indices
+ *    in the numbering of pass 1.  Sorted by the keys the vertices and quads are in the order of the dense entries.  The
+ *    arguments a pass does not use may be null.  A neighbour whose brick is not stored counts as wsum = 0.
+ * Every entry returns CLMGS_EINVAL, before anything is launched, for what the dense entries refuse and for a brick grid
+ * above 2^30, S outside the limits above or above the brick grid, and a pass outside 0..3. */
+int clmgs_tsdf_mark(void* stream, int nx, int ny, int nz, uint8_t* marks, int B, int H, int W, const float* depth,
+                    const float* alpha, const double* cams, float near, float depth_max, float alpha_min, float trunc,
+                    double voxel_cam);
+int clmgs_tsdf_sparse_integrate(void* stream, int nx, int ny, int nz, int S, const int32_t* bricks, float* pool, int B, int H,
+                                int W, const float* depth, const float* alpha, const float* rgb, const double* cams, float near,
+                                float depth_max, float alpha_min, float trunc, float inv_trunc, int cull);
+int clmgs_tsdf_sparse_extract(void* stream, int pass, int nx, int ny, int nz, int S, const int32_t* bricks, const int32_t* table,
+                              const float* pool, float min_weight, int32_t* count, const int32_t* cell_scan,
+                              const int32_t* quad_scan, int V, int Q, const double* grid_to_world, float* verts, uint8_t* colours,
+                              int64_t* vert_keys, int32_t* faces, int64_t* quad_keys);
+
 /* ---- mesh cleanup (csrc/mesh.hip; clm_gs_amd/mesh_clean.py): the connected components of a triangle list and their face
  * counts.  faces int32 [F,3] on the device, any triangle list over V vertices, 1 <= V < 2^31, 1 <= F < 2^31; two vertices
  * are connected when a face names both.  A face with an index outside [0, V) is skipped by every kernel.
