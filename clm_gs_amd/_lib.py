@@ -140,6 +140,14 @@ SIGNATURES = {
     "clmgs_mesh_hook": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
     "clmgs_mesh_shortcut": (_i, [_vp, _i, _vp, _vp]),
     "clmgs_mesh_component_faces": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
+    # mesh decimation: V, F, faces, mark | V, verts, mark, cell, keys, flag | V, F, C, faces, cluster, out_faces, collapsed,
+    # inc | V, F, C, verts, colours, faces, cluster_keys, vert_order, vert_start, n_members, inc, inc_start, n_inc, lane_order,
+    # cell, out_verts, out_colours, code
+    "clmgs_mesh_decimate_mark": (_i, [_vp, _i, _i, _vp, _vp]),
+    "clmgs_mesh_decimate_keys": (_i, [_vp, _i, _vp, _vp, _d, _vp, _vp]),
+    "clmgs_mesh_decimate_faces": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "clmgs_mesh_decimate_place": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _d, _vp, _vp,
+                                       _vp]),
     "clmgs_mcmc_relocation": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "clmgs_mcmc_reg_grad": (_i, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _f, _f]),
     "clmgs_mcmc_noise": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _f, _vp]),

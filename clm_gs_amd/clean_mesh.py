@@ -1,5 +1,5 @@
-"""python -m clm_gs_amd.clean_mesh -i <mesh.ply> -o <out.ply> [--min_faces N] [--keep_largest K]: the command line of
-mesh_clean.py ("Mesh cleanup")."""
+"""python -m clm_gs_amd.clean_mesh -i <mesh.ply> -o <out.ply> [--min_faces N] [--keep_largest K] [--decimate_cell C]: the
+command line of mesh_clean.py and mesh_decimate.py ("Mesh cleanup" and "Mesh decimation")."""
 import sys
 
 from .mesh_clean import main

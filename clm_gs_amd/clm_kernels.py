@@ -995,6 +995,106 @@ def mesh_component_faces(faces, labels):
     return count
 
 
+# ------------------------------------------------------------------ mesh decimation
+MESH_DECIMATE_NONFINITE, MESH_DECIMATE_RANGE = 1, 2  # the bits of mesh_decimate_keys' flag
+
+
+def _mesh_cell(cell, what):
+    if isinstance(cell, bool) or not isinstance(cell, (int, float)) or not (0 < cell < float("inf")):
+        raise ValueError(f"{what}: cell must be a positive finite number, got {cell!r}")
+    return float(cell)
+
+
+def _mesh_dev(t, dtype, shape, what, name):
+    """t: a contiguous device tensor of that dtype and shape (None = any size), or ClmgsError by name."""
+    if not (isinstance(t, torch.Tensor) and t.is_cuda):
+        raise _lib.ClmgsError(f"{what}: {name} must be a tensor on the device (no CPU fallback in clm_gs_amd), got "
+                              f"{getattr(t, 'device', type(t))}")
+    if t.dtype != dtype or t.dim() != len(shape) or any(s is not None and int(n) != s for n, s in zip(t.shape, shape)):
+        want = "[" + ",".join("N" if s is None else str(s) for s in shape) + "]"
+        raise _lib.ClmgsError(f"{what}: {name} must be {str(dtype).replace('torch.', '')} {want}, got {t.dtype} {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise _lib.ClmgsError(f"{what}: {name} must be contiguous")
+
+
+@torch.no_grad()
+def mesh_decimate_keys(verts, faces, cell):
+    """The key pass of the decimation (csrc/mesh_decimate.hip; DESIGN.md section 3, "Mesh decimation"): verts float32 [V,3]
+    and faces int32 [F,3] on the device, cell > 0 -> (keys int64 [V], flag int32 [1]), both on the device: the key of the
+    cell of every vertex a face names, -1 for the others; flag holds MESH_DECIMATE_NONFINITE and / or MESH_DECIMATE_RANGE
+    when such a vertex has a non-finite coordinate or a cell index outside [-2^20, 2^20).  F == 0 or V == 0 launches
+    nothing."""
+    what = "mesh_decimate_keys"
+    cell = _mesh_cell(cell, what)
+    _mesh_dev(verts, F32, (None, 3), what, "verts")
+    V = int(verts.shape[0])
+    F = _mesh_faces(faces, V, what)
+    keys = torch.full((V,), -1, dtype=I64, device=verts.device)
+    flag = torch.zeros((1,), dtype=I32, device=verts.device)
+    if F == 0 or V == 0:
+        return keys, flag
+    L = _lib.lib()
+    mark = torch.zeros((V,), dtype=U8, device=verts.device)
+    check(L.clmgs_mesh_decimate_mark(stream(), V, F, dptr(faces, I32), dptr(mark, U8)))
+    check(L.clmgs_mesh_decimate_keys(stream(), V, dptr(verts, F32), dptr(mark, U8), cell, dptr(keys, I64), dptr(flag, I32)))
+    return keys, flag
+
+
+@torch.no_grad()
+def mesh_decimate_faces(faces, cluster, C):
+    """The face pass (csrc/mesh_decimate.hip): faces int32 [F,3], cluster int32 [V] (the new index of every vertex a face
+    names), C clusters -> (rotated int32 [F,3], collapsed uint8 [F], inc int64 [3F]): the corners' clusters with the smallest
+    first and the orientation kept, 1 where two corners share a cluster, and per face one (cluster << 32 | face) for every
+    distinct cluster among its corners, INT64_MAX in the unused slots."""
+    what = "mesh_decimate_faces"
+    _mesh_dev(cluster, I32, (None,), what, "cluster")
+    V = int(cluster.shape[0])
+    F = _mesh_faces(faces, V, what)
+    if isinstance(C, bool) or int(C) != C or not 1 <= C <= V:
+        raise ValueError(f"{what}: C must be an integer in [1, {V}], got {C!r}")
+    C = int(C)
+    dev = faces.device
+    rotated = torch.empty((F, 3), dtype=I32, device=dev)
+    collapsed = torch.empty((F,), dtype=U8, device=dev)
+    inc = torch.empty((3 * F,), dtype=I64, device=dev)
+    if F:
+        check(_lib.lib().clmgs_mesh_decimate_faces(stream(), V, F, C, dptr(faces, I32), dptr(cluster, I32),
+                                                   dptr(rotated, I32), dptr(collapsed, U8), dptr(inc, I64)))
+    return rotated, collapsed, inc
+
+
+@torch.no_grad()
+def mesh_decimate_place(verts, colours, faces, cluster_keys, vert_order, vert_start, inc, inc_start, lane_order, cell):
+    """The placement kernel (csrc/mesh_decimate.hip), one lane per cluster: cluster_keys int64 [C] ascending, vert_order
+    int32 [M] the participating vertices by cluster then index, vert_start int64 [C+1], inc int64 [I] the incidences of
+    mesh_decimate_faces sorted ascending, inc_start int64 [C+1] their segments, lane_order int32 [C] the permutation of the
+    clusters in which the lanes take them (it changes the speed, not one bit of the output) -> (verts float32 [C,3], colours uint8 [C,3], code uint8 [C]); code 0 =
+    the quadric's minimiser, 1 = the mean (degenerate quadric), 2 = the mean (minimiser outside)."""
+    what = "mesh_decimate_place"
+    cell = _mesh_cell(cell, what)
+    _mesh_dev(verts, F32, (None, 3), what, "verts")
+    V = int(verts.shape[0])
+    _mesh_dev(colours, U8, (V, 3), what, "colours")
+    F = _mesh_faces(faces, V, what)
+    _mesh_dev(cluster_keys, I64, (None,), what, "cluster_keys")
+    C = int(cluster_keys.shape[0])
+    _mesh_dev(vert_order, I32, (None,), what, "vert_order")
+    _mesh_dev(vert_start, I64, (C + 1,), what, "vert_start")
+    _mesh_dev(inc, I64, (None,), what, "inc")
+    _mesh_dev(inc_start, I64, (C + 1,), what, "inc_start")
+    _mesh_dev(lane_order, I32, (C,), what, "lane_order")
+    dev = verts.device
+    out_verts = torch.empty((C, 3), dtype=F32, device=dev)
+    out_colours = torch.empty((C, 3), dtype=U8, device=dev)
+    code = torch.empty((C,), dtype=U8, device=dev)
+    if C:
+        check(_lib.lib().clmgs_mesh_decimate_place(
+            stream(), V, F, C, dptr(verts, F32), dptr(colours, U8), dptr(faces, I32), dptr(cluster_keys, I64),
+            dptr(vert_order, I32), dptr(vert_start, I64), int(vert_order.shape[0]), dptr(inc, I64), dptr(inc_start, I64),
+            int(inc.shape[0]), dptr(lane_order, I32), cell, dptr(out_verts, F32), dptr(out_colours, U8), dptr(code, U8)))
+    return out_verts, out_colours, code
+
+
 # ------------------------------------------------------------ MCMC densification
 def _f32_dev(t, shape, what):
     assert t.is_cuda and t.dtype == F32 and t.is_contiguous() and tuple(t.shape) == tuple(shape), \

@@ -1,6 +1,8 @@
 """Mesh cleanup ("Mesh cleanup"): drops the small connected components of a triangle mesh.
 
-    python -m clm_gs_amd.clean_mesh -i <mesh.ply> -o <out.ply> [--min_faces N] [--keep_largest K]
+    python -m clm_gs_amd.clean_mesh -i <mesh.ply> -o <out.ply> [--min_faces N] [--keep_largest K] [--decimate_cell C]
+
+(--decimate_cell: mesh_decimate.decimate after the two filters, or alone; DESIGN.md section 3, "Mesh decimation".)
 
 The components are labelled on the device (clm_kernels.mesh_components / mesh_component_faces, csrc/mesh.hip): two vertices
 are connected when a face names both, a component's label is its smallest vertex index and its size its number of faces.
@@ -92,24 +94,33 @@ def json_path(mesh_path):
 
 
 def main(argv=None):
+    from . import mesh_decimate
     ap = argparse.ArgumentParser(prog="clm_gs_amd.clean_mesh",
-                                 description="drop the small connected components of a mesh written by clm_gs_amd.mesh_model")
+                                 description="drop the small connected components of a mesh written by clm_gs_amd.mesh_model, "
+                                             "and / or decimate it")
     ap.add_argument("-i", "--input", required=True, help="the mesh (.ply as io_ply.save_mesh_ply writes it)")
     ap.add_argument("-o", "--output", required=True, help="the cleaned mesh; <output>.json is written when <input>.json exists")
     ap.add_argument("--min_faces", type=int, default=0, metavar="N", help="drop the components with fewer than N faces")
     ap.add_argument("--keep_largest", type=int, default=0, metavar="K", help="keep only the K components with the most faces")
+    ap.add_argument("--decimate_cell", type=float, default=0.0, metavar="C",
+                    help="after the two filters, merge the vertices of every cell of C world units (mesh_decimate.decimate)")
     a = ap.parse_args(argv)
     try:  # refusals before anything is read
         check_options(a.min_faces, a.keep_largest)
-        if a.min_faces == 0 and a.keep_largest == 0:
-            raise ValueError("nothing to do: give --min_faces N or --keep_largest K")
+        mesh_decimate.check_cell(a.decimate_cell)
+        if a.min_faces == 0 and a.keep_largest == 0 and a.decimate_cell == 0:
+            raise ValueError("nothing to do: give --min_faces N, --keep_largest K or --decimate_cell C")
     except ValueError as e:
         raise SystemExit(str(e))
     from . import io_ply
     t0 = time.perf_counter()
     verts, colours, faces = (torch.from_numpy(t).to("cuda") for t in io_ply.load_mesh_ply(a.input))
     V, F = int(verts.shape[0]), int(faces.shape[0])
-    verts, colours, faces, report = clean(verts, colours, faces, a.min_faces, a.keep_largest)
+    try:
+        verts, colours, faces, report = clean(verts, colours, faces, a.min_faces, a.keep_largest)
+        verts, colours, faces, decimation = mesh_decimate.decimate(verts, colours, faces, a.decimate_cell)
+    except ValueError as e:  # (a cell too small for the mesh's extent)
+        raise SystemExit(str(e))
     d = os.path.dirname(a.output)
     if d:
         os.makedirs(d, exist_ok=True)
@@ -117,11 +128,16 @@ def main(argv=None):
     if os.path.exists(json_path(a.input)):
         with open(json_path(a.input)) as f:
             meta = json.load(f)
+        if report is not None:
+            meta = json_record(meta, a.min_faces, a.keep_largest, report, verts.shape[0], faces.shape[0])
+        if decimation is not None:
+            meta = mesh_decimate.json_record(meta, decimation, verts.shape[0], faces.shape[0])
         with open(json_path(a.output), "w") as f:
-            json.dump(json_record(meta, a.min_faces, a.keep_largest, report, verts.shape[0], faces.shape[0]), f, indent=1)
-    print("mesh cleanup: components {} kept {} vertices {} -> {} faces {} -> {} rounds {} in {:.3f} s -> {}".format(
-        report["components"], report["components_kept"], V, int(verts.shape[0]), F, int(faces.shape[0]), report["rounds"],
-        time.perf_counter() - t0, a.output))
+            json.dump(meta, f, indent=1)
+    print("mesh cleanup:{} vertices {} -> {} faces {} -> {}{}{} in {:.3f} s -> {}".format(
+        "" if report is None else " components {} kept {}".format(report["components"], report["components_kept"]),
+        V, int(verts.shape[0]), F, int(faces.shape[0]), "" if report is None else " rounds {}".format(report["rounds"]),
+        "" if decimation is None else mesh_decimate.log_words(decimation), time.perf_counter() - t0, a.output))
     return 0
 
 

@@ -3,7 +3,8 @@
     python -m clm_gs_amd.mesh_model -m <model dir | .ply | .vq.npz> -s <colmap dir> -o <mesh.ply> --voxel V
         [--trunc_voxels 4] [--bounds emin nmin umin emax nmax umax] [--up X Y Z] [--east X Y Z] [--every K] [-r R]
         [--alpha_min 0.5] [--depth_max D] [--min_weight 2] [--grid_gb 16] [--antialiased] [--undistort --undistort_zoom Z]
-        [--depth_mode expected|median] [--min_component_faces N] [--keep_components K] [--sparse] [--eval]
+        [--depth_mode expected|median] [--min_component_faces N] [--keep_components K] [--sparse] [--decimate_cell C]
+        [--eval]
         [--clm_offload | --naive_offload | --no_offload]
 
 renders every selected training camera of the scene through the strategy's own eval entry (render_mode "RGB+ED":
@@ -25,6 +26,10 @@ mark the bricks and once to fuse, and mesh.ply is byte for byte the file the den
 dense limits (2^31 voxels, 24 B per voxel under --grid_gb) give way to a brick grid of at most 2^30 bricks, 2^31 STORED
 voxels and marks + table + pool under --grid_gb.  The .json gains "sparse" and the log line the brick counts, the pool's GB
 and the marking rate.  Without the flag every file is what it was.
+--decimate_cell C merges, after the cleanup, the vertices of every cell of C world units into one, placed by the quadric of
+the faces that touch the cell (mesh_decimate.decimate, csrc/mesh_decimate.hip; DESIGN.md section 3, "Mesh decimation"); the
+.json gains "decimation" (the report) and the log line " decimated V -> V' vertices F -> F' faces cell C".  A negative or
+non-finite value is refused by name; 0, the default, changes nothing.  The decimated mesh need not be a manifold.
 """
 import argparse
 import json
@@ -34,7 +39,7 @@ import time
 
 import torch
 
-from . import io_ply, mesh_clean, tsdf, utils
+from . import io_ply, mesh_clean, mesh_decimate, tsdf, utils
 from .render_ortho import map_frame, percentile_sorted
 from .render_trajectory import _find_ply, depth_render_mode, eval_one_cam
 
@@ -58,14 +63,17 @@ def json_path(mesh_path):
 @torch.no_grad()
 def build_mesh(gaussians, cameras, args, out_path, voxel, frame=None, bounds=None, trunc_voxels=4.0, every=1, alpha_min=0.5,
                depth_max=None, min_weight=2.0, grid_gb=16.0, near=0.01, background=None, log=None, depth_mode="expected",
-               min_component_faces=0, keep_components=0, sparse=False):
+               min_component_faces=0, keep_components=0, sparse=False, decimate_cell=0.0):
     """Renders cameras[::every] from `gaussians` through the eval entry of the strategy `args` names, fuses them, extracts
     and writes out_path and its .json.  -> the dict written to the .json.  The global image size (utils.set_img_size)
     must be the cameras' size.  depth_mode "expected" fuses the "RGB+ED" depth, "median" the "RGB+MD" one (the .json gains
     "depth_mode" only then).  min_component_faces / keep_components: mesh_clean.clean between the extraction and the file
     (the .json gains "cleanup" and the log line its component counts only when one of them is on).  sparse: the
     brick-allocated volume; every camera is rendered twice, to mark and to fuse (the eval forward is deterministic: see
-    DESIGN.md section 3, "Sparse volume"), and the .json gains "sparse"."""
+    DESIGN.md section 3, "Sparse volume"), and the .json gains "sparse".  decimate_cell: mesh_decimate.decimate after the
+    cleanup, which sees the full-resolution mesh (the .json gains "decimation" and the log line its counts only when it is
+    on)."""
+    decimate_cell = mesh_decimate.check_cell(decimate_cell)
     min_component_faces, keep_components = mesh_clean.check_options(min_component_faces, keep_components,
                                                                     ("--min_component_faces", "--keep_components"))
     render_mode = depth_render_mode(depth_mode)
@@ -108,6 +116,7 @@ def build_mesh(gaussians, cameras, args, out_path, voxel, frame=None, bounds=Non
     torch.cuda.synchronize()
     t_extract = time.perf_counter() - t0
     verts, colours, faces, report = mesh_clean.clean(verts, colours, faces, min_component_faces, keep_components)
+    verts, colours, faces, decimation = mesh_decimate.decimate(verts, colours, faces, decimate_cell)
     d = os.path.dirname(out_path)
     if d:
         os.makedirs(d, exist_ok=True)
@@ -124,24 +133,28 @@ def build_mesh(gaussians, cameras, args, out_path, voxel, frame=None, bounds=Non
         meta["sparse"] = dict(bricks=volume.S, bricks_total=volume.bricks_total, pool_gb=volume.S * tsdf.BYTES_PER_BRICK / 1e9)
     if report is not None:
         meta = mesh_clean.json_record(meta, min_component_faces, keep_components, report, verts.shape[0], faces.shape[0])
+    if decimation is not None:
+        meta = mesh_decimate.json_record(meta, decimation, verts.shape[0], faces.shape[0])
     with open(json_path(out_path), "w") as f:
         json.dump(meta, f, indent=1)
     log.write("mesh export: grid {} x {} x {} voxel {:g} cameras {} render {:.1f} cameras/s integration {:.1f} cameras/s "
-              "extraction {:.3f} s vertices {} faces {}{}{} -> {}\n".format(
+              "extraction {:.3f} s vertices {} faces {}{}{}{} -> {}\n".format(
                   volume.nx, volume.ny, volume.nz, volume.voxel, len(cams), len(cams) / max(t_render, 1e-9),
                   len(cams) / max(t_fuse, 1e-9), t_extract, meta["vertices"], meta["faces"],
                   "" if report is None else " components {} kept {}".format(report["components"], report["components_kept"]),
                   "" if not sparse else " sparse bricks {} of {} pool {:.3f} GB marking {:.1f} cameras/s".format(
                       volume.S, volume.bricks_total, meta["sparse"]["pool_gb"], len(cams) / max(t_mark, 1e-9)),
+                  "" if decimation is None else mesh_decimate.log_words(decimation),
                   out_path))
     return meta
 
 
 def check_options(voxel, bounds=None, grid_gb=16.0, trunc_voxels=4.0, min_weight=2.0, every=1, depth_mode="expected",
-                  min_component_faces=0, keep_components=0, sparse=False):
+                  min_component_faces=0, keep_components=0, sparse=False, decimate_cell=0.0):
     """The refusals that need nothing loaded (ValueError by name); with sparse the brick-grid limits take the place of the
     dense ones."""
     mesh_clean.check_options(min_component_faces, keep_components, ("--min_component_faces", "--keep_components"))
+    mesh_decimate.check_cell(decimate_cell)
     tsdf.grid_shape((0, 0, 0, 1, 1, 1), voxel)  # (--voxel alone)
     depth_render_mode(depth_mode)
     if not trunc_voxels > 0:
@@ -182,6 +195,9 @@ def main(argv=None):
                     help="drop the connected components of the mesh with fewer than N faces")
     ap.add_argument("--keep_components", type=int, default=0, metavar="K",
                     help="keep only the K connected components with the most faces")
+    ap.add_argument("--decimate_cell", type=float, default=0.0, metavar="C",
+                    help="decimate the mesh before it is written: merge the vertices of every cell of C world units "
+                         "(quadric vertex clustering, after the cleanup); 0 = off")
     ap.add_argument("--sparse", action="store_true",
                     help="a brick-allocated volume: the same mesh.ply, on boxes far beyond 2^31 voxels (renders every camera twice)")
     ap.add_argument("--antialiased", action="store_true", help="for a model trained with trainer --antialiased")
@@ -195,7 +211,7 @@ def main(argv=None):
     a = ap.parse_args(argv)
     try:  # refusals before anything is loaded or written
         check_options(a.voxel, a.bounds, a.grid_gb, a.trunc_voxels, a.min_weight, a.every, a.depth_mode,
-                      a.min_component_faces, a.keep_components, a.sparse)
+                      a.min_component_faces, a.keep_components, a.sparse, a.decimate_cell)
         frame = map_frame(a.up, a.east)
     except ValueError as e:
         raise SystemExit(str(e))
@@ -225,7 +241,8 @@ def main(argv=None):
     try:
         build_mesh(gaussians, cams, args, a.output, a.voxel, frame, a.bounds, a.trunc_voxels, a.every, a.alpha_min,
                    a.depth_max, a.min_weight, a.grid_gb, depth_mode=a.depth_mode,
-                   min_component_faces=a.min_component_faces, keep_components=a.keep_components, sparse=a.sparse)
+                   min_component_faces=a.min_component_faces, keep_components=a.keep_components, sparse=a.sparse,
+                   decimate_cell=a.decimate_cell)
     except ValueError as e:  # (the size of a grid whose bounds come from the model)
         raise SystemExit(str(e))
     return 0

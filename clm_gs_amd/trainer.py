@@ -336,13 +336,17 @@ def mesh_rules(args):
     try:  # (refused with and without --mesh_voxel)
         from .mesh_clean import check_options as check_components
         check_components(*components, names=("--mesh_min_component_faces", "--mesh_keep_components"))
+        from .mesh_decimate import check_cell
+        decimate_cell = check_cell(getattr(args, "mesh_decimate_cell", 0.0), "--mesh_decimate_cell")
     except ValueError as e:
         return [(True, str(e))]
     if not voxel:
         return ([] if depth_mode is None else [(True, f"--mesh_depth_mode {depth_mode} has effect only with --mesh_voxel: "
                                                        "give both, or neither")]) + \
             ([(True, "--mesh_sparse has effect only with --mesh_voxel: give both, or neither")]
-             if getattr(args, "mesh_sparse", False) else [])
+             if getattr(args, "mesh_sparse", False) else []) + \
+            ([(True, "--mesh_decimate_cell has effect only with --mesh_voxel: give both, or neither")]
+             if decimate_cell else [])
     from .mesh_model import check_options
     try:
         check_options(voxel, None, getattr(args, "mesh_grid_gb", 16.0), getattr(args, "mesh_trunc_voxels", 4.0),
@@ -837,7 +841,8 @@ def train_from_colmap(source_path, model_path, strategy="clm_offload", iteration
                                depth_mode=getattr(args, "mesh_depth_mode", None) or "expected",
                                min_component_faces=getattr(args, "mesh_min_component_faces", 0),
                                keep_components=getattr(args, "mesh_keep_components", 0),
-                               sparse=bool(getattr(args, "mesh_sparse", False)))
+                               sparse=bool(getattr(args, "mesh_sparse", False)),
+                               decimate_cell=getattr(args, "mesh_decimate_cell", 0.0))
             for row in SIDE_MODELS:
                 if getattr(scene, row.name) is not None:
                     getattr(scene, row.name).save_to(model_path, scene.train_cameras)
@@ -937,6 +942,8 @@ OPTIONS = (
          "most faces; 0 = off"),
     _opt("--mesh_sparse", action="store_true", help="--mesh_voxel: the brick-allocated volume (mesh_model --sparse): the same "
          "mesh.ply, on boxes beyond the dense volume's 2^31 voxels; renders every camera twice"),
+    _opt("--mesh_decimate_cell", type=float, metavar="C", help="--mesh_voxel: decimate the mesh before it is written: merge "
+         "the vertices of every cell of C world units (quadric vertex clustering, clm_gs_amd.mesh_decimate); 0 = off"),
 )
 
 

@@ -1083,6 +1083,43 @@ int clmgs_mesh_hook(void* stream, int V, int F, const int32_t* faces, int32_t* p
 int clmgs_mesh_shortcut(void* stream, int V, int32_t* parent, int32_t* flag);
 int clmgs_mesh_component_faces(void* stream, int V, int F, const int32_t* faces, const int32_t* labels, int32_t* count);
 
+/* ---- mesh decimation (csrc/mesh_decimate.hip, csrc/decimate_math.h; clm_gs_amd/mesh_decimate.py): vertex clustering on a
+ * world-aligned grid of `cell` units with quadric-error representatives; DESIGN.md section 3, "Mesh decimation".  verts
+ * float32 [V,3], colours uint8 [V,3], faces int32 [F,3] on the device, 1 <= V < 2^31, 1 <= F < 2^31, cell > 0 and finite.
+ * The sorts, prefix sums and compactions between the entries are the caller's.
+ *  - clmgs_mesh_decimate_mark stores 1 to mark[v] (uint8 [V], zeroed by the caller) for every vertex a face names.
+ *  - clmgs_mesh_decimate_keys writes keys int64 [V]: for a marked vertex ((i + 2^20) << 42) | ((j + 2^20) << 21) |
+ *    (k + 2^20) with (i, j, k) = floor(double(x) / cell) per axis, -1 for an unmarked one.  A marked vertex with a
+ *    non-finite coordinate ORs 1 into *flag (device int32, zeroed by the caller), one with an index outside
+ *    [-2^20, 2^20) ORs 2; their keys are -1.
+ *  - clmgs_mesh_decimate_faces maps every face through cluster int32 [V] (the rank of a vertex's key among the C distinct
+ *    keys; unmarked vertices are never read): out_faces int32 [F,3] the three clusters rotated so that the smallest comes
+ *    first, collapsed uint8 [F] 1 when two of them are equal, inc int64 [3F] one entry (cluster << 32 | face) per
+ *    DISTINCT cluster among the corners and INT64_MAX in the unused slots.
+ *  - clmgs_mesh_decimate_place, one lane per cluster, forms the output vertex of each of the C clusters.  lane_order int32
+ *    [C] is a permutation of the clusters: lane t of the launch takes cluster lane_order[t].  Any permutation gives the
+ *    same output; one that puts clusters whose vertices are neighbours in memory on neighbouring lanes is faster.
+ *    cluster_keys int64 [C] ascending; vert_order int32 [n_members] the marked vertices ordered by cluster then index and
+ *    vert_start int64 [C + 1] the segments of that list; inc int64 [n_inc] the used incidences sorted ascending
+ *    (cluster, then face) and inc_start int64 [C + 1] their segments.  It sums in float64 without
+ *    contraction, in list order, solves
+ *    (A + mu I) x = r + mu m by the adjugate and writes out_verts float32 [C,3], out_colours uint8 [C,3] (the channel
+ *    means, rounded half up, in integers) and code uint8 [C]: 0 the quadric's minimiser, 1 the mean because the quadric is
+ *    degenerate, 2 the mean because the minimiser lies more than `cell` from the cell's centre along an axis.
+ * Every entry returns CLMGS_EINVAL, before anything is launched, for a size outside its range, a bad cell, a null or
+ * misaligned pointer, and outputs that overlap an input or each other.  An index read from memory that lies outside its
+ * array is skipped by every kernel. */
+int clmgs_mesh_decimate_mark(void* stream, int V, int F, const int32_t* faces, uint8_t* mark);
+int clmgs_mesh_decimate_keys(void* stream, int V, const float* verts, const uint8_t* mark, double cell, int64_t* keys,
+                             int32_t* flag);
+int clmgs_mesh_decimate_faces(void* stream, int V, int F, int C, const int32_t* faces, const int32_t* cluster,
+                              int32_t* out_faces, uint8_t* collapsed, int64_t* inc);
+int clmgs_mesh_decimate_place(void* stream, int V, int F, int C, const float* verts, const uint8_t* colours,
+                              const int32_t* faces, const int64_t* cluster_keys, const int32_t* vert_order,
+                              const int64_t* vert_start, int64_t n_members, const int64_t* inc, const int64_t* inc_start,
+                              int64_t n_inc, const int32_t* lane_order, double cell, float* out_verts, uint8_t* out_colours,
+                              uint8_t* code);
+
 /* ---- pinned host memory  (numba.cuda.pinned_array at clm_offload/gaussian_model.py:34-44) */
 void* clmgs_pinned_alloc(size_t bytes);
 int clmgs_pinned_free(void* p);
