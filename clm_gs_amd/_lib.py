@@ -58,6 +58,8 @@ SIGNATURES = {
     # median depth: per pixel the depth and row of the entry at which T falls through one half
     "clmgs_rasterize_median_pack_bytes": (_sz, [_i, _i]),
     "clmgs_rasterize_median": (_i, [_vp, _i, _i, _i64, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    # ray depth: per pixel the depth at which the median Gaussian's 3-D density peaks along the pixel's ray
+    "clmgs_ray_depth": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _d, _i, _vp]),
     "clmgs_rasterize4_fwd": (_i, [_vp, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "clmgs_rasterize4_bwd": (_i, [_vp, _i, _i, _i64, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     # four channels on the slot route and in the device-count forms: the argument lists of the 3-channel entries

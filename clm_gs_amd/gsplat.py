@@ -706,3 +706,51 @@ def rasterize_median_depth(means2d, conics, opacities, depths, image_width, imag
         int(tile_size), tw, th, dptr(offsets, I32), dptr(fids, I32), dptr(packed), dptr(median_depth, F32),
         dptr(median_ids, I32)))
     return median_depth, median_ids
+
+
+# ------------------------------------------------------------------ ray depth
+RAY_CAMERA_MODELS = {"pinhole": 0, "ortho": 1}
+
+
+def ray_camera_table(viewmats, Ks):
+    """viewmats [C,4,4], Ks [C,3,3] -> the float64 [C,16] table csrc/ray_depth.hip reads: per camera the top 3x4 of the view
+    matrix (row-major), then fx, fy, cx, cy.  Made on the device, nothing is read back."""
+    C = viewmats.shape[0]
+    return torch.cat([viewmats[:, :3, :4].reshape(C, 12), Ks[:, 0, 0:1], Ks[:, 1, 1:2], Ks[:, 0, 2:3], Ks[:, 1, 2:3]],
+                     dim=1).to(torch.float64).contiguous()
+
+
+@torch.no_grad()
+def ray_gaussian_depth(means, quats, scales, viewmats, Ks, median_depth, median_ids, near_plane=0.01,
+                       camera_model="pinhole"):
+    """The ray-Gaussian intersection depth of RaDe-GS / GOF for each pixel's median Gaussian (csrc/ray_depth.hip,
+    csrc/ray_math.h; DESIGN.md section 3, "Ray depth"): the depth of the point on the pixel's ray at which that Gaussian's
+    3-D density is largest,  t* = d^T S^-1 (m - o) / d^T S^-1 d,  where rasterize_median_depth reports its centre depth.
+    means [N,3], quats [N,4] (w,x,y,z; normalised inside), scales [N,3] (ACTIVATED), viewmats [C,4,4], Ks [C,3,3] as
+    fully_fused_projection takes them; median_depth float32 [C,H,W] and median_ids int32 [C,H,W] (the row within its camera)
+    as rasterize_median_depth returns them.  The ray of pixel (x, y): u = (x + 0.5 - cx) / fx, v = (y + 0.5 - cy) / fy;
+    "pinhole": origin 0, direction (u, v, 1); "ortho" (K in pixels per world unit): origin (u, v, 0), direction (0, 0, 1) --
+    in both the parameter t is a camera z-depth.  Computed in float64 from the float32 inputs, every operation rounded on
+    its own (bit-reproducible; tests/ray_depth_reference.py restates it).
+    -> ray_depth float32 [C,H,W]: (float32) t* where t* is finite and > near_plane; else median_depth of the pixel, copied
+    (a zero scale, a maximum behind the near plane, non-finite inputs); 0.0 where the id lies outside [0, N).
+    Not differentiable: runs under no_grad, inputs that require grad are detached."""
+    if camera_model not in RAY_CAMERA_MODELS:
+        raise ValueError(f"camera_model must be 'pinhole' or 'ortho', got {camera_model!r}")
+    L = _lib.lib()
+    means, quats, scales, median_depth, median_ids = (t.detach().contiguous() for t in (means, quats, scales, median_depth,
+                                                                                        median_ids))
+    N = int(means.shape[0])
+    C, H, W = (int(v) for v in median_ids.shape)
+    if tuple(median_depth.shape) != (C, H, W) or tuple(viewmats.shape) != (C, 4, 4) or tuple(Ks.shape) != (C, 3, 3):
+        raise ValueError(f"ray_gaussian_depth: median_depth {tuple(median_depth.shape)}, viewmats {tuple(viewmats.shape)} and Ks "
+                         f"{tuple(Ks.shape)} do not match median_ids {tuple(median_ids.shape)}")
+    if tuple(quats.shape) != (N, 4) or tuple(scales.shape) != (N, 3) or tuple(means.shape) != (N, 3):
+        raise ValueError(f"ray_gaussian_depth: means [N,3], quats [N,4] and scales [N,3] expected, got {tuple(means.shape)}, "
+                         f"{tuple(quats.shape)} and {tuple(scales.shape)}")
+    cams = ray_camera_table(viewmats.detach(), Ks.detach())
+    out = torch.empty((C, H, W), dtype=F32, device=median_ids.device)
+    check(L.clmgs_ray_depth(stream(), C, N, H, W, dptr(means, F32), dptr(quats, F32), dptr(scales, F32),
+                            dptr(cams, torch.float64), dptr(median_ids, I32), dptr(median_depth, F32), float(near_plane),
+                            RAY_CAMERA_MODELS[camera_model], dptr(out, F32)))
+    return out

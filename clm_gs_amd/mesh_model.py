@@ -3,7 +3,7 @@
     python -m clm_gs_amd.mesh_model -m <model dir | .ply | .vq.npz> -s <colmap dir> -o <mesh.ply> --voxel V
         [--trunc_voxels 4] [--bounds emin nmin umin emax nmax umax] [--up X Y Z] [--east X Y Z] [--every K] [-r R]
         [--alpha_min 0.5] [--depth_max D] [--min_weight 2] [--grid_gb 16] [--antialiased] [--undistort --undistort_zoom Z]
-        [--depth_mode expected|median] [--min_component_faces N] [--keep_components K] [--sparse] [--decimate_cell C]
+        [--depth_mode expected|median|ray] [--min_component_faces N] [--keep_components K] [--sparse] [--decimate_cell C]
         [--eval]
         [--clm_offload | --naive_offload | --no_offload]
 
@@ -15,7 +15,10 @@ and, next to it, <mesh>.json: frame, bounds, voxel, truncation, grid, counts and
 --grid_gb or 2^31 voxels are refused by name (with the voxel size that fits) before anything is loaded or written.
 --depth_mode median fuses the median depth (render_mode "RGB+MD": the depth of the Gaussian at which the transmittance
 falls through one half; DESIGN.md section 3, "Median depth") instead of the expected depth, which a translucent layer in
-front of a surface pulls forward; the .json then carries "depth_mode": "median".  An unknown mode is refused by name.
+front of a surface pulls forward; the .json then carries "depth_mode": "median".  --depth_mode ray fuses the ray depth (render_mode
+"RGB+RD": per pixel the depth at which that same Gaussian's 3-D density peaks along the pixel's ray, not the depth of its
+centre, which turns an obliquely seen flat splat into a fronto-parallel step; DESIGN.md section 3, "Ray depth"); the .json
+then carries "depth_mode": "ray".  An unknown mode is refused by name.
 --min_component_faces N and --keep_components K drop the small connected components of the extracted mesh on the device
 before it is written (mesh_clean.clean; DESIGN.md section 3, "Mesh cleanup"): those with fewer than N faces, and all but
 the K with the most faces; the .json then carries "cleanup" (the options and the report) and the log line the component
@@ -66,9 +69,9 @@ def build_mesh(gaussians, cameras, args, out_path, voxel, frame=None, bounds=Non
                min_component_faces=0, keep_components=0, sparse=False, decimate_cell=0.0):
     """Renders cameras[::every] from `gaussians` through the eval entry of the strategy `args` names, fuses them, extracts
     and writes out_path and its .json.  -> the dict written to the .json.  The global image size (utils.set_img_size)
-    must be the cameras' size.  depth_mode "expected" fuses the "RGB+ED" depth, "median" the "RGB+MD" one (the .json gains
-    "depth_mode" only then).  min_component_faces / keep_components: mesh_clean.clean between the extraction and the file
-    (the .json gains "cleanup" and the log line its component counts only when one of them is on).  sparse: the
+    must be the cameras' size.  depth_mode "expected" fuses the "RGB+ED" depth, "median" the "RGB+MD" one, "ray" the "RGB+RD"
+    one (the .json gains "depth_mode" only with these two).  min_component_faces / keep_components: mesh_clean.clean
+    between the extraction and the file (the .json gains "cleanup" and the log line its component counts only when one of them is on).  sparse: the
     brick-allocated volume; every camera is rendered twice, to mark and to fuse (the eval forward is deterministic: see
     DESIGN.md section 3, "Sparse volume"), and the .json gains "sparse".  decimate_cell: mesh_decimate.decimate after the
     cleanup, which sees the full-resolution mesh (the .json gains "decimation" and the log line its counts only when it is
@@ -127,8 +130,8 @@ def build_mesh(gaussians, cameras, args, out_path, voxel, frame=None, bounds=Non
                 grid=[volume.nx, volume.ny, volume.nz], min_weight=float(min_weight), alpha_min=float(alpha_min),
                 depth_max=None if depth_max == float("inf") else depth_max, vertices=int(verts.shape[0]),
                 faces=int(faces.shape[0]), cameras=len(cams), camera_names=[str(c.image_name) for c in cams])
-    if depth_mode == "median":
-        meta["depth_mode"] = "median"
+    if depth_mode in ("median", "ray"):
+        meta["depth_mode"] = depth_mode
     if sparse:
         meta["sparse"] = dict(bricks=volume.S, bricks_total=volume.bricks_total, pool_gb=volume.S * tsdf.BYTES_PER_BRICK / 1e9)
     if report is not None:
@@ -188,8 +191,9 @@ def main(argv=None):
     ap.add_argument("--depth_max", type=float, default=None, help="pixels deeper than this are not fused")
     ap.add_argument("--min_weight", type=float, default=2.0, help="a voxel counts when at least this many cameras observed it")
     ap.add_argument("--grid_gb", type=float, default=16.0, help="the largest grid allocated (24 B per voxel)")
-    ap.add_argument("--depth_mode", default="expected", metavar="expected|median",
-                    help="the depth map fused: the expected depth D / alpha, or the median depth (the Gaussian at which "
+    ap.add_argument("--depth_mode", default="expected", metavar="expected|median|ray",
+                    help="the depth map fused: the expected depth D / alpha, the ray depth (where the median Gaussian's "
+                         "density peaks along the pixel's ray), or the median depth (the Gaussian at which "
                          "the transmittance falls through one half)")
     ap.add_argument("--min_component_faces", type=int, default=0, metavar="N",
                     help="drop the connected components of the mesh with fewer than N faces")

@@ -4,7 +4,7 @@ perspective lean -- with the matching elevation raster.
 
     python -m clm_gs_amd.render_ortho -m <model dir | .ply> --clm_offload --gsd 0.05 [--bounds emin nmin emax nmax]
         [--up X Y Z] [--east X Y Z] [--camera_height H] [--tile 4096] [--output_dir DIR] [--antialiased] [--white_background]
-        [--depth_mode expected|median]
+        [--depth_mode expected|median|ray]
 
 Map frame: u = --up (default 0 0 1), e = --east projected onto the plane perpendicular to u (default 1 0 0; 0 1 0 if that
 is parallel to u), n = u x e.  The camera's rows are x = e, y = -n, z = -u: it looks straight down and image row 0 is
@@ -18,7 +18,9 @@ Outputs in --output_dir: ortho.png (8-bit RGB), ortho_height.npy (float32 [H,W]:
 where alpha < 0.5), ortho_alpha.npy (float32 [H,W]) and ortho.json (origin, east, north, up, gsd, width, height,
 camera_height).  --depth_mode median: the height map is camera_height - median depth (render_mode "RGB+MD": the depth of
 the Gaussian at which the transmittance falls through one half, which a translucent layer above the ground does not pull
-up) under the same alpha < 0.5 -> NaN rule, and ortho.json gains "depth_mode": "median"."""
+up) under the same alpha < 0.5 -> NaN rule, and ortho.json gains "depth_mode": "median".  --depth_mode ray: camera_height -
+ray depth (render_mode "RGB+RD": the depth at which that same Gaussian's 3-D density peaks along the pixel's vertical ray,
+so a tilted flat splat gives a slope, not a terrace) under the same rule; ortho.json gains "depth_mode": "ray"."""
 import argparse
 import json
 import math
@@ -189,7 +191,7 @@ def window_sees_anything(camera, gaussians):
 
 def render_window(camera, gaussians, background, args, depth_mode="expected"):
     """One OrthoCamera (the global image size must be its size) -> (image[3,h,w], expected depth[h,w], alpha[h,w]) on the
-    GPU (depth_mode "median": the median depth); a window that sees no Gaussian is background, depth 0 and alpha 0."""
+    GPU (depth_mode "median": the median depth, "ray": the ray depth); a window that sees no Gaussian is background, depth 0 and alpha 0."""
     h, w = camera.image_height, camera.image_width
     if not window_sees_anything(camera, gaussians):
         bg = background if background is not None else torch.zeros(3, device="cuda")
@@ -200,7 +202,7 @@ def render_window(camera, gaussians, background, args, depth_mode="expected"):
 
 
 def render_mosaic(gaussians, geometry, args, tile=4096, background=None, quantise=False, log=None, depth_mode="expected"):
-    """The whole map, window by window, assembled on the host (depth_mode "median": heights from the median depth).
+    """The whole map, window by window, assembled on the host (depth_mode "median" / "ray": heights from the median / ray depth).
     -> (rgb [H,W,3]: float32 as rendered, or uint8 (clamped, x255) with quantise -- a 20 000^2 map is 1.2 GB of uint8 --,
         height float32 [H,W]: camera_height - expected depth, NaN where alpha < 0.5, alpha float32 [H,W]).
     Windows are min(tile, size rounded up to 16) pixels on a side; the last row and column are rendered whole and
@@ -233,13 +235,13 @@ def render_mosaic(gaussians, geometry, args, tile=4096, background=None, quantis
 
 
 def write_outputs(output_dir, geometry, rgb_u8, height, alpha, depth_mode="expected"):
-    """(ortho.json carries "depth_mode" only when it is "median")"""
+    """(ortho.json carries "depth_mode" only when it is "median" or "ray")"""
     os.makedirs(output_dir, exist_ok=True)
     write_png(os.path.join(output_dir, "ortho.png"), rgb_u8)
     np.save(os.path.join(output_dir, "ortho_height.npy"), height.astype(np.float32))
     np.save(os.path.join(output_dir, "ortho_alpha.npy"), alpha.astype(np.float32))
     with open(os.path.join(output_dir, "ortho.json"), "w") as f:
-        json.dump(dict(geometry.to_json(), **({"depth_mode": "median"} if depth_mode == "median" else {})), f, indent=1)
+        json.dump(dict(geometry.to_json(), **({"depth_mode": depth_mode} if depth_mode in ("median", "ray") else {})), f, indent=1)
 
 
 def main(argv=None):
@@ -258,8 +260,9 @@ def main(argv=None):
     ap.add_argument("--white_background", action="store_true")
     ap.add_argument("--antialiased", action="store_true",
                     help="gsplat's rasterize_mode=\"antialiased\": for a model trained with trainer --antialiased")
-    ap.add_argument("--depth_mode", default="expected", metavar="expected|median",
-                    help="the depth behind the height map: the expected depth D / alpha, or the median depth (the Gaussian "
+    ap.add_argument("--depth_mode", default="expected", metavar="expected|median|ray",
+                    help="the depth behind the height map: the expected depth D / alpha, the ray depth (where the median "
+                         "Gaussian's density peaks along the pixel's ray), or the median depth (the Gaussian "
                          "at which the transmittance falls through one half)")
     g = ap.add_mutually_exclusive_group()
     g.add_argument("--clm_offload", action="store_true")

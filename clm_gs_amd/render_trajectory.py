@@ -7,13 +7,15 @@ training) and is written as an 8-bit PNG.
 
     python -m clm_gs_amd.render_trajectory -m <model dir | .ply> --clm_offload --n_frames 120 \
         --manual_height 30 --width 1920 --height 1080 [--output_dir DIR] [--hull x,y x,y ...] [--render_depth]
-        [--depth_mode expected|median]
+        [--depth_mode expected|median|ray]
 
 --render_depth: next to each frame_%05d.png, depth_%05d.npy (float32 [H,W], expected depth D / alpha) and
 depth_%05d.png (the same map in grey, normalised to its min / max over the pixels with alpha > 0.5).
 --depth_mode median (only with --render_depth; refused by name without it): the two files hold the median depth, the depth
 of the Gaussian at which the transmittance falls through one half (render mode "RGB+MD"; DESIGN.md section 3, "Median
-depth"), 0.0 where nothing is accumulated.
+depth"), 0.0 where nothing is accumulated.  --depth_mode ray (likewise): the ray depth, per pixel the depth at which that
+same Gaussian's 3-D density peaks along the pixel's ray, where the other two modes report the depth of its centre
+(render mode "RGB+RD"; DESIGN.md section 3, "Ray depth").
 
 `render_single_image` keeps the reference's signature and return value ([H,W,3] in [0,1] on the GPU).
 No imageio / PIL in this image: PNGs are written with zlib (8-bit RGB, no interlace).
@@ -100,11 +102,12 @@ def read_png(path):
 
 
 # --depth_mode of the command lines that render depth maps -> the render mode their eval entry is asked for
-DEPTH_MODES = {"expected": "RGB+ED", "median": "RGB+MD"}
+DEPTH_MODES = {"expected": "RGB+ED", "median": "RGB+MD", "ray": "RGB+RD"}
 
 
 def depth_render_mode(depth_mode, flag="--depth_mode"):
-    """"expected" (None: the default) -> "RGB+ED", "median" -> "RGB+MD"; anything else: ValueError naming the flag."""
+    """"expected" (None: the default) -> "RGB+ED", "median" -> "RGB+MD", "ray" -> "RGB+RD"; anything else: ValueError
+    naming the flag."""
     if depth_mode is None:
         return DEPTH_MODES["expected"]
     if depth_mode not in DEPTH_MODES:
@@ -154,7 +157,7 @@ def render_single_image(camera, gaussians, background, save_path, args, scene=No
     args.save_video (render_bigcity_images.py:638-722).  -> colors [H,W,3] on the GPU.
     depth_path: the same render also blends the depth channel ("RGB+ED"); the expected depth goes to
     depth_path + ".npy" (float32 [H,W]) and, in grey over the range of the pixels with alpha > 0.5, depth_path + ".png".
-    args.depth_mode "median": the median depth ("RGB+MD") instead."""
+    args.depth_mode "median": the median depth ("RGB+MD") instead; "ray": the ray depth ("RGB+RD")."""
     if depth_path:
         img, depth, alpha = eval_one_cam(camera, gaussians, background, args, scene,
                                          render_mode=depth_render_mode(getattr(args, "depth_mode", None)))
@@ -213,9 +216,10 @@ def main(argv=None):
     ap.add_argument("--save_video", action="store_true", help="skip the per-frame PNGs (no video writer in this image)")
     ap.add_argument("--render_depth", action="store_true",
                     help="also write depth_%%05d.npy (float32 expected depth) and depth_%%05d.png (grey) per frame")
-    ap.add_argument("--depth_mode", default=None, metavar="expected|median",
-                    help="with --render_depth: the expected depth D / alpha (default) or the median depth, the depth of the "
-                         "Gaussian at which the transmittance falls through one half")
+    ap.add_argument("--depth_mode", default=None, metavar="expected|median|ray",
+                    help="with --render_depth: the expected depth D / alpha (default), the median depth, the depth of the "
+                         "Gaussian at which the transmittance falls through one half, or the ray depth, the depth at which "
+                         "that Gaussian's density peaks along the pixel's ray")
     ap.add_argument("--antialiased", action="store_true",
                     help="gsplat's rasterize_mode=\"antialiased\": for a model trained with trainer --antialiased")
     ap.add_argument("--sky", action="store_true",

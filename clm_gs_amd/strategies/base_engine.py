@@ -8,7 +8,7 @@ from .. import utils
 from ..cameras import camera_loss_mask, camera_model as camera_model_of, camera_sky, check_sky_background, refuse_ortho
 from ..clm_kernels import apply_camera_colour, apply_camera_sky, camera_depth_term, fused_l1_ssim_loss, fused_ssim
 from ..gsplat import (fully_fused_projection, isect_offset_encode, isect_tiles,
-                      rasterize_median_depth, rasterize_to_pixels, spherical_harmonics, visibility_radii)
+                      rasterize_median_depth, rasterize_to_pixels, ray_gaussian_depth, spherical_harmonics, visibility_radii)
 
 LAMBDA_DSSIM = 0.2
 TILE_SIZE = 16
@@ -109,15 +109,17 @@ def torch_compiled_loss(image, image_gt_original, loss_mask=None, loss_mask_coun
     return loss_combined(image, image_gt, ssim_loss)
 
 
-RENDER_MODES = ("RGB", "RGB+D", "RGB+ED", "RGB+ID", "RGB+MD")
+RENDER_MODES = ("RGB", "RGB+D", "RGB+ED", "RGB+ID", "RGB+MD", "RGB+RD")
 MEDIAN_DEPTH = "RGB+MD"  # no fourth colour: the 3-channel forward, then a pass of its own (gsplat.rasterize_median_depth)
+RAY_DEPTH = "RGB+RD"     # "RGB+MD", then per pixel the median Gaussian's ray-intersection depth (gsplat.ray_gaussian_depth)
+UNBLENDED_DEPTH = {MEDIAN_DEPTH: "median depth", RAY_DEPTH: "ray depth"}
 
 
 def refuse_median_training(render_mode, where):
-    """The median depth has no gradient: the training entries refuse the mode by name."""
-    if render_mode == MEDIAN_DEPTH:
-        raise ValueError(f'{where}: render_mode "RGB+MD" (median depth) is not differentiable and cannot be trained on; '
-                         'render it through an eval entry, or train with "RGB+ED" / "RGB+ID"')
+    """The median depth and the ray depth have no gradient: the training entries refuse the modes by name."""
+    if render_mode in UNBLENDED_DEPTH:
+        raise ValueError(f'{where}: render_mode "{render_mode}" ({UNBLENDED_DEPTH[render_mode]}) is not differentiable and '
+                         'cannot be trained on; render it through an eval entry, or train with "RGB+ED" / "RGB+ID"')
 
 
 def colors_with_depth(colors, depths, backgrounds, render_mode):
@@ -127,7 +129,7 @@ def colors_with_depth(colors, depths, backgrounds, render_mode):
     the camera plane (they reach no tile list)."""
     if render_mode not in RENDER_MODES:
         raise ValueError(f"render_mode must be one of {RENDER_MODES}, got {render_mode!r}")
-    if render_mode in ("RGB", MEDIAN_DEPTH):  # the median depth is not blended: three channels, backgrounds as they are
+    if render_mode == "RGB" or render_mode in UNBLENDED_DEPTH:  # not blended: three channels, backgrounds as they are
         return colors, backgrounds
     if render_mode == "RGB+ID":
         front = depths > 0
@@ -186,6 +188,10 @@ def camera_forward_ops(means, quats, scales, opacities, coeffs, sh_degree, viewm
     gsplat.rasterize_median_depth walks the same lists with the same means2D, conics, depths and the opacities the forward
     got (x compensation under rasterize_mode="antialiased"); depth is the median depth, 0.0 where nothing is accumulated,
     alpha the forward's.  A sky is composited behind the splats and changes neither.
+    render_mode "RGB+RD" (eval only, refused likewise): everything "RGB+MD" runs, then gsplat.ray_gaussian_depth on the
+    median ids with the means, quats, scales, viewmat, K and camera_model handed in: depth is, per pixel, the depth at which
+    the median Gaussian's 3-D density peaks along the pixel's ray ("Ray depth") in place of its centre
+    depth; 0.0 exactly where "RGB+MD" gives 0.0, image and alpha the same bits.  The ids do not leave this function.
     -> (image[3,H,W] view, means2D[1,V,2], radii[1,V], () | (depth[1,H,W], alpha[1,H,W]) by split_depth,
         () | (colours leaf[1,V,3], dirs[1,V,3]) without sh_autograd)."""
     if render_mode not in RENDER_MODES:
@@ -235,9 +241,12 @@ def camera_forward_ops(means, quats, scales, opacities, coeffs, sh_degree, viewm
         image_width=image_width, image_height=image_height, tile_size=tile_size,
         isect_offsets=isect_offsets, flatten_ids=flatten_ids, backgrounds=backgrounds,
         absgrad=train and bool(getattr(utils.get_args(), "absgrad", False)))  # -> means2D.absgrad after backward
-    if render_mode == MEDIAN_DEPTH:
-        depth, _ = rasterize_median_depth(means2D, conics, opacities, depths, image_width, image_height, tile_size,
-                                          isect_offsets, flatten_ids)
+    if render_mode in UNBLENDED_DEPTH:
+        depth, median_ids = rasterize_median_depth(means2D, conics, opacities, depths, image_width, image_height, tile_size,
+                                                   isect_offsets, flatten_ids)
+        if render_mode == RAY_DEPTH:
+            depth = ray_gaussian_depth(means, quats, scales, viewmat.unsqueeze(0), K.unsqueeze(0), depth, median_ids,
+                                       camera_model=camera_model)
         rendered_image = rendered_image.squeeze(0).permute(2, 0, 1)
         if sky_camera is not None:
             rendered_image = apply_camera_sky(rendered_image, alphas[0, ..., 0], sky_camera)

@@ -46,8 +46,8 @@ def pipeline_forward_one_step_shs_inplace(filtered_opacity_gpu, filtered_scaling
     """One camera over the gathered rows; SH evaluated under no_grad and the colours re-leafed so
     the SH backward can later accumulate in place (engine.py:30-127).
     Returns (image[3,H,W], means2D[1,V,2], radii[1,V], colors_detached[1,V,3], dirs[1,V,3]); with a depth render mode
-    (base_engine.colors_with_depth) a sixth result depth[1,H,W].  "RGB+MD" is refused by name: this is a training entry
-    and the median depth has no gradient."""
+    (base_engine.colors_with_depth) a sixth result depth[1,H,W].  "RGB+MD" and "RGB+RD" are refused by name: this is a
+    training entry and the median and the ray depth have no gradient."""
     image, means2D, radiis, depth_alpha, sh_leaf = camera_forward_ops(
         filtered_xyz_gpu, filtered_rotation_gpu, filtered_scaling_gpu, filtered_opacity_gpu,
         filtered_shs.reshape(1, filtered_xyz_gpu.shape[0], 16, 3), gaussians.active_sh_degree,
@@ -867,7 +867,8 @@ def clm_offload_train_one_batch(gaussians, scene, batched_cameras, parameters_gr
 
 def clm_offload_eval_one_cam(camera, gaussians, background, scene, render_mode="RGB", return_alpha=False):
     """Single-camera render of the visible rows (engine.py:928-979) -> image[3,H,W]; with render_mode "RGB+D" /
-    "RGB+ED" / "RGB+MD" (median depth) -> (image, depth[1,H,W]) or, with return_alpha, (image, depth, alpha[1,H,W])."""
+    "RGB+ED" / "RGB+MD" (median depth) / "RGB+RD" (ray depth) -> (image, depth[1,H,W]) or, with return_alpha,
+    (image, depth, alpha[1,H,W])."""
     with torch.no_grad():
         a_ = utils.get_args()
         dp_partial = bool(getattr(gaussians, "lazy_rows", False) and dp.active()

@@ -79,7 +79,7 @@ def naive_offload_train_one_batch(gaussians, scene, batched_cameras, background,
 
 def naive_offload_eval_one_cam(gaussians, scene, camera, background, render_mode="RGB", return_alpha=False):
     """Whole model to the GPU, one render (engine.py:20-46) -> image[3,H,W]; with render_mode "RGB+D" / "RGB+ED" /
-    "RGB+MD" (median depth) -> (image, depth[1,H,W]) or, with return_alpha, (image, depth, alpha[1,H,W])."""
+    "RGB+MD" (median depth) / "RGB+RD" (ray depth) -> (image, depth[1,H,W]) or, with return_alpha, (image, depth, alpha[1,H,W])."""
     with torch.no_grad():
         rep = _DeviceReplica(gaussians)
         res = pipeline_forward_one_step(

@@ -17,7 +17,7 @@ def baseline_accumGrads_micro_step(means3D, opacities, scales, rotations, shs, s
     rasterize -> [3,H,W].  Returns (image, means2D (grad retained), radii, None); with render_mode "RGB+D" /
     "RGB+ED" / "RGB+ID" a fifth result depth[1,H,W] (accumulated / expected / inverse depth, base_engine.split_depth), and
     with return_alpha a sixth, alpha[1,H,W].  "RGB+MD" (mode="eval" only; refused by name when training: it has no
-    gradient): the fifth result is the median depth (base_engine.camera_forward_ops)."""
+    gradient): the fifth result is the median depth (base_engine.camera_forward_ops); "RGB+RD" likewise: the ray depth."""
     viewmat, K, centre = fov_camera(camera, means3D.device)
     image, means2D, radiis, depth_alpha, _ = camera_forward_ops(
         means3D, rotations, scales, opacities, shs.unsqueeze(0), sh_degree, viewmat, K, centre, background, render_mode,

@@ -934,8 +934,9 @@ OPTIONS = (
          "(clm_gs_amd.mesh_model; single GPU); 0 = off"),
     _opt("--mesh_trunc_voxels", type=float), _opt("--mesh_min_weight", type=float), _opt("--mesh_every", type=int),
     _opt("--mesh_grid_gb", type=float),
-    _opt("--mesh_depth_mode", metavar="expected|median", help="--mesh_voxel: fuse the expected depth (default) or the "
-         "median depth, the depth of the Gaussian at which the transmittance falls through one half"),
+    _opt("--mesh_depth_mode", metavar="expected|median|ray", help="--mesh_voxel: fuse the expected depth (default), the "
+         "median depth, the depth of the Gaussian at which the transmittance falls through one half, or the ray depth, "
+         "the depth at which that Gaussian's density peaks along the pixel's ray"),
     _opt("--mesh_min_component_faces", type=int, metavar="N", help="--mesh_voxel: drop the connected components of the mesh "
          "with fewer than N faces (clm_gs_amd.mesh_clean); 0 = off"),
     _opt("--mesh_keep_components", type=int, metavar="K", help="--mesh_voxel: keep only the K connected components with the "

@@ -96,7 +96,8 @@ def default_args(**over):
         # this build: mesh export (mesh_model.py, tsdf.py; csrc/tsdf.hip): after the final .ply, <model_path>/mesh.ply -- the
         # training cameras' depth maps fused into a TSDF volume of mesh_voxel world units per voxel over the 1st-99th
         # percentile box of the rows, and its surface; 0 = off, nothing more is called.  mesh_depth_mode: None / "expected" =
-        # the expected depth, "median" = the median depth (render mode "RGB+MD"; csrc/median.hip).  mesh_min_component_faces /
+        # the expected depth, "median" = the median depth (render mode "RGB+MD"; csrc/median.hip), "ray" = the ray
+        # depth (render mode "RGB+RD"; csrc/ray_depth.hip).  mesh_min_component_faces /
         # mesh_keep_components: mesh cleanup (mesh_clean.py; csrc/mesh.hip) -- connected components with fewer faces than
         # the first, and all but the second's number of largest ones, are dropped before the mesh is written; 0 = off.
         # mesh_sparse: the brick-allocated volume (tsdf.SparseTsdfVolume; csrc/tsdf_sparse.hip): the same mesh.ply.

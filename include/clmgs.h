@@ -256,6 +256,26 @@ int clmgs_rasterize_median(void* stream, int C, int N, int64_t n_isects, const f
                            int tile_size, int tile_width, int tile_height, const int32_t* offsets,
                            const int32_t* flatten_ids, void* packed, float* median_depth, int32_t* median_id);
 
+/* ---- ray depth (csrc/ray_depth.hip, csrc/ray_math.h; DESIGN.md section 3, "Ray depth")
+ * The ray-Gaussian intersection depth of RaDe-GS (Zhang et al. 2024, "Rasterizing Depth in Gaussian Splatting") and GOF
+ * (Yu et al. 2024, "Gaussian Opacity Fields"): the depth of the point on a pixel's ray at which a Gaussian's 3-D density
+ * exp(-0.5 (x - m)^T S^-1 (x - m)) is largest,  t* = d^T S^-1 (m - o) / d^T S^-1 d,  evaluated for the pixel's MEDIAN
+ * Gaussian (clmgs_rasterize_median's median_id) instead of that Gaussian's centre depth.  Per pixel, not blended over
+ * the pixel's contributors.  Forward-only, not differentiable.
+ *   means[N,3] quats[N,4] (w,x,y,z; normalised here) scales[N,3] (ACTIVATED, as clmgs_projection_fwd takes
+ *   them): the rows every camera indexes;  cams: DEVICE array [C,16] of doubles, per camera the top 3x4 of the view matrix
+ *   (row-major) then fx, fy, cx, cy;  median_id int32 [C,H,W]: the row within its camera;  median_depth[C,H,W]: the
+ *   depth returned where t* is unusable;  camera_model 0 = pinhole (origin 0, direction (u, v, 1)), 1 = orthographic
+ *   (K in pixels per world unit: origin (u, v, 0), direction (0, 0, 1)), u = (x + 0.5 - cx) / fx, v = (y + 0.5 - cy) / fy.
+ *   ray_depth[C,H,W] = (float) t* where t* is finite and > near_plane, else median_depth[] of the pixel, copied; 0.0 where
+ *   the id lies outside [0, N): such a pixel reads no row.  float64 arithmetic without contraction (ray_math.h): bit-
+ *   reproducible, every pixel written exactly once, no atomics.
+ * Argument errors (a negative size, C H W or the grid beyond 2^31 - 1, camera_model outside 0..1, a null or misaligned
+ * pointer) return CLMGS_EINVAL before anything is written; C H W == 0 is a no-op, N == 0 writes 0.0 to every pixel. */
+int clmgs_ray_depth(void* stream, int C, int N, int height, int width, const float* means, const float* quats,
+                    const float* scales, const double* cams, const int32_t* median_id, const float* median_depth,
+                    double near_plane, int camera_model, float* ray_depth);
+
 /* ---- gsplat.rasterize_to_pixels with colors[..., 4]  (what gsplat's rasterization(render_mode="RGB+D" / "RGB+ED")
  * calls: the camera-space depth rides as a fourth colour channel and is blended with the same weights)
  * Same contract as clmgs_rasterize_fwd / _bwd with rows of four: colors[C*N,4], backgrounds[C,4] or NULL ->
