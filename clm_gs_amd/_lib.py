@@ -150,6 +150,10 @@ SIGNATURES = {
     "clmgs_mesh_decimate_faces": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "clmgs_mesh_decimate_place": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _d, _vp, _vp,
                                        _vp]),
+    # mesh smoothing and normals: V, F, verts_in, faces, order, start, factor, verts_out | V, F, verts, faces, order, start,
+    # normals
+    "clmgs_mesh_smooth_step": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _d, _vp]),
+    "clmgs_mesh_vertex_normals": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "clmgs_mcmc_relocation": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "clmgs_mcmc_reg_grad": (_i, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _f, _f]),
     "clmgs_mcmc_noise": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _f, _vp]),

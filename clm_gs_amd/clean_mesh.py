@@ -1,5 +1,6 @@
-"""python -m clm_gs_amd.clean_mesh -i <mesh.ply> -o <out.ply> [--min_faces N] [--keep_largest K] [--decimate_cell C]: the
-command line of mesh_clean.py and mesh_decimate.py ("Mesh cleanup" and "Mesh decimation")."""
+"""python -m clm_gs_amd.clean_mesh -i <mesh.ply> -o <out.ply> [--min_faces N] [--keep_largest K] [--decimate_cell C]
+[--smooth_iterations N --smooth_lambda L --smooth_mu M] [--normals]: the command line of mesh_clean.py, mesh_smooth.py and
+mesh_decimate.py ("Mesh cleanup", "Mesh smoothing and normals" and "Mesh decimation")."""
 import sys
 
 from .mesh_clean import main

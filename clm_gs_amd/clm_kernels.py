@@ -1095,6 +1095,70 @@ def mesh_decimate_place(verts, colours, faces, cluster_keys, vert_order, vert_st
     return out_verts, out_colours, code
 
 
+# ------------------------------------------------------------------ mesh smoothing and vertex normals
+@torch.no_grad()
+def mesh_incidence(faces, V):
+    """The vertex -> face incidence lists of a mesh ("Mesh smoothing and normals"): faces int32 [F,3]
+    on the device with indices in [0, V) -> (order int64 [3F], start int64 [V+1]).  order holds the corner slots
+    e = 3 f + k sorted by the vertex faces[f,k], ascending e within a vertex (a stable sort: faces ascending, then corners);
+    the segment of vertex v is order[start[v]:start[v+1]].  A face that names a vertex twice is in its segment twice.  The
+    sort and the searchsorted are torch."""
+    F = _mesh_faces(faces, V, "mesh_incidence")
+    V, dev = int(V), faces.device
+    skeys, order = torch.sort(faces.reshape(-1), stable=True)
+    start = torch.full((V + 1,), 3 * F, dtype=I64, device=dev)  # (every index is below V: the last boundary is 3F)
+    if F and V:
+        start[:V] = torch.searchsorted(skeys, torch.arange(V, dtype=I32, device=dev))
+    return order.contiguous(), start
+
+
+def _mesh_lists(verts, faces, order, start, what):
+    """The checks mesh_smooth_step and mesh_vertex_normals share, all before any launch.  -> (V, F)."""
+    _mesh_dev(verts, F32, (None, 3), what, "verts")
+    V = int(verts.shape[0])
+    F = _mesh_faces(faces, V, what)
+    _mesh_dev(order, I64, (3 * F,), what, "order")
+    _mesh_dev(start, I64, (V + 1,), what, "start")
+    if not (faces.device == order.device == start.device == verts.device):
+        raise _lib.ClmgsError(f"{what}: verts are on {verts.device}, faces on {faces.device}, order on {order.device}, "
+                              f"start on {start.device}")
+    return V, F
+
+
+@torch.no_grad()
+def mesh_smooth_step(verts, faces, order, start, factor):
+    """One umbrella step (csrc/mesh_smooth.hip, one lane per vertex): verts float32 [V,3], faces int32 [F,3] and the lists
+    of mesh_incidence on the device, factor a finite number -> a NEW float32 [V,3]: every vertex moved by `factor` towards
+    the mean of its neighbours over its incidences (each neighbour weighted by the number of faces sharing the edge;
+    float64 sums in list order without contraction), a vertex no face names with its own bits.  F == 0 or V == 0 launches
+    nothing and returns a copy."""
+    what = "mesh_smooth_step"
+    if isinstance(factor, bool) or not isinstance(factor, (int, float)) or not (-float("inf") < factor < float("inf")):
+        raise ValueError(f"{what}: factor must be a finite number, got {factor!r}")
+    V, F = _mesh_lists(verts, faces, order, start, what)
+    if F == 0 or V == 0:
+        return verts.clone()
+    out = torch.empty_like(verts)
+    check(_lib.lib().clmgs_mesh_smooth_step(stream(), V, F, dptr(verts, F32), dptr(faces, I32), dptr(order, I64),
+                                            dptr(start, I64), float(factor), dptr(out, F32)))
+    return out
+
+
+@torch.no_grad()
+def mesh_vertex_normals(verts, faces, order, start):
+    """Area-weighted vertex normals (csrc/mesh_smooth.hip, one lane per vertex): the sum over a vertex's incidences of
+    (p1 - p0) x (p2 - p0) from each face's corners in stored order, normalised -> float32 [V,3] on the device; (0, 0, 0) for
+    a vertex no face names or whose sum has no direction.  F == 0 or V == 0 launches nothing and returns zeros."""
+    what = "mesh_vertex_normals"
+    V, F = _mesh_lists(verts, faces, order, start, what)
+    if F == 0 or V == 0:
+        return torch.zeros((V, 3), dtype=F32, device=verts.device)
+    out = torch.empty_like(verts)
+    check(_lib.lib().clmgs_mesh_vertex_normals(stream(), V, F, dptr(verts, F32), dptr(faces, I32), dptr(order, I64),
+                                               dptr(start, I64), dptr(out, F32)))
+    return out
+
+
 # ------------------------------------------------------------ MCMC densification
 def _f32_dev(t, shape, what):
     assert t.is_cuda and t.dtype == F32 and t.is_contiguous() and tuple(t.shape) == tuple(shape), \

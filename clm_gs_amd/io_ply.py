@@ -83,6 +83,8 @@ def load_model(path):
 
 
 _MESH_VERTEX = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+_MESH_VERTEX_NORMALS = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"),
+                                 ("red", "u1"), ("green", "u1"), ("blue", "u1")])
 _MESH_FACE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])
 
 
@@ -90,25 +92,34 @@ def _host(a, dtype):
     return np.ascontiguousarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=dtype)
 
 
-def save_mesh_ply(path, verts, colours, faces):
+def save_mesh_ply(path, verts, colours, faces, normals=None):
     """A triangle mesh (clm_gs_amd/tsdf.py) as a binary little-endian .ply: vertex properties x y z (float) and red green
     blue (uchar), faces as `property list uchar int vertex_indices`.  verts [V,3], colours [V,3] in 0..255, faces [F,3]
-    (tensors or arrays); V = F = 0 is a valid, empty mesh."""
+    (tensors or arrays); V = F = 0 is a valid, empty mesh.  With normals (float32 [V,3]) the vertex element is x y z nx ny
+    nz red green blue, the property order MeshLab and open3d write; without them the file is what it always was."""
     verts, colours, faces = _host(verts, np.float32), _host(colours, np.uint8), _host(faces, np.int32)
     verts, colours, faces = verts.reshape(-1, 3), colours.reshape(-1, 3), faces.reshape(-1, 3)
     if len(colours) != len(verts):
         raise ValueError(f"save_mesh_ply: {len(verts)} vertices and {len(colours)} colours")
     if len(faces) and (int(faces.min()) < 0 or int(faces.max()) >= len(verts)):
         raise ValueError(f"save_mesh_ply: a face index lies outside [0, {len(verts)})")
-    v = np.empty(len(verts), dtype=_MESH_VERTEX)
+    if normals is not None:
+        normals = _host(normals, np.float32)
+        if normals.shape != verts.shape:
+            raise ValueError(f"save_mesh_ply: normals must be float32 [{len(verts)},3], got {tuple(normals.shape)}")
+    v = np.empty(len(verts), dtype=_MESH_VERTEX if normals is None else _MESH_VERTEX_NORMALS)
     for k, name in enumerate(("x", "y", "z")):
         v[name] = verts[:, k]
     for k, name in enumerate(("red", "green", "blue")):
         v[name] = colours[:, k]
+    for k, name in enumerate(("nx", "ny", "nz") if normals is not None else ()):
+        v[name] = normals[:, k]
     f = np.empty(len(faces), dtype=_MESH_FACE)
     f["n"], f["v"] = 3, faces
     header = "ply\nformat binary_little_endian 1.0\nelement vertex %d\n" % len(v)
     header += "property float x\nproperty float y\nproperty float z\n"
+    if normals is not None:
+        header += "property float nx\nproperty float ny\nproperty float nz\n"
     header += "property uchar red\nproperty uchar green\nproperty uchar blue\n"
     header += "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % len(f)
     with open(path, "wb") as out:
@@ -117,9 +128,14 @@ def save_mesh_ply(path, verts, colours, faces):
         out.write(f.tobytes())
 
 
-def load_mesh_ply(path):
-    """Inverse of save_mesh_ply -> (verts float32 [V,3], colours uint8 [V,3], faces int32 [F,3]) numpy arrays.  Reads
-    the layout save_mesh_ply writes (triangles only); anything else is refused by name."""
+_MESH_PROPS = ["float x", "float y", "float z", "uchar red", "uchar green", "uchar blue"]
+_MESH_PROPS_NORMALS = _MESH_PROPS[:3] + ["float nx", "float ny", "float nz"] + _MESH_PROPS[3:]
+
+
+def load_mesh_ply(path, with_normals=False):
+    """Inverse of save_mesh_ply -> (verts float32 [V,3], colours uint8 [V,3], faces int32 [F,3]) numpy arrays; with
+    with_normals a fourth item, the normals float32 [V,3] or None when the file has none.  Reads the two layouts
+    save_mesh_ply writes (triangles only); anything else is refused by name."""
     with open(path, "rb") as f:
         if f.readline().strip() != b"ply" or f.readline().decode().split()[1:2] != ["binary_little_endian"]:
             raise ValueError(f"{path}: a binary little-endian .ply expected")
@@ -133,13 +149,20 @@ def load_mesh_ply(path):
                 counts[element], props[element] = int(tok[2]), []
             elif tok[:1] == ["property"]:
                 props[element].append(" ".join(tok[1:]))
-        if props.get("vertex") != ["float x", "float y", "float z", "uchar red", "uchar green", "uchar blue"] or \
+        if props.get("vertex") not in (_MESH_PROPS, _MESH_PROPS_NORMALS) or \
                 props.get("face") != ["list uchar int vertex_indices"]:
             raise ValueError(f"{path}: not a mesh written by save_mesh_ply (properties {props})")
-        v = np.frombuffer(f.read(counts["vertex"] * _MESH_VERTEX.itemsize), dtype=_MESH_VERTEX)
+        vertex = _MESH_VERTEX if props["vertex"] == _MESH_PROPS else _MESH_VERTEX_NORMALS
+        v = np.frombuffer(f.read(counts["vertex"] * vertex.itemsize), dtype=vertex)
         fc = np.frombuffer(f.read(counts["face"] * _MESH_FACE.itemsize), dtype=_MESH_FACE)
     if len(v) != counts["vertex"] or len(fc) != counts["face"] or (len(fc) and not (fc["n"] == 3).all()):
         raise ValueError(f"{path}: truncated, or a face that is no triangle")
     verts = np.stack([v["x"], v["y"], v["z"]], axis=1).astype(np.float32).reshape(-1, 3)
     colours = np.stack([v["red"], v["green"], v["blue"]], axis=1).astype(np.uint8).reshape(-1, 3)
-    return verts, colours, np.ascontiguousarray(fc["v"], dtype=np.int32).reshape(-1, 3)
+    faces = np.ascontiguousarray(fc["v"], dtype=np.int32).reshape(-1, 3)
+    if not with_normals:
+        return verts, colours, faces
+    normals = None
+    if vertex is _MESH_VERTEX_NORMALS:
+        normals = np.stack([v["nx"], v["ny"], v["nz"]], axis=1).astype(np.float32).reshape(-1, 3)
+    return verts, colours, faces, normals

@@ -1,8 +1,12 @@
 """Mesh cleanup ("Mesh cleanup"): drops the small connected components of a triangle mesh.
 
     python -m clm_gs_amd.clean_mesh -i <mesh.ply> -o <out.ply> [--min_faces N] [--keep_largest K] [--decimate_cell C]
+        [--smooth_iterations N --smooth_lambda 0.5 --smooth_mu -0.53] [--normals]
 
-(--decimate_cell: mesh_decimate.decimate after the two filters, or alone; DESIGN.md section 3, "Mesh decimation".)
+(--decimate_cell: mesh_decimate.decimate after the two filters, or alone; DESIGN.md section 3, "Mesh decimation".
+--smooth_iterations: mesh_smooth.smooth between the filters and the decimation; --normals: the vertex normals of the
+OUTPUT mesh in the file; DESIGN.md section 3, "Mesh smoothing and normals".  The input may be either layout of
+io_ply.save_mesh_ply; normals it stores are ignored, never carried through.)
 
 The components are labelled on the device (clm_kernels.mesh_components / mesh_component_faces, csrc/mesh.hip): two vertices
 are connected when a face names both, a component's label is its smallest vertex index and its size its number of faces.
@@ -94,22 +98,31 @@ def json_path(mesh_path):
 
 
 def main(argv=None):
-    from . import mesh_decimate
+    from . import mesh_decimate, mesh_smooth
     ap = argparse.ArgumentParser(prog="clm_gs_amd.clean_mesh",
                                  description="drop the small connected components of a mesh written by clm_gs_amd.mesh_model, "
-                                             "and / or decimate it")
+                                             "and / or smooth it, decimate it, give it vertex normals")
     ap.add_argument("-i", "--input", required=True, help="the mesh (.ply as io_ply.save_mesh_ply writes it)")
     ap.add_argument("-o", "--output", required=True, help="the cleaned mesh; <output>.json is written when <input>.json exists")
     ap.add_argument("--min_faces", type=int, default=0, metavar="N", help="drop the components with fewer than N faces")
     ap.add_argument("--keep_largest", type=int, default=0, metavar="K", help="keep only the K components with the most faces")
     ap.add_argument("--decimate_cell", type=float, default=0.0, metavar="C",
                     help="after the two filters, merge the vertices of every cell of C world units (mesh_decimate.decimate)")
+    ap.add_argument("--smooth_iterations", type=int, default=0, metavar="N",
+                    help="after the two filters and before the decimation, N Taubin smoothing passes (mesh_smooth.smooth)")
+    ap.add_argument("--smooth_lambda", type=float, default=0.5, metavar="L", help="the factor of a pass's first step, in (0, 1]")
+    ap.add_argument("--smooth_mu", type=float, default=-0.53, metavar="M",
+                    help="the factor of a pass's second step, in [-1, 0]; 0 = plain Laplacian smoothing")
+    ap.add_argument("--normals", action="store_true",
+                    help="write area-weighted vertex normals of the output mesh (nx ny nz) into the file")
     a = ap.parse_args(argv)
     try:  # refusals before anything is read
         check_options(a.min_faces, a.keep_largest)
         mesh_decimate.check_cell(a.decimate_cell)
-        if a.min_faces == 0 and a.keep_largest == 0 and a.decimate_cell == 0:
-            raise ValueError("nothing to do: give --min_faces N, --keep_largest K or --decimate_cell C")
+        mesh_smooth.check_options(a.smooth_iterations, a.smooth_lambda, a.smooth_mu)
+        if a.min_faces == 0 and a.keep_largest == 0 and a.decimate_cell == 0 and a.smooth_iterations == 0 and not a.normals:
+            raise ValueError("nothing to do: give --min_faces N, --keep_largest K, --decimate_cell C, --smooth_iterations N "
+                             "or --normals")
     except ValueError as e:
         raise SystemExit(str(e))
     from . import io_ply
@@ -118,13 +131,16 @@ def main(argv=None):
     V, F = int(verts.shape[0]), int(faces.shape[0])
     try:
         verts, colours, faces, report = clean(verts, colours, faces, a.min_faces, a.keep_largest)
+        verts, colours, faces, smoothing = mesh_smooth.smooth(verts, colours, faces, a.smooth_iterations, a.smooth_lambda,
+                                                              a.smooth_mu)
         verts, colours, faces, decimation = mesh_decimate.decimate(verts, colours, faces, a.decimate_cell)
     except ValueError as e:  # (a cell too small for the mesh's extent)
         raise SystemExit(str(e))
+    normals = mesh_smooth.vertex_normals(verts, faces) if a.normals else None
     d = os.path.dirname(a.output)
     if d:
         os.makedirs(d, exist_ok=True)
-    io_ply.save_mesh_ply(a.output, verts, colours, faces)
+    io_ply.save_mesh_ply(a.output, verts, colours, faces, normals)
     if os.path.exists(json_path(a.input)):
         with open(json_path(a.input)) as f:
             meta = json.load(f)
@@ -132,12 +148,15 @@ def main(argv=None):
             meta = json_record(meta, a.min_faces, a.keep_largest, report, verts.shape[0], faces.shape[0])
         if decimation is not None:
             meta = mesh_decimate.json_record(meta, decimation, verts.shape[0], faces.shape[0])
+        meta.pop("normals", None)  # (of the input file: they are not carried through)
+        meta = mesh_smooth.json_record(meta, smoothing, a.normals)
         with open(json_path(a.output), "w") as f:
             json.dump(meta, f, indent=1)
-    print("mesh cleanup:{} vertices {} -> {} faces {} -> {}{}{} in {:.3f} s -> {}".format(
+    print("mesh cleanup:{} vertices {} -> {} faces {} -> {}{}{}{} in {:.3f} s -> {}".format(
         "" if report is None else " components {} kept {}".format(report["components"], report["components_kept"]),
         V, int(verts.shape[0]), F, int(faces.shape[0]), "" if report is None else " rounds {}".format(report["rounds"]),
-        "" if decimation is None else mesh_decimate.log_words(decimation), time.perf_counter() - t0, a.output))
+        "" if decimation is None else mesh_decimate.log_words(decimation), mesh_smooth.log_words(smoothing, a.normals),
+        time.perf_counter() - t0, a.output))
     return 0
 
 

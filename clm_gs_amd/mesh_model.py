@@ -4,7 +4,7 @@
         [--trunc_voxels 4] [--bounds emin nmin umin emax nmax umax] [--up X Y Z] [--east X Y Z] [--every K] [-r R]
         [--alpha_min 0.5] [--depth_max D] [--min_weight 2] [--grid_gb 16] [--antialiased] [--undistort --undistort_zoom Z]
         [--depth_mode expected|median|ray] [--min_component_faces N] [--keep_components K] [--sparse] [--decimate_cell C]
-        [--eval]
+        [--smooth_iterations N --smooth_lambda 0.5 --smooth_mu -0.53] [--normals] [--eval]
         [--clm_offload | --naive_offload | --no_offload]
 
 renders every selected training camera of the scene through the strategy's own eval entry (render_mode "RGB+ED":
@@ -33,6 +33,12 @@ and the marking rate.  Without the flag every file is what it was.
 the faces that touch the cell (mesh_decimate.decimate, csrc/mesh_decimate.hip; DESIGN.md section 3, "Mesh decimation"); the
 .json gains "decimation" (the report) and the log line " decimated V -> V' vertices F -> F' faces cell C".  A negative or
 non-finite value is refused by name; 0, the default, changes nothing.  The decimated mesh need not be a manifold.
+--smooth_iterations N runs, between the cleanup and the decimation, N passes of Taubin's lambda | mu smoothing
+(mesh_smooth.smooth, csrc/mesh_smooth.hip; DESIGN.md section 3, "Mesh smoothing and normals"): a step with --smooth_lambda
+(0.5), then one with --smooth_mu (-0.53; 0 = plain Laplacian smoothing, which shrinks).  Vertex count, colours and faces
+stay; the decimation's quadrics then see denoised faces.  --normals writes the area-weighted vertex normals of the FINAL
+mesh into the file (x y z nx ny nz red green blue).  The .json gains "smoothing" (the report) and "normals": true, the
+log line " smoothed N x (lam, mu)" and " normals", each only with its flag; without them every file is what it was.
 """
 import argparse
 import json
@@ -42,7 +48,7 @@ import time
 
 import torch
 
-from . import io_ply, mesh_clean, mesh_decimate, tsdf, utils
+from . import io_ply, mesh_clean, mesh_decimate, mesh_smooth, tsdf, utils
 from .render_ortho import map_frame, percentile_sorted
 from .render_trajectory import _find_ply, depth_render_mode, eval_one_cam
 
@@ -66,7 +72,8 @@ def json_path(mesh_path):
 @torch.no_grad()
 def build_mesh(gaussians, cameras, args, out_path, voxel, frame=None, bounds=None, trunc_voxels=4.0, every=1, alpha_min=0.5,
                depth_max=None, min_weight=2.0, grid_gb=16.0, near=0.01, background=None, log=None, depth_mode="expected",
-               min_component_faces=0, keep_components=0, sparse=False, decimate_cell=0.0):
+               min_component_faces=0, keep_components=0, sparse=False, decimate_cell=0.0, smooth_iterations=0,
+               smooth_lambda=0.5, smooth_mu=-0.53, normals=False):
     """Renders cameras[::every] from `gaussians` through the eval entry of the strategy `args` names, fuses them, extracts
     and writes out_path and its .json.  -> the dict written to the .json.  The global image size (utils.set_img_size)
     must be the cameras' size.  depth_mode "expected" fuses the "RGB+ED" depth, "median" the "RGB+MD" one, "ray" the "RGB+RD"
@@ -75,8 +82,11 @@ def build_mesh(gaussians, cameras, args, out_path, voxel, frame=None, bounds=Non
     brick-allocated volume; every camera is rendered twice, to mark and to fuse (the eval forward is deterministic: see
     DESIGN.md section 3, "Sparse volume"), and the .json gains "sparse".  decimate_cell: mesh_decimate.decimate after the
     cleanup, which sees the full-resolution mesh (the .json gains "decimation" and the log line its counts only when it is
-    on)."""
+    on).  smooth_iterations / smooth_lambda / smooth_mu: mesh_smooth.smooth between the cleanup and the decimation;
+    normals: the vertex normals of the final mesh in the file (the .json gains "smoothing" / "normals" and the log line
+    its words only then)."""
     decimate_cell = mesh_decimate.check_cell(decimate_cell)
+    smooth_iterations, smooth_lambda, smooth_mu = mesh_smooth.check_options(smooth_iterations, smooth_lambda, smooth_mu)
     min_component_faces, keep_components = mesh_clean.check_options(min_component_faces, keep_components,
                                                                     ("--min_component_faces", "--keep_components"))
     render_mode = depth_render_mode(depth_mode)
@@ -119,11 +129,13 @@ def build_mesh(gaussians, cameras, args, out_path, voxel, frame=None, bounds=Non
     torch.cuda.synchronize()
     t_extract = time.perf_counter() - t0
     verts, colours, faces, report = mesh_clean.clean(verts, colours, faces, min_component_faces, keep_components)
+    verts, colours, faces, smoothing = mesh_smooth.smooth(verts, colours, faces, smooth_iterations, smooth_lambda, smooth_mu)
     verts, colours, faces, decimation = mesh_decimate.decimate(verts, colours, faces, decimate_cell)
+    vertex_normals = mesh_smooth.vertex_normals(verts, faces) if normals else None
     d = os.path.dirname(out_path)
     if d:
         os.makedirs(d, exist_ok=True)
-    io_ply.save_mesh_ply(out_path, verts, colours, faces)
+    io_ply.save_mesh_ply(out_path, verts, colours, faces, vertex_normals)
     e, n, u = volume.frame
     meta = dict(east=[float(v) for v in e], north=[float(v) for v in n], up=[float(v) for v in u],
                 bounds=[float(v) for v in volume.bounds], voxel=volume.voxel, trunc=volume.trunc,
@@ -138,26 +150,30 @@ def build_mesh(gaussians, cameras, args, out_path, voxel, frame=None, bounds=Non
         meta = mesh_clean.json_record(meta, min_component_faces, keep_components, report, verts.shape[0], faces.shape[0])
     if decimation is not None:
         meta = mesh_decimate.json_record(meta, decimation, verts.shape[0], faces.shape[0])
+    meta = mesh_smooth.json_record(meta, smoothing, bool(normals))
     with open(json_path(out_path), "w") as f:
         json.dump(meta, f, indent=1)
     log.write("mesh export: grid {} x {} x {} voxel {:g} cameras {} render {:.1f} cameras/s integration {:.1f} cameras/s "
-              "extraction {:.3f} s vertices {} faces {}{}{}{} -> {}\n".format(
+              "extraction {:.3f} s vertices {} faces {}{}{}{}{} -> {}\n".format(
                   volume.nx, volume.ny, volume.nz, volume.voxel, len(cams), len(cams) / max(t_render, 1e-9),
                   len(cams) / max(t_fuse, 1e-9), t_extract, meta["vertices"], meta["faces"],
                   "" if report is None else " components {} kept {}".format(report["components"], report["components_kept"]),
                   "" if not sparse else " sparse bricks {} of {} pool {:.3f} GB marking {:.1f} cameras/s".format(
                       volume.S, volume.bricks_total, meta["sparse"]["pool_gb"], len(cams) / max(t_mark, 1e-9)),
                   "" if decimation is None else mesh_decimate.log_words(decimation),
+                  mesh_smooth.log_words(smoothing, bool(normals)),
                   out_path))
     return meta
 
 
 def check_options(voxel, bounds=None, grid_gb=16.0, trunc_voxels=4.0, min_weight=2.0, every=1, depth_mode="expected",
-                  min_component_faces=0, keep_components=0, sparse=False, decimate_cell=0.0):
+                  min_component_faces=0, keep_components=0, sparse=False, decimate_cell=0.0, smooth_iterations=0,
+                  smooth_lambda=0.5, smooth_mu=-0.53):
     """The refusals that need nothing loaded (ValueError by name); with sparse the brick-grid limits take the place of the
     dense ones."""
     mesh_clean.check_options(min_component_faces, keep_components, ("--min_component_faces", "--keep_components"))
     mesh_decimate.check_cell(decimate_cell)
+    mesh_smooth.check_options(smooth_iterations, smooth_lambda, smooth_mu)
     tsdf.grid_shape((0, 0, 0, 1, 1, 1), voxel)  # (--voxel alone)
     depth_render_mode(depth_mode)
     if not trunc_voxels > 0:
@@ -202,6 +218,13 @@ def main(argv=None):
     ap.add_argument("--decimate_cell", type=float, default=0.0, metavar="C",
                     help="decimate the mesh before it is written: merge the vertices of every cell of C world units "
                          "(quadric vertex clustering, after the cleanup); 0 = off")
+    ap.add_argument("--smooth_iterations", type=int, default=0, metavar="N",
+                    help="smooth the mesh before the decimation: N passes of Taubin's lambda | mu smoothing; 0 = off")
+    ap.add_argument("--smooth_lambda", type=float, default=0.5, metavar="L", help="the factor of a pass's first step, in (0, 1]")
+    ap.add_argument("--smooth_mu", type=float, default=-0.53, metavar="M",
+                    help="the factor of a pass's second step, in [-1, 0]; 0 = plain Laplacian smoothing")
+    ap.add_argument("--normals", action="store_true",
+                    help="write area-weighted vertex normals of the final mesh (nx ny nz) into the file")
     ap.add_argument("--sparse", action="store_true",
                     help="a brick-allocated volume: the same mesh.ply, on boxes far beyond 2^31 voxels (renders every camera twice)")
     ap.add_argument("--antialiased", action="store_true", help="for a model trained with trainer --antialiased")
@@ -215,7 +238,8 @@ def main(argv=None):
     a = ap.parse_args(argv)
     try:  # refusals before anything is loaded or written
         check_options(a.voxel, a.bounds, a.grid_gb, a.trunc_voxels, a.min_weight, a.every, a.depth_mode,
-                      a.min_component_faces, a.keep_components, a.sparse, a.decimate_cell)
+                      a.min_component_faces, a.keep_components, a.sparse, a.decimate_cell, a.smooth_iterations,
+                      a.smooth_lambda, a.smooth_mu)
         frame = map_frame(a.up, a.east)
     except ValueError as e:
         raise SystemExit(str(e))
@@ -246,7 +270,8 @@ def main(argv=None):
         build_mesh(gaussians, cams, args, a.output, a.voxel, frame, a.bounds, a.trunc_voxels, a.every, a.alpha_min,
                    a.depth_max, a.min_weight, a.grid_gb, depth_mode=a.depth_mode,
                    min_component_faces=a.min_component_faces, keep_components=a.keep_components, sparse=a.sparse,
-                   decimate_cell=a.decimate_cell)
+                   decimate_cell=a.decimate_cell, smooth_iterations=a.smooth_iterations, smooth_lambda=a.smooth_lambda,
+                   smooth_mu=a.smooth_mu, normals=a.normals)
     except ValueError as e:  # (the size of a grid whose bounds come from the model)
         raise SystemExit(str(e))
     return 0

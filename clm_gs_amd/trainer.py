@@ -338,6 +338,10 @@ def mesh_rules(args):
         check_components(*components, names=("--mesh_min_component_faces", "--mesh_keep_components"))
         from .mesh_decimate import check_cell
         decimate_cell = check_cell(getattr(args, "mesh_decimate_cell", 0.0), "--mesh_decimate_cell")
+        from .mesh_smooth import check_options as check_smoothing
+        smooth_iterations = check_smoothing(getattr(args, "mesh_smooth_iterations", 0), getattr(args, "mesh_smooth_lambda", 0.5),
+                                            getattr(args, "mesh_smooth_mu", -0.53),
+                                            ("--mesh_smooth_iterations", "--mesh_smooth_lambda", "--mesh_smooth_mu"))[0]
     except ValueError as e:
         return [(True, str(e))]
     if not voxel:
@@ -346,7 +350,10 @@ def mesh_rules(args):
             ([(True, "--mesh_sparse has effect only with --mesh_voxel: give both, or neither")]
              if getattr(args, "mesh_sparse", False) else []) + \
             ([(True, "--mesh_decimate_cell has effect only with --mesh_voxel: give both, or neither")]
-             if decimate_cell else [])
+             if decimate_cell else []) + \
+            [(True, f"{flag} has effect only with --mesh_voxel: give both, or neither")
+             for flag, on in (("--mesh_smooth_iterations", smooth_iterations),
+                              ("--mesh_normals", getattr(args, "mesh_normals", False))) if on]
     from .mesh_model import check_options
     try:
         check_options(voxel, None, getattr(args, "mesh_grid_gb", 16.0), getattr(args, "mesh_trunc_voxels", 4.0),
@@ -842,7 +849,11 @@ def train_from_colmap(source_path, model_path, strategy="clm_offload", iteration
                                min_component_faces=getattr(args, "mesh_min_component_faces", 0),
                                keep_components=getattr(args, "mesh_keep_components", 0),
                                sparse=bool(getattr(args, "mesh_sparse", False)),
-                               decimate_cell=getattr(args, "mesh_decimate_cell", 0.0))
+                               decimate_cell=getattr(args, "mesh_decimate_cell", 0.0),
+                               smooth_iterations=getattr(args, "mesh_smooth_iterations", 0),
+                               smooth_lambda=getattr(args, "mesh_smooth_lambda", 0.5),
+                               smooth_mu=getattr(args, "mesh_smooth_mu", -0.53),
+                               normals=bool(getattr(args, "mesh_normals", False)))
             for row in SIDE_MODELS:
                 if getattr(scene, row.name) is not None:
                     getattr(scene, row.name).save_to(model_path, scene.train_cameras)
@@ -945,6 +956,14 @@ OPTIONS = (
          "mesh.ply, on boxes beyond the dense volume's 2^31 voxels; renders every camera twice"),
     _opt("--mesh_decimate_cell", type=float, metavar="C", help="--mesh_voxel: decimate the mesh before it is written: merge "
          "the vertices of every cell of C world units (quadric vertex clustering, clm_gs_amd.mesh_decimate); 0 = off"),
+    _opt("--mesh_smooth_iterations", type=int, metavar="N", help="--mesh_voxel: smooth the mesh before the decimation: N "
+         "passes of Taubin's lambda | mu smoothing (clm_gs_amd.mesh_smooth); 0 = off"),
+    _opt("--mesh_smooth_lambda", type=float, metavar="L", help="--mesh_smooth_iterations: the factor of a pass's first "
+         "step, in (0, 1]"),
+    _opt("--mesh_smooth_mu", type=float, metavar="M", help="--mesh_smooth_iterations: the factor of a pass's second step, "
+         "in [-1, 0]; 0 = plain Laplacian smoothing"),
+    _opt("--mesh_normals", action="store_true", help="--mesh_voxel: write area-weighted vertex normals (nx ny nz) into "
+         "mesh.ply"),
 )
 
 

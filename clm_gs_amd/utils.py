@@ -102,9 +102,12 @@ def default_args(**over):
         # the first, and all but the second's number of largest ones, are dropped before the mesh is written; 0 = off.
         # mesh_sparse: the brick-allocated volume (tsdf.SparseTsdfVolume; csrc/tsdf_sparse.hip): the same mesh.ply.
         # mesh_decimate_cell: mesh decimation (mesh_decimate.py; csrc/mesh_decimate.hip) -- after the cleanup the vertices of
-        # every cell of that many world units are merged into one before the mesh is written; 0 = off
+        # every cell of that many world units are merged into one before the mesh is written; 0 = off.
+        # mesh_smooth_iterations / mesh_smooth_lambda / mesh_smooth_mu: Taubin smoothing (mesh_smooth.py; csrc/mesh_smooth.hip)
+        # between the cleanup and the decimation; 0 iterations = off.  mesh_normals: vertex normals in mesh.ply
         mesh_voxel=0.0, mesh_trunc_voxels=4.0, mesh_min_weight=2.0, mesh_every=1, mesh_grid_gb=16.0, mesh_depth_mode=None,
         mesh_min_component_faces=0, mesh_keep_components=0, mesh_sparse=False, mesh_decimate_cell=0.0,
+        mesh_smooth_iterations=0, mesh_smooth_lambda=0.5, mesh_smooth_mu=-0.53, mesh_normals=False,
         lr_scale_mode="sqrt", bsz=1, exact_filter=True, log_cpu_adam_trailing_overhead=False,
         # Debug
         stop_update_param=False, drop_initial_3dgs_p=0.0,

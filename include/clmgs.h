@@ -1140,6 +1140,24 @@ int clmgs_mesh_decimate_place(void* stream, int V, int F, int C, const float* ve
                               int64_t n_inc, const int32_t* lane_order, double cell, float* out_verts, uint8_t* out_colours,
                               uint8_t* code);
 
+/* ---- mesh smoothing and vertex normals (csrc/mesh_smooth.hip, csrc/mesh_vertex_math.h; clm_gs_amd/mesh_smooth.py):
+ * DESIGN.md section 3, "Mesh smoothing and normals".  verts float32 [V,3] and faces int32 [F,3] on the device,
+ * 1 <= V < 2^31, 1 <= F < 2^31.  order int64 [3F] holds the corner slots e = 3 f + k sorted by the vertex faces[f,k],
+ * ascending e within a vertex (a stable sort); start int64 [V + 1] the segment boundaries.  Both lists are the caller's.
+ * One lane per vertex walks its segment; all sums are float64, left to right, without contraction.
+ *  - clmgs_mesh_smooth_step writes verts_out float32 [V,3], a buffer apart from verts_in: per entry s += p[faces[f,(k+1)%3]],
+ *    then s += p[faces[f,(k+2)%3]], n += 2; out = float32(p + factor * (s / double(n) - p)), or p's own bits for n == 0.
+ *    factor is finite.  A face that names a vertex twice is in its segment twice.
+ *  - clmgs_mesh_vertex_normals writes normals float32 [V,3]: per entry a += (p1 - p0) x (p2 - p0) from the corners of f in
+ *    stored order; q = (a0 a0 + a1 a1) + a2 a2; float32(a * (1.0 / sqrt(q))) for a finite q > 0, else (0, 0, 0).
+ * Both return CLMGS_EINVAL, before anything is launched, for a size outside its range, a non-finite factor, a null or
+ * misaligned pointer, and an output that overlaps an input.  An index read from memory that lies outside its array is
+ * skipped by both kernels. */
+int clmgs_mesh_smooth_step(void* stream, int V, int F, const float* verts_in, const int32_t* faces, const int64_t* order,
+                           const int64_t* start, double factor, float* verts_out);
+int clmgs_mesh_vertex_normals(void* stream, int V, int F, const float* verts, const int32_t* faces, const int64_t* order,
+                              const int64_t* start, float* normals);
+
 /* ---- pinned host memory  (numba.cuda.pinned_array at clm_offload/gaussian_model.py:34-44) */
 void* clmgs_pinned_alloc(size_t bytes);
 int clmgs_pinned_free(void* p);
