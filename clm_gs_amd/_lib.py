@@ -154,7 +154,16 @@ SIGNATURES = {
     # normals
     "clmgs_mesh_smooth_step": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _d, _vp]),
     "clmgs_mesh_vertex_normals": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
-    "clmgs_mcmc_relocation": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    # mesh evaluation: V, F, verts, faces, spacing, area, count | V, F, verts, faces, area, offsets, sample_face, S, points,
+    # weight | V, N, verts, faces, ox, oy, oz, h, gx, gy, gz, count | ..., offsets, pairs, cell, prim | P, queries, V, N, verts,
+    # faces, ox, oy, oz, h, gx, gy, gz, cell_start, pair_prim, pairs, max_distance, dist, prim, evaluated
+    "clmgs_mesh_sample_count": (_i, [_vp, _i, _i, _vp, _vp, _d, _vp, _vp]),
+    "clmgs_mesh_sample_emit": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "clmgs_mesh_bin_count": (_i, [_vp, _i, _i, _vp, _vp, _d, _d, _d, _d, _i, _i, _i, _vp]),
+    "clmgs_mesh_bin_emit": (_i, [_vp, _i, _i, _vp, _vp, _d, _d, _d, _d, _i, _i, _i, _vp, _i64, _vp, _vp]),
+    "clmgs_mesh_distance": (_i, [_vp, _i64, _vp, _i, _i, _vp, _vp, _d, _d, _d, _d, _i, _i, _i, _vp, _vp, _i64, _d, _vp, _vp,
+                                 _vp]),
+    "clmgs_mcmc_relocation": (_i,[_vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "clmgs_mcmc_reg_grad": (_i, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _f, _f]),
     "clmgs_mcmc_noise": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _f, _vp]),
     "clmgs_rows_gather": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _i]),

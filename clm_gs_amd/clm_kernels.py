@@ -1159,6 +1159,212 @@ def mesh_vertex_normals(verts, faces, order, start):
     return out
 
 
+# ------------------------------------------------------------------ mesh evaluation
+MESH_MAX_SAMPLES = 1 << 28          # the default limit of mesh_sample; the entry itself takes S < 2^31
+MESH_GRID_MAX_CELLS = 1 << 27
+MESH_GRID_MAX_AXIS = 1 << 20
+MESH_GRID_PAIR_BYTES = 32           # per (cell, primitive) pair: the two lists, their sorted forms and the sort's indices
+
+
+def _mesh_number(x, what, name, allow_inf=False):
+    """x: a positive finite number (or +inf where allowed) -> float, or ValueError by name."""
+    if isinstance(x, bool) or not isinstance(x, (int, float)) or not (0 < x and (x < float("inf") or (allow_inf and x == float("inf")))):
+        raise ValueError(f"{what}: {name} must be a positive {'number' if allow_inf else 'finite number'}, got {x!r}")
+    return float(x)
+
+
+def _mesh_sample_count(verts, faces, V, F, spacing):
+    area = torch.empty((F,), dtype=torch.float64, device=verts.device)
+    count = torch.empty((F,), dtype=I64, device=verts.device)
+    if F and V:
+        check(_lib.lib().clmgs_mesh_sample_count(stream(), V, F, dptr(verts, F32), dptr(faces, I32), spacing,
+                                                 dptr(area, torch.float64), dptr(count, I64)))
+    return area, count
+
+
+@torch.no_grad()
+def mesh_sample(verts, faces, spacing, max_samples=MESH_MAX_SAMPLES, name="max_samples"):
+    """Area-weighted surface samples (csrc/mesh_distance.hip; DESIGN.md section 3, "Mesh evaluation"): verts float32 [V,3]
+    and faces int32 [F,3] on the device, spacing > 0 -> (points float32 [S,3], face int32 [S], weight float64 [S], area
+    float64 [F]), all on the device.  Face f gets n_f = ceil(area_f / spacing^2) samples of weight area_f / n_f each, at
+    the first n_f points of the R2 sequence folded into the triangle; a face whose area is zero or not finite gets none.
+    A total above max_samples is refused (ValueError, by `name`, with the spacing that fits) before the samples are
+    allocated."""
+    what = "mesh_sample"
+    spacing = _mesh_number(spacing, what, "spacing")
+    if isinstance(max_samples, bool) or not isinstance(max_samples, int) or not 1 <= max_samples < 1 << 31:
+        raise ValueError(f"{what}: {name} must be an integer in [1, 2^31), got {max_samples!r}")
+    _mesh_dev(verts, F32, (None, 3), what, "verts")
+    V = int(verts.shape[0])
+    F = _mesh_faces(faces, V, what)
+    if faces.device != verts.device:
+        raise _lib.ClmgsError(f"{what}: verts are on {verts.device}, faces on {faces.device}")
+    dev = verts.device
+    area, count = _mesh_sample_count(verts, faces, V, F, spacing)
+    S = int(count.sum()) if F else 0
+    if S > max_samples:
+        ok = (area > 0) & torch.isfinite(area)
+        total, n_ok = float(area[ok].sum()), int(ok.sum())
+        fits = (f"a spacing of {1.001 * (total / (max_samples - n_ok)) ** 0.5:g} fits" if max_samples > n_ok
+                else f"no spacing fits: {n_ok} faces have an area")
+        raise ValueError(f"{what}: spacing {spacing:g} gives {S} samples, above {name} {max_samples}; {fits}")
+    points = torch.empty((S, 3), dtype=F32, device=dev)
+    weight = torch.empty((S,), dtype=torch.float64, device=dev)
+    if S == 0:
+        return points, torch.empty((0,), dtype=I32, device=dev), weight, area
+    offsets = torch.zeros((F + 1,), dtype=I64, device=dev)
+    torch.cumsum(count, 0, out=offsets[1:])
+    face = torch.repeat_interleave(torch.arange(F, dtype=I32, device=dev), count, output_size=S).contiguous()
+    check(_lib.lib().clmgs_mesh_sample_emit(stream(), V, F, dptr(verts, F32), dptr(faces, I32), dptr(area, torch.float64),
+                                            dptr(offsets, I64), dptr(face, I32), S, dptr(points, F32),
+                                            dptr(weight, torch.float64)))
+    return points, face, weight, area
+
+
+class MeshDistanceGrid:
+    """What mesh_distance_grid builds and mesh_distance reads: the primitives (verts, faces or None for points), the grid
+    (origin, h, dims) and the lists (cell_start int64 [cells + 1], pair_prim int32 [pairs]); primitives = how many of the
+    n faces / points are primitives, degenerate = the others."""
+    __slots__ = ("verts", "faces", "n", "origin", "h", "dims", "cell_start", "pair_prim", "pairs", "primitives", "degenerate")
+
+
+def _mesh_grid_default_cell(lo, hi, used, corners):
+    """A speed choice, no part of the contract: the median longest bounding-box side of the triangles (measured against
+    twice that in DESIGN.md section 3, "Mesh evaluation"); for points the spacing that puts about four of them into an
+    occupied cell of a surface."""
+    extent = [b - a for a, b in zip(lo, hi)]
+    if corners is not None:
+        side = (corners.amax(1) - corners.amin(1)).amax(1)
+        h = float(side.median())
+    else:
+        ex, ey, ez = extent
+        surface = ex * ey + ey * ez + ex * ez
+        n = int(used.shape[0])
+        h = (4.0 * surface / n) ** 0.5 if surface > 0 else 4.0 * max(extent) / n
+    if not (h > 0 and h < float("inf")):
+        h = max(extent) if max(extent) > 0 else 1.0
+    return max(h, max(extent) * 2.0 ** -19)  # (at most 2^19 cells along an axis)
+
+
+@torch.no_grad()
+def mesh_distance_grid(verts, faces=None, cell=None, grid_gb=4.0, name="cell"):
+    """The primitive grid of mesh_distance (csrc/mesh_distance.hip; DESIGN.md section 3, "Mesh evaluation"): verts float32
+    [V,3] on the device and faces int32 [F,3] (the primitives are the triangles) or None (the points) -> MeshDistanceGrid.
+    A uniform grid of cell size h over the float64 bounding box of the primitives; a triangle is listed in every cell of
+    the index range of its bounding box, a point in its own.  A face whose area is zero or not finite and a point with a
+    non-finite coordinate are not primitives.  Without `cell` h is chosen here and raised until the grid has at most 2^27
+    cells (2^20 per axis) and its pairs fit grid_gb; a given cell that breaks a limit is refused (ValueError, by `name`,
+    with the size that fits).  mesh_distance gives the same result for any h."""
+    what = "mesh_distance_grid"
+    if cell is not None:
+        cell = _mesh_number(cell, what, name)
+    grid_gb = _mesh_number(grid_gb, what, "grid_gb")
+    _mesh_dev(verts, F32, (None, 3), what, "verts")
+    V = int(verts.shape[0])
+    N = V if faces is None else _mesh_faces(faces, V, what)
+    if faces is not None and faces.device != verts.device:
+        raise _lib.ClmgsError(f"{what}: verts are on {verts.device}, faces on {faces.device}")
+    dev = verts.device
+    g = MeshDistanceGrid()
+    g.verts, g.faces, g.n = verts, faces, N
+    corners = None
+    if faces is not None:
+        area, _ = _mesh_sample_count(verts, faces, V, N, 1.0)
+        valid = (area > 0) & torch.isfinite(area)
+        corners = verts[faces[valid].long().reshape(-1)].double().reshape(-1, 3, 3)
+        used = corners.reshape(-1, 3)
+    else:
+        valid = torch.isfinite(verts).all(dim=1)
+        used = verts[valid].double()
+    g.primitives = int(valid.sum()) if N else 0
+    g.degenerate = N - g.primitives
+    if g.primitives == 0:
+        g.origin, g.h, g.dims, g.pairs = (0.0, 0.0, 0.0), cell or 1.0, (1, 1, 1), 0
+        g.cell_start = torch.zeros((2,), dtype=I64, device=dev)
+        g.pair_prim = torch.empty((0,), dtype=I32, device=dev)
+        return g
+    lo, hi = [float(v) for v in used.amin(0)], [float(v) for v in used.amax(0)]
+    L = _lib.lib()
+    count = torch.empty((N,), dtype=I64, device=dev)
+    fptr = dptr(faces, I32, allow_none=True)
+
+    def fit(h):
+        dims = tuple(int((b - a) / h // 1) + 1 for a, b in zip(lo, hi))
+        if max(dims) > MESH_GRID_MAX_AXIS or dims[0] * dims[1] * dims[2] > MESH_GRID_MAX_CELLS:
+            return dims, None
+        check(L.clmgs_mesh_bin_count(stream(), V, N, dptr(verts, F32), fptr, lo[0], lo[1], lo[2], h, *dims, dptr(count, I64)))
+        pairs = int(count.sum())
+        return dims, pairs if pairs * MESH_GRID_PAIR_BYTES <= grid_gb * 1e9 else None
+
+    h0 = cell if cell is not None else _mesh_grid_default_cell(lo, hi, used, corners)
+    h = h0
+    for _ in range(400):
+        dims, pairs = fit(h)
+        if pairs is not None:
+            break
+        if dims == (1, 1, 1):  # (one cell lists every primitive once: nothing coarser exists)
+            raise ValueError(f"{what}: no cell size fits grid_gb {grid_gb:g}: {g.primitives} primitives need "
+                             f"{g.primitives * MESH_GRID_PAIR_BYTES} B")
+        h *= 1.25
+    if pairs is None:
+        raise ValueError(f"{what}: no cell size up to {h:g} fits the limits of the grid")
+    if cell is not None and h != h0:
+        raise ValueError(f"{what}: {name} {cell:g} breaks the limits of the grid (2^27 cells, 2^20 along an axis, pairs "
+                         f"of {MESH_GRID_PAIR_BYTES} B within grid_gb {grid_gb:g}); {h:g} fits")
+    g.origin, g.h, g.dims, g.pairs = tuple(lo), h, dims, pairs
+    offsets = torch.zeros((N + 1,), dtype=I64, device=dev)
+    torch.cumsum(count, 0, out=offsets[1:])
+    cells = torch.empty((pairs,), dtype=I64, device=dev)
+    prims = torch.empty((pairs,), dtype=I32, device=dev)
+    check(L.clmgs_mesh_bin_emit(stream(), V, N, dptr(verts, F32), fptr, lo[0], lo[1], lo[2], h, *dims, dptr(offsets, I64),
+                                pairs, dptr(cells, I64), dptr(prims, I32)))
+    cells, order = torch.sort(cells, stable=True)
+    g.pair_prim = prims[order].contiguous()
+    n_cells = dims[0] * dims[1] * dims[2]
+    g.cell_start = torch.searchsorted(cells, torch.arange(n_cells + 1, dtype=I64, device=dev)).contiguous()
+    return g
+
+
+@torch.no_grad()
+def mesh_distance(points, grid, max_distance=float("inf"), with_evaluated=False):
+    """The exact distance from every point to its nearest primitive (csrc/mesh_distance.hip, one lane per query): points
+    float32 [P,3] on the device, grid from mesh_distance_grid -> (dist float32 [P], prim int32 [P]) on the device: the
+    minimum over ALL primitives of the float64 distance of csrc/mesh_distance_math.h, rounded to float32, and the index of
+    the primitive, the smallest on ties; (+inf, -1) where that distance exceeds max_distance, where the grid has no
+    primitive, and for a point with a non-finite coordinate.  The result does not depend on the grid's cell size.  The
+    queries are sorted by cell for the launch and the results scattered back (torch).  with_evaluated: a third item,
+    int32 [P], the number of primitives each lane evaluated."""
+    what = "mesh_distance"
+    if not isinstance(grid, MeshDistanceGrid):
+        raise ValueError(f"{what}: grid must come from mesh_distance_grid, got {type(grid).__name__}")
+    max_distance = _mesh_number(max_distance, what, "max_distance", allow_inf=True)
+    _mesh_dev(points, F32, (None, 3), what, "points")
+    if points.device != grid.verts.device:
+        raise _lib.ClmgsError(f"{what}: points are on {points.device}, the grid on {grid.verts.device}")
+    P, dev = int(points.shape[0]), points.device
+    dist = torch.full((P,), float("inf"), dtype=F32, device=dev)
+    prim = torch.full((P,), -1, dtype=I32, device=dev)
+    evaluated = torch.zeros((P,), dtype=I32, device=dev)
+    if P and grid.pairs:
+        q = torch.nan_to_num(points.double(), nan=0.0, posinf=0.0, neginf=0.0)
+        key = torch.zeros((P,), dtype=I64, device=dev)
+        for axis in (2, 1, 0):
+            i = torch.floor((q[:, axis] - grid.origin[axis]) / grid.h).clamp_(0, grid.dims[axis] - 1).long()
+            key = key * grid.dims[axis] + i
+        order = torch.sort(key).indices
+        sorted_points = points[order].contiguous()
+        d, p, e = torch.empty_like(dist), torch.empty_like(prim), torch.empty_like(evaluated)
+        check(_lib.lib().clmgs_mesh_distance(
+            stream(), P, dptr(sorted_points, F32), int(grid.verts.shape[0]), grid.n, dptr(grid.verts, F32),
+            dptr(grid.faces, I32, allow_none=True), grid.origin[0], grid.origin[1], grid.origin[2], grid.h, *grid.dims,
+            dptr(grid.cell_start, I64), dptr(grid.pair_prim, I32), grid.pairs, max_distance, dptr(d, F32), dptr(p, I32),
+            dptr(e, I32) if with_evaluated else None))
+        dist[order], prim[order] = d, p
+        if with_evaluated:
+            evaluated[order] = e
+    return (dist, prim, evaluated) if with_evaluated else (dist, prim)
+
+
 # ------------------------------------------------------------ MCMC densification
 def _f32_dev(t, shape, what):
     assert t.is_cuda and t.dtype == F32 and t.is_contiguous() and tuple(t.shape) == tuple(shape), \

@@ -166,3 +166,135 @@ def load_mesh_ply(path, with_normals=False):
     if vertex is _MESH_VERTEX_NORMALS:
         normals = np.stack([v["nx"], v["ny"], v["nz"]], axis=1).astype(np.float32).reshape(-1, 3)
     return verts, colours, faces, normals
+
+
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2",
+              "uint16": "u2", "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4",
+              "double": "f8", "float64": "f8"}
+
+
+def _reference_header(f, path):
+    """-> (format, [(element, count, [property tokens after the word `property`])]) of a .ply, in file order."""
+    if f.readline().strip() != b"ply":
+        raise ValueError(f"{path}: not a .ply file")
+    fmt, elements = None, []
+    while True:
+        line = f.readline()
+        if not line:
+            raise ValueError(f"{path}: truncated: the header has no end_header")
+        tok = line.decode("ascii", "replace").split()
+        if tok[:1] == ["end_header"]:
+            break
+        if tok[:1] == ["format"]:
+            fmt = tok[1] if len(tok) > 1 else None
+        elif tok[:1] == ["element"] and len(tok) == 3:
+            elements.append((tok[1], int(tok[2]), []))
+        elif tok[:1] == ["property"] and elements:
+            elements[-1][2].append(tok[1:])
+    if fmt == "binary_big_endian":
+        raise ValueError(f"{path}: a big-endian .ply: only binary_little_endian and ascii are read")
+    if fmt not in ("binary_little_endian", "ascii"):
+        raise ValueError(f"{path}: format {fmt!r}: only binary_little_endian and ascii are read")
+    return fmt, elements
+
+
+def load_reference_ply(path):
+    """A reference scan or mesh for mesh_eval -> (points float32 [P,3], faces int32 [F,3] or None).  Reads a .ply in
+    binary_little_endian or ascii format whose vertex element has x y z as float or double among any other scalar
+    properties (skipped by their declared sizes) and, optionally, a face element with a list property vertex_indices or
+    vertex_index of an integer type.  Refused by name (ValueError): big-endian files, a face with other than 3 corners, a
+    missing x, y or z, a truncated file, a face index outside the vertices.  A file without a face element, or with zero
+    faces, gives faces = None."""
+    with open(path, "rb") as f:
+        fmt, elements = _reference_header(f, path)
+        body = f.read()
+    points = faces = None
+    tokens = body.split() if fmt == "ascii" else None
+    pos = 0  # in bytes (binary) or tokens (ascii)
+    for name, count, props in elements:
+        lists = [p for p in props if p[0] == "list"]
+        for p in props:
+            for t in (p[1:3] if p[0] == "list" else p[:1]):
+                if t not in _PLY_TYPES:
+                    raise ValueError(f"{path}: element {name}: unknown property type {t!r}")
+        if name == "face" and (len(lists) != 1 or lists[0][3] not in ("vertex_indices", "vertex_index")
+                               or _PLY_TYPES[lists[0][2]][0] not in "iu" or _PLY_TYPES[lists[0][1]][0] not in "iu"):
+            raise ValueError(f"{path}: the face element needs one list property vertex_indices (or vertex_index) of an "
+                             f"integer type, got {[' '.join(p) for p in props]}")
+        if name != "face" and lists:
+            if points is not None and (faces is not None or not any(e[0] == "face" for e in elements)):
+                break  # nothing that is read comes after it
+            raise ValueError(f"{path}: element {name} has a list property and comes before the data that is read")
+        # the row: scalar fields, with the face's list as a count and three indices
+        fields = []
+        for k, p in enumerate(props):
+            if p[0] == "list":
+                fields += [("_n", "<" + _PLY_TYPES[p[1]]), ("_v", "<" + _PLY_TYPES[p[2]], (3,))]
+            else:
+                fields.append((f"_{k}_{p[1]}" if p[1] in ("_n", "_v") else p[1], "<" + _PLY_TYPES[p[0]]))
+        if len({fd[0] for fd in fields}) != len(fields):
+            raise ValueError(f"{path}: element {name} declares a property twice")
+        row = np.dtype(fields)
+        if name == "vertex":
+            missing = [c for c in "xyz" if c not in row.names]
+            if missing:
+                raise ValueError(f"{path}: the vertex element has no property {', '.join(missing)}")
+            if any(row[c].kind != "f" for c in "xyz"):
+                raise ValueError(f"{path}: x, y and z must be float or double")
+        if fmt == "ascii":
+            width = sum(int(np.prod(row[n].shape)) if row[n].shape else 1 for n in row.names) if row.names else 0
+            chunk = tokens[pos:pos + count * width]
+            if name == "face" and count:
+                n_col = [n for n in row.names].index("_n")  # (scalars before the list are one token each)
+                bad = len(chunk) < count * width
+                try:
+                    first = np.array(chunk[n_col::width], dtype=np.float64) if not bad else None
+                except ValueError:
+                    first = None
+                if bad or first is None or not (first == 3).all():
+                    j = pos  # walk the rows to name the reason
+                    for _ in range(count):
+                        if j + n_col >= len(tokens):
+                            raise ValueError(f"{path}: truncated: element face ends early")
+                        n = int(float(tokens[j + n_col]))
+                        if n != 3:
+                            raise ValueError(f"{path}: a face with {n} corners: only triangles are read")
+                        j += width
+                    raise ValueError(f"{path}: truncated: element face ends early")
+            if len(chunk) < count * width:
+                raise ValueError(f"{path}: truncated: element {name} ends early")
+            pos += count * width
+            try:
+                table = np.array(chunk, dtype=np.float64).reshape(count, width)
+            except ValueError:
+                raise ValueError(f"{path}: element {name}: a value that is no number")
+            data, col = {}, 0
+            for n in row.names:
+                w = 3 if row[n].shape else 1
+                data[n] = table[:, col:col + w] if w == 3 else table[:, col]
+                col += w
+        else:
+            size = count * row.itemsize
+            if name == "face" and count:  # a face that is no triangle shifts every row after it: look at the counts in turn
+                n_off, n_dt = row.fields["_n"][1], row.fields["_n"][0]
+                whole = min(count, (len(body) - pos) // row.itemsize)
+                ns = np.ndarray((whole,), dtype=n_dt, buffer=body, offset=pos + n_off, strides=(row.itemsize,)) if whole else \
+                    np.zeros((0,), dtype=n_dt)
+                if not (ns == 3).all():
+                    raise ValueError(f"{path}: a face with {int(ns[np.nonzero(ns != 3)[0][0]])} corners: only triangles are read")
+            if pos + size > len(body):
+                raise ValueError(f"{path}: truncated: element {name} ends early")
+            data = np.frombuffer(body, dtype=row, count=count, offset=pos)
+            pos += size
+        if name == "vertex":
+            points = np.ascontiguousarray(np.stack([data["x"], data["y"], data["z"]], axis=1).astype(np.float32)).reshape(-1, 3)
+        elif name == "face":
+            idx = np.asarray(data["_v"]).reshape(-1, 3)
+            if points is None:
+                raise ValueError(f"{path}: the face element comes before the vertex element")
+            if len(idx) and (idx.min() < 0 or idx.max() >= len(points)):
+                raise ValueError(f"{path}: a face index lies outside [0, {len(points)})")
+            faces = np.ascontiguousarray(idx.astype(np.int32)).reshape(-1, 3)
+    if points is None:
+        raise ValueError(f"{path}: no vertex element")
+    return points, (faces if faces is not None and len(faces) else None)

@@ -5,6 +5,7 @@
         [--alpha_min 0.5] [--depth_max D] [--min_weight 2] [--grid_gb 16] [--antialiased] [--undistort --undistort_zoom Z]
         [--depth_mode expected|median|ray] [--min_component_faces N] [--keep_components K] [--sparse] [--decimate_cell C]
         [--smooth_iterations N --smooth_lambda 0.5 --smooth_mu -0.53] [--normals] [--eval]
+        [--reference REF.ply --eval_tau T [T ...] --eval_spacing S --eval_max_distance D]
         [--clm_offload | --naive_offload | --no_offload]
 
 renders every selected training camera of the scene through the strategy's own eval entry (render_mode "RGB+ED":
@@ -39,6 +40,12 @@ non-finite value is refused by name; 0, the default, changes nothing.  The decim
 stay; the decimation's quadrics then see denoised faces.  --normals writes the area-weighted vertex normals of the FINAL
 mesh into the file (x y z nx ny nz red green blue).  The .json gains "smoothing" (the report) and "normals": true, the
 log line " smoothed N x (lam, mu)" and " normals", each only with its flag; without them every file is what it was.
+--reference REF.ply --eval_tau T [T ...] evaluates the final mesh, after it is written, against a reference scan or mesh in
+the same frame (mesh_eval.evaluate, csrc/mesh_distance.hip; DESIGN.md section 3, "Mesh evaluation"): accuracy, completeness,
+chamfer distance and precision / recall / F-score per tau, with --eval_spacing (the smallest tau / 2) and
+--eval_max_distance (10 x the largest tau).  The .json gains "evaluation" (the report) and the log line " F <F>@tau <T>" per
+tau; mesh.ply is the file it was.  One of --reference and --eval_tau without the other, and a bad value, are refused by
+name before anything is loaded.
 """
 import argparse
 import json
@@ -48,7 +55,7 @@ import time
 
 import torch
 
-from . import io_ply, mesh_clean, mesh_decimate, mesh_smooth, tsdf, utils
+from . import io_ply, mesh_clean, mesh_decimate, mesh_eval, mesh_smooth, tsdf, utils
 from .render_ortho import map_frame, percentile_sorted
 from .render_trajectory import _find_ply, depth_render_mode, eval_one_cam
 
@@ -73,7 +80,8 @@ def json_path(mesh_path):
 def build_mesh(gaussians, cameras, args, out_path, voxel, frame=None, bounds=None, trunc_voxels=4.0, every=1, alpha_min=0.5,
                depth_max=None, min_weight=2.0, grid_gb=16.0, near=0.01, background=None, log=None, depth_mode="expected",
                min_component_faces=0, keep_components=0, sparse=False, decimate_cell=0.0, smooth_iterations=0,
-               smooth_lambda=0.5, smooth_mu=-0.53, normals=False):
+               smooth_lambda=0.5, smooth_mu=-0.53, normals=False, reference=None, eval_taus=None, eval_spacing=None,
+               eval_max_distance=None):
     """Renders cameras[::every] from `gaussians` through the eval entry of the strategy `args` names, fuses them, extracts
     and writes out_path and its .json.  -> the dict written to the .json.  The global image size (utils.set_img_size)
     must be the cameras' size.  depth_mode "expected" fuses the "RGB+ED" depth, "median" the "RGB+MD" one, "ray" the "RGB+RD"
@@ -84,7 +92,9 @@ def build_mesh(gaussians, cameras, args, out_path, voxel, frame=None, bounds=Non
     cleanup, which sees the full-resolution mesh (the .json gains "decimation" and the log line its counts only when it is
     on).  smooth_iterations / smooth_lambda / smooth_mu: mesh_smooth.smooth between the cleanup and the decimation;
     normals: the vertex normals of the final mesh in the file (the .json gains "smoothing" / "normals" and the log line
-    its words only then)."""
+    its words only then).  reference (a .ply path) with eval_taus: mesh_eval.evaluate of the final mesh against it, after
+    the mesh is written (the .json gains "evaluation" and the log line " F <F>@tau <T>" only then)."""
+    check_eval_options(reference, eval_taus, eval_spacing, eval_max_distance)
     decimate_cell = mesh_decimate.check_cell(decimate_cell)
     smooth_iterations, smooth_lambda, smooth_mu = mesh_smooth.check_options(smooth_iterations, smooth_lambda, smooth_mu)
     min_component_faces, keep_components = mesh_clean.check_options(min_component_faces, keep_components,
@@ -151,29 +161,47 @@ def build_mesh(gaussians, cameras, args, out_path, voxel, frame=None, bounds=Non
     if decimation is not None:
         meta = mesh_decimate.json_record(meta, decimation, verts.shape[0], faces.shape[0])
     meta = mesh_smooth.json_record(meta, smoothing, bool(normals))
+    evaluation = None
+    if reference is not None:
+        ref_points, ref_faces = mesh_eval.load_reference(reference, verts.device)
+        evaluation = mesh_eval.evaluate(verts, faces, ref_points, ref_faces, eval_taus, eval_spacing, eval_max_distance,
+                                        names=mesh_eval.MODEL_NAMES)
+        meta = mesh_eval.json_record(meta, evaluation)
     with open(json_path(out_path), "w") as f:
         json.dump(meta, f, indent=1)
     log.write("mesh export: grid {} x {} x {} voxel {:g} cameras {} render {:.1f} cameras/s integration {:.1f} cameras/s "
-              "extraction {:.3f} s vertices {} faces {}{}{}{}{} -> {}\n".format(
+              "extraction {:.3f} s vertices {} faces {}{}{}{}{}{} -> {}\n".format(
                   volume.nx, volume.ny, volume.nz, volume.voxel, len(cams), len(cams) / max(t_render, 1e-9),
                   len(cams) / max(t_fuse, 1e-9), t_extract, meta["vertices"], meta["faces"],
                   "" if report is None else " components {} kept {}".format(report["components"], report["components_kept"]),
                   "" if not sparse else " sparse bricks {} of {} pool {:.3f} GB marking {:.1f} cameras/s".format(
                       volume.S, volume.bricks_total, meta["sparse"]["pool_gb"], len(cams) / max(t_mark, 1e-9)),
                   "" if decimation is None else mesh_decimate.log_words(decimation),
-                  mesh_smooth.log_words(smoothing, bool(normals)),
+                  mesh_smooth.log_words(smoothing, bool(normals)), mesh_eval.log_words(evaluation),
                   out_path))
     return meta
 
 
+def check_eval_options(reference=None, eval_taus=None, eval_spacing=None, eval_max_distance=None):
+    """--reference and --eval_tau come together; the values are mesh_eval.check_options' (ValueError by name)."""
+    if reference is None and eval_taus is None:
+        if eval_spacing is not None or eval_max_distance is not None:
+            raise ValueError("--eval_spacing and --eval_max_distance have effect only with --reference and --eval_tau")
+        return
+    if reference is None or eval_taus is None:
+        raise ValueError("--reference and --eval_tau come together: give both, or neither")
+    mesh_eval.check_options(eval_taus, eval_spacing, eval_max_distance, names=mesh_eval.MODEL_NAMES)
+
+
 def check_options(voxel, bounds=None, grid_gb=16.0, trunc_voxels=4.0, min_weight=2.0, every=1, depth_mode="expected",
                   min_component_faces=0, keep_components=0, sparse=False, decimate_cell=0.0, smooth_iterations=0,
-                  smooth_lambda=0.5, smooth_mu=-0.53):
+                  smooth_lambda=0.5, smooth_mu=-0.53, reference=None, eval_taus=None, eval_spacing=None, eval_max_distance=None):
     """The refusals that need nothing loaded (ValueError by name); with sparse the brick-grid limits take the place of the
     dense ones."""
     mesh_clean.check_options(min_component_faces, keep_components, ("--min_component_faces", "--keep_components"))
     mesh_decimate.check_cell(decimate_cell)
     mesh_smooth.check_options(smooth_iterations, smooth_lambda, smooth_mu)
+    check_eval_options(reference, eval_taus, eval_spacing, eval_max_distance)
     tsdf.grid_shape((0, 0, 0, 1, 1, 1), voxel)  # (--voxel alone)
     depth_render_mode(depth_mode)
     if not trunc_voxels > 0:
@@ -225,6 +253,13 @@ def main(argv=None):
                     help="the factor of a pass's second step, in [-1, 0]; 0 = plain Laplacian smoothing")
     ap.add_argument("--normals", action="store_true",
                     help="write area-weighted vertex normals of the final mesh (nx ny nz) into the file")
+    ap.add_argument("--reference", default=None, metavar="PLY",
+                    help="evaluate the final mesh against this reference scan or mesh (same frame); needs --eval_tau")
+    ap.add_argument("--eval_tau", type=float, nargs="+", default=None, metavar="T", help="the distance thresholds of the F-score")
+    ap.add_argument("--eval_spacing", type=float, default=None, metavar="S",
+                    help="the sampling distance of the evaluation (default: the smallest tau / 2)")
+    ap.add_argument("--eval_max_distance", type=float, default=None, metavar="D",
+                    help="distances are capped here (default: 10 x the largest tau)")
     ap.add_argument("--sparse", action="store_true",
                     help="a brick-allocated volume: the same mesh.ply, on boxes far beyond 2^31 voxels (renders every camera twice)")
     ap.add_argument("--antialiased", action="store_true", help="for a model trained with trainer --antialiased")
@@ -239,7 +274,7 @@ def main(argv=None):
     try:  # refusals before anything is loaded or written
         check_options(a.voxel, a.bounds, a.grid_gb, a.trunc_voxels, a.min_weight, a.every, a.depth_mode,
                       a.min_component_faces, a.keep_components, a.sparse, a.decimate_cell, a.smooth_iterations,
-                      a.smooth_lambda, a.smooth_mu)
+                      a.smooth_lambda, a.smooth_mu, a.reference, a.eval_tau, a.eval_spacing, a.eval_max_distance)
         frame = map_frame(a.up, a.east)
     except ValueError as e:
         raise SystemExit(str(e))
@@ -271,7 +306,8 @@ def main(argv=None):
                    a.depth_max, a.min_weight, a.grid_gb, depth_mode=a.depth_mode,
                    min_component_faces=a.min_component_faces, keep_components=a.keep_components, sparse=a.sparse,
                    decimate_cell=a.decimate_cell, smooth_iterations=a.smooth_iterations, smooth_lambda=a.smooth_lambda,
-                   smooth_mu=a.smooth_mu, normals=a.normals)
+                   smooth_mu=a.smooth_mu, normals=a.normals, reference=a.reference, eval_taus=a.eval_tau,
+                   eval_spacing=a.eval_spacing, eval_max_distance=a.eval_max_distance)
     except ValueError as e:  # (the size of a grid whose bounds come from the model)
         raise SystemExit(str(e))
     return 0

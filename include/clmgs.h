@@ -1158,6 +1158,48 @@ int clmgs_mesh_smooth_step(void* stream, int V, int F, const float* verts_in, co
 int clmgs_mesh_vertex_normals(void* stream, int V, int F, const float* verts, const int32_t* faces, const int64_t* order,
                               const int64_t* start, float* normals);
 
+/* ---- mesh evaluation (csrc/mesh_distance.hip, csrc/mesh_distance_math.h; clm_gs_amd/mesh_eval.py): DESIGN.md section 3,
+ * "Mesh evaluation".  verts float32 [V,3] and faces int32 [F,3] on the device, 1 <= V < 2^31, 1 <= F < 2^31.  All
+ * arithmetic is float64 without contraction, in the order of csrc/mesh_distance_math.h.
+ *  - clmgs_mesh_sample_count, one lane per face: area float64 [F] = 0.5 sqrt(|(b - a) x (c - a)|^2) and count int64 [F] =
+ *    min(max(ceil(area / spacing^2), 1), 2^31), or 0 for a face whose area is zero or not finite (no primitive) or that
+ *    names a vertex outside [0, V) (area 0).
+ *  - clmgs_mesh_sample_emit, one lane per sample: offsets int64 [F+1] the exclusive prefix sum of count, sample_face
+ *    int32 [S] the face of every sample (ascending), 1 <= S < 2^31.  Sample s of face f is number k = s - offsets[f] of
+ *    n = offsets[f+1] - offsets[f]: u = frac(0.5 + (k+1) 0.7548776662466927), v = frac(0.5 + (k+1) 0.5698402909980532),
+ *    both replaced by one minus themselves when u + v > 1; points float32 [S,3] = float32((a + u (b - a)) + v (c - a)),
+ *    weight float64 [S] = area[f] / n.  A sample whose face or number is out of range gets zeros.
+ *  - The primitive grid: origin (ox, oy, oz), cell size h > 0, gx x gy x gz cells, each at most 2^20 and at most 2^27 in
+ *    all; the cell of a coordinate along an axis is clamp(floor((x - o) / h), 0, g - 1).  The primitives are the N = F
+ *    triangles, or, with faces == NULL, the N = V points.  A face without a positive finite area and a point with a
+ *    non-finite coordinate are not primitives.  clmgs_mesh_bin_count, one lane per primitive, writes count int64 [N]: the
+ *    number of cells in the index range of its bounding box (0 for what is no primitive).  clmgs_mesh_bin_emit writes, at
+ *    offsets[i] (int64 [N+1], the exclusive prefix sum), the pairs cell int64 [pairs] = (z gy + y) gx + x and prim int32
+ *    [pairs] = i of that range, x fastest.
+ *  - clmgs_mesh_distance, one lane per query: queries float32 [P,3]; cell_start int64 [gx gy gz + 1] and pair_prim int32
+ *    [pairs] the pairs sorted by cell.  The lane walks growing Chebyshev shells of cells around the clamped cell of its
+ *    query and keeps the smallest squared distance (md_closest_d2 / md_point_d2), ties to the smaller primitive index; it
+ *    stops after shell R once best < (R h (1 - 2^-16))^2 or R h (1 - 2^-16) > max_distance.  dist float32 [P] =
+ *    float32(sqrt(best)), prim int32 [P]; (+inf, -1) when sqrt(best) > max_distance, when there is no primitive, and for
+ *    a query with a non-finite coordinate.  The result equals the minimum over ALL primitives for any h.  evaluated
+ *    int32 [P] (or NULL): the number of primitives the lane evaluated.
+ * Every entry returns CLMGS_EINVAL, before anything is launched, for a size outside its range, a spacing, cell size or
+ * max_distance that is not positive (or NaN), a grid beyond the limits and a null or misaligned pointer.  An index read
+ * from memory that lies outside its array is skipped by every kernel. */
+int clmgs_mesh_sample_count(void* stream, int V, int F, const float* verts, const int32_t* faces, double spacing,
+                            double* area, int64_t* count);
+int clmgs_mesh_sample_emit(void* stream, int V, int F, const float* verts, const int32_t* faces, const double* area,
+                           const int64_t* offsets, const int32_t* sample_face, int64_t S, float* points, double* weight);
+int clmgs_mesh_bin_count(void* stream, int V, int N, const float* verts, const int32_t* faces, double ox, double oy,
+                         double oz, double h, int gx, int gy, int gz, int64_t* count);
+int clmgs_mesh_bin_emit(void* stream, int V, int N, const float* verts, const int32_t* faces, double ox, double oy, double oz,
+                        double h, int gx, int gy, int gz, const int64_t* offsets, int64_t pairs, int64_t* cell,
+                        int32_t* prim);
+int clmgs_mesh_distance(void* stream, int64_t P, const float* queries, int V, int N, const float* verts,
+                        const int32_t* faces, double ox, double oy, double oz, double h, int gx, int gy, int gz,
+                        const int64_t* cell_start, const int32_t* pair_prim, int64_t pairs, double max_distance, float* dist,
+                        int32_t* prim, int32_t* evaluated);
+
 /* ---- pinned host memory  (numba.cuda.pinned_array at clm_offload/gaussian_model.py:34-44) */
 void* clmgs_pinned_alloc(size_t bytes);
 int clmgs_pinned_free(void* p);
