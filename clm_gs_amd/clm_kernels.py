@@ -666,101 +666,6 @@ def _tsdf_grid(grid):
     return nx, ny, nz
 
 
-@torch.no_grad()
-def tsdf_integrate(grid, depth, alpha, rgb, cams, near=0.01, depth_max=float("inf"), alpha_min=0.5, trunc=1.0, cull=True):
-    """Fuses cameras into a TSDF volume in place (csrc/tsdf.hip; DESIGN.md section 3, "Mesh export"): grid float32
-    [6,nz,ny,nx] (tsum, wsum, cr, cg, cb, cw); depth [B,H,W] (expected depth), alpha [B,H,W], rgb [B,3,H,W], float32 on the
-    device; cams float64 [B,16] on the HOST (numpy or tensor): per camera the 3x4 matrix from grid coordinates (voxel
-    (i,j,k) at (i+0.5, j+0.5, k+0.5)) to camera space, then fx, fy, cx, cy; trunc in camera-space units.  More than 16
-    cameras go in launches of 16, in order: the result does not depend on how they are split.  `cull`: the brick-level
-    frustum test (the same bits with and without).  Returns grid."""
-    import numpy as np
-    nx, ny, nz = _tsdf_grid(grid)
-    cams = np.ascontiguousarray(cams.numpy() if isinstance(cams, torch.Tensor) else cams, dtype=np.float64)
-    if not (isinstance(depth, torch.Tensor) and depth.dim() == 3 and cams.shape == (depth.shape[0], 16) and depth.shape[0] >= 1):
-        raise _lib.ClmgsError(f"tsdf_integrate: depth [B,H,W] and cams [B,16] expected, got {tuple(getattr(depth, 'shape', ()))} "
-                              f"and {cams.shape}")
-    B, H, W = (int(v) for v in depth.shape)
-    for t, shape, what in ((depth, (B, H, W), "depth"), (alpha, (B, H, W), "alpha"), (rgb, (B, 3, H, W), "rgb")):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.dtype == F32 and tuple(t.shape) == shape
-                and t.device == grid.device):
-            raise _lib.ClmgsError(f"tsdf_integrate: {what} must be a contiguous float32 {shape} tensor on {grid.device}, got "
-                                  f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
-    trunc32 = float(torch.tensor(float(trunc), dtype=F32))
-    if not (_finite(trunc32) and trunc32 > 0):
-        raise ValueError(f"tsdf_integrate: trunc must be positive and finite, got {trunc}")
-    inv_trunc = float(torch.tensor(1.0, dtype=F32) / torch.tensor(trunc32, dtype=F32))  # the float32 quotient
-    L = _lib.lib()
-    for b0 in range(0, B, TSDF_MAX_B):
-        b1 = min(B, b0 + TSDF_MAX_B)
-        rec = (ctypes.c_double * (16 * (b1 - b0)))(*cams[b0:b1].reshape(-1))
-        check(L.clmgs_tsdf_integrate(stream(), nx, ny, nz, dptr(grid, F32), b1 - b0, H, W, dptr(depth[b0:b1], F32),
-                                     dptr(alpha[b0:b1], F32), dptr(rgb[b0:b1], F32), rec, float(near), float(depth_max),
-                                     float(alpha_min), trunc32, inv_trunc, 1 if cull else 0))
-    return grid
-
-
-@torch.no_grad()
-def tsdf_extract(grid, min_weight, grid_to_world):
-    """Naive Surface Nets on a TSDF volume (csrc/tsdf.hip): a voxel is valid iff wsum >= min_weight and inside iff
-    tsum < 0; every cell of eight valid voxels whose flags differ gets one vertex, every sign-changing grid edge whose four
-    cells are active one quad (two triangles).  grid_to_world: float64 [3,4] on the host, from grid coordinates to the
-    frame the vertices are wanted in.  -> (verts float32 [V,3], colours uint8 [V,3], faces int32 [F,3]) on the device,
-    vertices in cell order, faces in (owner voxel, axis) order; V = F = 0 for a volume without a surface."""
-    import numpy as np
-    nx, ny, nz = _tsdf_grid(grid)
-    g2w = np.ascontiguousarray(grid_to_world.numpy() if isinstance(grid_to_world, torch.Tensor) else grid_to_world,
-                               dtype=np.float64)
-    if g2w.shape != (3, 4) or not np.isfinite(g2w).all():
-        raise ValueError(f"tsdf_extract: grid_to_world must be a finite 3x4 matrix, got shape {g2w.shape}")
-    mw = float(torch.tensor(float(min_weight), dtype=F32))
-    if not (_finite(mw) and mw > 0):
-        raise ValueError(f"tsdf_extract: min_weight must be positive and finite, got {min_weight}")
-    L, dev, n = _lib.lib(), grid.device, nx * ny * nz
-    empty = (torch.empty((0, 3), dtype=F32, device=dev), torch.empty((0, 3), dtype=U8, device=dev),
-             torch.empty((0, 3), dtype=I32, device=dev))
-    count = torch.empty((n,), dtype=I32, device=dev)
-    check(L.clmgs_tsdf_cells(stream(), nx, ny, nz, dptr(grid, F32), mw, dptr(count, I32)))
-    cell_scan = torch.cumsum(count, 0, dtype=I32)
-    V = int(cell_scan[-1])
-    if V == 0:
-        return empty
-    verts = torch.empty((V, 3), dtype=F32, device=dev)
-    colours = torch.empty((V, 3), dtype=U8, device=dev)
-    rec = (ctypes.c_double * 12)(*g2w.reshape(-1))
-    check(L.clmgs_tsdf_vertices(stream(), nx, ny, nz, dptr(grid, F32), dptr(cell_scan, I32), V, rec, dptr(verts, F32),
-                                dptr(colours, U8)))
-    check(L.clmgs_tsdf_quad_count(stream(), nx, ny, nz, dptr(grid, F32), mw, dptr(cell_scan, I32), dptr(count, I32)))
-    Q = int(count.sum(dtype=I64))
-    if Q >= 1 << 30:
-        raise _lib.ClmgsError(f"tsdf_extract: {Q} quads, 2^30 at the most: extract with a larger voxel or a smaller box")
-    if Q == 0:
-        return verts, colours, empty[2]
-    quad_scan = torch.cumsum(count, 0, dtype=I32)
-    del count
-    faces = torch.empty((2 * Q, 3), dtype=I32, device=dev)
-    check(L.clmgs_tsdf_quads(stream(), nx, ny, nz, dptr(grid, F32), mw, dptr(cell_scan, I32), dptr(quad_scan, I32), V, Q,
-                             dptr(faces, I32)))
-    return verts, colours, faces
-
-
-# ------------------------------------------------------------------ mesh export, sparse volume
-TSDF_BRICK = 8
-TSDF_MAX_BRICK_GRID = 1 << 30
-
-
-def tsdf_brick_grid(nx, ny, nz):
-    """(nbx, nby, nbz) of a grid of nx x ny x nz voxels in bricks of 8 x 8 x 8; sides below 2 and a brick grid above 2^30 are
-    refused by name."""
-    nx, ny, nz = int(nx), int(ny), int(nz)
-    if min(nx, ny, nz) < 2 or max(nx, ny, nz) >= 1 << 31:
-        raise _lib.ClmgsError(f"tsdf: every side of the volume must be >= 2 and below 2^31, got {nx} x {ny} x {nz}")
-    nb = tuple(-(-v // TSDF_BRICK) for v in (nx, ny, nz))
-    if nb[0] * nb[1] * nb[2] > TSDF_MAX_BRICK_GRID:
-        raise _lib.ClmgsError(f"tsdf: the brick grid {nb[0]} x {nb[1]} x {nb[2]} of {nx} x {ny} x {nz} voxels is above 2^30 bricks")
-    return nb
-
-
 def _tsdf_images(what, dev, cams, depth, alpha, rgb=None):
     """The checks tsdf_integrate makes of its images and records -> (cams float64 [B,16], B, H, W)."""
     import numpy as np
@@ -786,6 +691,119 @@ def _tsdf_trunc(what, trunc):
     return trunc32
 
 
+
+def _tsdf_batches(cams, B):
+    """The launches of at most 16 cameras, in order -> (b0, b1, the ctypes record of cams[b0:b1]) each."""
+    for b0 in range(0, B, TSDF_MAX_B):
+        b1 = min(B, b0 + TSDF_MAX_B)
+        yield b0, b1, (ctypes.c_double * (16 * (b1 - b0)))(*cams[b0:b1].reshape(-1))
+
+
+def _tsdf_g2w(what, grid_to_world):
+    """A finite 3x4 grid_to_world (numpy or tensor, on the host) -> the ctypes record of its 12 doubles."""
+    import numpy as np
+    g2w = np.ascontiguousarray(grid_to_world.numpy() if isinstance(grid_to_world, torch.Tensor) else grid_to_world,
+                               dtype=np.float64)
+    if g2w.shape != (3, 4) or not np.isfinite(g2w).all():
+        raise ValueError(f"{what}: grid_to_world must be a finite 3x4 matrix, got shape {g2w.shape}")
+    return (ctypes.c_double * 12)(*g2w.reshape(-1))
+
+
+def _tsdf_min_weight(what, min_weight):
+    """min_weight as the float32 the kernels compare with."""
+    mw = float(torch.tensor(float(min_weight), dtype=F32))
+    if not (_finite(mw) and mw > 0):
+        raise ValueError(f"{what}: min_weight must be positive and finite, got {min_weight}")
+    return mw
+
+
+def _tsdf_surface(what, dev, n, cells, vertices, quad_count, quads):
+    """The sequence of the four Surface Nets passes (csrc/tsdf_extract.h) over n lane indices, with the two prefix sums and
+    the two readbacks between them.  The callables launch the passes of a volume: cells(count), vertices(cell_scan, V, verts,
+    colours), quad_count(cell_scan, count), quads(cell_scan, quad_scan, V, Q, faces).  -> (verts float32 [V,3], colours uint8
+    [V,3], faces int32 [2 Q,3]) in lane-index order; V = 0 and Q = 0 give empty tensors."""
+    empty = (torch.empty((0, 3), dtype=F32, device=dev), torch.empty((0, 3), dtype=U8, device=dev),
+             torch.empty((0, 3), dtype=I32, device=dev))
+    count = torch.empty((n,), dtype=I32, device=dev)
+    cells(count)
+    cell_scan = torch.cumsum(count, 0, dtype=I32)
+    V = int(cell_scan[-1])
+    if V == 0:
+        return empty
+    verts = torch.empty((V, 3), dtype=F32, device=dev)
+    colours = torch.empty((V, 3), dtype=U8, device=dev)
+    vertices(cell_scan, V, verts, colours)
+    quad_count(cell_scan, count)
+    Q = int(count.sum(dtype=I64))
+    if Q >= 1 << 30:
+        raise _lib.ClmgsError(f"{what}: {Q} quads, 2^30 at the most: extract with a larger voxel or a smaller box")
+    if Q == 0:
+        return verts, colours, empty[2]
+    quad_scan = torch.cumsum(count, 0, dtype=I32)
+    del count
+    faces = torch.empty((2 * Q, 3), dtype=I32, device=dev)
+    quads(cell_scan, quad_scan, V, Q, faces)
+    return verts, colours, faces
+
+
+@torch.no_grad()
+def tsdf_integrate(grid, depth, alpha, rgb, cams, near=0.01, depth_max=float("inf"), alpha_min=0.5, trunc=1.0, cull=True):
+    """Fuses cameras into a TSDF volume in place (csrc/tsdf.hip; DESIGN.md section 3, "Mesh export"): grid float32
+    [6,nz,ny,nx] (tsum, wsum, cr, cg, cb, cw); depth [B,H,W] (expected depth), alpha [B,H,W], rgb [B,3,H,W], float32 on the
+    device; cams float64 [B,16] on the HOST (numpy or tensor): per camera the 3x4 matrix from grid coordinates (voxel
+    (i,j,k) at (i+0.5, j+0.5, k+0.5)) to camera space, then fx, fy, cx, cy; trunc in camera-space units.  More than 16
+    cameras go in launches of 16, in order: the result does not depend on how they are split.  `cull`: the brick-level
+    frustum test (the same bits with and without).  Returns grid."""
+    nx, ny, nz = _tsdf_grid(grid)
+    cams, B, H, W = _tsdf_images("tsdf_integrate", grid.device, cams, depth, alpha, rgb)
+    trunc32 = _tsdf_trunc("tsdf_integrate", trunc)
+    inv_trunc = float(torch.tensor(1.0, dtype=F32) / torch.tensor(trunc32, dtype=F32))  # the float32 quotient
+    L = _lib.lib()
+    for b0, b1, rec in _tsdf_batches(cams, B):
+        check(L.clmgs_tsdf_integrate(stream(), nx, ny, nz, dptr(grid, F32), b1 - b0, H, W, dptr(depth[b0:b1], F32),
+                                     dptr(alpha[b0:b1], F32), dptr(rgb[b0:b1], F32), rec, float(near), float(depth_max),
+                                     float(alpha_min), trunc32, inv_trunc, 1 if cull else 0))
+    return grid
+
+
+@torch.no_grad()
+def tsdf_extract(grid, min_weight, grid_to_world):
+    """Naive Surface Nets on a TSDF volume (csrc/tsdf.hip): a voxel is valid iff wsum >= min_weight and inside iff
+    tsum < 0; every cell of eight valid voxels whose flags differ gets one vertex, every sign-changing grid edge whose four
+    cells are active one quad (two triangles).  grid_to_world: float64 [3,4] on the host, from grid coordinates to the
+    frame the vertices are wanted in.  -> (verts float32 [V,3], colours uint8 [V,3], faces int32 [F,3]) on the device,
+    vertices in cell order, faces in (owner voxel, axis) order; V = F = 0 for a volume without a surface."""
+    nx, ny, nz = _tsdf_grid(grid)
+    rec = _tsdf_g2w("tsdf_extract", grid_to_world)
+    mw = _tsdf_min_weight("tsdf_extract", min_weight)
+    L, g, dims = _lib.lib(), dptr(grid, F32), (nx, ny, nz)
+    return _tsdf_surface(
+        "tsdf_extract", grid.device, nx * ny * nz,
+        lambda count: check(L.clmgs_tsdf_cells(stream(), *dims, g, mw, dptr(count, I32))),
+        lambda cell_scan, V, verts, colours: check(L.clmgs_tsdf_vertices(
+            stream(), *dims, g, dptr(cell_scan, I32), V, rec, dptr(verts, F32), dptr(colours, U8))),
+        lambda cell_scan, count: check(L.clmgs_tsdf_quad_count(stream(), *dims, g, mw, dptr(cell_scan, I32), dptr(count, I32))),
+        lambda cell_scan, quad_scan, V, Q, faces: check(L.clmgs_tsdf_quads(
+            stream(), *dims, g, mw, dptr(cell_scan, I32), dptr(quad_scan, I32), V, Q, dptr(faces, I32))))
+
+
+# ------------------------------------------------------------------ mesh export, sparse volume
+TSDF_BRICK = 8
+TSDF_MAX_BRICK_GRID = 1 << 30
+
+
+def tsdf_brick_grid(nx, ny, nz):
+    """(nbx, nby, nbz) of a grid of nx x ny x nz voxels in bricks of 8 x 8 x 8; sides below 2 and a brick grid above 2^30 are
+    refused by name."""
+    nx, ny, nz = int(nx), int(ny), int(nz)
+    if min(nx, ny, nz) < 2 or max(nx, ny, nz) >= 1 << 31:
+        raise _lib.ClmgsError(f"tsdf: every side of the volume must be >= 2 and below 2^31, got {nx} x {ny} x {nz}")
+    nb = tuple(-(-v // TSDF_BRICK) for v in (nx, ny, nz))
+    if nb[0] * nb[1] * nb[2] > TSDF_MAX_BRICK_GRID:
+        raise _lib.ClmgsError(f"tsdf: the brick grid {nb[0]} x {nb[1]} x {nb[2]} of {nx} x {ny} x {nz} voxels is above 2^30 bricks")
+    return nb
+
+
 @torch.no_grad()
 def tsdf_mark(marks, shape, depth, alpha, cams_inv, near=0.01, depth_max=float("inf"), alpha_min=0.5, trunc=1.0, voxel_cam=1.0):
     """Marks, in place, the bricks of a sparse TSDF volume that the cameras can put a surface into (csrc/tsdf_sparse.hip;
@@ -807,9 +825,7 @@ def tsdf_mark(marks, shape, depth, alpha, cams_inv, near=0.01, depth_max=float("
         raise ValueError(f"tsdf_mark: voxel_cam must be positive and finite and trunc at most 4096 voxels, got {voxel_cam}, "
                          f"trunc {trunc}")
     L = _lib.lib()
-    for b0 in range(0, B, TSDF_MAX_B):
-        b1 = min(B, b0 + TSDF_MAX_B)
-        rec = (ctypes.c_double * (16 * (b1 - b0)))(*cams[b0:b1].reshape(-1))
+    for b0, b1, rec in _tsdf_batches(cams, B):
         check(L.clmgs_tsdf_mark(stream(), nx, ny, nz, dptr(marks), b1 - b0, H, W, dptr(depth[b0:b1], F32),
                                 dptr(alpha[b0:b1], F32), rec, float(near), float(depth_max), float(alpha_min), trunc32,
                                 float(voxel_cam)))
@@ -857,9 +873,7 @@ def tsdf_sparse_integrate(pool, bricks, shape, depth, alpha, rgb, cams, near=0.0
     trunc32 = _tsdf_trunc("tsdf_sparse_integrate", trunc)
     inv_trunc = float(torch.tensor(1.0, dtype=F32) / torch.tensor(trunc32, dtype=F32))  # the float32 quotient
     L = _lib.lib()
-    for b0 in range(0, B, TSDF_MAX_B):
-        b1 = min(B, b0 + TSDF_MAX_B)
-        rec = (ctypes.c_double * (16 * (b1 - b0)))(*cams[b0:b1].reshape(-1))
+    for b0, b1, rec in _tsdf_batches(cams, B):
         check(L.clmgs_tsdf_sparse_integrate(stream(), nx, ny, nz, S, dptr(bricks, I32), dptr(pool, F32), b1 - b0, H, W,
                                             dptr(depth[b0:b1], F32), dptr(alpha[b0:b1], F32), dptr(rgb[b0:b1], F32), rec,
                                             float(near), float(depth_max), float(alpha_min), trunc32, inv_trunc,
@@ -873,17 +887,10 @@ def tsdf_sparse_extract(pool, bricks, table, shape, min_weight, grid_to_world, w
     the vertices sorted by the dense linear index of their cell and the quads by (owner voxel, axis), on the device
     (torch.sort), so that the output is in tsdf_extract's order.  -> (verts, colours, faces), with want_keys also the
     sorted int64 keys of the vertices (cell index) and the quads (3 * voxel index + axis)."""
-    import numpy as np
     nx, ny, nz, S = _tsdf_sparse("tsdf_sparse_extract", shape, bricks, table, pool)
-    g2w = np.ascontiguousarray(grid_to_world.numpy() if isinstance(grid_to_world, torch.Tensor) else grid_to_world,
-                               dtype=np.float64)
-    if g2w.shape != (3, 4) or not np.isfinite(g2w).all():
-        raise ValueError(f"tsdf_sparse_extract: grid_to_world must be a finite 3x4 matrix, got shape {g2w.shape}")
-    mw = float(torch.tensor(float(min_weight), dtype=F32))
-    if not (_finite(mw) and mw > 0):
-        raise ValueError(f"tsdf_sparse_extract: min_weight must be positive and finite, got {min_weight}")
-    L, dev, n = _lib.lib(), pool.device, S * 512
-    rec = (ctypes.c_double * 12)(*g2w.reshape(-1))
+    rec = _tsdf_g2w("tsdf_sparse_extract", grid_to_world)
+    mw = _tsdf_min_weight("tsdf_sparse_extract", min_weight)
+    L, dev = _lib.lib(), pool.device
 
     def run(ps, count=None, cell_scan=None, quad_scan=None, V=0, Q=0, verts=None, colours=None, vkeys=None, faces=None,
             qkeys=None):
@@ -892,36 +899,28 @@ def tsdf_sparse_extract(pool, bricks, table, shape, min_weight, grid_to_world, w
                                           o(count, I32), o(cell_scan, I32), o(quad_scan, I32), V, Q, rec, o(verts, F32),
                                           o(colours, U8), o(vkeys, I64), o(faces, I32), o(qkeys, I64)))
 
-    e64 = torch.empty((0,), dtype=I64, device=dev)
-    empty = (torch.empty((0, 3), dtype=F32, device=dev), torch.empty((0, 3), dtype=U8, device=dev),
-             torch.empty((0, 3), dtype=I32, device=dev))
-    count = torch.empty((n,), dtype=I32, device=dev)
-    run(0, count=count)
-    cell_scan = torch.cumsum(count, 0, dtype=I32)
-    V = int(cell_scan[-1])
-    if V == 0:
-        return empty + (e64, e64) if want_keys else empty
-    verts = torch.empty((V, 3), dtype=F32, device=dev)
-    colours = torch.empty((V, 3), dtype=U8, device=dev)
-    vkeys = torch.empty((V,), dtype=I64, device=dev)
-    run(1, cell_scan=cell_scan, V=V, verts=verts, colours=colours, vkeys=vkeys)
-    vkeys, order = torch.sort(vkeys)
-    verts, colours = verts[order], colours[order]
-    run(2, count=count, cell_scan=cell_scan)
-    Q = int(count.sum(dtype=I64))
-    if Q >= 1 << 30:
-        raise _lib.ClmgsError(f"tsdf_sparse_extract: {Q} quads, 2^30 at the most: extract with a larger voxel or a smaller box")
-    if Q == 0:
-        return (verts, colours, empty[2], vkeys, e64) if want_keys else (verts, colours, empty[2])
-    quad_scan = torch.cumsum(count, 0, dtype=I32)
-    del count
-    faces = torch.empty((2 * Q, 3), dtype=I32, device=dev)
-    qkeys = torch.empty((Q,), dtype=I64, device=dev)
-    run(3, cell_scan=cell_scan, quad_scan=quad_scan, V=V, Q=Q, faces=faces, qkeys=qkeys)
-    new_id = torch.empty((V,), dtype=I32, device=dev)  # the inverse permutation: the rank of every vertex in the dense order
-    new_id[order] = torch.arange(V, dtype=I32, device=dev)
-    qkeys, qorder = torch.sort(qkeys)
-    faces = new_id[faces.long()].reshape(Q, 6)[qorder].reshape(2 * Q, 3).contiguous()
+    keys = {}  # of the vertices and the quads, as the passes wrote them
+
+    def vertices(cell_scan, V, verts, colours):
+        keys["v"] = torch.empty((V,), dtype=I64, device=dev)
+        run(1, cell_scan=cell_scan, V=V, verts=verts, colours=colours, vkeys=keys["v"])
+
+    def quads(cell_scan, quad_scan, V, Q, faces):
+        keys["q"] = torch.empty((Q,), dtype=I64, device=dev)
+        run(3, cell_scan=cell_scan, quad_scan=quad_scan, V=V, Q=Q, faces=faces, qkeys=keys["q"])
+
+    verts, colours, faces = _tsdf_surface("tsdf_sparse_extract", dev, S * 512, lambda count: run(0, count=count), vertices,
+                                          lambda cell_scan, count: run(2, count=count, cell_scan=cell_scan), quads)
+    V, Q = verts.shape[0], faces.shape[0] // 2
+    vkeys = qkeys = torch.empty((0,), dtype=I64, device=dev)
+    if V:
+        vkeys, order = torch.sort(keys["v"])
+        verts, colours = verts[order], colours[order]
+    if Q:
+        new_id = torch.empty((V,), dtype=I32, device=dev)  # the inverse permutation: the rank of every vertex in the dense order
+        new_id[order] = torch.arange(V, dtype=I32, device=dev)
+        qkeys, qorder = torch.sort(keys["q"])
+        faces = new_id[faces.long()].reshape(Q, 6)[qorder].reshape(2 * Q, 3).contiguous()
     return (verts, colours, faces, vkeys, qkeys) if want_keys else (verts, colours, faces)
 
 

@@ -123,4 +123,22 @@ static inline bool ts_apart(const void* a, uint64_t na, const void* b, uint64_t 
 
 static inline bool ts_weight(float w) { return isfinite(w) && w > 0.0f; }
 
+constexpr int TS_MAX_SIDE = 32768;  // of an image
+
+static inline bool ts_image(int H, int W) { return H >= 1 && W >= 1 && H <= TS_MAX_SIDE && W <= TS_MAX_SIDE; }
+
+// B records of TSDF_CAM_DOUBLES doubles as the kernel argument, the rest zero; false: null, B outside 1 .. TSDF_MAX_B, an
+// entry that is not finite or above max_entry in magnitude (the marking's bound; INFINITY: none), a focal length <= 0.
+static inline bool ts_load_cams(const double* cams, int B, double max_entry, TsdfCams& C) {
+  if (cams == nullptr || B < 1 || B > TSDF_MAX_B) return false;
+  for (int b = 0; b < TSDF_MAX_B; ++b)
+    for (int e = 0; e < TSDF_CAM_DOUBLES; ++e) {
+      C.c[b][e] = b < B ? cams[b * TSDF_CAM_DOUBLES + e] : 0.0;
+      if (!isfinite(C.c[b][e]) || fabs(C.c[b][e]) > max_entry) return false;
+    }
+  for (int b = 0; b < B; ++b)
+    if (!(C.c[b][12] > 0.0 && C.c[b][13] > 0.0)) return false;
+  return true;
+}
+
 }  // namespace clmgs

@@ -41,12 +41,13 @@
 // as in the dense kernel; voxels of a border brick beyond nx, ny, nz are never touched.  A voxel has one owner: no atomics,
 // and the result does not depend on how the cameras are split into launches.
 //
-// 3. Extraction over the S * 512 slot voxels, mirroring the four dense passes (cells -> prefix sum -> vertices;
-// quad_count -> prefix sum -> quads).  A neighbour in the lane's own brick is an offset; any other is read through the
-// table, and a missing brick counts as wsum = 0 and unranked.  The vertices pass also writes the dense linear cell index
-// (k ny + j) nx + i as an int64 key per vertex, the quads pass 3 * (owner's linear index) + axis per quad: sorted by them
-// (the host, torch.sort) the output is in the dense order.
+// 3. Extraction: the four Surface Nets passes of csrc/tsdf_extract.h, the very code of the dense kernel, over the S * 512
+// slot voxels (cells -> prefix sum -> vertices; quad_count -> prefix sum -> quads).  A neighbour in the lane's own brick
+// is an offset; any other is read through the table, and a missing brick counts as wsum = 0 and unranked.  The vertices
+// pass also writes the dense linear cell index (k ny + j) nx + i as an int64 key per vertex, the quads pass 3 * (owner's
+// linear index) + axis per quad: sorted by them (the host, torch.sort) the output is in the dense order.
 #include "common.h"
+#include "tsdf_extract.h"
 #include "tsdf_fuse.h"
 #include "tsdf_math.h"
 
@@ -54,8 +55,6 @@ namespace clmgs {
 
 constexpr int SP_SIDE = 8, SP_VOX = 512, SP_BRICK_FLOATS = TSDF_PLANES * SP_VOX;
 constexpr int SP_THREADS = 256;
-constexpr int SP_MAX_SIDE = 32768;  // of an image
-constexpr int SP_EX_MAX_BLOCKS = 8192;
 constexpr int64_t SP_MAX_BRICK_GRID = (int64_t)1 << 30;
 constexpr double TS_MARK_ZREL = 1.0 / 1048576.0;  // 2^-20
 constexpr double TS_MARK_GEPS = 1.0 / 65536.0;    // 2^-16 voxel
@@ -160,164 +159,39 @@ tsdf_sparse_integrate_kernel(float* __restrict__ pool, const int32_t* __restrict
 }
 
 // ---------------------------------------------------------------------------------------------- 3. extraction
-// Slot voxel sv -> its voxel (p[0], p[1], p[2]); false for a voxel of a border brick beyond the grid (or a brick list that
-// does not belong to this grid).
-__device__ __forceinline__ bool sp_decode(const SpDims& D, const int32_t* __restrict__ bricks, int sv, int (&p)[3]) {
-  const int bidx = bricks[sv >> 9];
-  if (bidx < 0 || (int64_t)bidx >= D.nb) return false;
-  const int l = sv & 511;
-  p[0] = (bidx % D.nbx) * SP_SIDE + (l & 7);
-  p[1] = ((bidx / D.nbx) % D.nby) * SP_SIDE + ((l >> 3) & 7);
-  p[2] = (bidx / D.nbx / D.nby) * SP_SIDE + (l >> 6);
-  return p[0] < D.nx && p[1] < D.ny && p[2] < D.nz;
-}
+// The accessor of csrc/tsdf_extract.h: a lane index is a slot voxel, and the passes write sort keys.
+struct BrickVol : SpDims {
+  static constexpr bool KEYS = true;
+  const float* pool;
+  const int32_t *bricks, *table;
+  int64_t* keys;  // of the pass that writes them, else null
 
-// The slot voxel of the voxel p + (dx, dy, dz), which lies in the grid, seen from slot voxel sv = voxel p: an offset inside
-// the lane's own brick, else through the table; -1 where no brick is stored.
-__device__ __forceinline__ int sp_neighbour(const SpDims& D, const int32_t* __restrict__ table, int sv, const int (&p)[3], int dx,
-                                            int dy, int dz) {
-  const int x = (p[0] & 7) + dx, y = (p[1] & 7) + dy, z = (p[2] & 7) + dz;
-  if (((x | y | z) & ~7) == 0) return sv + dx + 8 * dy + 64 * dz;  // the fast path
-  const int i = p[0] + dx, j = p[1] + dy, k = p[2] + dz;
-  const int slot = table[((int64_t)(k >> 3) * D.nby + (j >> 3)) * D.nbx + (i >> 3)];
-  if (slot < 0 || slot >= D.S) return -1;
-  return slot * SP_VOX + (k & 7) * 64 + (j & 7) * 8 + (i & 7);
-}
-
-__device__ __forceinline__ float sp_plane(const float* __restrict__ pool, int sv, int plane) {
-  return sv < 0 ? 0.0f : pool[(int64_t)(sv >> 9) * SP_BRICK_FLOATS + plane * SP_VOX + (sv & 511)];
-}
-
-__device__ __forceinline__ bool sp_is_cell(const SpDims& D, const int (&p)[3]) {
-  return p[0] + 1 < D.nx && p[1] + 1 < D.ny && p[2] + 1 < D.nz;
-}
-
-__device__ __forceinline__ bool sp_ranked(const int32_t* __restrict__ scan, int sv) {
-  return sv >= 0 && scan[sv] != (sv > 0 ? scan[sv - 1] : 0);
-}
-
-__global__ void __launch_bounds__(SP_THREADS)
-tsdf_sparse_cells_kernel(const float* __restrict__ pool, const int32_t* __restrict__ bricks, const int32_t* __restrict__ table,
-                         SpDims D, float min_weight, int32_t* __restrict__ cell_count) {
-  const int64_t n = (int64_t)D.S * SP_VOX;
-  for (int64_t v64 = (int64_t)blockIdx.x * SP_THREADS + threadIdx.x; v64 < n; v64 += (int64_t)gridDim.x * SP_THREADS) {
-    const int sv = (int)v64;
-    int p[3], active = 0;
-    if (sp_decode(D, bricks, sv, p) && sp_is_cell(D, p)) {
-      float t8[8], w8[8];
-#pragma unroll
-      for (int c = 0; c < 8; ++c) {
-        const int vc = sp_neighbour(D, table, sv, p, c & 1, (c >> 1) & 1, c >> 2);
-        t8[c] = sp_plane(pool, vc, 0);
-        w8[c] = sp_plane(pool, vc, 1);
-      }
-      active = tsdf_cell_active(t8, w8, min_weight) ? 1 : 0;
-    }
-    cell_count[sv] = active;
+  __host__ __device__ __forceinline__ int64_t lanes() const { return (int64_t)S * SP_VOX; }
+  // false for a voxel of a border brick beyond the grid (or a brick list that does not belong to this grid)
+  __device__ __forceinline__ bool decode(int sv, int (&p)[3]) const {
+    const int bidx = bricks[sv >> 9];
+    if (bidx < 0 || (int64_t)bidx >= nb) return false;
+    const int l = sv & 511;
+    p[0] = (bidx % nbx) * SP_SIDE + (l & 7);
+    p[1] = ((bidx / nbx) % nby) * SP_SIDE + ((l >> 3) & 7);
+    p[2] = (bidx / nbx / nby) * SP_SIDE + (l >> 6);
+    return p[0] < nx && p[1] < ny && p[2] < nz;
   }
-}
-
-__global__ void __launch_bounds__(SP_THREADS)
-tsdf_sparse_vertices_kernel(const float* __restrict__ pool, const int32_t* __restrict__ bricks,
-                            const int32_t* __restrict__ table, SpDims D, const int32_t* __restrict__ cell_scan, int V,
-                            const TsdfCams g2w, float* __restrict__ verts, uint8_t* __restrict__ colours,
-                            int64_t* __restrict__ keys) {
-  const int64_t n = (int64_t)D.S * SP_VOX;
-  for (int64_t v64 = (int64_t)blockIdx.x * SP_THREADS + threadIdx.x; v64 < n; v64 += (int64_t)gridDim.x * SP_THREADS) {
-    const int sv = (int)v64;
-    if (!sp_ranked(cell_scan, sv)) continue;
-    const int id = cell_scan[sv] - 1;
-    int p[3];
-    if (id < 0 || id >= V || !sp_decode(D, bricks, sv, p) || !sp_is_cell(D, p)) continue;  // (a foreign scan writes nothing outside)
-    float vox[TSDF_PLANES][8];
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      const int vc = sp_neighbour(D, table, sv, p, c & 1, (c >> 1) & 1, c >> 2);
-#pragma unroll
-      for (int pl = 0; pl < TSDF_PLANES; ++pl) vox[pl][c] = sp_plane(pool, vc, pl);
-    }
-    float xyz[3];
-    uint8_t q[3];
-    tsdf_cell_vertex(vox, p[0], p[1], p[2], g2w.c[0], xyz, q);
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      verts[(int64_t)id * 3 + d] = xyz[d];
-      colours[(int64_t)id * 3 + d] = q[d];
-    }
-    keys[id] = ((int64_t)p[2] * D.ny + p[1]) * D.nx + p[0];
+  // an offset inside the lane's own brick, else through the table; -1 where no brick is stored
+  __device__ __forceinline__ int neighbour(int sv, const int (&p)[3], int dx, int dy, int dz) const {
+    const int x = (p[0] & 7) + dx, y = (p[1] & 7) + dy, z = (p[2] & 7) + dz;
+    if (((x | y | z) & ~7) == 0) return sv + dx + 8 * dy + 64 * dz;  // the fast path
+    const int i = p[0] + dx, j = p[1] + dy, k = p[2] + dz;
+    const int slot = table[((int64_t)(k >> 3) * nby + (j >> 3)) * nbx + (i >> 3)];
+    if (slot < 0 || slot >= S) return -1;
+    return slot * SP_VOX + (k & 7) * 64 + (j & 7) * 8 + (i & 7);
   }
-}
-
-// ts_quad of csrc/tsdf.hip on slot voxels: q[0..3] are the slot voxels of the four cells around the edge.
-__device__ __forceinline__ bool sp_quad(const float* __restrict__ pool, const int32_t* __restrict__ table, const SpDims& D,
-                                        const int32_t* __restrict__ cell_scan, float min_weight, int sv, const int (&p)[3],
-                                        int axis, int (&q)[4], bool& inside) {
-  const int dim[3] = {D.nx, D.ny, D.nz};
-  const int a1 = (axis + 1) % 3, a2 = (axis + 2) % 3;
-  if (p[axis] + 1 >= dim[axis]) return false;
-  if (p[a1] < 1 || p[a1] + 1 >= dim[a1] || p[a2] < 1 || p[a2] + 1 >= dim[a2]) return false;
-  int e[3] = {0, 0, 0}, e1[3] = {0, 0, 0}, e2[3] = {0, 0, 0};
-  e[axis] = 1;
-  e1[a1] = -1;
-  e2[a2] = -1;
-  const int v2 = sp_neighbour(D, table, sv, p, e[0], e[1], e[2]);
-  if (!tsdf_valid(sp_plane(pool, sv, 1), min_weight) || !tsdf_valid(sp_plane(pool, v2, 1), min_weight)) return false;
-  inside = tsdf_inside(sp_plane(pool, sv, 0));
-  if (inside == tsdf_inside(sp_plane(pool, v2, 0))) return false;
-  q[0] = sp_neighbour(D, table, sv, p, e1[0] + e2[0], e1[1] + e2[1], e1[2] + e2[2]);
-  q[1] = sp_neighbour(D, table, sv, p, e2[0], e2[1], e2[2]);
-  q[2] = sv;
-  q[3] = sp_neighbour(D, table, sv, p, e1[0], e1[1], e1[2]);
-  return sp_ranked(cell_scan, q[0]) && sp_ranked(cell_scan, q[1]) && sp_ranked(cell_scan, q[2]) && sp_ranked(cell_scan, q[3]);
-}
-
-// EMIT false: quad_count[sv] = the number of quads the voxel owns; true: their triangles and keys at rank quad_scan[sv] - that number.
-template <bool EMIT>
-__global__ void __launch_bounds__(SP_THREADS)
-tsdf_sparse_quads_kernel(const float* __restrict__ pool, const int32_t* __restrict__ bricks, const int32_t* __restrict__ table,
-                         SpDims D, float min_weight, const int32_t* __restrict__ cell_scan, int32_t* __restrict__ quad_count,
-                         const int32_t* __restrict__ quad_scan, int V, int Q, int32_t* __restrict__ faces,
-                         int64_t* __restrict__ keys) {
-  const int64_t n = (int64_t)D.S * SP_VOX;
-  for (int64_t v64 = (int64_t)blockIdx.x * SP_THREADS + threadIdx.x; v64 < n; v64 += (int64_t)gridDim.x * SP_THREADS) {
-    const int sv = (int)v64;
-    if (EMIT && !sp_ranked(quad_scan, sv)) continue;
-    int p[3];
-    const bool in_grid = sp_decode(D, bricks, sv, p);
-    int count = 0, rank = EMIT ? (sv > 0 ? quad_scan[sv - 1] : 0) : 0;
-    if (in_grid) {
-      const int64_t lin = ((int64_t)p[2] * D.ny + p[1]) * D.nx + p[0];
-#pragma unroll
-      for (int axis = 0; axis < 3; ++axis) {
-        int q[4];
-        bool inside = false;
-        if (!sp_quad(pool, table, D, cell_scan, min_weight, sv, p, axis, q, inside)) continue;
-        ++count;
-        if (EMIT) {
-          int id[4];
-          bool ok = rank >= 0 && rank < Q;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            id[e] = cell_scan[q[e]] - 1;
-            ok = ok && id[e] >= 0 && id[e] < V;
-          }
-          if (ok) {  // two triangles along the diagonal q0 - q2; the owner inside: right-handed about the axis
-            int32_t* f = faces + (int64_t)rank * 6;
-            f[0] = id[0];
-            f[1] = inside ? id[1] : id[2];
-            f[2] = inside ? id[2] : id[1];
-            f[3] = id[0];
-            f[4] = inside ? id[2] : id[3];
-            f[5] = inside ? id[3] : id[2];
-            keys[rank] = 3 * lin + axis;
-          }
-          ++rank;
-        }
-      }
-    }
-    if (!EMIT) quad_count[sv] = count;
+  __device__ __forceinline__ bool stored(int sv) const { return sv >= 0; }
+  __device__ __forceinline__ float plane(int sv, int pl) const {
+    return sv < 0 ? 0.0f : pool[(int64_t)(sv >> 9) * SP_BRICK_FLOATS + pl * SP_VOX + (sv & 511)];
   }
-}
+  __device__ __forceinline__ int64_t linear(const int (&p)[3]) const { return ((int64_t)p[2] * ny + p[1]) * nx + p[0]; }
+};
 
 // ---------------------------------------------------------------------------------------------- host
 static bool sp_dims(int nx, int ny, int nz, int S, SpDims& D) {
@@ -330,22 +204,6 @@ static bool sp_dims(int nx, int ny, int nz, int S, SpDims& D) {
   return (int64_t)S <= D.nb;
 }
 
-static bool sp_cams(const double* cams, int B, bool mark, TsdfCams& C) {
-  if (cams == nullptr || B < 1 || B > TSDF_MAX_B) return false;
-  for (int b = 0; b < TSDF_MAX_B; ++b)
-    for (int e = 0; e < TSDF_CAM_DOUBLES; ++e) {
-      C.c[b][e] = b < B ? cams[b * TSDF_CAM_DOUBLES + e] : 0.0;
-      if (!isfinite(C.c[b][e]) || (mark && fabs(C.c[b][e]) > TS_MARK_MAX_ENTRY)) return false;
-    }
-  for (int b = 0; b < B; ++b)
-    if (!(C.c[b][12] > 0.0 && C.c[b][13] > 0.0)) return false;
-  return true;
-}
-
-static dim3 sp_ex_grid(const SpDims& D) {
-  return dim3((unsigned)min((int64_t)SP_EX_MAX_BLOCKS, ((int64_t)D.S * SP_VOX + SP_THREADS - 1) / SP_THREADS));
-}
-
 }  // namespace clmgs
 
 using namespace clmgs;
@@ -355,13 +213,13 @@ extern "C" int clmgs_tsdf_mark(void* stream, int nx, int ny, int nz, uint8_t* ma
                                float trunc, double voxel_cam) {
   SpDims D;
   CLMGS_CHECK_ARG(sp_dims(nx, ny, nz, 1, D));
-  CLMGS_CHECK_ARG(H >= 1 && W >= 1 && H <= SP_MAX_SIDE && W <= SP_MAX_SIDE);
+  CLMGS_CHECK_ARG(ts_image(H, W));
   CLMGS_CHECK_ARG(marks != nullptr && ts_aligned(depth, 4) && ts_aligned(alpha, 4));
   CLMGS_CHECK_ARG(isfinite(trunc) && trunc > 0.0f && isfinite(voxel_cam) && voxel_cam > 0.0);
   CLMGS_CHECK_ARG((double)trunc / voxel_cam <= (double)TS_MARK_MAX_SLABS);
   CLMGS_CHECK_ARG(isfinite(near) && !isnan(depth_max) && !isnan(alpha_min));
   TsdfCams C;
-  CLMGS_CHECK_ARG(sp_cams(cams, B, true, C));
+  CLMGS_CHECK_ARG(ts_load_cams(cams, B, TS_MARK_MAX_ENTRY, C));
   const uint64_t ibytes = (uint64_t)B * H * W * 4;
   CLMGS_CHECK_ARG(ts_apart(marks, (uint64_t)D.nb, depth, ibytes) && ts_apart(marks, (uint64_t)D.nb, alpha, ibytes));
   const int64_t blocks = ((int64_t)B * H * W + SP_THREADS - 1) / SP_THREADS;  // <= 2^26
@@ -377,14 +235,14 @@ extern "C" int clmgs_tsdf_sparse_integrate(void* stream, int nx, int ny, int nz,
                                            float inv_trunc, int cull) {
   SpDims D;
   CLMGS_CHECK_ARG(sp_dims(nx, ny, nz, S, D));
-  CLMGS_CHECK_ARG(H >= 1 && W >= 1 && H <= SP_MAX_SIDE && W <= SP_MAX_SIDE);
+  CLMGS_CHECK_ARG(ts_image(H, W));
   CLMGS_CHECK_ARG(ts_aligned(bricks, 4) && ts_aligned(pool, 4) && ts_aligned(depth, 4) && ts_aligned(alpha, 4) &&
                   ts_aligned(rgb, 4));
   CLMGS_CHECK_ARG(cull == 0 || cull == 1);
   CLMGS_CHECK_ARG(isfinite(trunc) && trunc > 0.0f && isfinite(inv_trunc) && inv_trunc > 0.0f);
   CLMGS_CHECK_ARG(isfinite(near) && !isnan(depth_max) && !isnan(alpha_min));
   TsdfCams C;
-  CLMGS_CHECK_ARG(sp_cams(cams, B, false, C));
+  CLMGS_CHECK_ARG(ts_load_cams(cams, B, INFINITY, C));
   const uint64_t pbytes = (uint64_t)S * SP_BRICK_FLOATS * 4, ibytes = (uint64_t)B * H * W * 4, bbytes = (uint64_t)S * 4;
   CLMGS_CHECK_ARG(ts_apart(pool, pbytes, depth, ibytes) && ts_apart(pool, pbytes, alpha, ibytes) &&
                   ts_apart(pool, pbytes, rgb, 3 * ibytes) && ts_apart(pool, pbytes, bricks, bbytes));
@@ -399,13 +257,16 @@ extern "C" int clmgs_tsdf_sparse_extract(void* stream, int pass, int nx, int ny,
                                          const int32_t* cell_scan, const int32_t* quad_scan, int V, int Q,
                                          const double* grid_to_world, float* verts, uint8_t* colours, int64_t* vert_keys,
                                          int32_t* faces, int64_t* quad_keys) {
-  SpDims D;
+  BrickVol D;
   CLMGS_CHECK_ARG(sp_dims(nx, ny, nz, S, D));
   CLMGS_CHECK_ARG(pass >= 0 && pass <= 3);
   CLMGS_CHECK_ARG(ts_aligned(bricks, 4) && ts_aligned(table, 4) && ts_aligned(pool, 4));
+  D.pool = pool; D.bricks = bricks; D.table = table;
+  D.keys = pass == 1 ? vert_keys : pass == 3 ? quad_keys : nullptr;
   const uint64_t pbytes = (uint64_t)S * SP_BRICK_FLOATS * 4, sbytes = (uint64_t)S * SP_VOX * 4, bbytes = (uint64_t)S * 4,
                  tbytes = (uint64_t)D.nb * 4;
   const hipStream_t st = (hipStream_t)stream;
+  const dim3 grid = ts_ex_grid(D.lanes()), block(TS_EX_THREADS);
   // an output overlaps no input
   auto clear = [&](const void* out, uint64_t obytes) {
     return ts_apart(out, obytes, pool, pbytes) && ts_apart(out, obytes, bricks, bbytes) && ts_apart(out, obytes, table, tbytes) &&
@@ -415,34 +276,29 @@ extern "C" int clmgs_tsdf_sparse_extract(void* stream, int pass, int nx, int ny,
   if (pass == 0 || pass == 2) {
     CLMGS_CHECK_ARG(ts_aligned(count, 4) && ts_weight(min_weight) && clear(count, sbytes));
     if (pass == 0) {
-      hipLaunchKernelGGL(tsdf_sparse_cells_kernel, sp_ex_grid(D), dim3(SP_THREADS), 0, st, pool, bricks, table, D, min_weight,
-                         count);
+      hipLaunchKernelGGL(tsdf_cells_kernel<BrickVol>, grid, block, 0, st, D, min_weight, count);
     } else {
       CLMGS_CHECK_ARG(ts_aligned(cell_scan, 4));
-      hipLaunchKernelGGL(tsdf_sparse_quads_kernel<false>, sp_ex_grid(D), dim3(SP_THREADS), 0, st, pool, bricks, table, D,
-                         min_weight, cell_scan, count, (const int32_t*)nullptr, 0, 0, (int32_t*)nullptr, (int64_t*)nullptr);
+      hipLaunchKernelGGL((tsdf_quads_kernel<BrickVol, false>), grid, block, 0, st, D, min_weight, cell_scan, count,
+                         (const int32_t*)nullptr, 0, 0, (int32_t*)nullptr);
     }
   } else if (pass == 1) {
-    CLMGS_CHECK_ARG(V >= 1 && (int64_t)V <= (int64_t)S * SP_VOX && grid_to_world != nullptr);
+    CLMGS_CHECK_ARG(V >= 1 && (int64_t)V <= (int64_t)S * SP_VOX);
     CLMGS_CHECK_ARG(ts_aligned(cell_scan, 4) && ts_aligned(verts, 4) && colours != nullptr && ts_aligned(vert_keys, 8));
     TsdfCams G;
-    for (int e = 0; e < TSDF_MAX_B * TSDF_CAM_DOUBLES; ++e) {
-      G.c[0][e] = e < 12 ? grid_to_world[e] : 0.0;
-      CLMGS_CHECK_ARG(isfinite(G.c[0][e]));
-    }
+    CLMGS_CHECK_ARG(ts_load_g2w(grid_to_world, G));
     const uint64_t vbytes = (uint64_t)V * 12, cbytes = (uint64_t)V * 3, kbytes = (uint64_t)V * 8;
     CLMGS_CHECK_ARG(clear(verts, vbytes) && clear(colours, cbytes) && clear(vert_keys, kbytes) &&
                     ts_apart(verts, vbytes, colours, cbytes) && ts_apart(verts, vbytes, vert_keys, kbytes) &&
                     ts_apart(colours, cbytes, vert_keys, kbytes));
-    hipLaunchKernelGGL(tsdf_sparse_vertices_kernel, sp_ex_grid(D), dim3(SP_THREADS), 0, st, pool, bricks, table, D, cell_scan, V,
-                       G, verts, colours, vert_keys);
+    hipLaunchKernelGGL(tsdf_vertices_kernel<BrickVol>, grid, block, 0, st, D, cell_scan, V, G, verts, colours);
   } else {
     CLMGS_CHECK_ARG(V >= 1 && (int64_t)V <= (int64_t)S * SP_VOX && Q >= 1 && Q < (1 << 30) && ts_weight(min_weight));
     CLMGS_CHECK_ARG(ts_aligned(cell_scan, 4) && ts_aligned(quad_scan, 4) && ts_aligned(faces, 4) && ts_aligned(quad_keys, 8));
     const uint64_t fbytes = (uint64_t)Q * 24, kbytes = (uint64_t)Q * 8;
     CLMGS_CHECK_ARG(clear(faces, fbytes) && clear(quad_keys, kbytes) && ts_apart(faces, fbytes, quad_keys, kbytes));
-    hipLaunchKernelGGL(tsdf_sparse_quads_kernel<true>, sp_ex_grid(D), dim3(SP_THREADS), 0, st, pool, bricks, table, D, min_weight,
-                       cell_scan, (int32_t*)nullptr, quad_scan, V, Q, faces, quad_keys);
+    hipLaunchKernelGGL((tsdf_quads_kernel<BrickVol, true>), grid, block, 0, st, D, min_weight, cell_scan, (int32_t*)nullptr,
+                       quad_scan, V, Q, faces);
   }
   CLMGS_LAUNCH_CHECK();
   return 0;

@@ -85,66 +85,79 @@ def camera_record(camera, g2w):
     return np.concatenate([(w2c @ g4)[:3].reshape(12), [K[0, 0], K[1, 1], K[0, 2], K[1, 2]]])
 
 
+class _Staging:
+    """Up to 16 cameras staged for one launch.  Two slots of stacked float32 planes [16, *lead, H, W], one per entry of
+    `leads`, allocated once per image size: a slot is filled while the launch that reads the other one may still be running.
+    launch(*planes[:fill], records [fill,16], *gates) runs at 16 cameras, before a camera whose gates or image size differ,
+    and on flush().  (The owner passes `launch` with every call: a stored bound method would tie the volume into a cycle
+    and keep its tensors until the collector runs.)"""
+
+    def __init__(self, leads):
+        self.leads = leads
+        self.ring, self.size, self.slot, self.fill, self.records, self.gates = None, None, 0, 0, [], None
+
+    def add(self, launch, device, record, planes, H, W, gates):
+        if self.fill and (self.gates != gates or self.size != (H, W)):
+            self.flush(launch)
+        self.gates = gates
+        if self.size != (H, W):
+            self.ring = [tuple(torch.empty((BATCH,) + lead + (H, W), dtype=torch.float32, device=device) for lead in self.leads)
+                         for _ in range(2)]
+            self.size = (H, W)
+        for dst, src in zip(self.ring[self.slot], planes):
+            dst[self.fill].copy_(src.reshape(dst.shape[1:]))
+        self.records.append(record)
+        self.fill += 1
+        if self.fill == BATCH:
+            self.flush(launch)
+
+    def flush(self, launch):
+        if not self.fill:
+            return
+        launch(*(t[:self.fill] for t in self.ring[self.slot]), np.stack(self.records), *self.gates)
+        self.slot, self.fill, self.records = 1 - self.slot, 0, []
+
+
 class TsdfVolume:
     """The volume and its two operations.  integrate() may be called any number of times; the sums continue."""
 
     def __init__(self, frame, bounds, voxel, trunc_voxels=4.0, device="cuda", grid_gb=16.0):
         self.frame = tuple(np.asarray(v, dtype=np.float64) for v in frame)
         self.bounds = tuple(float(v) for v in bounds)
-        self.nx, self.ny, self.nz = check_grid(self.bounds, voxel, grid_gb)
+        self._size(voxel, grid_gb)
         self.voxel = float(voxel)
         if not (math.isfinite(trunc_voxels) and trunc_voxels > 0):
             raise ValueError(f"--trunc_voxels must be positive and finite, got {trunc_voxels}")
         self.trunc = float(trunc_voxels) * self.voxel
         self.grid_to_world = grid_to_world(self.frame, self.bounds, self.voxel)
-        self.grid = torch.zeros((6, self.nz, self.ny, self.nx), dtype=torch.float32, device=device)
         self.cameras_used = 0
-        self._ring, self._slot, self._fill, self._records = None, 0, 0, []
-        self._gates = None
+        self._staged = _Staging(((), (), (3,)))
+        self._allocate(device)
 
-    # ------------------------------------------------------------------------------------------ fusion
-    def _buffers(self, H, W):
-        """Two slots of stacked batch inputs, allocated once per image size: a slot is filled while the launch that reads
-        the other one may still be running."""
-        if self._ring is None or self._ring[0][0].shape[1:] != (H, W):
-            dev = self._device()
-            self._ring = [(torch.empty((BATCH, H, W), dtype=torch.float32, device=dev),
-                           torch.empty((BATCH, H, W), dtype=torch.float32, device=dev),
-                           torch.empty((BATCH, 3, H, W), dtype=torch.float32, device=dev)) for _ in range(2)]
-        return self._ring[self._slot]
+    def _size(self, voxel, grid_gb):
+        self.nx, self.ny, self.nz = check_grid(self.bounds, voxel, grid_gb)
+
+    def _allocate(self, device):
+        self.grid = torch.zeros((6, self.nz, self.ny, self.nx), dtype=torch.float32, device=device)
 
     def _device(self):
         return self.grid.device
 
+    # ------------------------------------------------------------------------------------------ fusion
     def _fuse(self, depth, alpha, rgb, records, near, depth_max, alpha_min):
         clm_kernels.tsdf_integrate(self.grid, depth, alpha, rgb, records, near=near, depth_max=depth_max, alpha_min=alpha_min,
                                    trunc=self.trunc)
+        self.cameras_used += len(records)
 
     def add(self, camera, image, depth, alpha, near=0.01, depth_max=float("inf"), alpha_min=0.5):
         """Stages one camera's render (image [3,H,W], expected depth and alpha [H,W] or [1,H,W]) and launches the fusion
         when 16 are staged; flush() launches what is left.  The gates must not change inside a batch."""
-        gates = (float(near), float(depth_max), float(alpha_min))
         H, W = (int(v) for v in image.shape[-2:])
-        if self._fill and (self._gates != gates or self._ring[0][0].shape[1:] != (H, W)):
-            self.flush()
-        self._gates = gates
-        d, a, c = self._buffers(H, W)
-        d[self._fill].copy_(depth.reshape(H, W))
-        a[self._fill].copy_(alpha.reshape(H, W))
-        c[self._fill].copy_(image.reshape(3, H, W))
-        self._records.append(camera_record(camera, self.grid_to_world))
-        self._fill += 1
-        if self._fill == BATCH:
-            self.flush()
+        self._staged.add(self._fuse, self._device(), camera_record(camera, self.grid_to_world), (depth, alpha, image), H, W,
+                         (float(near), float(depth_max), float(alpha_min)))
 
     def flush(self):
-        if not self._fill:
-            return
-        d, a, c = self._ring[self._slot]
-        near, depth_max, alpha_min = self._gates
-        self._fuse(d[:self._fill], a[:self._fill], c[:self._fill], np.stack(self._records), near, depth_max, alpha_min)
-        self.cameras_used += self._fill
-        self._slot, self._fill, self._records = 1 - self._slot, 0, []
+        self._staged.flush(self._fuse)
 
     def integrate(self, cameras, renders, near=0.01, depth_max=float("inf"), alpha_min=0.5):
         """cameras: pinhole cameras; renders: per camera (image [3,H,W], expected depth, alpha) as the eval entries return
@@ -227,21 +240,15 @@ class SparseTsdfVolume(TsdfVolume):
     then add() / integrate() the SAME cameras and depth maps, then extract(): the mesh is the dense volume's, bit for bit
     ("Sparse volume").  The dense limits do not apply; grid_gb bounds marks + table + pool."""
 
-    def __init__(self, frame, bounds, voxel, trunc_voxels=4.0, device="cuda", grid_gb=16.0):
-        self.frame = tuple(np.asarray(v, dtype=np.float64) for v in frame)
-        self.bounds = tuple(float(v) for v in bounds)
+    def _size(self, voxel, grid_gb):
         (self.nx, self.ny, self.nz), (self.nbx, self.nby, self.nbz) = check_brick_grid(self.bounds, voxel, grid_gb)
-        self.voxel, self.grid_gb = float(voxel), float(grid_gb)
-        if not (math.isfinite(trunc_voxels) and trunc_voxels > 0):
-            raise ValueError(f"--trunc_voxels must be positive and finite, got {trunc_voxels}")
-        self.trunc = float(trunc_voxels) * self.voxel
-        self.grid_to_world = grid_to_world(self.frame, self.bounds, self.voxel)
+        self.grid_gb = float(grid_gb)
+
+    def _allocate(self, device):
         self.marks = torch.zeros((self.nbz, self.nby, self.nbx), dtype=torch.uint8, device=device)
         self.table = self.bricks = self.pool = None
-        self.cameras_used = self.cameras_marked = 0
-        self._ring, self._slot, self._fill, self._records = None, 0, 0, []
-        self._gates = None
-        self._mring, self._mslot, self._mfill, self._mrecords, self._mgates = None, 0, 0, [], None
+        self.cameras_marked = 0
+        self._marked = _Staging(((), ()))
 
     @property
     def shape(self):
@@ -271,39 +278,22 @@ class SparseTsdfVolume(TsdfVolume):
         if self.pool is not None:
             raise ValueError("SparseTsdfVolume: mark() after allocate(): a brick allocated late would lack the earlier "
                              "cameras' observations; mark every camera first")
-        gates = (float(near), float(depth_max), float(alpha_min))
         H, W = (int(v) for v in depth.shape[-2:])
-        if self._mfill and (self._mgates != gates or self._mring[0][0].shape[1:] != (H, W)):
-            self._flush_marks()
-        self._mgates = gates
-        if self._mring is None or self._mring[0][0].shape[1:] != (H, W):
-            dev = self._device()
-            self._mring = [tuple(torch.empty((BATCH, H, W), dtype=torch.float32, device=dev) for _ in range(2)) for _ in range(2)]
-        d, a = self._mring[self._mslot]
-        d[self._mfill].copy_(depth.reshape(H, W))
-        a[self._mfill].copy_(alpha.reshape(H, W))
-        self._mrecords.append(camera_mark_record(camera, self.grid_to_world))
-        self._mfill += 1
-        if self._mfill == BATCH:
-            self._flush_marks()
+        self._marked.add(self._mark, self._device(), camera_mark_record(camera, self.grid_to_world), (depth, alpha), H, W,
+                         (float(near), float(depth_max), float(alpha_min)))
 
-    def _flush_marks(self):
-        if not self._mfill:
-            return
-        d, a = self._mring[self._mslot]
-        near, depth_max, alpha_min = self._mgates
-        clm_kernels.tsdf_mark(self.marks, self.shape, d[:self._mfill], a[:self._mfill], np.stack(self._mrecords), near=near,
-                              depth_max=depth_max, alpha_min=alpha_min, trunc=self.trunc, voxel_cam=self.voxel)
-        self.cameras_marked += self._mfill
-        self._mslot, self._mfill, self._mrecords = 1 - self._mslot, 0, []
+    def _mark(self, depth, alpha, records, near, depth_max, alpha_min):
+        clm_kernels.tsdf_mark(self.marks, self.shape, depth, alpha, records, near=near, depth_max=depth_max,
+                              alpha_min=alpha_min, trunc=self.trunc, voxel_cam=self.voxel)
+        self.cameras_marked += len(records)
 
     def allocate(self):
         """Builds table, bricks and the zeroed pool from the marks; refuses by name S * 512 >= 2^31 and marks + table + pool
         above grid_gb.  -> S.  No marked brick is a result (S = 0), not an error."""
         if self.pool is not None:
             raise ValueError("SparseTsdfVolume: allocate() has been called already")
-        self._flush_marks()
-        self._mring = None
+        self._marked.flush(self._mark)
+        self._marked = _Staging(((), ()))  # (the staging buffers are free before the pool is allocated)
         flat = self.marks.reshape(-1) != 0
         S = int(flat.sum())
         check_sparse_size(S, self.bricks_total, self.voxel, self.grid_gb)
@@ -327,6 +317,7 @@ class SparseTsdfVolume(TsdfVolume):
     def _fuse(self, depth, alpha, rgb, records, near, depth_max, alpha_min):
         clm_kernels.tsdf_sparse_integrate(self.pool, self.bricks, self.shape, depth, alpha, rgb, records, near=near,
                                           depth_max=depth_max, alpha_min=alpha_min, trunc=self.trunc)
+        self.cameras_used += len(records)
 
     # ------------------------------------------------------------------------------------------ surface
     def extract(self, min_weight=2.0):

@@ -172,10 +172,20 @@ def _all_outside():
     return g, R.G2W
 
 
+def _one_voxel():
+    """3 x 3 x 3, every voxel valid and outside but the middle one: the smallest grid that can hold a quad at all (a quad needs
+    a neighbour on both sides of its two cross axes).  The eight cells are active and the six edges out of the middle voxel
+    have a quad each: V = 8, F = 12."""
+    g = np.zeros((6, 3, 3, 3), dtype=np.float32)
+    g[0] = g[1] = g[5] = 2.0
+    g[0, 1, 1, 1] = -2.0
+    return g, np.hstack([np.eye(3), np.zeros((3, 1))])
+
+
 EXTRACT_CASES = {
     "sphere": lambda: (R.grid_from_sdf(R.sphere_sdf()), R.G2W), "torus": lambda: (R.grid_from_sdf(R.torus_sdf()), R.G2W),
     "sphere_unseen_interior": lambda: (R.grid_from_sdf(R.sphere_sdf(), unseen_interior=True), R.G2W),
-    "random": _random_grid, "all_outside": _all_outside,
+    "random": _random_grid, "all_outside": _all_outside, "one_voxel": _one_voxel,
 }
 
 
@@ -197,7 +207,10 @@ def test_extraction_equals_the_reference(dev, name):
     if name == "all_outside":
         assert len(rv) == 0 and len(rf) == 0
         return
-    assert len(rv) > 100 and len(rf) > (20 if name == "random" else 100)
+    if name == "one_voxel":
+        assert len(rv) == 8 and len(rf) == 12
+    else:
+        assert len(rv) > 100 and len(rf) > (20 if name == "random" else 100)
     assert np.array_equal(faces, rf)
     assert _ulp_close(verts, rv).all()
     assert int(np.abs(colours.astype(np.int32) - rc.astype(np.int32)).max()) <= 1
@@ -205,7 +218,7 @@ def test_extraction_equals_the_reference(dev, name):
         assert 0 < int((grid[1] < 2).sum()) and len(rf) < 2 * 3 * grid[0].size
     else:  # the topology assertions of the CPU test on the kernel's own output
         t = R.check_closed_surface(verts, faces, cells, g2w, 0 if name == "torus" else 2)
-        assert (t["V"], t["F"]) == ((728, 1456) if name == "torus" else (746, 1488))
+        assert (t["V"], t["F"]) == {"torus": (728, 1456), "one_voxel": (8, 12)}.get(name, (746, 1488))
 
 
 # ------------------------------------------------------------------------------------------------ 3. a rendered plane

@@ -211,6 +211,44 @@ def test_sparse_mesh_equals_the_dense_mesh(dev, name):
     assert four >= 1
 
 
+def _pack(grid, marks, dev):
+    """A dense grid [6,nz,ny,nx] -> (pool, bricks, table) of the marked bricks: the inverse of SparseTsdfVolume.to_dense."""
+    _, nz, ny, nx = grid.shape
+    nbz, nby, nbx = marks.shape
+    full = torch.zeros((6, nbz * 8, nby * 8, nbx * 8), dtype=torch.float32)
+    full[:, :nz, :ny, :nx] = torch.from_numpy(grid)
+    full = full.reshape(6, nbz, 8, nby, 8, nbx, 8).permute(1, 3, 5, 0, 2, 4, 6).reshape(-1, 6, 8, 8, 8)
+    flat = torch.from_numpy(np.ascontiguousarray(marks)).reshape(-1)
+    scan = torch.cumsum(flat, 0, dtype=torch.int32)
+    table = torch.where(flat, scan - 1, torch.full_like(scan, -1)).reshape(nbz, nby, nbx)
+    bricks = torch.nonzero(flat).reshape(-1)
+    return full[bricks].contiguous().to(dev), bricks.to(torch.int32).to(dev), table.contiguous().to(dev)
+
+
+def test_missing_bricks_next_to_the_surface(dev):
+    """tsdf_sparse_extract on a pool packed from a dense grid, where -- unlike in a fused volume -- bricks are missing right
+    next to active cells: the "not stored" branch of the neighbour lookup decides cells and quads.  The result must be the
+    dense extraction of the grid restricted to the stored bricks.  The counts (the numpy reference) show that the missing
+    bricks matter on this input.  And the smallest grid with a quad, as one brick."""
+    from clm_gs_amd import clm_kernels
+    from tests.test_gpu_tsdf import EXTRACT_CASES
+    grid, g2w = EXTRACT_CASES["random"]()  # 31 x 27 x 23 voxels: 4 x 4 x 3 bricks, border bricks on every axis
+    marks = np.random.default_rng(7).random((3, 4, 4)) < 0.7
+    restricted = SR.restrict(grid, marks)
+    assert int(marks.sum()) == 35
+    (rv, _, rf, _), (fv, _, ff, _) = R.extract(restricted, 2.0, g2w), R.extract(grid, 2.0, g2w)
+    assert (len(rv), len(rf)) == (1012, 224) and (len(fv), len(ff)) == (1534, 332)
+    want = clm_kernels.tsdf_extract(torch.from_numpy(restricted).to(dev), 2.0, g2w)
+    got = clm_kernels.tsdf_sparse_extract(*_pack(grid, marks, dev), (31, 27, 23), 2.0, g2w)
+    assert want[0].shape[0] == 1012 and want[2].shape[0] == 224
+    _same_mesh(got, want, "random, 35 of 48 bricks")
+    grid, g2w = EXTRACT_CASES["one_voxel"]()
+    want = clm_kernels.tsdf_extract(torch.from_numpy(grid).to(dev), 2.0, g2w)
+    got = clm_kernels.tsdf_sparse_extract(*_pack(grid, np.ones((1, 1, 1), dtype=bool), dev), (3, 3, 3), 2.0, g2w)
+    assert got[0].shape[0] == 8 and got[2].shape[0] == 12
+    _same_mesh(got, want, "one voxel")
+
+
 def test_no_observation_is_an_empty_result(dev):
     from clm_gs_amd import tsdf
     sc = dict(SR.sphere_scene())
